@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- EM iterations/s of the MI355X EM hot path on BASELINE.json's workloads.
 
-  python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c5|c2|c1|c5fit]
+  python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c5|c2|c1|c5fit] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the steps and prints the result line; nothing else.  --full adds what the headline does
+not need: `roofline`, `stability`, `cpu_baseline` and, for c3, the other workloads as `secondary` (each can still be turned
+off there with its own option).  --dump-outputs DIR writes what the timed path left after its last step as float64 .npy
+files (rank 0's; at most 64 MB): for the single fits q.npy (I x K), p.npy (K x T) and logL.npy, for c4 the per-unit log
+likelihoods and iteration counts, for c5 the per-replicate statistics.  Inputs depend only on the arguments.
+
+--steps and --warmup count timed and warm-up steps of the single fits (c3, c2, c1, c5fit), and the line's `steps` and
+`ms_per_step` are theirs.  Not so on the sharded workloads: on c4 --steps is the SQUAREM cycles of every unit, --warmup the
+untimed cycles of one unit before them, and `ms_per_step` the timed region over the busiest rank's units x cycles; on c5
+--steps is each model's iteration budget (-T), --warmup is unused, and a step on the line is one replicate (`steps` =
+replicates, `ms_per_step` per replicate of the busiest rank).
 
 With N > 1 and no RANK in the environment this process only checks that N devices are visible and starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` as a
@@ -24,8 +36,8 @@ Workloads
   c2, c1, c5fit: single fits at the shapes of configs[1], configs[0] and configs[4] (plain EM), measured like c3.
 
 value = EM iterations/s summed over ranks (n_iter increments of stop(), em_alg.c:103, over the barrier-to-barrier wall time,
-max over ranks), inputs resident in HBM.  The same JSON line carries `roofline` for the dominant kernel (HIP events on the
-library's own stream) and, at N = 1, `cpu_baseline`: rank 0 times the reference's own em() (oracle/_ref/ref_time: the
+max over ranks), inputs resident in HBM.  With --full the same JSON line carries `roofline` for the dominant kernel (HIP events
+on the library's own stream) and, at N = 1, `cpu_baseline`: rank 0 times the reference's own em() (oracle/_ref/ref_time: the
 unmodified sources of the path compiled by oracle/Makefile where /root/reference exists; the binary travels with the tree,
 the sources do not; kind "reference") on a bounded sample of the workload -- all individuals, the first loci, the same
 iterations -- and, under `port`, the CPU oracle on a larger one (one host core for the single fits, min(units, 16) processes
@@ -574,7 +586,7 @@ def data_counts(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ single fit per GPU (c3, c2, c1, c5fit)
-def run_single_fit(args, env, name, ua, geno, steps, warmup, with_roofline=True):
+def run_single_fit(args, env, name, ua, geno, steps, warmup, with_roofline=True, dump=False):
     from multiclust_amd import hip, host
     w = WORKLOADS[name]
     accel = w["accel"] if args.accel is None else args.accel
@@ -631,6 +643,8 @@ def run_single_fit(args, env, name, ua, geno, steps, warmup, with_roofline=True)
 
     env.barrier(ctx)
     n_iter0 = fit.mod.n_iter
+    # the timed batch carries the library's event marks around every pass (eager launches) with or without --full, so that the
+    # headline is measured the same way in both and as on earlier lines; only --full reads them into `roofline`
     if with_roofline:
         profile_begin(ctx)
     t0 = time.perf_counter()
@@ -649,12 +663,14 @@ def run_single_fit(args, env, name, ua, geno, steps, warmup, with_roofline=True)
     }
     if accel:      # with an accelerated scheme both rates; a cycle = 2 EM iterations + 2 log-likelihood evaluations
         out["config"]["accelerated_cycles_per_s"] = steps * env.world / dt
-    if with_roofline and env.rank == 0:
+    if with_roofline and args.full and env.rank == 0:
         nnz, _ = data_counts(ctx)
         out["roofline"] = roofline_object(ctx, w, T, w["K"], value / env.world, name, nnz, steps)
     elif with_roofline:
         hlib.mchip_profile_end(ctx, None, None, None)
-    if with_roofline and args.stability > 0:
+    if dump:
+        out["outputs"] = {"q": fit.get_q(fit.mod.pindex), "p": fit.get_p(fit.mod.pindex), "logL": np.array([fit.mod.logL])}
+    if with_roofline and args.full and args.stability > 0:
         # how stable is a figure taken over `steps` steps?  The same batch again, args.stability times, right behind the timed one,
         # launched the same way (event pairs around the passes), each timed by itself on this rank: min / median / max
         rates = []
@@ -735,7 +751,7 @@ def run_c1_reader(env, iters=200):
 
 
 # ------------------------------------------------------------------------------------------------ c4: initialisations sharded
-def run_units(env, fit, w, T, n_units, cycles, warmup, with_roofline=True):
+def run_units(env, fit, w, T, n_units, cycles, warmup, with_roofline=True, full=True, dump=False):
     """n_units random initialisations of one data set, unit u on rank u mod N; every unit = mc_fit_unit (stream jumped to the
     unit's first draw, device-side initialisation, em() with -T 2*cycles-1) and is timed whole."""
     from multiclust_amd import hip, host, shard
@@ -777,7 +793,9 @@ def run_units(env, fit, w, T, n_units, cycles, warmup, with_roofline=True):
                    "best_unit": summary.best_unit, "best_logL": summary.max_logL,
                    "unit_logL": [r.logL for r in results]},
     }
-    if with_roofline and env.rank == 0:
+    if dump:
+        out["outputs"] = {"unit_logL": np.array([r.logL for r in results]), "unit_n_iter": np.array([float(r.n_iter) for r in results])}
+    if with_roofline and full and env.rank == 0:
         nnz, _ = data_counts(ctx)
         out["roofline"] = roofline_object(ctx, w, T, w["K"], total_iters / dt / env.world, "c4", nnz, len(mine) * cycles)
     elif with_roofline:
@@ -786,7 +804,7 @@ def run_units(env, fit, w, T, n_units, cycles, warmup, with_roofline=True):
 
 
 # ------------------------------------------------------------------------------------------------ c5: bootstrap replicates sharded
-def run_bootstrap(env, w, ua, geno, n_rep, budget, n_init=1, n_streams=1):
+def run_bootstrap(env, w, ua, geno, n_rep, budget, n_init=1, n_streams=1, dump=False):
     """-b n_rep of K-1 vs K (multiclust.c:675-708): the observed-data fits (untimed setup, every rank computes the same bits),
     then replicate b on rank b mod N = mc_fit_replicate, timed whole."""
     from multiclust_amd import host
@@ -857,7 +875,7 @@ def run_bootstrap(env, w, ua, geno, n_rep, budget, n_init=1, n_streams=1):
     total_iters = float(rows[:, 3].sum())
     n_ge = int(np.sum(rows[:, 0] >= ts_obs))
     del keep
-    return {
+    out = {
         "value": total_iters / dt, "ms_per_step": dt * 1e3 / max(1, len(range(0, n_rep, env.world))), "steps": n_rep,
         "config": {"workload": "%s: %s" % ("c5" if w["I"] == 5000 else "c5s", w["desc"]), "I": w["I"], "L": w["L"], "T": T, "ploidy": w["ploidy"], "K": [K0, K1],
                    "accel_scheme": 0, "replicates": n_rep, "replicate_to_rank": "b mod %d" % env.world, "n_init": n_init,
@@ -869,6 +887,9 @@ def run_bootstrap(env, w, ua, geno, n_rep, budget, n_init=1, n_streams=1):
                    "ts_first": rows[:8, 0].tolist(), "ts_checksum": float(rows[:, 0].sum()),
                    "nonempty_cells_observed": nnz},
     }
+    if dump:
+        out["outputs"] = {"ts": rows[:, 0], "logL_H0": rows[:, 1], "logL_HA": rows[:, 2], "n_iter": rows[:, 3], "ts_obs": np.array([ts_obs])}
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ main
@@ -888,6 +909,20 @@ def keep_stdout_for_the_result_line():
 def emit(text):
     sys.stdout.flush()
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (text + "\n").encode())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(dirname, outputs):
+    """--dump-outputs: every array as DIR/<name>.npy in float64"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def finish(env, args, out, scaling):
@@ -919,14 +954,18 @@ def main():
     ap.add_argument("--streams", type=int, default=2, help="c5: concurrent replicates per GPU (host thread + contexts + streams each)")
     ap.add_argument("--settle", type=float, default=1.5, help="seconds of untimed log-likelihood passes before the warm-up steps of a "
                     "single-fit workload, so that the timed steps run at the clocks of a busy device (0: none)")
-    ap.add_argument("--stability", type=int, default=5, help="single-fit workloads: repeat the timed batch this many times behind the "
+    ap.add_argument("--stability", type=int, default=5, help="--full, single-fit workloads: repeat the timed batch this many times behind the "
                     "timed region and report min / median / max EM iterations/s (0: off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of one host core for the CPU oracle's sample")
     ap.add_argument("--ref-budget", type=float, default=15.0, help="seconds of one host core for the reference's own em() on the "
                     "head of that sample (oracle/_ref/ref_time; 0: skip)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the extra workloads carried on the default line (profiling "
+    ap.add_argument("--no-secondary", action="store_true", help="skip the extra workloads carried on the --full line (profiling "
                     "runs: their kernels have the same names as the headline workload's)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline, stability, "
+                    "cpu_baseline and (c3) the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy "
+                    "(float64)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -937,11 +976,14 @@ def main():
     env = Env(args.gpus)
     name = args.workload
     w = WORKLOADS[name]
-    want_cpu = env.world == 1 and env.rank == 0 and not args.no_cpu_baseline
+    want_cpu = args.full and env.world == 1 and env.rank == 0 and not args.no_cpu_baseline
+    dump = bool(args.dump_outputs) and env.rank == 0
 
     if name in ("c5", "c5s"):
         ua, geno = workload_data(w, env)
-        out = run_bootstrap(env, w, ua, geno, args.replicates, args.steps, n_streams=args.streams)
+        out = run_bootstrap(env, w, ua, geno, args.replicates, args.steps, n_streams=args.streams, dump=dump)
+        if dump:
+            write_outputs(args.dump_outputs, out["outputs"])
         if want_cpu:
             attach_cpu_baseline(out, w, ua, geno, 0, args.cpu_budget, env.local_rank, units=args.replicates, ref_budget_s=args.ref_budget)
         if env.rank == 0:
@@ -955,8 +997,10 @@ def main():
         from multiclust_amd import host
         accel = w["accel"] if args.accel is None else args.accel
         fit = host.Fit(ua, geno, w["K"], device=env.local_rank, admixture=1, accel_scheme=accel, verbosity=1, abs_error=1e-300)
-        out = run_units(env, fit, w, T, args.units, args.steps, args.warmup)
+        out = run_units(env, fit, w, T, args.units, args.steps, args.warmup, full=args.full, dump=dump)
         fit.close()
+        if dump:
+            write_outputs(args.dump_outputs, out["outputs"])
         if want_cpu:
             attach_cpu_baseline(out, w, ua, geno, accel, args.cpu_budget, env.local_rank, units=args.units, ref_budget_s=args.ref_budget)
         if env.rank == 0:
@@ -964,13 +1008,15 @@ def main():
         env.close()
         return
 
-    out, fit, accel = run_single_fit(args, env, name, ua, geno, args.steps, args.warmup)
+    out, fit, accel = run_single_fit(args, env, name, ua, geno, args.steps, args.warmup, dump=dump)
+    if dump:
+        write_outputs(args.dump_outputs, out["outputs"])
     if want_cpu:
         attach_cpu_baseline(out, w, ua, geno, accel, args.cpu_budget, env.local_rank, ref_budget_s=args.ref_budget)
     # the other BASELINE.json configurations on the same line (plain numbers, same measurement rules): configs[3] (c4: 50
     # initialisations sharded) and configs[4] (c5: 200 bootstrap replicates sharded) at every N; configs[1] (c2) and configs[0]
     # (c1, through the STRUCTURE reader) at N = 1
-    if name == "c3" and not args.no_secondary:
+    if name == "c3" and args.full and not args.no_secondary:
         sec = {}
         c4 = run_units(env, fit, WORKLOADS["c4"], T, args.units, args.steps, 0, with_roofline=False)
         sec["c4"] = {k: c4[k] for k in ("value", "ms_per_step", "steps", "config")}

@@ -52,22 +52,22 @@ int main(int argc, char **argv)
 			int K = 3; double *q = calloc((size_t)d.I*K,8), *p = calloc((size_t)K*d.T,8), *s = calloc((size_t)d.I*K,8); int cnt[3];
 			for (int i = 0; i < d.I*K; i++) { q[i] = 1.0/K; s[i] = i % 7; }
 			mc_fit_view fv = {K, 1, -1.0, 2.0, 3.0, q, p, s};
-			o.path = "/tmp/asan"; o.filename_file = "x.stru"; o.em.admixture = 1;
+			o.path = "."; o.filename_file = "x.stru"; o.em.admixture = 1;
 			mc_partition(&d, &fv, NULL, cnt);
 			mc_write_results(&o, &d, &fv, cnt);
 			{	/* -A: a partition file of I labels, the adjusted Rand index against the MAP partition, the failure paths */
 				int *I_K = calloc((size_t)d.I, sizeof *I_K), *lab = NULL, pK = 0;
-				FILE *af = fopen("/tmp/asan/partition.txt", "w");
+				FILE *af = fopen("partition.txt", "w");
 				for (int i = 0; i < d.I; i++) fprintf(af, "%d\n", 1 + i % 4);
 				fclose(af);
 				mc_partition(&d, &fv, I_K, cnt);
-				if (mc_read_afile("/tmp/asan/partition.txt", d.I, &lab, &pK) || pK != 4) { printf("afile failed\n"); return 1; }
+				if (mc_read_afile("partition.txt", d.I, &lab, &pK) || pK != 4) { printf("afile failed\n"); return 1; }
 				const double ar = mc_adjusted_rand(d.I, pK, K, lab, I_K), self = mc_adjusted_rand(d.I, pK, pK, lab, lab);
 				printf("adjusted rand %f, of a partition with itself %f\n", ar, self);
 				if (!(self > 0.999999 && self < 1.000001)) return 1;
 				free(lab);
-				if (mc_read_afile("/tmp/asan/partition.txt", d.I + 1, &lab, &pK) != MC_EXIT_FILE_FORMAT_ERROR || lab) return 1;
-				if (mc_read_afile("/tmp/asan/absent.txt", d.I, &lab, &pK) != MC_EXIT_FILE_OPEN_ERROR || lab) return 1;
+				if (mc_read_afile("partition.txt", d.I + 1, &lab, &pK) != MC_EXIT_FILE_FORMAT_ERROR || lab) return 1;
+				if (mc_read_afile("absent.txt", d.I, &lab, &pK) != MC_EXIT_FILE_OPEN_ERROR || lab) return 1;
 				free(I_K);
 				mc_watchdog_report(stdout, 0.0);	/* the report a stalled run would leave */
 			}

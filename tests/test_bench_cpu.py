@@ -89,3 +89,18 @@ def test_traffic_figure_is_tied_to_the_build_it_was_taken_from():
     newest = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_c3_traffic.json")))[-1]
     if os.path.basename(newest) >= "r04":
         assert "library_sha256" in json.load(open(newest))["_build"]
+
+
+def test_dumped_outputs_are_float64_and_bounded(tmp_path):
+    """bench.write_outputs (--dump-outputs): every array as <name>.npy in float64; more than 64 MB in all is refused before
+    anything is written"""
+    import numpy as np
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    bench.write_outputs(str(tmp_path / "d"), {"q": np.arange(6, dtype=np.float32).reshape(2, 3), "n_iter": [1, 2]})
+    q, n = np.load(str(tmp_path / "d" / "q.npy")), np.load(str(tmp_path / "d" / "n_iter.npy"))
+    assert q.dtype == np.float64 and q.shape == (2, 3) and q[1, 2] == 5.0 and n.dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "e"), {"big": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "e").exists()

@@ -136,7 +136,7 @@ def test_cpu_baseline_legs_on_small_workloads(workload, extra):
     """`cpu_baseline` leads with the reference's own em() (oracle/_ref/ref_time, kind "reference") where that binary is in the
     tree, the oracle ("port") under it; both carry the HIP path's distance from them on their own sample, inside BASELINE.json's
     tolerances."""
-    out = run_bench(["--workload", workload, "--steps", "4", "--warmup", "1", "--settle", "0", "--stability", "0", "--no-secondary",
+    out = run_bench(["--workload", workload, "--full", "--steps", "4", "--warmup", "1", "--settle", "0", "--stability", "0", "--no-secondary",
                      "--cpu-budget", "0.5", "--ref-budget", "0.5"] + extra, {})
     cb = out["cpu_baseline"]
     have_ref = os.access(os.path.join(ROOT, "oracle", "_ref", "ref_time"), os.X_OK)
@@ -158,9 +158,46 @@ def test_cpu_baseline_legs_on_small_workloads(workload, extra):
 def test_a_reference_binary_that_does_not_run_costs_the_line_nothing():
     """oracle/_ref/ref_time is built in one container and run in another: if it cannot run there, cpu_baseline falls back to
     the oracle and says why; the result line is still printed."""
-    out = run_bench(["--workload", "c1", "--steps", "4", "--warmup", "1", "--settle", "0", "--stability", "0", "--no-secondary",
+    out = run_bench(["--workload", "c1", "--full", "--steps", "4", "--warmup", "1", "--settle", "0", "--stability", "0", "--no-secondary",
                      "--cpu-budget", "0.3", "--ref-budget", "0.3"], {"MC_BENCH_REF_TIME": "/bin/false"})
     cb = out["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and "the reference leg failed" in cb["reference"]
     assert out["value"] > 0
 
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A run without --full carries the headline alone (`roofline`, `stability`, `cpu_baseline` and `secondary` are --full's);
+    --dump-outputs writes the timed fit's q, p and logL after its last step in float64, and a second run with the same
+    arguments writes the same bits (the inputs depend on the arguments only)."""
+    args = ["--workload", "c1", "--steps", "6", "--warmup", "1", "--settle", "0"]
+    a = run_bench(args + ["--dump-outputs", str(tmp_path / "a")], {})
+    b = run_bench(args + ["--dump-outputs", str(tmp_path / "b")], {})
+    for key in ("roofline", "stability", "cpu_baseline", "secondary"):
+        assert key not in a, key
+    assert a["steps"] == 6 and a["ms_per_step"] > 0 and a["value"] > 0
+    cfg = a["config"]
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("q", "p", "logL")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["q"].shape == (cfg["I"], cfg["K"]) and got["p"].shape == (cfg["K"], cfg["T"]) and got["logL"].shape == (1,)
+    np.testing.assert_allclose(got["q"].sum(axis=1), 1.0, rtol=1e-12)
+    for n, v in got.items():
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / (n + ".npy")))), n
+    # the dump is the iterate the timed steps ended on: the same data set (generated in a child process, as bench.py does:
+    # torch stays out of this one), the same initialisation and warm-up + timed EM steps one by one through the host driver
+    # (bitwise the batched loop's: test_gpu_host_driver.py::test_batched_em_equals_step_by_step)
+    import bench
+    from multiclust_amd import host
+    w, data = bench.WORKLOADS["c1"], str(tmp_path / "c1.npz")
+    gen = ("import sys, numpy as np, torch; sys.path.insert(0, %r); import bench; w = bench.WORKLOADS['c1']; "
+           "ua, geno = bench.gen_dataset(w['I'], w['L'], w['K'], w['ploidy'], w['maxal'], 20250117 + w['dseed'], torch.device('cuda', 0)); "
+           "np.savez(%r, ua=ua, geno=geno)" % (ROOT, data))
+    subprocess.run([sys.executable, "-c", gen], check=True, timeout=300)
+    d = np.load(data)
+    fit = host.Fit(d["ua"], d["geno"], w["K"], admixture=1, accel_scheme=0, verbosity=1, abs_error=1e-300)
+    fit.initialize(bench.SEED)
+    for _ in range(1 + 6):
+        assert not fit.em_step() and not fit.mod.fatal
+    assert np.array_equal(fit.get_q(fit.mod.pindex), got["q"]) and np.array_equal(fit.get_p(fit.mod.pindex), got["p"])
+    assert fit.mod.logL == got["logL"][0] == cfg["best_logL"]
+    fit.close()

@@ -22,8 +22,7 @@ def test_host_c_code_is_sanitizer_clean(tmp_path):
     for fn, p in (("multi.stru", 2), ("missing.stru", 2), ("tetra.stru", 4), ("multi_interleaved.stru", 2),
                   ("c1_tiny.stru", 2), ("multi.stru", 3), ("missing99.stru", 2)):
         args += [os.path.join(data, fn), str(p)]
-    os.makedirs("/tmp/asan", exist_ok=True)
-    res = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+    res = subprocess.run([exe] + args, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
     assert res.returncode == 0, res.stderr[-2000:]
     assert "ok 1" in res.stdout and "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
