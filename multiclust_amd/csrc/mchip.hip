@@ -368,9 +368,13 @@ __global__ __launch_bounds__(256) void k_draw_partition(rng_window base, const u
 /* parametric_bootstrap_admixture (bootstrap.c:84-124) on the device.  Allele copy j (i, l, n order) takes draws 2j
  * (source cluster: inverse-CDF walk over the individual's eta) and 2j+1 (allele: walk over p[k][l][.]) of the rand()
  * stream, r = rand() / RAND_MAX in double.  The reference's walk `while (k < K && r > sum) sum += eta[k++]; if (k) k--;`
- * stops at the largest k whose left-to-right partial sum c_k = eta[0] + ... + eta[k-1] lies below r (partial sums of
- * non-negative terms never decrease), and r > c_k is a statement about the integer the generator returned: v / RAND_MAX,
- * rounded, never decreases in v, so r > c_k  <=>  v >= V(c_k) with V(c) the smallest v whose quotient exceeds c.
+ * stops at the first t with !(r > c_t), c_t = eta[0] + ... + eta[t-1] the left-to-right partial sum (t = K if there is none),
+ * and returns t - 1 (0 for t = 0).  r > c is a statement about the integer the generator returned: v / RAND_MAX, rounded,
+ * never decreases in v, so r > c  <=>  v >= V(c) with V(c) the smallest v whose quotient exceeds c.  Fitted parameters
+ * need not be non-negative (no projection: entries below 0; an individual with no observed copy: NaN), so the partial
+ * sums need not rise; the first t with r <= c_t is also the first t with r <= max(c_0, ..., c_t), and a NaN sum stops the
+ * walk there and at every later t.  The thresholds are therefore taken of the running maximum, and 2^31 (no draw reaches
+ * it) from the first NaN sum on: they never decrease, and t - 1 is the number of thresholds t_1 .. t_{K-1} the draw reaches.
  * k_walk_tables finds every V once per call -- with the same double additions and the same division the reference executes
  * per copy -- and the per-copy work is integer compares against those thresholds: no running sums, no divisions, and none
  * of a copy's loads waits for another.  Every copy is simulated (in the default build the "missing stays missing" count is
@@ -391,7 +395,15 @@ __device__ uint32_t walk_threshold(double c)
 }
 
 /* thq[i][j] = V(q[i][0] + ... + q[i][j-1]) (j < K; rows of SIM_QW padded with 2^31 when fast); thp[k][c0 + m] =
- * V(p[k][c0] + ... + p[k][c0 + m - 1]), or rows of SIM_PW per (k, l), padded, when fast */
+ * V(p[k][c0] + ... + p[k][c0 + m - 1]), or rows of SIM_PW per (k, l), padded, when fast; V of the running maximum of the
+ * partial sums, and 2^31 from the first NaN sum on (see above) */
+__device__ __forceinline__ uint32_t walk_step(double sum, double &peak, bool &nan_seen)
+{
+	nan_seen = nan_seen || sum != sum;
+	if (sum > peak) peak = sum;
+	return nan_seen ? 0x80000000u : walk_threshold(peak);
+}
+
 __global__ void k_walk_tables(int n_qrows, int K, int L, int T, const int32_t *__restrict__ toff, const double *__restrict__ q,
 			      const double *__restrict__ p, int fast, uint32_t *thq, uint32_t *thp)
 {
@@ -399,8 +411,9 @@ __global__ void k_walk_tables(int n_qrows, int K, int L, int T, const int32_t *_
 	if (idx < (size_t)n_qrows) {
 		const double *src = q + idx * K;
 		uint32_t *dst = thq + idx * (size_t)(fast ? SIM_QW : K);
-		double sum = 0.0;
-		for (int j = 0; j < K; j++) { dst[j] = walk_threshold(sum); sum += src[j]; }
+		double sum = 0.0, peak = 0.0;
+		bool nan_seen = false;
+		for (int j = 0; j < K; j++) { dst[j] = walk_step(sum, peak, nan_seen); sum += src[j]; }
 		if (fast) for (int j = K; j < SIM_QW; j++) dst[j] = 0x80000000u;
 	}
 	if (idx < (size_t)K * L) {
@@ -408,13 +421,15 @@ __global__ void k_walk_tables(int n_qrows, int K, int L, int T, const int32_t *_
 		const int c0 = toff[l], M = toff[l + 1] - c0;
 		const double *src = p + (size_t)k * T + c0;
 		uint32_t *dst = fast ? thp + idx * SIM_PW : thp + (size_t)k * T + c0;
-		double sum = 0.0;
-		for (int m = 0; m < M; m++) { dst[m] = walk_threshold(sum); sum += src[m]; }
+		double sum = 0.0, peak = 0.0;
+		bool nan_seen = false;
+		for (int m = 0; m < M; m++) { dst[m] = walk_step(sum, peak, nan_seen); sum += src[m]; }
 		if (fast) for (int m = M; m < SIM_PW; m++) dst[m] = 0x80000000u;
 	}
 }
 
-/* largest j in [0, n) with v >= tab[j], 0 if there is none (tab never decreases) */
+/* largest j in [0, n) with v >= tab[j], 0 if there is none; tab never decreases (k_walk_tables: thresholds of the running
+ * maximum of the partial sums), so that is the count of tab[1 .. n-1] that v reaches */
 __device__ __forceinline__ int walk_search(const uint32_t *__restrict__ tab, int n, uint32_t v)
 {
 	int lo = 0;

@@ -18,9 +18,17 @@
  * usage: ref_time <dir> <I> <L> <ploidy> <K> <max_iter> -- <multiclust argv: -f x [-a [-c]] -k K [-s n]>
  *   <dir>/ua.i32 [L], geno.u8 [I][L][ploidy] (allele index), q0.f64 [I][K] ([K] with -c and for the mixture model), p0.f64 [K][T]
  * writes <dir>/q_ref.f64, p_ref.f64 (final iterate) and prints one JSON line.
+ *
+ * Bootstrap mode (tests only): ref_time --bootstrap <dir> <I> <L> <ploidy> <K> <seed | -> -- <multiclust argv>
+ *   the *unmodified* parametric_bootstrap() (bootstrap.c:31-175) on the same data, from the H0 parameters q_mle.f64 (shaped as
+ *   q0.f64) and p_mle.f64 [K][T], with rand() either seeded by srand(seed) or, for "-", standing on the 31-word window
+ *   window.u32 (the words behind the next draw, oldest first: the form mchip_simulate_genotypes takes).  Writes <dir>/bs_ilm.u8
+ *   [I][T] (the simulated allele counts, as the golden fixtures hold them) and prints the next rand().
  */
 #define _POSIX_C_SOURCE 200809L
+#define _XOPEN_SOURCE 700		/* initstate / setstate */
 #include "multiclust.h"
+#include <errno.h>
 #include <stdint.h>
 #include <time.h>
 
@@ -52,21 +60,87 @@ static double now(void)
 	return ts.tv_sec + 1e-9 * ts.tv_nsec;
 }
 
+/* libc's own rand() stood on a 31-word window w (oldest first).  glibc's TYPE_3 state is a header word 5 * rear + 3 followed by
+ * 31 words; rand() adds the word at rear to the word at front = rear + 3 (mod 31), which is the oldest.  The state in force is
+ * first moved to a buffer of its own, because setstate() writes the old state's header into the old buffer. */
+static void rand_from_window(const uint32_t *w)
+{
+	static int32_t dummy[32], state[32];
+	initstate(1, (char *)dummy, sizeof dummy);
+	const int rear = 0;
+	state[0] = 5 * rear + 3;
+	for (int t = 0; t < 31; t++) state[1 + (rear + 3 + t) % 31] = (int32_t)w[t];
+	setstate((char *)state);
+}
+
+/* bootstrap mode: the fitted H0 parameters go where run_bootstrap's fit leaves them (multiclust.c:561-580; the aliases of
+ * ref_harness.c section 6), then parametric_bootstrap() and cleanup_parametric_bootstrap() as the reference calls them */
+static int bootstrap(options *opt, data *dat, model *mod, const char *dir, const char *seed, size_t T)
+{
+	const int I = dat->I, L = dat->L, K = mod->K;
+	const int shared_eta = !opt->admixture || opt->eta_constrained;
+	double *q = slurp(dir, "q_mle.f64", (shared_eta ? (size_t)K : (size_t)I * K) * sizeof(double));
+	double *p = slurp(dir, "p_mle.f64", (size_t)K * T * sizeof(double));
+	mod->mle_pKLM = malloc(K * sizeof *mod->mle_pKLM);
+	double **prow = malloc((size_t)K * L * sizeof *prow);
+	double **qrow = malloc((size_t)I * sizeof *qrow);
+	if (!mod->mle_pKLM || !prow || !qrow) die("out of memory");
+	for (int k = 0; k < K; k++) {
+		mod->mle_pKLM[k] = prow + (size_t)k * L;
+		size_t t = 0;
+		for (int l = 0; l < L; t += dat->uniquealleles[l], l++) mod->mle_pKLM[k][l] = p + (size_t)k * T + t;
+	}
+	if (shared_eta) {
+		mod->mle_etak = q;
+	} else {
+		for (int i = 0; i < I; i++) qrow[i] = q + (size_t)i * K;
+		mod->mle_etaik = qrow;
+	}
+	if (!strcmp(seed, "-")) {
+		uint32_t *w = slurp(dir, "window.u32", 31 * sizeof(uint32_t));
+		rand_from_window(w);
+		free(w);
+	} else {
+		srand((unsigned)strtoul(seed, NULL, 10));
+	}
+	if (parametric_bootstrap(opt, dat, mod)) die("parametric_bootstrap failed");
+	const int next = rand();
+	char path[4096];
+	snprintf(path, sizeof path, "%s/bs_ilm.u8", dir);
+	FILE *f = fopen(path, "wb");
+	if (!f) die("cannot write bs_ilm.u8");
+	for (int i = 0; i < I; i++)
+		for (int l = 0; l < L; l++)
+			for (int m = 0; m < dat->uniquealleles[l]; m++) {
+				if (dat->ILM[i][l][m] < 0 || dat->ILM[i][l][m] > 255) die("bootstrap count out of range");
+				fputc(dat->ILM[i][l][m], f);
+			}
+	fclose(f);
+	cleanup_parametric_bootstrap(dat);
+	printf("%d\n", next);
+	return 0;
+}
+
 int main(int argc, const char **argv)
 {
 	options *opt = NULL;
 	data *dat = NULL;
 	model *mod = NULL;
 	int sep = -1;
+	const int boot = argc > 1 && !strcmp(argv[1], "--bootstrap");
 
+	if (boot) { argc--; argv++; }
 	for (int i = 1; i < argc; i++)
 		if (!strcmp(argv[i], "--")) { sep = i; break; }
-	if (sep != 7) die("usage: ref_time <dir> <I> <L> <ploidy> <K> <max_iter> -- <args>");
+	if (sep != 7) die("usage: ref_time [--bootstrap] <dir> <I> <L> <ploidy> <K> <max_iter | seed | -> -- <args>");
 	const char *dir = argv[1];
-	int I = atoi(argv[2]), L = atoi(argv[3]), ploidy = atoi(argv[4]), K = atoi(argv[5]), max_iter = atoi(argv[6]);
+	int I = atoi(argv[2]), L = atoi(argv[3]), ploidy = atoi(argv[4]), K = atoi(argv[5]), max_iter = boot ? 1 : atoi(argv[6]);
 	if (I < 1 || L < 1 || ploidy < 1 || K < 1 || max_iter < 1) die("bad dimensions");
 
 	if (make_options(&opt) || make_data(&dat) || make_model(&mod)) die("make_* failed");
+	/* the reference's parser reads errno after strtol()/strtod() without clearing it first (cline.c:76-77, multiclust.c:1538):
+	 * a value some library left there while the process started would turn "-k 4" into a usage error */
+	errno = 0;
 	if (parse_options(opt, dat, argc - sep, argv + sep)) die("parse_options failed");
 	opt->write_files = 0;
 	opt->verbosity = 1;		/* QUIET */
@@ -115,6 +189,7 @@ int main(int argc, const char **argv)
 
 	if (synchronize(opt, dat, mod)) die("synchronize failed");
 	mod->K = K;
+	if (boot) return bootstrap(opt, dat, mod, dir, argv[6], T);
 	dat->max_M = dat->M > mod->K ? dat->M : mod->K;
 	if (allocate_model_for_k(opt, mod, dat)) die("allocate_model_for_k failed");
 	double t_alloc = now() - t0;

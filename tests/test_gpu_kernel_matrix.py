@@ -159,7 +159,7 @@ def geometry(K, I, L, T, ploidy, max_M, admixture, cbits, knobs, n_cu=N_CU):
     lchunk = cdiv(lblocks, want) * 8
     n_lchunks = cdiv(L, lchunk)
     xcd_rows = coop and cdiv(n_lchunks, waves) % 8 == 0
-    return dict(n_ichunks=n_ichunks, n_lchunks=n_lchunks, sparse=sparse, coop=coop, waves=waves, xcd_rows=xcd_rows)
+    return dict(n_ichunks=n_ichunks, lchunk=lchunk, n_lchunks=n_lchunks, sparse=sparse, coop=coop, waves=waves, xcd_rows=xcd_rows)
 
 
 def bial_pays(K, accum):     # launch_sparse (mchip_kernels_k.hip): SPLIT == 1 && (ACCUM ? K >= 10 : K >= 6)
