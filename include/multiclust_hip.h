@@ -85,6 +85,19 @@ int mchip_get_genotypes(mchip_context *ctx, uint8_t *geno);
 int mchip_simulate_genotypes(mchip_context *ctx, int I, int L, int ploidy, const int32_t *uniquealleles,
 			     const uint32_t *window, int K, int eta_constrained, const double *q, const double *p);
 /*
+ * The mixture model's generator: parametric_bootstrap_mixture (bootstrap.c:132-175).  Individual i owns draws
+ * i * (1 + L*ploidy) ... (i + 1) * (1 + L*ploidy) - 1 of the stream described by `window`: the first chooses its cluster k by the
+ * walk over eta[0..K), draw 1 + l*ploidy + a chooses copy (l, a) by the walk over p[k][l][.].  Consumes I + I*L*ploidy draws;
+ * every copy is simulated.  eta is [K], p is [K][T].  In everything else the contract of mchip_simulate_genotypes: drops the
+ * model, re-uses the buffers of a same-shaped previous replicate, leaves mchip_set_init_genotypes in force, accepts every shape
+ * mchip_set_genotypes accepts and parameters that are negative, do not sum to 1 or are NaN (the same integer thresholds).
+ * Loci with at most 4 alleles and ploidy <= 8 are generated tile by tile straight into the device layouts at any K; other
+ * shapes (and MCHIP_SIM_NO_TILE) take the general form through the upload order.
+ * One limit of its own: K <= 256 (the cluster of an individual is kept as a byte), else MCHIP_ERR_INVALID; a model takes K <= 64.
+ */
+int mchip_simulate_genotypes_mixture(mchip_context *ctx, int I, int L, int ploidy, const int32_t *uniquealleles,
+				     const uint32_t *window, int K, const double *eta /* [K] */, const double *p /* [K][T] */);
+/*
  * The data set `src` holds, copied into `ctx` on the device (both contexts on one device).  run_bootstrap fits the null and the
  * alternative model to the SAME simulated data set (multiclust.c:675-708: one parametric_bootstrap(), then estimate_model()
  * over both K): the second model's context takes the first one's instead of generating it again.  Like
@@ -210,6 +223,18 @@ int mchip_mstep_from_rand_partition(mchip_context *ctx, const uint32_t *window, 
  */
 int mchip_init_from_allele_centers(mchip_context *ctx, const uint8_t *centers, const uint64_t *draw_offset, const uint32_t *window,
 				   uint64_t n_draws, int to);
+/*
+ * The mixture model's initialisation from K center individuals the host drew: random_individual_center +
+ * initialize_parameters_mixture (rnd_init.c:192-339) into slot `to`.
+ * centers[K]: distinct individuals in [0, I) (else MCHIP_ERR_INVALID).  A center k joins cluster k; every other individual joins
+ * the first center of minimal L1 distance between the allele-count vectors (observed copies only); K = 1: cluster 0.  Then
+ * eta[k] = (1 + n_k) / (I + K) and, per (k, l), p = e / sum_m e with e = 1 + (K - k) * (copies of allele m in cluster k) -- the
+ * reference's quirk included.  Distances and counts are integers and the divisions are IEEE divisions of the operands the host
+ * form divides: the parameters have the host form's bits.  Works on the data set the context holds (the simulated one while
+ * bootstrapping: the mixture initialisation reads dat->ILM, not the observed haplotypes -- init genotypes are NOT used here).
+ * assign_out: NULL, or I int32 receiving the assignment.  Needs a mixture model (admixture = 0), else MCHIP_ERR_STATE.
+ */
+int mchip_init_from_individual_centers(mchip_context *ctx, const int32_t *centers, int to, int32_t *assign_out);
 /* parameters of slot `from` copied to slot `to`: Rand-EM keeps its best candidate (rnd_init.c:431-436 keeps the partition) */
 int mchip_copy_slot(mchip_context *ctx, int to, int from);
 

@@ -99,6 +99,11 @@ struct mchip_context {
 	struct lattice { uint32_t *d_i, *d_r; uint64_t A, B; unsigned nA, nB; } lat[2];
 	uint32_t *d_part_slabs;		/* tiled random partition: packed 16-bit N-side counts per block of 256 individuals */
 	size_t part_slab_bytes;
+	/* mixture model on generated data: the cluster of every individual of the data set (mchip_simulate_genotypes_mixture), and the
+	 * workspaces of mchip_init_from_individual_centers (partial distances [chunk][K][I]; counts [T][K], n_k, centers, assignment) */
+	uint8_t *d_sim_cluster;
+	uint32_t *d_cen_part, *d_cen_work;
+	size_t cen_part_bytes, cen_work_bytes;
 	/* model */
 	int K, admixture, constrained, do_projection, nsec, nq, qstride;
 	double eta_lb, p_lb;
@@ -394,9 +399,10 @@ __device__ uint32_t walk_threshold(double c)
 	return v;
 }
 
-/* thq[i][j] = V(q[i][0] + ... + q[i][j-1]) (j < K; rows of SIM_QW padded with 2^31 when fast); thp[k][c0 + m] =
- * V(p[k][c0] + ... + p[k][c0 + m - 1]), or rows of SIM_PW per (k, l), padded, when fast; V of the running maximum of the
- * partial sums, and 2^31 from the first NaN sum on (see above) */
+/* thq[i][j] = V(q[i][0] + ... + q[i][j-1]) (j < K; rows of SIM_QW padded with 2^31 when fast_q); thp[k][c0 + m] =
+ * V(p[k][c0] + ... + p[k][c0 + m - 1]), or rows of SIM_PW per (k, l), padded, when fast_p; V of the running maximum of the
+ * partial sums, and 2^31 from the first NaN sum on (see above).  The admixture generator sets both flags together (K <= 8 and
+ * at most 4 alleles); the mixture generator walks one shared row of any K unpadded and pads the allele rows alone. */
 __device__ __forceinline__ uint32_t walk_step(double sum, double &peak, bool &nan_seen)
 {
 	nan_seen = nan_seen || sum != sum;
@@ -405,26 +411,26 @@ __device__ __forceinline__ uint32_t walk_step(double sum, double &peak, bool &na
 }
 
 __global__ void k_walk_tables(int n_qrows, int K, int L, int T, const int32_t *__restrict__ toff, const double *__restrict__ q,
-			      const double *__restrict__ p, int fast, uint32_t *thq, uint32_t *thp)
+			      const double *__restrict__ p, int fast_q, int fast_p, uint32_t *thq, uint32_t *thp)
 {
 	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (idx < (size_t)n_qrows) {
 		const double *src = q + idx * K;
-		uint32_t *dst = thq + idx * (size_t)(fast ? SIM_QW : K);
+		uint32_t *dst = thq + idx * (size_t)(fast_q ? SIM_QW : K);
 		double sum = 0.0, peak = 0.0;
 		bool nan_seen = false;
 		for (int j = 0; j < K; j++) { dst[j] = walk_step(sum, peak, nan_seen); sum += src[j]; }
-		if (fast) for (int j = K; j < SIM_QW; j++) dst[j] = 0x80000000u;
+		if (fast_q) for (int j = K; j < SIM_QW; j++) dst[j] = 0x80000000u;
 	}
 	if (idx < (size_t)K * L) {
 		const int l = (int)(idx % L), k = (int)(idx / L);
 		const int c0 = toff[l], M = toff[l + 1] - c0;
 		const double *src = p + (size_t)k * T + c0;
-		uint32_t *dst = fast ? thp + idx * SIM_PW : thp + (size_t)k * T + c0;
+		uint32_t *dst = fast_p ? thp + idx * SIM_PW : thp + (size_t)k * T + c0;
 		double sum = 0.0, peak = 0.0;
 		bool nan_seen = false;
 		for (int m = 0; m < M; m++) { dst[m] = walk_step(sum, peak, nan_seen); sum += src[m]; }
-		if (fast) for (int m = M; m < SIM_PW; m++) dst[m] = 0x80000000u;
+		if (fast_p) for (int m = M; m < SIM_PW; m++) dst[m] = 0x80000000u;
 	}
 }
 
@@ -644,6 +650,150 @@ static void launch_simulate_tile(mchip_context *ctx, const rng_window &base, int
 			   tile, thq, per_individual, thp, ctx->d_gtA, ctx->d_gtS);
 }
 
+/* parametric_bootstrap_mixture (bootstrap.c:132-175) on the device.  Individual i owns draws i * (1 + L*PL) .. of the rand()
+ * stream: the first chooses its cluster by the walk over eta, draw 1 + l*PL + a chooses copy (l, a) by the walk over
+ * p[k][l][.]; the decisions are the integer compares against k_walk_tables' thresholds described above.
+ * k_simulate_mixture_source: thread = individual, its window taken at the individual's first draw (jump_i[i]; jump_r[0] = x^0),
+ * one draw, one search of the shared row thq[0..K), the cluster stored as a byte. */
+__global__ __launch_bounds__(256) void k_simulate_mixture_source(rng_window base, const uint32_t *__restrict__ jump_i,
+		const uint32_t *__restrict__ jump_r, int I, int K, const uint32_t *__restrict__ thq, uint8_t *__restrict__ cluster)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= I) return;
+	uint32_t w[RNG_LAG];
+	rng_window_at(base, jump_r, jump_i, (size_t)I, (size_t)i, w);
+	const uint32_t v = (w[0] + w[RNG_LAG - 3]) >> 1;	/* rand(): x_{j-31} + x_{j-3} */
+	cluster[i] = (uint8_t)walk_search(thq, K, v);
+}
+
+/* The copies, tile by tile (at most 4 alleles per locus, ploidy <= 8; any K: the cluster is fixed per thread): the geometry of
+ * k_simulate_tile with one draw per copy.  `base` stands one draw into the stream, so that jump_i[i] * jump_r[blockIdx.x] =
+ * x^(i * (1 + L*PL) + l0 * PL) lands on the thread's first copy draw of the tile.  Allele thresholds of the tile's loci in LDS
+ * ([locus][k][3]), copies straight into gtA and gtS, MISSING in the rows that pad the last block of 8 individuals. */
+template <int PL>
+__global__ __launch_bounds__(256) void k_simulate_mixture_tile(rng_window base, const uint32_t *__restrict__ jump_i,
+		const uint32_t *__restrict__ jump_r, int I, int L, int K, int tile_loci, const uint8_t *__restrict__ cluster,
+		const uint32_t *__restrict__ thp, uint8_t *__restrict__ gtA, uint8_t *__restrict__ gtS)
+{
+	extern __shared__ uint32_t sim_lds[];
+	uint32_t *ring = sim_lds, *tile = sim_lds + RNG_LAG * 256;
+	const int l0 = blockIdx.x * tile_loci;
+	const int nl = L - l0 < tile_loci ? L - l0 : tile_loci;
+	const int i = blockIdx.y * 256 + threadIdx.x;
+	for (int idx = threadIdx.x; idx < K * nl; idx += 256) {
+		const int k = idx / nl, ll = idx - k * nl;
+		const uint4 t = *reinterpret_cast<const uint4 *>(thp + ((size_t)k * L + l0 + ll) * SIM_PW);
+		uint32_t *dst = tile + ((size_t)ll * K + k) * 3;
+		dst[0] = t.y; dst[1] = t.z; dst[2] = t.w;	/* t.x = V(0): allele 0 either way */
+	}
+	__syncthreads();
+	if (i >= ((I + 7) & ~7)) return;
+	uint8_t *colA = gtA + ((((size_t)(i >> 3) * L + l0) * 8) + (i & 7)) * PL;	/* + ll * 8 * PL per locus */
+	if (i >= I) {		/* rows that pad the last block of 8 individuals */
+		for (int ll = 0; ll < nl; ll++)
+#pragma unroll
+			for (int a = 0; a < PL; a++) colA[(size_t)ll * 8 * PL + a] = MCHIP_MISSING;
+		return;
+	}
+	{
+		uint32_t w[RNG_LAG];
+		rng_window_at(base, jump_r + (size_t)blockIdx.x * RNG_LAG, jump_i, (size_t)I, (size_t)i, w);
+#pragma unroll
+		for (int e = 0; e < RNG_LAG; e++) ring[e * 256 + threadIdx.x] = w[e];
+	}
+	int e = 0;
+	auto next = [&]() -> uint32_t {
+		const int e3 = e >= 3 ? e - 3 : e + RNG_LAG - 3;
+		const uint32_t x = ring[e * 256 + threadIdx.x] + ring[e3 * 256 + threadIdx.x];	/* x_{j-31} + x_{j-3} */
+		ring[e * 256 + threadIdx.x] = x;
+		e = e + 1 == RNG_LAG ? 0 : e + 1;
+		return x >> 1;		/* rand() */
+	};
+	const uint32_t *mine = tile + (size_t)cluster[i] * 3;	/* + ll * K * 3 per locus */
+	for (int g = 0; g * 8 < nl; g++) {
+		unsigned long long run[PL];	/* the 8 * PL bytes of this individual's gtS group */
+#pragma unroll
+		for (int x = 0; x < PL; x++) run[x] = ~0ull;
+#pragma unroll
+		for (int t = 0; t < 8; t++) {
+			const int ll = g * 8 + t;
+			if (ll < nl) {		/* uniform */
+				const uint32_t *th = mine + (size_t)ll * K * 3;
+				const uint32_t t1 = th[0], t2 = th[1], t3 = th[2];
+				unsigned long long bytes = 0;
+#pragma unroll
+				for (int a = 0; a < PL; a++) {
+					const uint32_t v = next();
+					const unsigned m = (v >= t1) + (v >= t2) + (v >= t3);
+					bytes |= (unsigned long long)m << (8 * a);
+				}
+				uint8_t *dst = colA + (size_t)ll * 8 * PL;
+				if (PL == 4) *reinterpret_cast<uint32_t *>(dst) = (uint32_t)bytes;
+				else if (PL == 2) *reinterpret_cast<uint16_t *>(dst) = (uint16_t)bytes;
+				else if (PL == 8) *reinterpret_cast<unsigned long long *>(dst) = bytes;
+				else {
+#pragma unroll
+					for (int a = 0; a < PL; a++) dst[a] = (uint8_t)(bytes >> (8 * a));
+				}
+#pragma unroll
+				for (int a = 0; a < PL; a++) {
+					constexpr unsigned long long ff = 0xFFull;
+					const int b = t * PL + a;
+					run[b >> 3] = (run[b >> 3] & ~(ff << (8 * (b & 7)))) | (((bytes >> (8 * a)) & ff) << (8 * (b & 7)));
+				}
+			}
+		}
+		unsigned long long *dstS = reinterpret_cast<unsigned long long *>(gtS + (((size_t)(l0 / 8 + g) * I + i) * 8) * PL);
+#pragma unroll
+		for (int x = 0; x < PL; x++) dstS[x] = run[x];
+	}
+}
+
+template <int PL>
+static void launch_simulate_mixture_tile(mchip_context *ctx, const rng_window &base, int K, int tile, const uint32_t *thp)
+{
+	const unsigned R = (unsigned)((ctx->L + tile - 1) / tile), by = (unsigned)((((ctx->I + 7) & ~7) + 255) / 256);
+	const size_t lds = ((size_t)RNG_LAG * 256 + (size_t)tile * K * 3) * sizeof(uint32_t);
+	hipLaunchKernelGGL(k_simulate_mixture_tile<PL>, dim3(R, by), dim3(256), lds, ctx->stream, base, ctx->lat[0].d_i, ctx->lat[0].d_r, ctx->I,
+			   ctx->L, K, tile, ctx->d_sim_cluster, thp, ctx->d_gtA, ctx->d_gtS);
+}
+
+/* The general form (more than 4 alleles at some locus, ploidy > 8, MCHIP_SIM_NO_TILE): the same lattice -- workgroup = 256
+ * individuals x a chunk of `chunk_loci` loci, thread = individual, `base` one draw into the stream -- with the thresholds read
+ * from global memory through walk_search (rows [k][T], or the padded [k][l][SIM_PW] rows when no locus has more than 4 alleles)
+ * and the copies stored in raw [I][L][pl] order for install_raw. */
+__global__ __launch_bounds__(256) void k_simulate_mixture_general(rng_window base, const uint32_t *__restrict__ jump_i,
+		const uint32_t *__restrict__ jump_r, int I, int L, int pl, int T, int chunk_loci, const int32_t *__restrict__ toff,
+		const uint8_t *__restrict__ cluster, const uint32_t *__restrict__ thp, int fast_p, uint8_t *__restrict__ raw)
+{
+	__shared__ uint32_t ring[RNG_LAG * 256];
+	const int i = blockIdx.y * 256 + threadIdx.x;
+	if (i >= I) return;
+	const int l0 = blockIdx.x * chunk_loci;
+	const int l1 = L - l0 < chunk_loci ? L : l0 + chunk_loci;
+	{
+		uint32_t w[RNG_LAG];
+		rng_window_at(base, jump_r + (size_t)blockIdx.x * RNG_LAG, jump_i, (size_t)I, (size_t)i, w);
+#pragma unroll
+		for (int e = 0; e < RNG_LAG; e++) ring[e * 256 + threadIdx.x] = w[e];
+	}
+	int e = 0;
+	auto next = [&]() -> uint32_t {
+		const int e3 = e >= 3 ? e - 3 : e + RNG_LAG - 3;
+		const uint32_t x = ring[e * 256 + threadIdx.x] + ring[e3 * 256 + threadIdx.x];	/* x_{j-31} + x_{j-3} */
+		ring[e * 256 + threadIdx.x] = x;
+		e = e + 1 == RNG_LAG ? 0 : e + 1;
+		return x >> 1;		/* rand() */
+	};
+	const int k = cluster[i];
+	uint8_t *dst = raw + ((size_t)i * L + l0) * pl;
+	for (int l = l0; l < l1; l++) {
+		const int c0 = toff[l], M = toff[l + 1] - c0;
+		const uint32_t *tab = fast_p ? thp + ((size_t)k * L + l) * SIM_PW : thp + (size_t)k * T + c0;
+		for (int a = 0; a < pl; a++) *dst++ = (uint8_t)walk_search(tab, M, next());
+	}
+}
+
 /* random_allele_partition + the counts of the first M step (rnd_init.c:349-357,456-482) in one pass, nothing stored per copy.
  * Workgroup = 256 individuals x one locus chunk of the S-side pass (blockIdx.x; its loci taken `tile` at a time); thread =
  * individual i: copy (i, l, b) takes draw i*L*PL + l*PL + b of the stream, so the thread's draws for the chunk are consecutive
@@ -754,6 +904,197 @@ static void launch_partition_tile(mchip_context *ctx, const rng_window &base, ui
 	hipLaunchKernelGGL(k_partition_tile<PL>, dim3((unsigned)ctx->n_lchunks, by), dim3(256), lds, ctx->stream, base, ctx->lat[1].d_i,
 			   ctx->lat[1].d_r, ctx->I, ctx->L, ctx->K, magic, shift, ctx->lchunk, tile, ctx->d_toff, gtS, ctx->d_part_slabs, slab_words,
 			   ctx->d_Spart);
+}
+
+/* ------------------------------------------------------------------ mixture model: initialisation from individual centers
+ * random_individual_center + initialize_parameters_mixture (rnd_init.c:192-339) given the K centers the host drew.
+ *
+ * k_center_distance: ONE pass over the genotype for all K centers.  Workgroup = blockDim.x individuals x a chunk of blocks of
+ * 8 loci; thread = individual reading its contiguous gtS runs; the K center rows of a tile of locus blocks are staged in LDS
+ * (read from gtS too: the centers are individuals of the data set), so every lane reads the same center bytes (broadcast).
+ * Per (i, k, l): sum_m |n_ilm - n_c(k)lm| over observed copies = n_i + n_c - 2 * (size of the multiset intersection of the two
+ * lists of observed copies), the intersection found by matching every copy of the individual with an unused equal copy of the
+ * center.  Integer sums, kept per thread in LDS ([K][blockDim.x], 32 bits: a chunk holds at most 2 * 8 * chunk_groups * ploidy),
+ * written as part[chunk][k][i]; k_center_assign adds the chunks in 64 bits.  MISSING bytes (also the loci that pad the last
+ * block of 8) match nothing and count for nothing.
+ * PLT = ploidy 1..8: the run of 8 loci in registers.  PLT = 0: any ploidy; the thread's copies of one locus go through a
+ * private LDS row so that global memory is still read once. */
+template <int PLT>
+__global__ __launch_bounds__(256) void k_center_distance(const uint8_t *__restrict__ gtS, int I, int L, int pl_rt, int K,
+		const int32_t *__restrict__ centers, int chunk_groups, int tile_groups, uint32_t *__restrict__ part)
+{
+	extern __shared__ uint32_t cd_lds[];
+	const int pl = PLT ? PLT : pl_rt, nthr = blockDim.x, tid = threadIdx.x, grp = 8 * pl;
+	uint32_t *acc = cd_lds;					/* [K][nthr] */
+	uint32_t *cen32 = acc + (size_t)K * nthr;		/* [tile_groups][K][8][pl] bytes */
+	const uint8_t *cen = reinterpret_cast<const uint8_t *>(cen32);
+	uint8_t *own = reinterpret_cast<uint8_t *>(cen32 + (size_t)tile_groups * K * 2 * pl);	/* PLT = 0: [pl][nthr] */
+	const int i = blockIdx.x * nthr + tid;
+	const bool live = i < I;
+	const int n_groups = (L + 7) >> 3;
+	const int g_begin = blockIdx.y * chunk_groups, g_end = n_groups - g_begin < chunk_groups ? n_groups : g_begin + chunk_groups;
+	for (int k = 0; k < K; k++) acc[k * nthr + tid] = 0;
+	for (int g0 = g_begin; g0 < g_end; g0 += tile_groups) {
+		const int ng = g_end - g0 < tile_groups ? g_end - g0 : tile_groups;
+		__syncthreads();	/* the previous tile has been read */
+		for (int x = tid; x < ng * K * 2 * pl; x += nthr) {
+			const int w = x % (2 * pl), k = (x / (2 * pl)) % K, g = x / (2 * pl * K);
+			cen32[x] = reinterpret_cast<const uint32_t *>(gtS + ((size_t)(g0 + g) * I + centers[k]) * grp)[w];
+		}
+		__syncthreads();
+		if (!live) continue;
+		for (int g = 0; g < ng; g++) {
+			const uint8_t *src = gtS + ((size_t)(g0 + g) * I + i) * grp;
+			if constexpr (PLT > 0) {
+				unsigned long long run[PLT ? PLT : 1];
+#pragma unroll
+				for (int x = 0; x < PLT; x++) run[x] = reinterpret_cast<const unsigned long long *>(src)[x];
+				for (int k = 0; k < K; k++) {
+					unsigned long long crun[PLT ? PLT : 1];
+#pragma unroll
+					for (int x = 0; x < PLT; x++) crun[x] = reinterpret_cast<const unsigned long long *>(cen + (size_t)(g * K + k) * grp)[x];
+					int d = 0;
+#pragma unroll
+					for (int t = 0; t < 8; t++) {
+						unsigned used = 0;
+#pragma unroll
+						for (int b = 0; b < PLT; b++) {
+							const int at = t * PLT + b;
+							d += ((unsigned)(crun[at >> 3] >> (8 * (at & 7))) & 0xFFu) != MCHIP_MISSING;
+						}
+#pragma unroll
+						for (int a = 0; a < PLT; a++) {
+							const int at = t * PLT + a;
+							const unsigned gi = (unsigned)(run[at >> 3] >> (8 * (at & 7))) & 0xFFu;
+							const bool obs = gi != MCHIP_MISSING;
+							bool found = false;
+#pragma unroll
+							for (int b = 0; b < PLT; b++) {
+								const int bt = t * PLT + b;
+								const unsigned cb = (unsigned)(crun[bt >> 3] >> (8 * (bt & 7))) & 0xFFu;
+								const bool hit = obs && !found && !((used >> b) & 1u) && cb == gi;
+								used |= (unsigned)hit << b;
+								found = found || hit;
+							}
+							d += (int)obs - 2 * (int)found;
+						}
+					}
+					acc[k * nthr + tid] += (uint32_t)d;
+				}
+			} else {
+				for (int t = 0; t < 8; t++) {
+					for (int a = 0; a < pl; a++) own[a * nthr + tid] = src[t * pl + a];
+					for (int k = 0; k < K; k++) {
+						const uint8_t *ck = cen + (size_t)(g * K + k) * grp + t * pl;
+						unsigned long long used = 0;
+						int d = 0;
+						for (int b = 0; b < pl; b++) d += ck[b] != MCHIP_MISSING;
+						for (int a = 0; a < pl; a++) {
+							const unsigned gi = own[a * nthr + tid];
+							if (gi == MCHIP_MISSING) continue;
+							d++;
+							for (int b = 0; b < pl; b++)
+								if (!((used >> b) & 1ull) && ck[b] == gi) { used |= 1ull << b; d -= 2; break; }
+						}
+						acc[k * nthr + tid] += (uint32_t)d;
+					}
+				}
+			}
+		}
+	}
+	if (live)
+		for (int k = 0; k < K; k++) part[((size_t)blockIdx.y * K + k) * I + i] = acc[k * nthr + tid];
+}
+
+template <int PLT>
+static void launch_center_distance(mchip_context *ctx, unsigned n_iblocks, unsigned n_chunks, int nthr, size_t lds, const int32_t *d_centers,
+				   int chunk_groups, int tile_groups)
+{
+	hipLaunchKernelGGL(k_center_distance<PLT>, dim3(n_iblocks, n_chunks), dim3(nthr), lds, ctx->stream, ctx->d_gtS, ctx->I, ctx->L, ctx->ploidy,
+			   ctx->K, d_centers, chunk_groups, tile_groups, ctx->d_cen_part);
+}
+
+/* the assignment: a center k joins itself (the reference breaks out of its loop there, even when an earlier center is at
+ * distance 0); every other individual joins the FIRST center of minimal distance (diff < min_diff, strict).  n_k counted. */
+__global__ __launch_bounds__(256) void k_center_assign(const uint32_t *__restrict__ part, int n_chunks, int I, int K,
+		const int32_t *__restrict__ centers, int32_t *__restrict__ assign, uint32_t *__restrict__ nk)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= I) return;
+	int best = -1;
+	for (int k = 0; k < K; k++)
+		if (centers[k] == i) best = k;
+	if (best < 0) {
+		unsigned long long min_diff = ~0ull;
+		best = 0;
+		for (int k = 0; k < K; k++) {
+			unsigned long long diff = 0;
+			for (int c = 0; c < n_chunks; c++) diff += part[((size_t)c * K + k) * I + i];
+			if (diff < min_diff) { best = k; min_diff = diff; }
+		}
+	}
+	assign[i] = best;
+	atomicAdd(&nk[best], 1u);
+}
+
+/* c[column][k] = observed copies of the allele among the individuals assigned to k.  Workgroup = 256 individuals x a chunk of
+ * loci, thread = individual reading its gtS runs once, word by word; the counts of a tile of loci in LDS (integer atomics: the
+ * sums are order-free), added to the global table per tile; tile = 0 (a locus block's counters do not fit): global atomics. */
+__global__ __launch_bounds__(256) void k_center_counts(const uint8_t *__restrict__ gtS, int I, int L, int pl, int K,
+		const int32_t *__restrict__ toff, const int32_t *__restrict__ assign, int chunk_loci, int tile, uint32_t *__restrict__ cnt)
+{
+	extern __shared__ uint32_t cc_lds[];
+	const int i = blockIdx.y * 256 + threadIdx.x;
+	const bool live = i < I;
+	const int k = live ? assign[i] : 0;
+	const int l_begin = blockIdx.x * chunk_loci, l_end = L - l_begin < chunk_loci ? L : l_begin + chunk_loci;
+	const int step = tile ? tile : chunk_loci;
+	for (int t0 = l_begin; t0 < l_end; t0 += step) {
+		const int t1 = l_end - t0 < step ? l_end : t0 + step;
+		const int col0 = toff[t0], nwords = (toff[t1] - col0) * K;
+		if (tile) {
+			for (int x = threadIdx.x; x < nwords; x += 256) cc_lds[x] = 0;
+			__syncthreads();
+		}
+		if (live)
+			for (int g = t0 >> 3; g * 8 < t1; g++) {
+				const uint32_t *src = reinterpret_cast<const uint32_t *>(gtS + ((size_t)g * I + i) * 8 * pl);
+				for (int w = 0; w < 2 * pl; w++) {
+					const uint32_t v4 = src[w];
+#pragma unroll
+					for (int y = 0; y < 4; y++) {
+						const uint32_t mb = (v4 >> (8 * y)) & 0xFFu;
+						const int l = g * 8 + (w * 4 + y) / pl;
+						if (mb == MCHIP_MISSING || l >= t1) continue;
+						const int c = toff[l] + (int)mb;
+						if (tile) atomicAdd(&cc_lds[(size_t)(c - col0) * K + k], 1u);
+						else atomicAdd(&cnt[(size_t)c * K + k], 1u);
+					}
+				}
+			}
+		if (tile) {
+			__syncthreads();
+			for (int x = threadIdx.x; x < nwords; x += 256)
+				if (cc_lds[x]) atomicAdd(&cnt[(size_t)col0 * K + x], cc_lds[x]);
+			__syncthreads();
+		}
+	}
+}
+
+/* eta[k] = (1 + n_k) / (I + K); per (k, l), left to right over m: e = 1 + (K - k) * c (the reference re-adds every individual's
+ * counts inside its loop over k, rnd_init.c:296-318), temp += e, p = e / temp.  Exact integers below 2^53 divided by correctly
+ * rounded IEEE divisions: the bits of the host form. */
+__global__ void k_center_finish(int I, int L, int K, const int32_t *__restrict__ toff, const uint32_t *__restrict__ cnt,
+		const uint32_t *__restrict__ nk, double *__restrict__ eta, double *__restrict__ P)
+{
+	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx < (size_t)K) eta[idx] = (double)(1u + nk[idx]) / (double)(I + K);
+	if (idx >= (size_t)K * L) return;
+	const int k = (int)(idx % K), l = (int)(idx / K);
+	const int c0 = toff[l], M = toff[l + 1] - c0;
+	double temp = 0.0;
+	for (int m = 0; m < M; m++) temp += 1.0 + (double)(K - k) * (double)cnt[(size_t)(c0 + m) * K + k];
+	for (int m = 0; m < M; m++) P[(size_t)(c0 + m) * K + k] = (1.0 + (double)(K - k) * (double)cnt[(size_t)(c0 + m) * K + k]) / temp;
 }
 
 /* random_allele_center's assignment (rnd_init.c:552-580) given the centers the host drew: copy (i, a) of locus l goes to the
@@ -1390,6 +1731,8 @@ static void free_data(mchip_context *ctx)
 	for (int x = 0; x < 2; x++) { dfree(ctx->lat[x].d_i); dfree(ctx->lat[x].d_r); ctx->lat[x].nA = 0; }
 	dfree(ctx->d_part_slabs);
 	ctx->part_slab_bytes = 0;
+	dfree(ctx->d_sim_cluster); dfree(ctx->d_cen_part); dfree(ctx->d_cen_work);
+	ctx->cen_part_bytes = ctx->cen_work_bytes = 0;
 	ctx->init_geno_set = 0;
 	ctx->h_ua.clear();
 	ctx->I = ctx->L = ctx->T = 0;
@@ -2662,7 +3005,7 @@ int mchip_simulate_genotypes(mchip_context *ctx, int I, int L, int ploidy, const
 	{
 		const size_t n = n_qrows > (size_t)K * L ? n_qrows : (size_t)K * L;
 		hipLaunchKernelGGL(k_walk_tables, dim3(nblk(n)), dim3(256), 0, ctx->stream, (int)n_qrows, K, L, ctx->T, ctx->d_toff, d_q.p, d_p.p,
-				   fast, d_cq.p, d_cp.p);
+				   fast, fast, d_cq.p, d_cp.p);
 	}
 	if (fast && ploidy <= 8 && !ctx->knob.sim_no_tile) {
 		/* tile: as many loci as keep the staged thresholds near 16 KiB (three workgroups per compute unit), a multiple of 8 */
@@ -2700,6 +3043,172 @@ int mchip_simulate_genotypes(mchip_context *ctx, int I, int L, int ploidy, const
 	rc = install_raw(ctx, d_raw);
 	(void)MCHIP_WAIT(hipStreamSynchronize(ctx->stream));	/* the temporaries go out of scope */
 	return rc;
+}
+
+/* The mixture model's generator.  Dispatch: tile form (k_simulate_mixture_tile) when no locus has more than SIM_PW alleles and
+ * ploidy <= 8, at every K; otherwise, and under MCHIP_SIM_NO_TILE, the general form (k_simulate_mixture_general) in chunks of
+ * MIX_GENERAL_CHUNK loci.  Both follow k_simulate_mixture_source, which leaves every individual's cluster in d_sim_cluster.
+ * K <= 256: the cluster is a byte.  (As in mchip_simulate_genotypes, a HIPCHK that returns after the asynchronous uploads frees the
+ * scoped buffers without waiting for the stream; the runtime's hipFree synchronises, and the call has failed anyway.) */
+constexpr int MIX_GENERAL_CHUNK = 64;
+
+int mchip_simulate_genotypes_mixture(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, const uint32_t *window,
+				     int K, const double *eta, const double *p)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (!window || !eta || !p || K < 1) return fail(ctx, MCHIP_ERR_INVALID, "simulate_genotypes_mixture: null pointer or K < 1%s", nullptr);
+	if (K > 256) return fail(ctx, MCHIP_ERR_INVALID, "simulate_genotypes_mixture: more than 256 clusters%s", nullptr);
+	int rc = set_shape(ctx, I, L, ploidy, ua, 1);
+	if (rc) return rc;
+	ctx->first_empty = -1;		/* every copy of a generated data set is drawn */
+	ctx->empty_rows.clear();
+	rng_window base, base1;		/* at the first draw (the first individual's cluster); one draw on (its first copy) */
+	for (int t = 0; t < RNG_LAG; t++) base.s[t] = window[t];
+	for (int t = 0; t < RNG_LAG - 1; t++) base.s[RNG_LAG + t] = base.s[t] + base.s[RNG_LAG - 3 + t];
+	for (int t = 0; t < RNG_LAG; t++) base1.s[t] = base.s[t + 1];
+	for (int t = 0; t < RNG_LAG - 1; t++) base1.s[RNG_LAG + t] = base1.s[t] + base1.s[RNG_LAG - 3 + t];
+	const size_t np = (size_t)K * ctx->T;
+	const int fast_p = ctx->max_M <= SIM_PW;
+	const int tiled = fast_p && ploidy <= 8 && !ctx->knob.sim_no_tile;
+	const size_t ncp = fast_p ? (size_t)K * L * SIM_PW : np;
+	scoped_dev<double> d_q, d_p;
+	scoped_dev<uint32_t> d_cq, d_cp;
+	HIPCHK(d_q.alloc((size_t)K));
+	HIPCHK(d_p.alloc(np));
+	HIPCHK(d_cq.alloc((size_t)K));
+	HIPCHK(d_cp.alloc(ncp));
+	if (!ctx->d_sim_cluster) HIPCHK(hipMalloc((void **)&ctx->d_sim_cluster, (size_t)I));
+	HIPCHK(hipMemcpyAsync(d_q, eta, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipMemcpyAsync(d_p, p, np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	hipLaunchKernelGGL(k_walk_tables, dim3(nblk((size_t)K * L)), dim3(256), 0, ctx->stream, 1, K, L, ctx->T, ctx->d_toff, d_q.p, d_p.p,
+			   0, fast_p, d_cq.p, d_cp.p);
+	HIPCHK(hipGetLastError());
+	int chunk = MIX_GENERAL_CHUNK;
+	if (tiled) {
+		/* as many loci as keep the staged thresholds near 16 KiB, a multiple of 8 (K = 64: 16 loci, 12 KiB) */
+		chunk = (16384 / (K * 12)) & ~7;
+		if (chunk < 8) chunk = 8;
+		if (chunk > 512) chunk = 512;
+		if (chunk > ((L + 7) & ~7)) chunk = (L + 7) & ~7;
+	}
+	const unsigned n_chunks = (unsigned)((L + chunk - 1) / chunk);
+	if ((rc = lattice_tables(ctx, 0, 1ull + (uint64_t)L * ploidy, (unsigned)I, (uint64_t)chunk * ploidy, n_chunks))) return rc;
+	hipLaunchKernelGGL(k_simulate_mixture_source, dim3(nblk((size_t)I)), dim3(256), 0, ctx->stream, base, ctx->lat[0].d_i, ctx->lat[0].d_r, I, K,
+			   d_cq.p, ctx->d_sim_cluster);
+	HIPCHK(hipGetLastError());
+	if (tiled) {
+		switch (ploidy) {
+		case 1: launch_simulate_mixture_tile<1>(ctx, base1, K, chunk, d_cp.p); break;
+		case 2: launch_simulate_mixture_tile<2>(ctx, base1, K, chunk, d_cp.p); break;
+		case 3: launch_simulate_mixture_tile<3>(ctx, base1, K, chunk, d_cp.p); break;
+		case 4: launch_simulate_mixture_tile<4>(ctx, base1, K, chunk, d_cp.p); break;
+		case 5: launch_simulate_mixture_tile<5>(ctx, base1, K, chunk, d_cp.p); break;
+		case 6: launch_simulate_mixture_tile<6>(ctx, base1, K, chunk, d_cp.p); break;
+		case 7: launch_simulate_mixture_tile<7>(ctx, base1, K, chunk, d_cp.p); break;
+		default: launch_simulate_mixture_tile<8>(ctx, base1, K, chunk, d_cp.p); break;
+		}
+		HIPCHK(hipGetLastError());
+		rc = install_layouts(ctx, 0);
+		(void)MCHIP_WAIT(hipStreamSynchronize(ctx->stream));	/* the temporaries go out of scope */
+		return rc;
+	}
+	if ((rc = stream_buffer(ctx))) return rc;
+	hipLaunchKernelGGL(k_simulate_mixture_general, dim3(n_chunks, nblk((size_t)I)), dim3(256), 0, ctx->stream, base1, ctx->lat[0].d_i,
+			   ctx->lat[0].d_r, I, L, ploidy, ctx->T, chunk, ctx->d_toff, ctx->d_sim_cluster, d_cp.p, fast_p, ctx->d_draw);
+	HIPCHK(hipGetLastError());
+	rc = install_raw(ctx, ctx->d_draw);
+	(void)MCHIP_WAIT(hipStreamSynchronize(ctx->stream));	/* the temporaries go out of scope */
+	return rc;
+}
+
+int mchip_init_from_individual_centers(mchip_context *ctx, const int32_t *centers, int to, int32_t *assign_out)
+{
+	MCHIP_ENTRY();
+	int rc = check_slot(ctx, to);
+	if (rc) return rc;
+	ctx->s_cache_slot = -1;
+	if (!centers) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	if (ctx->admixture) return fail(ctx, MCHIP_ERR_STATE, "individual centers initialise the mixture model only%s", nullptr);
+	const int I = ctx->I, L = ctx->L, K = ctx->K, pl = ctx->ploidy, T = ctx->T;
+	for (int k = 0; k < K; k++) {
+		if (centers[k] < 0 || centers[k] >= I) return fail(ctx, MCHIP_ERR_INVALID, "center out of range%s", nullptr);
+		for (int j = 0; j < k; j++)
+			if (centers[j] == centers[k]) return fail(ctx, MCHIP_ERR_INVALID, "centers are not distinct%s", nullptr);
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	auto grow = [&](uint32_t **p, size_t *have, size_t want) -> hipError_t {
+		if (*have >= want) return hipSuccess;
+		if (*p) { (void)MCHIP_WAIT(hipStreamSynchronize(ctx->stream)); (void)MCHIP_WAIT(hipFree(*p)); *p = nullptr; *have = 0; }
+		const hipError_t e = hipMalloc((void **)p, want);
+		if (e == hipSuccess) *have = want;
+		return e;
+	};
+	/* work: counts [T][K], n_k [K], centers [K], assignment [I] */
+	const size_t n_cnt = (size_t)T * K;
+	HIPCHK(grow(&ctx->d_cen_work, &ctx->cen_work_bytes, (n_cnt + 2 * (size_t)K + (size_t)I) * sizeof(uint32_t)));
+	uint32_t *d_cnt = ctx->d_cen_work, *d_nk = d_cnt + n_cnt;
+	int32_t *d_centers = reinterpret_cast<int32_t *>(d_nk + K), *d_assign = d_centers + K;
+	HIPCHK(hipMemsetAsync(d_cnt, 0, (n_cnt + (size_t)K) * sizeof(uint32_t), ctx->stream));
+	HIPCHK(hipMemcpyAsync(d_centers, centers, sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, ctx->stream));
+	const int n_groups = (L + 7) / 8;
+	int n_dist_chunks = 0;
+	if (K > 1) {
+		/* threads per workgroup: the K accumulators of a thread live in LDS ([K][threads] words, at most 32 KiB) */
+		const int tiled = pl <= 8;
+		const int nthr = tiled ? (K <= 32 ? 256 : 128) : (K <= 32 ? 128 : 64);
+		const unsigned n_iblocks = (unsigned)((I + nthr - 1) / nthr);
+		int want = (int)(2048 / n_iblocks);
+		if (want < 1) want = 1;
+		int chunk_groups = (n_groups + want - 1) / want;
+		if (chunk_groups < 8) chunk_groups = 8;
+		if (chunk_groups > n_groups) chunk_groups = n_groups;
+		const unsigned n_chunks = (unsigned)((n_groups + chunk_groups - 1) / chunk_groups);
+		int tile_groups = 16384 / (K * 8 * pl);		/* staged center rows near 16 KiB */
+		if (tile_groups < 1) tile_groups = 1;
+		if (tile_groups > chunk_groups) tile_groups = chunk_groups;
+		const size_t lds = ((size_t)K * nthr + (size_t)tile_groups * K * 2 * pl) * sizeof(uint32_t) + (tiled ? 0 : (size_t)pl * nthr);
+		if (lds > 64 * 1024) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "center distances: the shape does not fit the kernel%s", nullptr);
+		HIPCHK(grow(&ctx->d_cen_part, &ctx->cen_part_bytes, (size_t)n_chunks * K * I * sizeof(uint32_t)));
+		switch (tiled ? pl : 0) {
+		case 1: launch_center_distance<1>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		case 2: launch_center_distance<2>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		case 3: launch_center_distance<3>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		case 4: launch_center_distance<4>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		case 5: launch_center_distance<5>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		case 6: launch_center_distance<6>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		case 7: launch_center_distance<7>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		case 8: launch_center_distance<8>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		default: launch_center_distance<0>(ctx, n_iblocks, n_chunks, nthr, lds, d_centers, chunk_groups, tile_groups); break;
+		}
+		HIPCHK(hipGetLastError());
+		n_dist_chunks = (int)n_chunks;
+	}
+	/* K = 1: no chunk, every distance 0, every individual joins cluster 0 (rnd_init.c:199-204) */
+	hipLaunchKernelGGL(k_center_assign, dim3(nblk((size_t)I)), dim3(256), 0, ctx->stream, ctx->d_cen_part, n_dist_chunks, I, K, d_centers,
+			   d_assign, d_nk);
+	HIPCHK(hipGetLastError());
+	{
+		const unsigned n_iblocks = (unsigned)((I + 255) / 256);
+		int want = (int)(2048 / n_iblocks);
+		if (want < 1) want = 1;
+		int chunk_loci = (((L + want - 1) / want) + 7) & ~7;
+		if (chunk_loci < 64) chunk_loci = 64;
+		/* counters of a tile: tile * max_M * K words, at most 32 KiB, a multiple of 8 loci; none when 8 loci do not fit */
+		int tile = (int)((8192 / ((size_t)ctx->max_M * K)) & ~(size_t)7);
+		if (tile > chunk_loci) tile = chunk_loci;
+		const size_t lds = (size_t)tile * ctx->max_M * K * sizeof(uint32_t);
+		hipLaunchKernelGGL(k_center_counts, dim3((unsigned)((L + chunk_loci - 1) / chunk_loci), n_iblocks), dim3(256), lds, ctx->stream,
+				   ctx->d_gtS, I, L, pl, K, ctx->d_toff, d_assign, chunk_loci, tile, d_cnt);
+		HIPCHK(hipGetLastError());
+	}
+	hipLaunchKernelGGL(k_center_finish, dim3(nblk((size_t)K * L)), dim3(256), 0, ctx->stream, I, L, K, ctx->d_toff, d_cnt, d_nk, ctx->d_q[to],
+			   ctx->d_p[to]);
+	HIPCHK(hipGetLastError());
+	ctx->empty_rows_nan[to] = 0;	/* as mchip_set_q leaves the slot for finite rows */
+	if (assign_out) HIPCHK(hipMemcpyAsync(assign_out, d_assign, sizeof(int32_t) * (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));	/* centers is the caller's: uploaded by now */
+	return MCHIP_OK;
 }
 
 int mchip_get_expected_counts(mchip_context *ctx, double *sik)

@@ -69,6 +69,8 @@ def load():
         "mchip_empty_individuals": ([vp, C.POINTER(C.c_int)], i32),
         "mchip_copy_genotypes": ([vp, vp], i32),
         "mchip_simulate_genotypes": ([vp, i32, i32, i32, vp, vp, i32, i32, vp, vp], i32),
+        "mchip_simulate_genotypes_mixture": ([vp, i32, i32, i32, vp, vp, i32, vp, vp], i32),
+        "mchip_init_from_individual_centers": ([vp, vp, i32, vp], i32),
         "mchip_set_init_genotypes": ([vp, vp], i32),
         "mchip_get_expected_counts": ([vp, vp], i32),
         "mchip_init_from_allele_centers": ([vp, vp, vp, vp, C.c_uint64, i32], i32),
@@ -111,6 +113,7 @@ ABI_SYMBOLS = [
     "mchip_secant_dots", "mchip_accel_update", "mchip_multisecant_update", "mchip_profile_begin",
     "mchip_profile_end", "mchip_device_info", "mchip_comm_create", "mchip_comm_all_reduce", "mchip_comm_destroy",
     "mchip_comm_last_error", "mchip_comm_info", "mchip_progress_report", "mchip_progress_note",
+    "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers",
 ]
 
 
@@ -184,6 +187,26 @@ class Context:
         self._chk(self.lib.mchip_simulate_genotypes(self.h, I, L, ploidy, ua.ctypes.data, w.ctypes.data, K,
                                                     eta_constrained, q.ctypes.data, p.ctypes.data))
         self.I, self.L, self.ploidy, self.T = I, L, ploidy, int(ua.sum())
+
+    def simulate_genotypes_mixture(self, I, L, ploidy, ua, window, K, eta, p):
+        """The mixture model's parametric-bootstrap data set drawn on the device (include/multiclust_hip.h); drops the model."""
+        ua = np.ascontiguousarray(ua, dtype=np.int32)
+        w = np.ascontiguousarray(window, dtype=np.uint32)
+        eta = np.ascontiguousarray(eta, dtype=np.float64)
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        assert w.size == 31 and ua.size == L and p.size == K * int(ua.sum()) and eta.size == K
+        self._chk(self.lib.mchip_simulate_genotypes_mixture(self.h, I, L, ploidy, ua.ctypes.data, w.ctypes.data, K,
+                                                            eta.ctypes.data, p.ctypes.data))
+        self.I, self.L, self.ploidy, self.T = I, L, ploidy, int(ua.sum())
+
+    def init_from_individual_centers(self, centers, to=0):
+        """Mixture model: assignment to the nearest of the K center individuals and the parameters initialised from it, into
+        slot `to`; returns the assignment [I]."""
+        c = np.ascontiguousarray(centers, dtype=np.int32)
+        assert c.size == self.K
+        out = np.empty(self.I, dtype=np.int32)
+        self._chk(self.lib.mchip_init_from_individual_centers(self.h, c.ctypes.data, to, out.ctypes.data))
+        return out
 
     def set_model(self, K, admixture=1, eta_constrained=0, do_projection=1, lower_bound=1e-8, n_secants=1):
         self._chk(self.lib.mchip_set_model(self.h, K, admixture, eta_constrained, do_projection,

@@ -104,6 +104,15 @@ def read_structure(path, ploidy=2, missing=-9, r_format=0):
     return 0, out
 
 
+def replicate_starts(opt, dat, base, n_replicates, null_K, alt_K, n_init):
+    """mc_replicate_starts: the generator at the start of every bootstrap replicate, [n_replicates + 1] McRng"""
+    starts = (McRng * (n_replicates + 1))()
+    rc = load().mc_replicate_starts(C.byref(opt), C.byref(dat), C.byref(base), n_replicates, null_K, alt_K, n_init, starts)
+    if rc:
+        raise hip.HipError("mc_replicate_starts failed (%d)" % rc)
+    return starts
+
+
 _lib = None
 
 
@@ -159,6 +168,10 @@ def load():
     lib.mc_model_get_genotypes.argtypes = [MP, C.c_void_p]
     lib.mc_fit_replicate.argtypes = [OP, DP, C.c_int, C.POINTER(McRng), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.POINTER(McReplicateResult), C.POINTER(MP)]
+    lib.mc_replicate_starts.argtypes = [OP, DP, C.POINTER(McRng), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(McRng)]
+    lib.mc_replicate_start.argtypes = [OP, DP, C.POINTER(McRng), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(McRng)]
+    lib.mc_test_center_walk.argtypes = [C.c_int, C.c_int, C.POINTER(McRng), C.POINTER(C.c_int)]
+    lib.mc_test_center_walk.restype = None
     lib.mc_aic.restype = C.c_double
     lib.mc_aic.argtypes = [C.c_double, C.c_int]
     lib.mc_bic.restype = C.c_double

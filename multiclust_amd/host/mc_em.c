@@ -113,6 +113,18 @@ void mc_reset_model_state(mc_model *mod)
 	mod->seconds_run = 0;
 }
 
+/* the replicate `sim` describes, generated on the device: parametric_bootstrap_admixture / _mixture (bootstrap.c:84-175) */
+static int simulate(mchip_context *dev, const mc_options *opt, const mc_data *dat, const mc_simulation *sim)
+{
+	/* Rand-EM for the mixture model scores its candidates from dat->geno on the host: not on a replicate the device alone holds */
+	if (!opt->admixture && opt->initialization_procedure == MC_RAND_EM) return MCHIP_ERR_UNSUPPORTED;
+	if (!opt->admixture && !mchip_simulate_genotypes_mixture) return MCHIP_ERR_UNSUPPORTED;	/* a stand-in device library (mc_host.h) */
+	if (!opt->admixture)
+		return mchip_simulate_genotypes_mixture(dev, dat->I, dat->L, dat->ploidy, dat->uniquealleles, sim->window, sim->K, sim->q, sim->p);
+	return mchip_simulate_genotypes(dev, dat->I, dat->L, dat->ploidy, dat->uniquealleles, sim->window, sim->K, opt->eta_constrained,
+					sim->q, sim->p);
+}
+
 static int model_create(mc_model **out, const mc_options *opt, const mc_data *dat, int K, int device, const mc_simulation *sim,
 			const mc_model *like)
 {
@@ -131,12 +143,12 @@ static int model_create(mc_model **out, const mc_options *opt, const mc_data *da
 	if (like)
 		rc = mchip_copy_genotypes(mod->dev, like->dev);
 	else if (sim)
-		rc = mchip_simulate_genotypes(mod->dev, dat->I, dat->L, dat->ploidy, dat->uniquealleles, sim->window, sim->K,
-					      opt->eta_constrained, sim->q, sim->p);
+		rc = simulate(mod->dev, opt, dat, sim);
 	else
 		rc = mchip_set_genotypes(mod->dev, dat->I, dat->L, dat->ploidy, dat->uniquealleles, dat->geno);
-	/* fits to a bootstrap data set initialise from the observed haplotypes (rnd_init.c:471): dat->geno when the data set
-	 * was generated on the device, dat->init_geno when the caller uploaded a replicate as dat->geno */
+	/* admixture fits to a bootstrap data set initialise from the observed haplotypes (rnd_init.c:471): dat->geno when the data set
+	 * was generated on the device, dat->init_geno when the caller uploaded a replicate as dat->geno.  (The mixture model's
+	 * initialisation reads the simulated data set itself, dat->ILM: nothing to install.) */
 	if (!rc && opt->admixture && (sim || like || dat->init_geno))
 		rc = mchip_set_init_genotypes(mod->dev, (sim || like) ? dat->geno : dat->init_geno);
 	if (rc || (rc = mchip_set_model(mod->dev, K, opt->admixture, opt->eta_constrained, opt->do_projection,
@@ -158,7 +170,7 @@ int mc_model_create(mc_model **out, const mc_options *opt, const mc_data *dat, i
 
 int mc_model_create_simulated(mc_model **out, const mc_options *opt, const mc_data *dat, int K, int device, const mc_simulation *sim)
 {
-	if (!sim || !opt->admixture) return MCHIP_ERR_INVALID;	/* the mixture model's replicate is drawn on the host */
+	if (!sim) return MCHIP_ERR_INVALID;
 	return model_create(out, opt, dat, K, device, sim, NULL);
 }
 
@@ -167,7 +179,7 @@ int mc_model_create_simulated(mc_model **out, const mc_options *opt, const mc_da
 int mc_model_share_simulated(mc_model **out, const mc_options *opt, const mc_data *dat, int K, int device, const mc_model *like)
 {
 	int rc;
-	if (!like || !opt->admixture) return MCHIP_ERR_INVALID;
+	if (!like) return MCHIP_ERR_INVALID;
 	if (!*out) return model_create(out, opt, dat, K, device, NULL, like);
 	rc = mchip_copy_genotypes((*out)->dev, like->dev);
 	if (!rc) rc = mchip_set_model((*out)->dev, (*out)->K, opt->admixture, opt->eta_constrained, opt->do_projection,
@@ -182,9 +194,8 @@ int mc_model_share_simulated(mc_model **out, const mc_options *opt, const mc_dat
 int mc_model_resimulate(mc_model *mod, const mc_options *opt, const mc_data *dat, const mc_simulation *sim)
 {
 	int rc;
-	if (!mod || !sim || !opt->admixture) return MCHIP_ERR_INVALID;
-	rc = mchip_simulate_genotypes(mod->dev, dat->I, dat->L, dat->ploidy, dat->uniquealleles, sim->window, sim->K,
-				      opt->eta_constrained, sim->q, sim->p);
+	if (!mod || !sim) return MCHIP_ERR_INVALID;
+	rc = simulate(mod->dev, opt, dat, sim);
 	if (!rc) rc = mchip_set_model(mod->dev, mod->K, opt->admixture, opt->eta_constrained, opt->do_projection,
 				      opt->eta_lower_bound, opt->p_lower_bound, opt->accel_scheme ? opt->q : 0);
 	if (rc) fprintf(stderr, "ERROR [mc_em.c::mc_model_resimulate]: %s\n", mchip_last_error(mod->dev));

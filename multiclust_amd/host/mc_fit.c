@@ -134,23 +134,25 @@ int mc_fit_unit(const mc_options *opt, const mc_data *dat, mc_model *mod, unsign
 
 /* One parametric-bootstrap replicate, the unit run_bootstrap shards (multiclust.c:675-708): data set b is generated on
  * `device` from the H0 fit (mle_K clusters, mle_q, mle_p) at the position replicate b has in the serial rand() stream
- * (`base` = the stream where the first replicate begins), then n_init initialisations of the null_K model and of the alt_K
+ * (`base` = the stream where the first replicate begins; mc_replicate_starts finds the position), for the admixture and for the
+ * mixture model (mle_q = eta[mle_K]; initialised on the device from the generated data set), then n_init initialisations of the null_K model and of the alt_K
  * model are fitted to it (only one when K = 1, multiclust.c:630), each from the stream where the serial program would be;
  * the test statistic is the difference of the two best log likelihoods. */
 int mc_fit_replicate(const mc_options *opt, const mc_data *dat, int device, const mc_rng *base, int b, int null_K, int alt_K,
 		     int n_init, int mle_K, const double *mle_q, const double *mle_p, mc_replicate_result *out, mc_model **models)
 {
-	const uint64_t per_init = mc_draws_per_init(opt, dat, alt_K);
 	const uint64_t units0 = null_K == 1 ? 1 : (uint64_t)n_init, units1 = alt_K == 1 ? 1 : (uint64_t)n_init;
-	const uint64_t per_replicate = mc_bootstrap_draws(opt, dat) + (units0 + units1) * per_init;
-	mc_rng rng = *base;
+	mc_rng rng;
 	mc_simulation gen;
 	int rc = 0;
-	if (!opt->admixture) return MCHIP_ERR_UNSUPPORTED;	/* the mixture model's replicate is drawn on the host */
-	if (opt->initialization_procedure == MC_RAND_EM) return MCHIP_ERR_UNSUPPORTED;	/* no closed form for a replicate's stream position */
+	if (opt->initialization_procedure == MC_RAND_EM) return MCHIP_ERR_UNSUPPORTED;	/* no cheap walk to a replicate's stream position */
+	/* the host form of the mixture initialisation reads dat->geno, and the generated data set exists on the device only */
+	if (!opt->admixture && getenv("MC_HOST_INIT")) return MCHIP_ERR_UNSUPPORTED;
+	if (b < 0) return MCHIP_ERR_INVALID;
 	memset(out, 0, sizeof *out);
 	out->replicate = b;
-	mc_rng_jump(&rng, (uint64_t)b * per_replicate);
+	/* where replicate b begins: a jump (admixture) or the replay of the earlier replicates' center draws (mixture) */
+	if ((rc = mc_replicate_start(opt, dat, base, b, null_K, alt_K, n_init, &rng))) return rc;
 	mc_simulation_begin(&gen, opt, dat, mle_K, mle_q, mle_p, &rng);
 	for (int h = 0; h < 2 && !rc; h++) {
 		const int K = h ? alt_K : null_K;

@@ -22,6 +22,14 @@
 extern "C" {
 #endif
 
+/* The two device entry points of the mixture model's bootstrap and initialisation are weak references on the host side: the
+ * host objects also link into CPU-only programs (sanitizer builds) that stand in for the device library with the entry points
+ * they know and never reach these; against the real library they resolve as any other symbol. */
+#if defined(__GNUC__) && !defined(__cplusplus)
+extern __typeof__(mchip_simulate_genotypes_mixture) mchip_simulate_genotypes_mixture __attribute__((weak));
+extern __typeof__(mchip_init_from_individual_centers) mchip_init_from_individual_centers __attribute__((weak));
+#endif
+
 /* acceleration schemes (reference multiclust.h:125-131; 5, 6 = QN with q = 2, 3, multiclust.c:818-820) */
 enum { MC_NONE = 0, MC_SQS1, MC_SQS2, MC_SQS3, MC_QN };
 /* verbosity (reference message.h:45-53) */
@@ -97,8 +105,8 @@ void mc_model_free(mc_model *mod);
 
 /* Parametric bootstrap (bootstrap.c:31-175).  mc_bootstrap_genotypes draws one data set on the host from the fitted
  * parameters q ([I][K] or [K]) and p ([K][T]) of a K-cluster model, consuming `rng` exactly as the reference consumes
- * rand(); mc_bootstrap_draws is the number of draws that takes.  For the admixture model the same data set can be
- * generated on the device instead of uploaded: fill an mc_simulation with mc_simulation_begin (which also moves rng
+ * rand(); mc_bootstrap_draws is the number of draws that takes.  The same data set can be generated on the device
+ * instead of uploaded (both models; q is then eta[K] for the mixture model): fill an mc_simulation with mc_simulation_begin (which also moves rng
  * past the data set's draws) and create the replicate's models with mc_model_create_simulated. */
 typedef struct mc_simulation { uint32_t window[31]; int K; const double *q, *p; } mc_simulation;
 void mc_bootstrap_genotypes(const mc_options *opt, const mc_data *dat, int K, const double *q, const double *p,
@@ -121,7 +129,9 @@ int mc_model_get_expected_counts(mc_model *mod, double *sik);
 /* initialize_model (rnd_init.c:54-89) for the admixture model, random allele partition (349-357,456-482) */
 int mc_initialize_model(const mc_options *opt, const mc_data *dat, mc_model *mod, mc_rng *rng);
 void mc_reset_model_state(mc_model *mod);	/* multiclust.c:518-524 + rnd_init.c:58-71 */
-/* random_initialize_mixture (rnd_init.c:103-110): random_individual_center + initialize_parameters_mixture, on the host */
+/* random_initialize_mixture (rnd_init.c:103-110): random_individual_center + initialize_parameters_mixture.  The host draws the
+ * K centers; distances, counts and parameters are the device's (mchip_init_from_individual_centers), or, with MC_HOST_INIT set,
+ * the host's from dat->geno */
 int mc_initialize_mixture(const mc_data *dat, mc_model *mod, mc_rng *rng);
 /* Rand-EM (rnd_init.c:123-160 mixture, 412-444 admixture): n_rand_em_init candidates -- random centers, parameters from the
  * partition, one EM iteration plus an E step (em_e_step) -- and the parameters of the candidate with the best log likelihood.
@@ -136,6 +146,15 @@ int mc_skip_initializations(const mc_options *opt, const mc_data *dat, mc_model 
  * holds the allele-count cache of the Rand-EM walk: a zeroed mc_model with K set will do, mc_init_cache_free() afterwards) */
 int mc_unit_starts(const mc_options *opt, const mc_data *dat, mc_model *mod, const mc_rng *base, int n_units, mc_rng *starts);
 void mc_init_cache_free(mc_model *mod);
+/* starts[b], b = 0..n_replicates: the generator at the start of bootstrap replicate b (data set, then n_init initialisations of
+ * the null_K and of the alt_K model, one when K = 1), `base` = where replicate 0 begins.  A jump per replicate for the admixture
+ * model; for the mixture model the center draws of every earlier unit are replayed (their number depends on their values).
+ * MCHIP_ERR_UNSUPPORTED with Rand-EM. */
+int mc_replicate_starts(const mc_options *opt, const mc_data *dat, const mc_rng *base, int n_replicates, int null_K, int alt_K,
+			int n_init, mc_rng *starts);
+/* replicate b alone (no table: one jump, or the walk with the running state only) */
+int mc_replicate_start(const mc_options *opt, const mc_data *dat, const mc_rng *base, int b, int null_K, int alt_K, int n_init,
+		       mc_rng *start);
 
 void mc_em(const mc_options *opt, const mc_data *dat, mc_model *mod);			/* em_alg.c:44 */
 int mc_em_step(const mc_options *opt, const mc_data *dat, mc_model *mod);		/* em_alg.c:195 */

@@ -3,6 +3,9 @@
  * Rand-EM for both models (reference rnd_init.c:103-160, 192-339, 412-444, 496-705).  Rand-EM is an opt-in: the
  * reference's own command line never selects it (initialization_procedure stays NOTHING, multiclust.c:935,1547-1552).
  *
+ * The mixture model's random centers: the host draws the K center individuals, the device does the rest (distances, counts,
+ * parameters); the host body stays behind MC_HOST_INIT and serves Rand-EM.
+ *
  * What stays on the host is what is sequential by construction: rand() is consumed locus by locus, and how much a locus
  * consumes depends on the centers drawn for it (uniqueness retries, copies that match no center).  That walk touches
  * only a table of allele counts per locus (built once per model from the observed haplotypes); the I*L*ploidy-sized work
@@ -15,8 +18,27 @@
 #include <string.h>
 
 /* ------------------------------------------------------------------ mixture model: random centers */
-/* random_individual_center (rnd_init.c:192-259): K distinct center individuals, every other individual joins the center
- * with the smallest L1 distance between allele-count vectors (first minimum wins; a center joins itself) */
+/* the K center draws of random_individual_center (rnd_init.c:206-218): rand() % I, rejection until distinct -- a clash redraws
+ * and the comparison starts over.  K = 1 draws nothing (rnd_init.c:199-204). */
+static void draw_centers(int I, int K, mc_rng *rng, int *center)
+{
+	if (K == 1) { center[0] = 0; return; }
+	for (int k = 0; k < K; k++) {
+		int c = mc_rand(rng) % I;
+		for (int j = 0; j < k;) {
+			if (center[j] == c) { c = mc_rand(rng) % I; j = 0; }
+			else j++;
+		}
+		center[k] = c;
+	}
+}
+
+/* test hook for tests/test_mixture_device_cpu.py: the center walk needs no model and no device */
+void mc_test_center_walk(int I, int K, mc_rng *rng, int *center) { draw_centers(I, K, rng, center); }
+
+/* random_individual_center (rnd_init.c:192-259) on the host (MC_HOST_INIT, Rand-EM): K distinct center individuals, every other
+ * individual joins the center with the smallest L1 distance between allele-count vectors (first minimum wins; a center joins
+ * itself) */
 static void mixture_centers(const mc_data *dat, int K, mc_rng *rng, int *I_K, int assign)
 {
 	const int I = dat->I, L = dat->L, pl = dat->ploidy;
@@ -26,14 +48,7 @@ static void mixture_centers(const mc_data *dat, int K, mc_rng *rng, int *I_K, in
 		if (assign) memset(I_K, 0, sizeof(int) * (size_t)I);
 		return;
 	}
-	for (int k = 0; k < K; k++) {		/* rejection until distinct: a clash redraws and the comparison starts over (rnd_init.c:206-218) */
-		int c = mc_rand(rng) % I;
-		for (int j = 0; j < k;) {
-			if (center[j] == c) { c = mc_rand(rng) % I; j = 0; }
-			else j++;
-		}
-		center[k] = c;
-	}
+	draw_centers(I, K, rng, center);
 	if (!assign) return;
 	for (int i = 0; i < I; i++) {
 		I_K[i] = 0;
@@ -97,8 +112,20 @@ static int mixture_parameters(const mc_data *dat, mc_model *mod, const int *I_K)
 	return rc;
 }
 
+/* The centers are a handful of data-independent draws: they stay on the host.  The distances of every individual to the K
+ * centers, the allele counts per cluster and the parameters are the device's (mchip_init_from_individual_centers: the data set
+ * the model holds, so a replicate generated on the device needs no host copy); MC_HOST_INIT keeps the host body, which reads
+ * dat->geno. */
 int mc_initialize_mixture(const mc_data *dat, mc_model *mod, mc_rng *rng)
 {
+	if (!getenv("MC_HOST_INIT")) {
+		int32_t center[mod->K];
+		int drawn[mod->K];
+		draw_centers(dat->I, mod->K, rng, drawn);
+		for (int k = 0; k < mod->K; k++) center[k] = drawn[k];
+		if (!mchip_init_from_individual_centers) return MCHIP_ERR_UNSUPPORTED;	/* a stand-in device library (mc_host.h) */
+		return mchip_init_from_individual_centers(mod->dev, center, mod->tindex, NULL);
+	}
 	int *I_K = calloc((size_t)dat->I, sizeof(int));
 	if (!I_K) return MCHIP_ERR_ALLOC;
 	mixture_centers(dat, mod->K, rng, I_K, 1);
@@ -271,6 +298,57 @@ int mc_unit_starts(const mc_options *opt, const mc_data *dat, mc_model *mod, con
 			if (rc) return rc;
 		}
 	}
+	return 0;
+}
+
+/* Where every bootstrap replicate starts in the stream: starts[b] = the generator at the first draw of replicate b's data set,
+ * b = 0..n_replicates (the last entry is where the serial program stands after them), `base` = where the first one begins.  A
+ * replicate is its data set (mc_bootstrap_draws) and then n_init initialisations of the null_K model and of the alt_K model (one
+ * when K = 1, multiclust.c:630).  Admixture: a fixed number of draws per replicate, one jump each.  Mixture: an initialisation
+ * consumes only its center draws, whose number depends on their values (clashes redraw), so the walk replays them -- K draws or
+ * a few more per unit, none for K = 1.  Rand-EM: no cheap walk on a data set that does not exist yet; refused. */
+static uint64_t admixture_replicate_draws(const mc_options *opt, const mc_data *dat, int null_K, int alt_K, int n_init)
+{
+	const uint64_t units0 = null_K == 1 ? 1 : (uint64_t)n_init, units1 = alt_K == 1 ? 1 : (uint64_t)n_init;
+	return mc_bootstrap_draws(opt, dat) + (units0 + units1) * mc_draws_per_init(opt, dat, alt_K);
+}
+
+/* moves rng from the start of one mixture replicate to the start of the next */
+static void mixture_replicate_advance(const mc_options *opt, const mc_data *dat, mc_rng *rng, int null_K, int alt_K, int n_init)
+{
+	mc_rng_jump(rng, mc_bootstrap_draws(opt, dat));
+	for (int h = 0; h < 2; h++) {
+		const int K = h ? alt_K : null_K;
+		int center[K];
+		for (int u = 0; u < (K == 1 ? 1 : n_init); u++) draw_centers(dat->I, K, rng, center);
+	}
+}
+
+int mc_replicate_starts(const mc_options *opt, const mc_data *dat, const mc_rng *base, int n_replicates, int null_K, int alt_K,
+			int n_init, mc_rng *starts)
+{
+	mc_rng rng = *base;
+	if (opt->initialization_procedure == MC_RAND_EM) return MCHIP_ERR_UNSUPPORTED;
+	if (null_K < 1 || alt_K < 1 || n_replicates < 0) return MCHIP_ERR_INVALID;
+	for (int b = 0; b <= n_replicates; b++) {
+		starts[b] = rng;
+		if (b == n_replicates) break;
+		if (opt->admixture) mc_rng_jump(&rng, admixture_replicate_draws(opt, dat, null_K, alt_K, n_init));
+		else mixture_replicate_advance(opt, dat, &rng, null_K, alt_K, n_init);
+	}
+	return 0;
+}
+
+/* the same for replicate b alone, nothing stored: one jump for the admixture model, the walk over the b earlier replicates with
+ * only the running state for the mixture model (what mc_fit_replicate needs) */
+int mc_replicate_start(const mc_options *opt, const mc_data *dat, const mc_rng *base, int b, int null_K, int alt_K, int n_init,
+		       mc_rng *start)
+{
+	if (opt->initialization_procedure == MC_RAND_EM) return MCHIP_ERR_UNSUPPORTED;
+	if (null_K < 1 || alt_K < 1 || b < 0) return MCHIP_ERR_INVALID;
+	*start = *base;
+	if (opt->admixture) mc_rng_jump(start, (uint64_t)b * admixture_replicate_draws(opt, dat, null_K, alt_K, n_init));
+	else for (int x = 0; x < b; x++) mixture_replicate_advance(opt, dat, start, null_K, alt_K, n_init);
 	return 0;
 }
 

@@ -11,7 +11,8 @@
  * Extensions: --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
  * the node (one host thread and one context per GPU, units u = d, d+n, ..., each starting from the serial program's
  * rand() position by jump-ahead), with a single RCCL all-reduce of the per-unit result table, after which the serial
- * bookkeeping is replayed in unit order (admixture model, fixed number of initialisations).
+ * bookkeeping is replayed in unit order (admixture model, fixed number of initialisations).  Bootstrap replicates (-b) are split
+ * over the same workers as whole units for both models; the mixture model's initialisations are not sharded.
  */
 #include "mc_cli.h"
 
@@ -45,7 +46,8 @@ static void usage(FILE *fp, const char *prog)
 		"  -d <dir> -o <stem>  output directory / file stem      -R  R-formatted STRUCTURE file\n"
 		"  --missing <n> missing-data code (default -9)           -M  print only the maximum log likelihood\n"
 		"  -v [level]    verbosity                                --device <n>  HIP device index\n"
-		"  --gpus <n>    shard the initialisations over n GPUs (admixture; one RCCL all-reduce of the results)\n"
+		"  --gpus <n>    shard the initialisations (admixture) and the bootstrap replicates (both models) over n GPUs;\n"
+		"                one RCCL all-reduce of each result table\n"
 		"  --streams <n> n concurrent fits per GPU, each on its own stream (small data sets do not fill a GPU)\n"
 		"  -P <file> -Q <file>  initial allele frequencies p[k][l][0] (L*K numbers, biallelic loci) and mixing proportions of the admixture model\n"
 		"  --randem      Rand-EM initialisation: the best of -m <n> (50) candidates from random allele centers\n"
@@ -570,17 +572,21 @@ DONE:
 	return rc;
 }
 
-static int shardable(const mc_cli_options *o)
+/* whole bootstrap replicates can be handed to workers: either model */
+static int replicates_shardable(const mc_cli_options *o)
 {
 	/* MC_FORCE_SHARDED=1 sends even --gpus 1 through the sharded path (threads, jump-ahead, RCCL exchange, replay): the
 	 * single-GPU rehearsal used by tests/test_gpu_cli.py */
 	const int force = getenv("MC_FORCE_SHARDED") != NULL;
-	return (o->n_gpus > 1 || o->n_streams > 1 || (force && o->n_gpus == 1)) && o->em.admixture && !o->target_revisit && !o->target_ll && !o->em.n_seconds &&
+	return (o->n_gpus > 1 || o->n_streams > 1 || (force && o->n_gpus == 1)) && !o->target_revisit && !o->target_ll && !o->em.n_seconds &&
 	       !(o->pfile && o->qfile);	/* initial parameters from files: every unit would be the same fit */
 }
 
+/* the initialisations of one fit can be handed to workers: the admixture model only */
+static int shardable(const mc_cli_options *o) { return replicates_shardable(o) && o->em.admixture; }
+
 /* estimate_model (multiclust.c:365-452): K = min_K..max_K, or H0 / HA when bootstrapping */
-/* sim != NULL: the models are fitted to the bootstrap data set it describes, generated on each device (admixture) */
+/* sim != NULL: the models are fitted to the bootstrap data set it describes, generated on each device */
 static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, int bootstrap, int *total_iter,
 			  const mc_simulation *sim)
 {
@@ -635,8 +641,9 @@ static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const m
 }
 
 /* ---- bootstrap replicates sharded over the GPUs of the node as whole units ----
- * Replicate b = data set + H0 fits + HA fits consumes a data-independent number of rand() draws, so device x takes
- * replicates x, x + n_dev, ... each from the stream jumped to where the serial program would be, generates the data
+ * Where replicate b = data set + H0 fits + HA fits begins in the rand() stream does not depend on any fit (mc_replicate_starts:
+ * a jump per replicate for the admixture model, the replay of the center draws for the mixture model), so device x takes
+ * replicates x, x + n_dev, ... each from where the serial program would be, generates the data
  * set on its own GPU and fits both models there; its stdout goes to a buffer.  One RCCL all-reduce completes the table
  * of test statistics on every device; the buffers are then printed in replicate order with the running p-value. */
 typedef struct bs_worker {
@@ -645,7 +652,7 @@ typedef struct bs_worker {
 	const mc_data *md;
 	const run_state *st;		/* observed-data results: null_K, alt_K, H0 MLEs, ts_obs */
 	int index, n_dev;
-	uint64_t draws_per_replicate;
+	const mc_rng *starts;		/* [n_bootstrap + 1]: the serial stream's state at the start of every replicate */
 	double *ts;			/* [n_bootstrap], shared: worker x writes entries b = x, x + n_dev, ... */
 	char **text;			/* [n_bootstrap] captured stdout of each replicate */
 	int rc;
@@ -669,7 +676,7 @@ static void *bs_main(void *arg)
 		mc_simulation gen;
 		size_t len = 0;
 		ls.mle_q = w->st->mle_q; ls.mle_p = w->st->mle_p;	/* read only */
-		mc_rng_jump(&ls.rng, (uint64_t)b * w->draws_per_replicate);
+		ls.rng = w->starts[b];
 		if (!(ls.out = open_memstream(&w->text[b], &len))) { w->rc = MCHIP_ERR_ALLOC; free(own_I_K); return NULL; }
 		fprintf(ls.out, "Bootstrap dataset %d (of %d):", b + 1, w->o->n_bootstrap);
 		mc_simulation_begin(&gen, &ow.em, w->md, ls.mle_K, ls.mle_q, ls.mle_p, &ls.rng);
@@ -687,18 +694,18 @@ static void *bs_main(void *arg)
 static int run_bootstrap_sharded(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, int *ntime_out)
 {
 	const int n_dev = n_workers(o), n_gpus = o->n_gpus < 1 ? 1 : o->n_gpus, B = o->n_bootstrap;
-	const uint64_t per_init = mc_draws_per_init(&o->em, md, st->alt_K);
-	const uint64_t units0 = st->null_K == 1 ? 1 : (uint64_t)o->n_init, units1 = (uint64_t)o->n_init;
+	mc_rng *starts = calloc((size_t)B + 1, sizeof *starts);
 	bs_worker *w = calloc((size_t)n_dev, sizeof *w);
 	pthread_t *th = calloc((size_t)n_dev, sizeof *th);
 	int *joinable = calloc((size_t)n_dev, sizeof *joinable);
 	double *ts = calloc((size_t)B, sizeof *ts), **tab = calloc((size_t)n_gpus, sizeof *tab);
 	char **text = calloc((size_t)B, sizeof *text);
 	int rc = 0, ntime = 0;
-	if (!w || !th || !joinable || !ts || !tab || !text) { rc = MCHIP_ERR_ALLOC; goto DONE; }
+	if (!w || !th || !joinable || !ts || !tab || !text || !starts) { rc = MCHIP_ERR_ALLOC; goto DONE; }
+	if ((rc = mc_replicate_starts(&o->em, md, &st->rng, B, st->null_K, st->alt_K, o->n_init, starts))) goto DONE;
 	for (int x = 0; x < n_dev; x++) {
 		w[x].o = o; w[x].d = d; w[x].md = md; w[x].st = st; w[x].index = x; w[x].n_dev = n_dev;
-		w[x].draws_per_replicate = mc_bootstrap_draws(&o->em, md) + (units0 + units1) * per_init;
+		w[x].starts = starts;
 		w[x].ts = ts; w[x].text = text;
 		if (pthread_create(&th[x], NULL, bs_main, &w[x])) bs_main(&w[x]);
 		else joinable[x] = 1;
@@ -706,7 +713,7 @@ static int run_bootstrap_sharded(const mc_cli_options *o, const mc_cli_data *d, 
 	for (int x = 0; x < n_dev; x++) if (joinable[x]) pthread_join(th[x], NULL);
 	for (int x = 0; x < n_dev; x++) if (w[x].rc) rc = w[x].rc;
 	if (rc) goto DONE;
-	mc_rng_jump(&st->rng, (uint64_t)B * w[0].draws_per_replicate);
+	st->rng = starts[B];
 	/* the one exchange: rows (test statistic, fitted flag) of the replicates each device's workers own, summed over devices */
 	for (int g = 0; g < n_gpus; g++)
 		if (!(tab[g] = calloc((size_t)B * 2, sizeof(double)))) { rc = MCHIP_ERR_ALLOC; goto DONE; }
@@ -727,7 +734,7 @@ static int run_bootstrap_sharded(const mc_cli_options *o, const mc_cli_data *d, 
 DONE:
 	if (tab) for (int x = 0; x < n_gpus; x++) free(tab[x]);
 	if (text) for (int b = 0; b < B; b++) free(text[b]);
-	free(w); free(th); free(joinable); free(ts); free(tab); free(text);
+	free(w); free(th); free(joinable); free(ts); free(tab); free(text); free(starts);
 	return rc;
 }
 
@@ -768,8 +775,14 @@ int main(int argc, const char **argv)
 	/* the reference seeds libc only when -r is given; otherwise rand() runs from glibc's default seed 1 although the
 	 * banner prints 1234567 */
 	mc_srand(&st.rng, o.seed_given ? o.em.seed : 1u);
-	if ((o.n_gpus > 1 || o.n_streams > 1) && !shardable(&o))
-		fprintf(stderr, "WARNING: --gpus / --streams apply to the admixture model with a fixed number of initialisations; running one fit at a time on one GPU\n");
+	if ((o.n_gpus > 1 || o.n_streams > 1) && !shardable(&o)) {
+		if (!o.em.admixture && o.n_bootstrap >= n_workers(&o) && replicates_shardable(&o) && !getenv("MC_HOST_BOOTSTRAP") &&
+		    !getenv("MC_HOST_INIT") && o.em.initialization_procedure != MC_RAND_EM)	/* the conditions of by_replicate below */
+			fprintf(stderr, "WARNING: --gpus / --streams split the bootstrap replicates of the mixture model; the two fits of the observed data run "
+				"one initialisation at a time on one GPU\n");
+		else
+			fprintf(stderr, "WARNING: --gpus / --streams apply to the admixture model with a fixed number of initialisations; running one fit at a time on one GPU\n");
+	}
 
 	if (o.n_repeat > 1 || o.repeat_seconds) {	/* timed_model_estimation (multiclust.c:201-347): same lines, same statistics */
 		const clock_t start = clock();
@@ -842,16 +855,18 @@ int main(int argc, const char **argv)
 	if (o.parallel) printf("%f\n", st.sum.max_logL);	/* multiclust.c:143-145 */
 
 	if (o.n_bootstrap) {	/* run_bootstrap (multiclust.c:675-708) */
-		/* admixture: the replicate is generated on the device(s) from the stream position (no host data set, no upload);
-		 * mixture (or MC_HOST_BOOTSTRAP): drawn on the host and uploaded like any data set */
-		const int on_device = o.em.admixture && !getenv("MC_HOST_BOOTSTRAP");
+		/* the replicate is generated on the device(s) from the stream position (no host data set, no upload), for both models;
+		 * MC_HOST_BOOTSTRAP: drawn on the host and uploaded like any data set.  The host form of the mixture initialisation
+		 * (MC_HOST_INIT) and its Rand-EM read the replicate on the host, so they take the host route too. */
+		const int on_device = !getenv("MC_HOST_BOOTSTRAP") &&
+				      (o.em.admixture || (!getenv("MC_HOST_INIT") && o.em.initialization_procedure != MC_RAND_EM));
 		uint8_t *orig = d.geno, *sim = on_device ? NULL : malloc((size_t)d.I * d.L * d.ploidy);
 		int ntime = 0;
 		if ((!on_device && !sim) || !st.mle_q) { rc = MCHIP_ERR_ALLOC; goto END; }
 		/* whole replicates per device when there is at least one for each; otherwise (or on one device) the replicates run in
 		 * turn and --gpus shards the initialisations inside each */
 		/* (Rand-EM draws a data-dependent number of values per initialisation: replicate b's place in the stream has no closed form) */
-		const int by_replicate = on_device && shardable(&o) && o.n_bootstrap >= n_workers(&o) && o.em.initialization_procedure != MC_RAND_EM;
+		const int by_replicate = on_device && replicates_shardable(&o) && o.n_bootstrap >= n_workers(&o) && o.em.initialization_procedure != MC_RAND_EM;
 		if (by_replicate && (rc = run_bootstrap_sharded(&o, &d, &md, &st, &ntime))) goto END;
 		mc_model *kept[2] = { NULL, NULL };
 		if (on_device && !shardable(&o)) st.sim_models = kept;
