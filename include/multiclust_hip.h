@@ -18,6 +18,7 @@
 #ifndef MULTICLUST_HIP_H
 #define MULTICLUST_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -60,6 +61,23 @@ int mchip_synchronize(mchip_context *ctx);
  */
 int mchip_set_genotypes(mchip_context *ctx, int I, int L, int ploidy,
 			const int32_t *uniquealleles, const uint8_t *geno);
+/*
+ * Upload one diploid biallelic data set in PLINK 1 packed form and unpack it on the device (an extension: the reference reads
+ * STRUCTURE text only).  bed points behind the three header bytes of a variant-major .bed file: L records, record l at
+ * bed + l * record_bytes (record_bytes >= ceil(I/4)), sample j of a record in byte j/4, bits 2(j%4) and 2(j%4)+1; the two bits
+ * (low bit first) mean 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2.  Padding bits of a record's last
+ * byte carry no sample, whatever they hold.
+ * The data set installed is, by definition, the one the STRUCTURE reader yields on the equivalent STRUCTURE file -- per
+ * individual two lines of L alleles: homozygous A1 -> 1 and 1, heterozygous -> 1 and 2, homozygous A2 -> 2 and 2, missing -> -9
+ * and -9 -- so with the reader's semantics (read_file.c:443-600): uniquealleles[l] = observed alleles + the phantom slot when
+ * the locus has a missing call, 0 when no call of the locus is observed; ascending allele indices (A1 -> 0 when observed,
+ * A2 -> 0 or 1); missing copies MCHIP_MISSING.  Exactly what mchip_set_genotypes(ctx, I, L, 2, uniquealleles, geno) installs for
+ * that data: mchip_get_genotypes, mchip_data_counts, mchip_empty_individuals, mchip_copy_genotypes and every fit behave the same
+ * afterwards, and any model is dropped.  uniquealleles_out receives the L allele counts (may be NULL).  I*L/4 bytes cross to the
+ * device instead of 2*I*L; the records are expanded straight into the kernels' two layouts, no [I][L][2] form exists on the way.
+ */
+int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes,
+			    int32_t *uniquealleles_out);
 /* Counted on the device when a data set is installed: cells (i, l, m) with ILM[i][l][m] > 0 -- the cells the reference's E step
  * visits (em_alg.c:338-342) and the unit the flop count of the path is stated in -- and non-missing allele copies. */
 int mchip_data_counts(mchip_context *ctx, uint64_t *nonempty_cells, uint64_t *allele_copies);

@@ -2019,6 +2019,55 @@ int mchip_set_genotypes(mchip_context *ctx, int I, int L, int ploidy, const int3
 	return install_raw(ctx, ctx->d_draw);
 }
 
+/* The packed records go up as they are; the locus pass tells the host the allele counts set_shape sizes the column tables from,
+ * the expand pass fills gtA / gtS (kernels: mchip_bed.hip).  No stream buffer (d_draw) and no k_relayout on this route. */
+int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int32_t *uniquealleles_out)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (I <= 0 || L <= 0 || !bed || record_bytes < ((size_t)I + 3) / 4)
+		return fail(ctx, MCHIP_ERR_INVALID, "set_genotypes_bed: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	const size_t bed_bytes = (size_t)L * record_bytes;
+	scoped_dev<uint8_t> d_bed, d_a1, d_seen;
+	scoped_dev<int32_t> d_ua;
+	HIPCHK(d_bed.alloc(bed_bytes + MCHIP_BED_PAD));
+	HIPCHK(d_a1.alloc((size_t)L));
+	HIPCHK(d_seen.alloc((size_t)I));
+	HIPCHK(d_ua.alloc((size_t)L));
+	int *d_bad = bad_flag(ctx);
+	HIPCHK(hipMemcpyAsync(d_bed.p, bed, bed_bytes, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_bed.p + bed_bytes, 0, MCHIP_BED_PAD, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
+	mchip_bed_locus_pass(ctx->stream, d_bed, record_bytes, I, L, d_ua, d_a1, d_bad);
+	HIPCHK(hipGetLastError());
+	std::vector<int32_t> ua((size_t)L);
+	int bad = 0;
+	HIPCHK(hipMemcpyAsync(ua.data(), d_ua.p, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	if (uniquealleles_out) memcpy(uniquealleles_out, ua.data(), sizeof(int32_t) * (size_t)L);
+	int rc = set_shape(ctx, I, L, 2, ua.data());
+	if (rc) return rc;
+	if (mchip_bed_expand(ctx->stream, d_bed, record_bytes, I, L, d_a1, ctx->d_gtA, ctx->d_gtS, d_seen)) {
+		free_data(ctx);
+		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "data set too large for the layout kernel%s", nullptr);
+	}
+	HIPCHK(hipGetLastError());
+	std::vector<uint8_t> seen((size_t)I);
+	HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	ctx->first_empty = -1;
+	ctx->empty_rows.clear();
+	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
+	for (int i = 0; i < I; i++)
+		if (!seen[i]) ctx->empty_rows.push_back(i);
+	if (!ctx->empty_rows.empty()) ctx->first_empty = ctx->empty_rows[0];
+	return install_layouts(ctx, (bad & 2) ? 1 : 0);
+}
+
 int mchip_copy_genotypes(mchip_context *ctx, const mchip_context *src)
 {
 	MCHIP_ENTRY();

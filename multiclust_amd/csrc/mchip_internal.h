@@ -188,6 +188,17 @@ struct mchip_ktable {
 
 const mchip_ktable *mchip_get_ktable(int K);
 
+/* PLINK .bed records on the device (mchip_bed.hip; mchip_set_genotypes_bed).  d_bed: L records of record_bytes bytes, the
+ * allocation at least MCHIP_BED_PAD bytes longer than that (records are read as dwords from any byte offset).
+ * Locus pass: ua[l] as the STRUCTURE reader counts it, a1[l] = 1 when allele A1 is observed at locus l (the one thing the recoding
+ * of a locus depends on), bit 1 of *flags set when any call is missing.  Expand pass: gtA and gtS of the ploidy-2 data set, padded
+ * with 0xFF like k_relayout's; seen[i] (zeroed by the caller) = 1 for every individual with an observed call.  Returns non-zero
+ * when the data set has too many tiles for one launch. */
+#define MCHIP_BED_PAD 8
+void mchip_bed_locus_pass(hipStream_t s, const uint8_t *d_bed, size_t record_bytes, int I, int L, int32_t *ua, uint8_t *a1, int *flags);
+int mchip_bed_expand(hipStream_t s, const uint8_t *d_bed, size_t record_bytes, int I, int L, const uint8_t *a1, uint8_t *gtA,
+		     uint8_t *gtS, uint8_t *seen);
+
 inline int mchip_ind_waves(int K, int tile_cols)
 {
 	/* (a buffer is rounded up to whole 1 KiB pieces where tiles are copied straight into LDS) */

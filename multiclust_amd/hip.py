@@ -48,6 +48,7 @@ def load():
         "mchip_last_error": ([vp], C.c_char_p),
         "mchip_synchronize": ([vp], i32),
         "mchip_set_genotypes": ([vp, i32, i32, i32, vp, vp], i32),
+        "mchip_set_genotypes_bed": ([vp, i32, i32, vp, C.c_size_t, vp], i32),
         "mchip_set_model": ([vp, i32, i32, i32, i32, C.c_double, C.c_double, i32], i32),
         "mchip_set_p": ([vp, i32, vp], i32),
         "mchip_get_p": ([vp, i32, vp], i32),
@@ -113,7 +114,7 @@ ABI_SYMBOLS = [
     "mchip_secant_dots", "mchip_accel_update", "mchip_multisecant_update", "mchip_profile_begin",
     "mchip_profile_end", "mchip_device_info", "mchip_comm_create", "mchip_comm_all_reduce", "mchip_comm_destroy",
     "mchip_comm_last_error", "mchip_comm_info", "mchip_progress_report", "mchip_progress_note",
-    "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers",
+    "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
 ]
 
 
@@ -150,6 +151,20 @@ class Context:
         I, L, p = geno.shape
         self._chk(self.lib.mchip_set_genotypes(self.h, I, L, p, ua.ctypes.data, geno.ctypes.data))
         self.I, self.L, self.ploidy, self.T = I, L, p, int(ua.sum())
+
+    def set_genotypes_bed(self, I, bed, record_bytes=None):
+        """PLINK 1 packed records [L][record_bytes] (the .bed file behind its three header bytes; record_bytes defaults to the
+        row length, at least ceil(I/4)), unpacked on the device (include/multiclust_hip.h); drops the model.  Returns the L
+        allele counts the data set was installed with."""
+        bed = np.ascontiguousarray(bed, dtype=np.uint8)
+        assert bed.ndim == 2
+        L = bed.shape[0]
+        rb = bed.shape[1] if record_bytes is None else record_bytes
+        assert rb == bed.shape[1] and rb >= (I + 3) // 4
+        ua = np.empty(L, dtype=np.int32)
+        self._chk(self.lib.mchip_set_genotypes_bed(self.h, I, L, bed.ctypes.data, rb, ua.ctypes.data))
+        self.I, self.L, self.ploidy, self.T = I, L, 2, int(ua.sum())
+        return ua
 
     def data_counts(self):
         """(cells with n_ic > 0, non-missing allele copies) of the data set held, counted on the device"""

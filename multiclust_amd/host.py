@@ -21,7 +21,8 @@ class McOptions(C.Structure):
 
 class McData(C.Structure):
     _fields_ = [("I", C.c_int), ("L", C.c_int), ("ploidy", C.c_int),
-                ("uniquealleles", C.c_void_p), ("geno", C.c_void_p), ("init_geno", C.c_void_p)]
+                ("uniquealleles", C.c_void_p), ("geno", C.c_void_p), ("init_geno", C.c_void_p),
+                ("bed", C.c_void_p), ("bed_record_bytes", C.c_size_t), ("lazy", C.c_void_p)]
 
 
 class McModel(C.Structure):
@@ -69,7 +70,7 @@ class CliOptions(C.Structure):
                 ("desired_ll", C.c_double), ("n_repeat", C.c_int), ("repeat_seconds", C.c_uint),
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
-                ("afile", C.c_char_p)]
+                ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
 
 
 class CliData(C.Structure):
@@ -78,7 +79,23 @@ class CliData(C.Structure):
                 ("interleaved", C.c_int), ("IL", C.POINTER(C.c_int)), ("uniquealleles", C.POINTER(C.c_int32)),
                 ("L_alleles", C.POINTER(C.POINTER(C.c_int))), ("geno", C.POINTER(C.c_uint8)),
                 ("names", C.POINTER(C.c_char_p)), ("locale", C.POINTER(C.c_int)), ("pops", C.POINTER(C.c_char_p)),
-                ("numpops", C.c_int), ("i_p", C.POINTER(C.c_int)), ("T", C.c_int), ("toff", C.POINTER(C.c_int32))]
+                ("numpops", C.c_int), ("i_p", C.POINTER(C.c_int)), ("T", C.c_int), ("toff", C.POINTER(C.c_int32)),
+                ("bed", C.POINTER(C.c_uint8)), ("bed_record_bytes", C.c_size_t), ("lazy", C.c_void_p)]
+
+
+def _cli_data_fields(d, geno):
+    """what both readers fill alike; L_alleles (the real alleles of every locus: uniquealleles less the phantom slot of a locus
+    with a missing copy) needs the genotype to know its lengths and is left out without it"""
+    ua = np.ctypeslib.as_array(d.uniquealleles, shape=(d.L,)).copy()
+    extra = {}
+    if geno is not None:
+        n_real = ua - ((geno == 0xFF).any(axis=(0, 2)) & (ua > 0))
+        extra["L_alleles"] = [[d.L_alleles[l][m] for m in range(int(n_real[l]))] for l in range(d.L)]
+    return dict(extra, I=d.I, L=d.L, ploidy=d.ploidy, T=d.T, M=d.M, missing_data=d.missing_data, interleaved=d.interleaved, ua=ua,
+                toff=np.ctypeslib.as_array(d.toff, shape=(d.L + 1,)).copy(),
+                locale=np.ctypeslib.as_array(d.locale, shape=(d.I,)).copy(), numpops=d.numpops,
+                names=[d.names[i].decode() for i in range(d.I)], pops=[d.pops[i].decode() for i in range(d.numpops)],
+                i_p=[d.i_p[n] for n in range(d.numpops)])
 
 
 def read_structure(path, ploidy=2, missing=-9, r_format=0):
@@ -94,12 +111,50 @@ def read_structure(path, ploidy=2, missing=-9, r_format=0):
     rc = lib.mc_read_structure(C.byref(o), C.byref(d))
     if rc:
         return rc, None
-    out = dict(I=d.I, L=d.L, ploidy=d.ploidy, T=d.T, M=d.M, missing_data=d.missing_data, interleaved=d.interleaved,
-               ua=np.ctypeslib.as_array(d.uniquealleles, shape=(d.L,)).copy(),
-               geno=np.ctypeslib.as_array(d.geno, shape=(d.I, d.L, d.ploidy)).copy(),
-               locale=np.ctypeslib.as_array(d.locale, shape=(d.I,)).copy(), numpops=d.numpops,
-               names=[d.names[i].decode() for i in range(d.I)], pops=[d.pops[i].decode() for i in range(d.numpops)],
-               i_p=[d.i_p[n] for n in range(d.numpops)])
+    geno = np.ctypeslib.as_array(d.geno, shape=(d.I, d.L, d.ploidy)).copy()
+    out = _cli_data_fields(d, geno)
+    out["geno"] = geno
+    lib.mc_free_data(C.byref(d))
+    return 0, out
+
+
+def bed_decode(I, bed):
+    """mc_bed_decode (host/mc_bed.c), the CPU form of the device's unpacking: packed records [L][record_bytes] ->
+    (uniquealleles [L], geno [I][L][2]) of the equivalent STRUCTURE file."""
+    lib = load()
+    lib.mc_bed_decode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.mc_bed_decode.restype = None
+    bed = np.ascontiguousarray(bed, dtype=np.uint8)
+    assert bed.ndim == 2 and bed.shape[1] >= (I + 3) // 4
+    L = bed.shape[0]
+    ua = np.empty(L, dtype=np.int32)
+    geno = np.empty((I, L, 2), dtype=np.uint8)
+    lib.mc_bed_decode(I, L, bed.ctypes.data, bed.shape[1], ua.ctypes.data, geno.ctypes.data)
+    return ua, geno
+
+
+def read_bed(prefix, decode=True):
+    """mc_read_bed (host/mc_bed.c) on the PLINK 1 fileset prefix.bed/.bim/.fam: (status, None) on failure, else (0, dict) with
+    the fields of read_structure.  The reader keeps the data set packed -- `bed` [L][record_bytes], geno_is_null says that it
+    built no genotype; `geno` (and L_alleles) come from mc_bed_decode on those records, unless decode is False."""
+    lib = load()
+    lib.mc_read_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
+    lib.mc_free_data.argtypes = [C.POINTER(CliData)]
+    o = CliOptions()
+    o.bed_prefix = prefix.encode()
+    o.ploidy = 2
+    d = CliData()
+    rc = lib.mc_read_bed(C.byref(o), C.byref(d))
+    if rc:
+        return rc, None
+    bed = np.ctypeslib.as_array(d.bed, shape=(d.L, d.bed_record_bytes)).copy()
+    geno = ua_dec = None
+    if decode:
+        ua_dec, geno = bed_decode(d.I, bed)
+    out = _cli_data_fields(d, geno)
+    out.update(geno_is_null=not bool(d.geno), bed=bed)
+    if decode:
+        out.update(geno=geno, ua_decoded=ua_dec)
     lib.mc_free_data(C.byref(d))
     return 0, out
 

@@ -44,6 +44,7 @@ typedef struct mc_cli_options {
 					 * stream; small data sets do not fill a GPU with one fit */
 	const char *pfile, *qfile;	/* -P / -Q: initial parameters of the admixture model from files (read_file.c:880-959) */
 	const char *afile;		/* -A: a partition of the individuals to compare the fitted one with (multiclust.c:1416-1418) */
+	const char *bed_prefix;		/* --bed (extension): read <prefix>.bed / .bim / .fam instead of the STRUCTURE file of -f */
 } mc_cli_options;
 
 typedef struct mc_cli_data {
@@ -61,11 +62,29 @@ typedef struct mc_cli_data {
 	int *i_p;			/* [numpops] individuals per locale */
 	int T;
 	int32_t *toff;			/* [L+1] */
+	/* a PLINK fileset (mc_read_bed) stays packed: geno is NULL; see mc_data in mc_host.h */
+	uint8_t *bed;			/* [L][bed_record_bytes]: the .bed file behind its three header bytes */
+	size_t bed_record_bytes;	/* ceil(I/4) */
+	struct mc_lazy_geno *lazy;
 } mc_cli_data;
 
 /* read_file + summarize_alleles + sufficient_statistics (read_file.c:38-300,443-663), default (allele-code) mode */
 int mc_read_structure(const mc_cli_options *opt, mc_cli_data *dat);
 void mc_free_data(mc_cli_data *dat);
+
+/* PLINK 1 binary fileset opt->bed_prefix + ".bed" / ".bim" / ".fam" (an extension: the reference reads STRUCTURE text only).
+ * The data set is BY DEFINITION what mc_read_structure yields on the equivalent STRUCTURE file -- a header of L locus names,
+ * then per individual of the .fam file, in its order, two lines "IID FID a_1 ... a_L" with homozygous A1 -> 1 / 1,
+ * heterozygous -> 1 / 2, homozygous A2 -> 2 / 2, missing -> -9 / -9 -- so names are the IIDs, locales the FIDs in order of
+ * first appearance, and uniquealleles, L_alleles, M, T, toff and missing_data are the reader's (a locus without an observed
+ * call has no allele column and does not set missing_data).  ploidy = 2; geno stays NULL, the records are kept packed (bed,
+ * bed_record_bytes) and models upload them as they are.  Returns 0 or the reference's exit status for the failure: a file that
+ * cannot be opened 5; magic bytes, sample-major mode, file size against the line counts of .bim and .fam 7. */
+int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat);
+/* The CPU form of the device's unpacking: L records of record_bytes bytes (sample j of a record in byte j/4, bits 2(j%4) and
+ * 2(j%4)+1: 0 homozygous A1, 1 missing, 2 heterozygous, 3 homozygous A2; padding bits ignored) -> uniquealleles[L] and
+ * geno[I][L][2] of the equivalent STRUCTURE file.  Either output may be NULL. */
+void mc_bed_decode(int I, int L, const uint8_t *bed, size_t record_bytes, int32_t *uniquealleles, uint8_t *geno);
 
 /* what a finished initialisation hands to the writers */
 typedef struct mc_fit_view {

@@ -125,6 +125,28 @@ static int simulate(mchip_context *dev, const mc_options *opt, const mc_data *da
 					sim->q, sim->p);
 }
 
+const uint8_t *mc_data_geno(const mc_data *dat)
+{
+	if (dat->geno || !dat->bed || !dat->lazy) return dat->geno;
+	return dat->lazy->get(dat->lazy, dat);
+}
+
+/* a data set held packed goes up packed; a stand-in device library without the entry (mc_host.h) gets the decoded form */
+static int upload_packed(mchip_context *dev, const mc_data *dat)
+{
+	if (mchip_set_genotypes_bed) {
+		int32_t *ua = malloc(sizeof *ua * (size_t)dat->L);
+		if (!ua) return MCHIP_ERR_ALLOC;
+		int rc = mchip_set_genotypes_bed(dev, dat->I, dat->L, dat->bed, dat->bed_record_bytes, ua);
+		if (!rc && memcmp(ua, dat->uniquealleles, sizeof *ua * (size_t)dat->L)) rc = MCHIP_ERR_INVALID;	/* (the reader counted them from the same bytes) */
+		free(ua);
+		return rc;
+	}
+	const uint8_t *geno = mc_data_geno(dat);
+	if (!geno) return MCHIP_ERR_ALLOC;
+	return mchip_set_genotypes(dev, dat->I, dat->L, dat->ploidy, dat->uniquealleles, geno);
+}
+
 static int model_create(mc_model **out, const mc_options *opt, const mc_data *dat, int K, int device, const mc_simulation *sim,
 			const mc_model *like)
 {
@@ -144,13 +166,16 @@ static int model_create(mc_model **out, const mc_options *opt, const mc_data *da
 		rc = mchip_copy_genotypes(mod->dev, like->dev);
 	else if (sim)
 		rc = simulate(mod->dev, opt, dat, sim);
+	else if (!dat->geno && dat->bed)
+		rc = upload_packed(mod->dev, dat);
 	else
 		rc = mchip_set_genotypes(mod->dev, dat->I, dat->L, dat->ploidy, dat->uniquealleles, dat->geno);
+	if (!rc && getenv("MC_READER_TIMING")) fprintf(stderr, "INFO [mc_em.c]: data set installed on device %d\n", device);
 	/* admixture fits to a bootstrap data set initialise from the observed haplotypes (rnd_init.c:471): dat->geno when the data set
 	 * was generated on the device, dat->init_geno when the caller uploaded a replicate as dat->geno.  (The mixture model's
 	 * initialisation reads the simulated data set itself, dat->ILM: nothing to install.) */
 	if (!rc && opt->admixture && (sim || like || dat->init_geno))
-		rc = mchip_set_init_genotypes(mod->dev, (sim || like) ? dat->geno : dat->init_geno);
+		rc = mchip_set_init_genotypes(mod->dev, (sim || like) ? mc_data_geno(dat) : dat->init_geno);
 	if (rc || (rc = mchip_set_model(mod->dev, K, opt->admixture, opt->eta_constrained, opt->do_projection,
 					opt->eta_lower_bound, opt->p_lower_bound, opt->accel_scheme ? opt->q : 0))) {
 		fprintf(stderr, "ERROR [mc_em.c::mc_model_create]: %s\n", mchip_last_error(mod->dev));

@@ -28,6 +28,8 @@ extern "C" {
 #if defined(__GNUC__) && !defined(__cplusplus)
 extern __typeof__(mchip_simulate_genotypes_mixture) mchip_simulate_genotypes_mixture __attribute__((weak));
 extern __typeof__(mchip_init_from_individual_centers) mchip_init_from_individual_centers __attribute__((weak));
+/* the same for the packed upload: without it the host decodes the records and uploads the genotype as before */
+extern __typeof__(mchip_set_genotypes_bed) mchip_set_genotypes_bed __attribute__((weak));
 #endif
 
 /* acceleration schemes (reference multiclust.h:125-131; 5, 6 = QN with q = 2, 3, multiclust.c:818-820) */
@@ -66,7 +68,19 @@ typedef struct mc_data {	/* flat form of reference struct _data's genotype field
 	const uint8_t *geno;		/* [I][L][ploidy] allele indices, MCHIP_MISSING = 0xFF */
 	const uint8_t *init_geno;	/* NULL, or the observed data set while `geno` is a bootstrap replicate: the random
 					 * partition of the admixture model keeps reading dat->IL (rnd_init.c:471) */
+	/* a data set read from a PLINK .bed file (mc_bed.c) is held packed: geno is NULL, models upload `bed`
+	 * (mchip_set_genotypes_bed), and what reads the genotype on the host asks mc_data_geno() for it */
+	const uint8_t *bed;		/* NULL, or L records of bed_record_bytes bytes (the file behind its three header bytes) */
+	size_t bed_record_bytes;
+	struct mc_lazy_geno *lazy;	/* decodes `bed` on first need and keeps the result */
 } mc_data;
+
+typedef struct mc_lazy_geno {	/* (function pointers: the EM layer links without the .bed reader) */
+	const uint8_t *(*get)(struct mc_lazy_geno *self, const mc_data *dat);	/* [I][L][2], NULL when out of memory; thread-safe */
+	void (*release)(struct mc_lazy_geno *self);
+} mc_lazy_geno;
+/* dat->geno, or the decoded form of a packed data set */
+const uint8_t *mc_data_geno(const mc_data *dat);
 
 typedef struct mc_model {	/* EM-layer state of reference struct _model (multiclust.h:259-360) */
 	int K;

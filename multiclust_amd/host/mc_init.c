@@ -42,6 +42,7 @@ void mc_test_center_walk(int I, int K, mc_rng *rng, int *center) { draw_centers(
 static void mixture_centers(const mc_data *dat, int K, mc_rng *rng, int *I_K, int assign)
 {
 	const int I = dat->I, L = dat->L, pl = dat->ploidy;
+	const uint8_t *geno = assign ? mc_data_geno(dat) : NULL;
 	int center[K];
 	int cnt[256];
 	if (K == 1) {
@@ -49,7 +50,7 @@ static void mixture_centers(const mc_data *dat, int K, mc_rng *rng, int *I_K, in
 		return;
 	}
 	draw_centers(I, K, rng, center);
-	if (!assign) return;
+	if (!assign || !geno) return;	/* (no genotype: out of memory while decoding a packed data set; mixture_parameters reports it) */
 	for (int i = 0; i < I; i++) {
 		I_K[i] = 0;
 		if (i == center[0]) continue;
@@ -59,8 +60,8 @@ static void mixture_centers(const mc_data *dat, int K, mc_rng *rng, int *I_K, in
 			double diff = 0;
 			for (int l = 0; l < L; l++) {
 				const int M = dat->uniquealleles[l];
-				const uint8_t *gi = dat->geno + ((size_t)i * L + l) * pl;
-				const uint8_t *gc = dat->geno + ((size_t)center[k] * L + l) * pl;
+				const uint8_t *gi = geno + ((size_t)i * L + l) * pl;
+				const uint8_t *gc = geno + ((size_t)center[k] * L + l) * pl;
 				for (int m = 0; m < M; m++) cnt[m] = 0;
 				for (int a = 0; a < pl; a++) {
 					if (gi[a] != MCHIP_MISSING) cnt[gi[a]]++;
@@ -78,8 +79,9 @@ static void mixture_centers(const mc_data *dat, int K, mc_rng *rng, int *I_K, in
 static int mixture_parameters(const mc_data *dat, mc_model *mod, const int *I_K)
 {
 	const int I = dat->I, L = dat->L, pl = dat->ploidy, K = mod->K;
+	const uint8_t *geno = mc_data_geno(dat);
 	int *toff = malloc(sizeof(int) * ((size_t)L + 1));
-	if (!toff) return MCHIP_ERR_ALLOC;
+	if (!toff || !geno) { free(toff); return MCHIP_ERR_ALLOC; }
 	toff[0] = 0;
 	for (int l = 0; l < L; l++) toff[l + 1] = toff[l] + dat->uniquealleles[l];
 	const int T = toff[L];
@@ -93,7 +95,7 @@ static int mixture_parameters(const mc_data *dat, mc_model *mod, const int *I_K)
 	for (int i = 0; i < I; i++)
 		for (int l = 0; l < L; l++)
 			for (int a = 0; a < pl; a++) {
-				const uint8_t m = dat->geno[((size_t)i * L + l) * pl + a];
+				const uint8_t m = geno[((size_t)i * L + l) * pl + a];
 				if (m != MCHIP_MISSING) p[(size_t)I_K[i] * T + toff[l] + m] += 1.0;
 			}
 	for (int k = 0; k < K; k++)
@@ -153,9 +155,9 @@ void mc_init_cache_free(mc_model *mod)
 static init_cache *get_cache(const mc_data *dat, mc_model *mod)
 {
 	if (mod->init_cache) return mod->init_cache;
-	const uint8_t *geno = dat->init_geno ? dat->init_geno : dat->geno;
+	const uint8_t *geno = dat->init_geno ? dat->init_geno : mc_data_geno(dat);
 	const int I = dat->I, L = dat->L, pl = dat->ploidy;
-	init_cache *c = calloc(1, sizeof *c);
+	init_cache *c = geno ? calloc(1, sizeof *c) : NULL;
 	if (!c) return NULL;
 	c->L = L;
 	c->toff = malloc(sizeof(int64_t) * ((size_t)L + 1));

@@ -32,7 +32,7 @@ static const char *accel_abbrev(const mc_cli_options *o, char *buf)
 static void usage(FILE *fp, const char *prog)
 {
 	fprintf(fp,
-		"Usage: %s -f <file> [-a] [-k <K> | -1 <minK> -2 <maxK>] [options]\n"
+		"Usage: %s -f <file> | --bed <prefix> [-a] [-k <K> | -1 <minK> -2 <maxK>] [options]\n"
 		"  -a            admixture model (default: mixture)      -c  shared mixing proportions (with -a)\n"
 		"  -k <n>        number of clusters K (default 6)        -1 <n>, -2 <n>  minimum / maximum K\n"
 		"  -n <n>        random initialisations (default 50)     -r <seed>  random seed\n"
@@ -51,7 +51,9 @@ static void usage(FILE *fp, const char *prog)
 		"  --streams <n> n concurrent fits per GPU, each on its own stream (small data sets do not fill a GPU)\n"
 		"  -P <file> -Q <file>  initial allele frequencies p[k][l][0] (L*K numbers, biallelic loci) and mixing proportions of the admixture model\n"
 		"  --randem      Rand-EM initialisation: the best of -m <n> (50) candidates from random allele centers\n"
-		"  -A <file>     a partition of the individuals (labels 1, 2, ...): the adjusted Rand index of the fitted one is reported\n", prog);
+		"  -A <file>     a partition of the individuals (labels 1, 2, ...): the adjusted Rand index of the fitted one is reported\n"
+		"  --bed <prefix>  read the PLINK 1 fileset <prefix>.bed/.bim/.fam instead of -f (diploid; not with -f, -R or -p other than 2;\n"
+		"                --missing is ignored); the 2-bit records are uploaded as they are and unpacked on the GPU\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -103,7 +105,8 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 		switch (a) {
 		case 'a': o->em.admixture = 1; break;
 		case 'b':
-			if (!strncmp(w, "bou", 3)) { if (arg_dbl(argc, argv, ++i, &d) || d < 0) BAD("--bound"); o->em.lower_bound = d; }
+			if (!strncmp(w, "bed", 3)) { if (++i >= argc) BAD("--bed"); o->bed_prefix = argv[i]; }
+			else if (!strncmp(w, "bou", 3)) { if (arg_dbl(argc, argv, ++i, &d) || d < 0) BAD("--bound"); o->em.lower_bound = d; }
 			else { if (arg_int(argc, argv, ++i, &v) || v < 0) BAD("-b"); o->n_bootstrap = (int)v; }
 			break;
 		case 'c': o->em.eta_constrained = 1; break;
@@ -196,6 +199,19 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: unknown option (argument '%s'); try -h\n", argv[i]);
 			return MC_EXIT_INVALID_CMD_OPTION;
 		}
+	}
+	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
+		if (o->filename || o->R_format || o->ploidy != 2) {
+			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
+			return MC_EXIT_INVALID_USER_SETUP;
+		}
+		char *name = malloc(strlen(o->bed_prefix) + 5);		/* (lives as long as the options) */
+		if (!name) return MC_EXIT_MEMORY_ALLOCATION;
+		strcpy(name, o->bed_prefix);
+		strcat(name, ".bed");
+		o->filename = o->filename_file = name;
+		for (size_t x = strlen(name); x-- > 1;)
+			if (name[x] == '/') { o->filename_file = &name[x + 1]; break; }
 	}
 	if (!o->filename) {
 		fprintf(stderr, "ERROR [mc_main.c::parse_options]: You must specify the data file with command line option '-f'.  Try '-h' for help.\n");
@@ -752,12 +768,12 @@ int main(int argc, const char **argv)
 	mchip_progress_note("parse_options");
 	defaults(&o);
 	if ((rc = parse_options(&o, argc, argv))) return rc;	/* -h included: the reference's -h leaves with status 1 */
-	mchip_progress_note("mc_read_structure");
-	if ((rc = mc_read_structure(&o, &d))) return rc;
+	mchip_progress_note(o.bed_prefix ? "mc_read_bed" : "mc_read_structure");
+	if ((rc = o.bed_prefix ? mc_read_bed(&o, &d) : mc_read_structure(&o, &d))) return rc;
 	mchip_progress_note("estimate_model");
 	if (o.em.verbosity >= MC_TALKATIVE)
 		fprintf(stderr, "INFO: Finished reading data: %d %d-ploid individuals at %d loci.\n", d.I, d.ploidy, d.L);
-	mc_data md = { d.I, d.L, d.ploidy, d.uniquealleles, d.geno, NULL };
+	mc_data md = { d.I, d.L, d.ploidy, d.uniquealleles, d.geno, NULL, d.bed, d.bed_record_bytes, d.lazy };
 	/* synchronize (multiclust.c:807-893) */
 	if (mc_synchronize(&o.em, &md)) return MC_EXIT_INVALID_USER_SETUP;
 	if (d.I < o.max_K) { fprintf(stderr, "ERROR: Maximum number of clusters (%d) (set with command-line argument -k) cannot exceed the number of individuals (%d)\n", o.max_K, d.I); return MC_EXIT_INVALID_USER_SETUP; }
@@ -861,8 +877,10 @@ int main(int argc, const char **argv)
 		const int on_device = !getenv("MC_HOST_BOOTSTRAP") &&
 				      (o.em.admixture || (!getenv("MC_HOST_INIT") && o.em.initialization_procedure != MC_RAND_EM));
 		uint8_t *orig = d.geno, *sim = on_device ? NULL : malloc((size_t)d.I * d.L * d.ploidy);
+		/* the observed haplotypes the fits to an uploaded replicate initialise from (decoded here when the data set is held packed) */
+		const uint8_t *observed = on_device ? NULL : mc_data_geno(&md);
 		int ntime = 0;
-		if ((!on_device && !sim) || !st.mle_q) { rc = MCHIP_ERR_ALLOC; goto END; }
+		if ((!on_device && (!sim || !observed)) || !st.mle_q) { rc = MCHIP_ERR_ALLOC; goto END; }
 		/* whole replicates per device when there is at least one for each; otherwise (or on one device) the replicates run in
 		 * turn and --gpus shards the initialisations inside each */
 		/* (Rand-EM draws a data-dependent number of values per initialisation: replicate b's place in the stream has no closed form) */
@@ -879,7 +897,7 @@ int main(int argc, const char **argv)
 			} else {
 				mc_bootstrap_genotypes(&o.em, &md, st.mle_K, st.mle_q, st.mle_p, &st.rng, sim);
 				md.geno = d.geno = sim;
-				md.init_geno = orig;
+				md.init_geno = observed;
 				rc = estimate_model(&o, &d, &md, &st, 1, NULL, NULL);
 				md.geno = d.geno = orig;
 				md.init_geno = NULL;

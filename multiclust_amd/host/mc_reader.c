@@ -369,5 +369,7 @@ void mc_free_data(mc_cli_data *dat)
 	free(dat->names);
 	if (dat->pops) for (int n = 0; n < dat->numpops; n++) free(dat->pops[n]);
 	free(dat->pops);
+	free(dat->bed);
+	if (dat->lazy) dat->lazy->release(dat->lazy);
 	memset(dat, 0, sizeof *dat);
 }
