@@ -262,6 +262,53 @@ int mchip_copy_slot(mchip_context *ctx, int to, int from);
  */
 int mchip_get_expected_counts(mchip_context *ctx, double *sik);
 
+/* ---- K-fold cross-validation of the admixture model (an extension: the reference offers AIC / BIC and the bootstrap only) ----
+ * Fit with a share of the genotypes hidden, score how well the fit predicts them: every genotype (i, l) -- all `ploidy` copies of
+ * it together -- belongs to one of n_folds folds, one byte per genotype kept on the device beside the data set.  The folds, the
+ * saved full data set and the hold-out in force are state of the data set: every call that installs a new one
+ * (mchip_set_genotypes, _bed, mchip_simulate_genotypes, _mixture, mchip_copy_genotypes) drops them.  Fold draw and hold-out work
+ * with any model (or none); the score is the admixture model's. */
+/*
+ * fold[i*L + l] = rand() % n_folds, genotypes in i, l order, rand() the glibc stream described by `window` exactly as for
+ * mchip_mstep_from_rand_partition (the same generator kernel with K := n_folds over I*L draws).  Consumes I*L draws: the caller
+ * advances its own copy of the stream.  n_folds in [2, 64], else MCHIP_ERR_INVALID; MCHIP_ERR_STATE without a data set.  A
+ * hold-out in force stays in force (it was built from the previous folds) until the next mchip_cv_hold_out.
+ */
+int mchip_cv_draw_folds(mchip_context *ctx, const uint32_t *window, int n_folds);
+/* The same with folds the caller chose: folds[i*L + l] < n_folds, else MCHIP_ERR_INVALID (and the folds held stay as they were). */
+int mchip_cv_set_folds(mchip_context *ctx, const uint8_t *folds /* [I][L], each < n_folds */, int n_folds);
+/* the folds held, [I][L]; MCHIP_ERR_STATE without folds */
+int mchip_cv_get_folds(mchip_context *ctx, uint8_t *folds /* [I][L] */);
+/*
+ * Install the data set with every copy of every genotype of fold `fold` turned into MCHIP_MISSING; fold = -1 installs the full
+ * data set again, bit-identical (mchip_get_genotypes, mchip_data_counts, mchip_empty_individuals, every fit) to the one held
+ * before the first hold-out.  The first call saves the full data set once, in upload form, on the device; each call masks it
+ * into the stream buffer and takes the route of an uploaded genotype from there (layouts, packed counts, individuals left
+ * without an observed copy).  Unlike mchip_set_genotypes it
+ *   keeps   uniquealleles and T as they are -- a locus that gains missing copies only through the mask gets no phantom slot;
+ *           the kernels accept a missing copy at such a locus;
+ *           the model and every parameter slot, secants included, so a fit can start from the full-data estimate;
+ *           the genotype and count buffers (written in place), the folds and the saved full data set;
+ *   drops   what is derived from the data: the S-side sums held for a slot (mchip_loglik_prefetch), the counts of
+ *           mchip_data_counts, and the per-slot "stands for NaN" marks of mchip_get_q, which are cleared as
+ *           mchip_copy_genotypes clears them -- a slot written by an M step on the masked data is marked again.
+ * MCHIP_ERR_STATE without a data set or without folds; MCHIP_ERR_INVALID for a fold outside [-1, n_folds).
+ */
+int mchip_cv_hold_out(mchip_context *ctx, int fold /* -1: the full data set again */);
+/*
+ * The held-out score of the parameters in `slot`: over every copy (i, l, a) of the saved full data set that is observed and whose
+ * genotype lies in the fold held out, t = sum_k q_ik p_klm (m the copy's allele; q_k when eta is constrained), t' = max(t, floor):
+ *   *sum_log = sum log t',  *n_copies = how many such copies,  *n_floored = how many of them had t < floor or t NaN.
+ * Reads Q as the device stores it: an individual whose observed copies all fall into the fold holds the finite 1 / K there (see
+ * the parameter slots above).  Partial sums are combined in a fixed order, no floating-point atomics: two calls on the same state
+ * return the same bits.  Any of the three pointers may be NULL.
+ * MCHIP_ERR_STATE without a data set, folds, a hold-out in force (fold >= 0) or a model; MCHIP_ERR_INVALID for a slot out of
+ * range or floor outside (0, 1]; MCHIP_ERR_UNSUPPORTED for the mixture model (admixture = 0), where a held-out copy's prediction
+ * needs the posterior of its individual's retained copies.
+ */
+int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor,
+			    double *sum_log, uint64_t *n_copies, uint64_t *n_floored);
+
 /* ---- acceleration (accel_em.c, em_alg.c:1072-1211) ---- */
 /* u (which=0) or v (which=1) secant j := x[to] - x[from], for p and eta (em_alg.c:1104-1161). */
 int mchip_secant(mchip_context *ctx, int which, int j, int to, int from);

@@ -87,6 +87,15 @@ struct mchip_context {
 	uint8_t *d_asA, *d_asS;		/* hard-partition scratch, allocated on first use */
 	uint8_t *d_initA, *d_initS;	/* genotype the hard-partition M step reads when it is not the data set itself (bootstrap) */
 	uint8_t *d_draw;		/* device-drawn partition in stream order [I][L][ploidy], padded to whole chunks */
+	/* K-fold cross-validation (mchip_cv_*; kernels: mchip_cv.hip): state of the data set, dropped with it */
+	uint8_t *d_cv_fold;		/* fold of every genotype [I][L], padded to whole generator chunks + MCHIP_CV_PAD; null = no folds */
+	int cv_n_folds;
+	uint8_t *d_cv_full;		/* the full data set in upload form [I][L][ploidy], saved by the first hold-out */
+	int cv_fold;			/* fold held out of the installed data set, -1 = none */
+	std::vector<int> cv_full_empty;	/* empty_rows of the full data set */
+	double *d_cv_part;		/* the score's partial sums, one per workgroup */
+	size_t cv_part_cap;
+	unsigned long long *d_cv_out;	/* [0] the score's sum (a double), [1] copies, [2] floored copies */
 	/* Rand-EM candidates (mchip_init_from_allele_centers), kept from one candidate to the next and grown when needed: the
 	 * rand() % K values of a candidate's span of the stream, its center alleles [L][K], its per-locus draw offsets */
 	uint8_t *d_cand_span, *d_cand_centers;
@@ -1719,8 +1728,18 @@ static void free_model(mchip_context *ctx)
 	ctx->s_cache_slot = -1;
 }
 
+static void drop_cv(mchip_context *ctx)
+{
+	dfree(ctx->d_cv_fold); dfree(ctx->d_cv_full); dfree(ctx->d_cv_part); dfree(ctx->d_cv_out);
+	ctx->cv_n_folds = 0;
+	ctx->cv_fold = -1;
+	ctx->cv_part_cap = 0;
+	ctx->cv_full_empty.clear();
+}
+
 static void free_data(mchip_context *ctx)
 {
+	drop_cv(ctx);
 	dfree(ctx->d_ua); dfree(ctx->d_toff); dfree(ctx->d_col_locus); dfree(ctx->d_col_allele);
 	dfree(ctx->d_gtA); dfree(ctx->d_gtS); dfree(ctx->d_gtC); dfree(ctx->d_asA); dfree(ctx->d_asS);
 	dfree(ctx->d_initA); dfree(ctx->d_initS);
@@ -1803,6 +1822,7 @@ int mchip_create(mchip_context **out, int device)
 	if (device < 0 || device >= n) return MCHIP_ERR_INVALID;
 	mchip_context *ctx = new mchip_context();
 	ctx->first_empty = -1;
+	ctx->cv_fold = -1;
 	ctx->device = device;
 	ctx->err[0] = 0;
 	ctx->ind_waves = 1;
@@ -1887,6 +1907,7 @@ static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const in
 	read_knobs(ctx);
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
+	drop_cv(ctx);	/* folds, the saved full data set and a hold-out in force belong to the data set that goes */
 	/* The same shape and allele lists as the data set held (the next bootstrap replicate, a re-upload): every buffer stays;
 	 * the model is dropped as the contract says, but its buffers are parked for an mchip_set_model with the same arguments.
 	 * Freeing and re-allocating ~10 GB per replicate costs little per call, but the runtime returns freed memory lazily and
@@ -2172,6 +2193,157 @@ int mchip_get_genotypes(mchip_context *ctx, uint8_t *geno)
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(geno, d_raw, n, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
+	return MCHIP_OK;
+}
+
+/* ---- K-fold cross-validation: folds, hold-out, held-out score (kernels: mchip_cv.hip) ---- */
+static int rng_stream_setup(mchip_context *ctx, const uint32_t *window, size_t n_draws, rng_window *base, size_t *n_chunks, size_t *n_blocks);
+static void mod_k_magic(int K, uint32_t *magic, uint32_t *shift);
+
+static int cv_check_data(mchip_context *ctx, int need_folds)
+{
+	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
+	if (need_folds && !ctx->d_cv_fold) return fail(ctx, MCHIP_ERR_STATE, "no folds: mchip_cv_draw_folds or mchip_cv_set_folds first%s", nullptr);
+	return MCHIP_OK;
+}
+
+/* one byte per genotype, whole generator chunks (k_draw_partition writes whole chunks) and the padding the score's reads want */
+static int cv_fold_buffer(mchip_context *ctx)
+{
+	if (ctx->d_cv_fold) return MCHIP_OK;
+	const size_t n = (size_t)ctx->I * ctx->L, bytes = ((n + RNG_CHUNK - 1) / RNG_CHUNK) * RNG_CHUNK + MCHIP_CV_PAD;
+	HIPCHK(hipMalloc((void **)&ctx->d_cv_fold, bytes));
+	HIPCHK(hipMemsetAsync(ctx->d_cv_fold, 0, bytes, ctx->stream));
+	return MCHIP_OK;
+}
+
+int mchip_cv_draw_folds(mchip_context *ctx, const uint32_t *window, int n_folds)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 0);
+	if (rc) return rc;
+	if (!window) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	if (n_folds < 2 || n_folds > 64) return fail(ctx, MCHIP_ERR_INVALID, "cv: n_folds must be in [2, 64]%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	rng_window base;
+	size_t n_chunks, n_blocks;
+	if ((rc = rng_stream_setup(ctx, window, (size_t)ctx->I * ctx->L, &base, &n_chunks, &n_blocks))) return rc;
+	if ((rc = cv_fold_buffer(ctx))) return rc;
+	uint32_t magic, shift;
+	mod_k_magic(n_folds, &magic, &shift);
+	hipLaunchKernelGGL(k_draw_partition, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, base, ctx->d_jump_hi, ctx->d_jump_lo,
+			   n_chunks, (uint32_t)n_folds, magic, shift, (uint32_t *)ctx->d_cv_fold);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	ctx->cv_n_folds = n_folds;
+	return MCHIP_OK;
+}
+
+int mchip_cv_set_folds(mchip_context *ctx, const uint8_t *folds, int n_folds)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 0);
+	if (rc) return rc;
+	if (!folds) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	if (n_folds < 2 || n_folds > 64) return fail(ctx, MCHIP_ERR_INVALID, "cv: n_folds must be in [2, 64]%s", nullptr);
+	const size_t n = (size_t)ctx->I * ctx->L;
+	for (size_t x = 0; x < n; x++)
+		if (folds[x] >= n_folds) return fail(ctx, MCHIP_ERR_INVALID, "cv: fold byte >= n_folds%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	if ((rc = cv_fold_buffer(ctx))) return rc;
+	HIPCHK(hipMemcpyAsync(ctx->d_cv_fold, folds, n, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	ctx->cv_n_folds = n_folds;
+	return MCHIP_OK;
+}
+
+int mchip_cv_get_folds(mchip_context *ctx, uint8_t *folds)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 1);
+	if (rc) return rc;
+	if (!folds) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	HIPCHK(hipMemcpyAsync(folds, ctx->d_cv_fold, (size_t)ctx->I * ctx->L, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	return MCHIP_OK;
+}
+
+int mchip_cv_hold_out(mchip_context *ctx, int fold)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 1);
+	if (rc) return rc;
+	if (fold < -1 || fold >= ctx->cv_n_folds) return fail(ctx, MCHIP_ERR_INVALID, "cv: fold outside [-1, n_folds)%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	const int I = ctx->I, L = ctx->L, pl = ctx->ploidy;
+	const size_t n = (size_t)I * L * pl;
+	if (!ctx->d_cv_full) {	/* the data set installed now is the full one: keep it, in upload form */
+		HIPCHK(hipMalloc((void **)&ctx->d_cv_full, n));
+		hipLaunchKernelGGL(k_unlayout, dim3(nblk_capped(n)), dim3(256), 0, ctx->stream, ctx->d_gtA, I, L, pl, ctx->d_cv_full);
+		HIPCHK(hipGetLastError());
+		ctx->cv_full_empty = ctx->empty_rows;
+	}
+	if (!ctx->d_cv_out) HIPCHK(hipMalloc((void **)&ctx->d_cv_out, 4 * sizeof(unsigned long long)));
+	if (fold < 0) {
+		if ((rc = install_raw(ctx, ctx->d_cv_full))) return rc;
+		ctx->empty_rows = ctx->cv_full_empty;
+	} else {
+		if ((rc = stream_buffer(ctx))) return rc;
+		scoped_dev<uint8_t> d_seen;
+		HIPCHK(d_seen.alloc((size_t)I));
+		HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
+		mchip_cv_mask(ctx->stream, ctx->d_cv_full, ctx->d_cv_fold, fold, I, L, pl, ctx->d_draw, d_seen.p);
+		HIPCHK(hipGetLastError());
+		std::vector<uint8_t> seen((size_t)I);
+		HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
+		if ((rc = install_raw(ctx, ctx->d_draw))) return rc;	/* (synchronises the stream) */
+		ctx->empty_rows.clear();
+		for (int i = 0; i < I; i++)
+			if (!seen[i]) ctx->empty_rows.push_back(i);
+	}
+	ctx->first_empty = ctx->empty_rows.empty() ? -1 : ctx->empty_rows[0];
+	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
+	ctx->s_cache_slot = -1;
+	ctx->cv_fold = fold;
+	return MCHIP_OK;
+}
+
+int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor, double *sum_log, uint64_t *n_copies, uint64_t *n_floored)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 1);
+	if (rc) return rc;
+	if ((rc = check_slot(ctx, slot))) return rc;
+	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "cv: the held-out score is the admixture model's%s", nullptr);
+	if (ctx->cv_fold < 0 || !ctx->d_cv_full) return fail(ctx, MCHIP_ERR_STATE, "cv: no fold is held out%s", nullptr);
+	if (!(floor > 0.0 && floor <= 1.0)) return fail(ctx, MCHIP_ERR_INVALID, "cv: floor must be in (0, 1]%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t parts = (size_t)mchip_cv_score_parts(ctx->I, ctx->L, ctx->K, ctx->max_M, ctx->n_cu);
+	if (ctx->cv_part_cap < parts) {
+		dfree(ctx->d_cv_part);
+		ctx->cv_part_cap = 0;
+		HIPCHK(hipMalloc((void **)&ctx->d_cv_part, parts * sizeof(double)));
+		ctx->cv_part_cap = parts;
+	}
+	HIPCHK(hipMemsetAsync(ctx->d_cv_out, 0, 4 * sizeof(unsigned long long), ctx->stream));
+	mchip_cv_score(ctx->stream, ctx->I, ctx->L, ctx->ploidy, ctx->K, ctx->max_M, ctx->n_cu, ctx->d_cv_full, ctx->d_cv_fold, ctx->cv_fold,
+		       ctx->d_toff, ctx->d_p[slot], ctx->d_q[slot], ctx->qstride, floor, ctx->d_cv_part, ctx->d_cv_out + 1);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_cv_part, (int)parts,
+			   reinterpret_cast<double *>(ctx->d_cv_out), (const int *)nullptr);
+	HIPCHK(hipGetLastError());
+	unsigned long long h[3];
+	HIPCHK(hipMemcpyAsync(h, ctx->d_cv_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	if (sum_log) memcpy(sum_log, &h[0], sizeof(double));
+	if (n_copies) *n_copies = h[1];
+	if (n_floored) *n_floored = h[2];
 	return MCHIP_OK;
 }
 

@@ -199,6 +199,22 @@ void mchip_bed_locus_pass(hipStream_t s, const uint8_t *d_bed, size_t record_byt
 int mchip_bed_expand(hipStream_t s, const uint8_t *d_bed, size_t record_bytes, int I, int L, const uint8_t *a1, uint8_t *gtA,
 		     uint8_t *gtS, uint8_t *seen);
 
+/* K-fold cross-validation (mchip_cv.hip; mchip_cv_hold_out, mchip_cv_heldout_loglik).  full: the saved data set in upload form
+ * [I][L][ploidy]; fold: one byte per genotype [I][L], the allocation MCHIP_CV_PAD bytes longer than that (fold bytes are read
+ * eight at a time from any byte offset).
+ * Mask: out = full with every copy of the genotypes of fold `fold_id` turned into 0xFF; seen[i] (zeroed by the caller) = 1 for
+ * every individual that keeps an observed copy.
+ * Score: sum of log max(t, floor) over the observed copies of the fold, one partial per workgroup in part[] (the return value
+ * says how many; mchip_cv_score_parts() is the same number, for sizing part[]), counts[0] += copies, counts[1] += floored copies
+ * (zeroed by the caller).  P is a slot's [T][K], Q its [I][K] (qstride = K) or [K] (qstride = 0). */
+#define MCHIP_CV_PAD 16
+void mchip_cv_mask(hipStream_t s, const uint8_t *full, const uint8_t *fold, int fold_id, int I, int L, int ploidy, uint8_t *out,
+		   uint8_t *seen);
+int mchip_cv_score_parts(int I, int L, int K, int max_M, int n_cu);
+int mchip_cv_score(hipStream_t s, int I, int L, int ploidy, int K, int max_M, int n_cu, const uint8_t *full, const uint8_t *fold,
+		   int fold_id, const int32_t *toff, const double *P, const double *Q, int qstride, double floor, double *part,
+		   unsigned long long *counts);
+
 inline int mchip_ind_waves(int K, int tile_cols)
 {
 	/* (a buffer is rounded up to whole 1 KiB pieces where tiles are copied straight into LDS) */

@@ -93,6 +93,11 @@ def load():
         "mchip_comm_info": ([vp, ip, ip, C.POINTER(C.c_ulonglong)], i32),
         "mchip_progress_report": ([C.c_char_p, i32, C.POINTER(C.c_ulonglong)], i32),
         "mchip_progress_note": ([C.c_char_p], i32),
+        "mchip_cv_draw_folds": ([vp, vp, i32], i32),
+        "mchip_cv_set_folds": ([vp, vp, i32], i32),
+        "mchip_cv_get_folds": ([vp, vp], i32),
+        "mchip_cv_hold_out": ([vp, i32], i32),
+        "mchip_cv_heldout_loglik": ([vp, i32, C.c_double, dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], i32),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("MCHIP_ALLOW_PARTIAL_ABI") == "1" and not hasattr(lib, name):
@@ -115,6 +120,7 @@ ABI_SYMBOLS = [
     "mchip_profile_end", "mchip_device_info", "mchip_comm_create", "mchip_comm_all_reduce", "mchip_comm_destroy",
     "mchip_comm_last_error", "mchip_comm_info", "mchip_progress_report", "mchip_progress_note",
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
+    "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
 ]
 
 
@@ -181,6 +187,39 @@ class Context:
         g = np.empty((self.I, self.L, self.ploidy), dtype=np.uint8)
         self._chk(self.lib.mchip_get_genotypes(self.h, g.ctypes.data))
         return g
+
+    def empty_individuals(self):
+        """(how many individuals of the data set held have no observed copy, the first one's index or -1)"""
+        first = C.c_int(-1)
+        n = self.lib.mchip_empty_individuals(self.h, C.byref(first))
+        return n, first.value
+
+    # ---- K-fold cross-validation (include/multiclust_hip.h, mchip_cv_*) ----
+    def cv_draw_folds(self, window, n_folds):
+        """fold of genotype (i, l) = rand() % n_folds from the stream `window` describes; consumes I*L draws"""
+        w = np.ascontiguousarray(window, dtype=np.uint32)
+        assert w.size == 31
+        self._chk(self.lib.mchip_cv_draw_folds(self.h, w.ctypes.data, n_folds))
+
+    def cv_set_folds(self, folds, n_folds):
+        f = np.ascontiguousarray(folds, dtype=np.uint8)
+        assert f.size == self.I * self.L
+        self._chk(self.lib.mchip_cv_set_folds(self.h, f.ctypes.data, n_folds))
+
+    def cv_get_folds(self):
+        f = np.empty((self.I, self.L), dtype=np.uint8)
+        self._chk(self.lib.mchip_cv_get_folds(self.h, f.ctypes.data))
+        return f
+
+    def cv_hold_out(self, fold):
+        """install the data set with fold `fold` missing (-1: the full data set again); keeps the model"""
+        self._chk(self.lib.mchip_cv_hold_out(self.h, fold))
+
+    def cv_heldout_loglik(self, slot, floor):
+        """(sum of log max(t, floor) over the observed copies of the fold held out, their number, how many were floored)"""
+        s, n, nf = C.c_double(), C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.mchip_cv_heldout_loglik(self.h, slot, floor, C.byref(s), C.byref(n), C.byref(nf)))
+        return s.value, n.value, nf.value
 
     def set_init_genotypes(self, geno):
         """The data set hard-partition initialisations read instead of the current one (None: back to the current one)."""

@@ -61,6 +61,17 @@ class McSummary(C.Structure):
                 ("aic", C.c_double), ("bic", C.c_double)]
 
 
+CV_MAX_FOLDS = 64
+
+
+class McCvResult(C.Structure):
+    """mc_cv_result (multiclust_amd/host/mc_host.h)"""
+    _fields_ = [("cv", C.c_double), ("sum_log", C.c_double), ("floor", C.c_double), ("n_copies", C.c_uint64),
+                ("n_floored", C.c_uint64), ("n_folds", C.c_int), ("fatal_fold", C.c_int),
+                ("fold_sum_log", C.c_double * CV_MAX_FOLDS), ("fold_copies", C.c_uint64 * CV_MAX_FOLDS),
+                ("fold_floored", C.c_uint64 * CV_MAX_FOLDS), ("fold_iter", C.c_int * CV_MAX_FOLDS)]
+
+
 class CliOptions(C.Structure):
     """mc_cli_options (multiclust_amd/host/mc_cli.h)"""
     _fields_ = [("em", McOptions), ("filename", C.c_char_p), ("filename_file", C.c_char_p), ("path", C.c_char_p),
@@ -71,6 +82,8 @@ class CliOptions(C.Structure):
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
                 ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
+    # (the C struct ends with cv_folds / cv_floor, the command line's --cv: only mc_main.c reads them, the readers this mirror is
+    # handed to stop at bed_prefix)
 
 
 class CliData(C.Structure):
@@ -227,6 +240,9 @@ def load():
     lib.mc_replicate_start.argtypes = [OP, DP, C.POINTER(McRng), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(McRng)]
     lib.mc_test_center_walk.argtypes = [C.c_int, C.c_int, C.POINTER(McRng), C.POINTER(C.c_int)]
     lib.mc_test_center_walk.restype = None
+    lib.mc_cross_validate.argtypes = [OP, DP, MP, C.c_int, C.c_double, C.POINTER(McCvResult)]
+    lib.mc_cv_default_floor.argtypes = [DP]
+    lib.mc_cv_default_floor.restype = C.c_double
     lib.mc_aic.restype = C.c_double
     lib.mc_aic.argtypes = [C.c_double, C.c_int]
     lib.mc_bic.restype = C.c_double
@@ -330,3 +346,14 @@ class Fit:
 
     def log_likelihood(self, which):
         return self.lib.mc_log_likelihood(C.byref(self.opt), C.byref(self.dat), self.mp, which)
+
+    def cross_validate(self, n_folds, floor=0.0):
+        """mc_cross_validate on the estimate in slot mod.pindex: (cv, sum_log, n_copies, n_floored, per-fold list of
+        (sum_log, n_copies, n_floored, EM iterations)); cv is NaN when a fold's fit stopped on NaN or a decrease.  floor <= 0:
+        the default 1 / (I ploidy + 1).  Leaves the model as it found it."""
+        r = McCvResult()
+        rc = self.lib.mc_cross_validate(C.byref(self.opt), C.byref(self.dat), self.mp, n_folds, floor, C.byref(r))
+        if rc:
+            raise hip.HipError("mc_cross_validate failed (%d)" % rc)
+        folds = [(r.fold_sum_log[f], r.fold_copies[f], r.fold_floored[f], r.fold_iter[f]) for f in range(n_folds)]
+        return r.cv, r.sum_log, r.n_copies, r.n_floored, folds

@@ -45,6 +45,8 @@ typedef struct mc_cli_options {
 	const char *pfile, *qfile;	/* -P / -Q: initial parameters of the admixture model from files (read_file.c:880-959) */
 	const char *afile;		/* -A: a partition of the individuals to compare the fitted one with (multiclust.c:1416-1418) */
 	const char *bed_prefix;		/* --bed (extension): read <prefix>.bed / .bim / .fam instead of the STRUCTURE file of -f */
+	int cv_folds;			/* --cv <F> (extension): F-fold cross-validation of the best fit of every K (admixture model); 0 = off */
+	double cv_floor;		/* --cv-floor <x>: smallest prediction a held-out copy is scored with; 0 = the default of mc_cross_validate */
 } mc_cli_options;
 
 typedef struct mc_cli_data {

@@ -219,6 +219,32 @@ typedef struct mc_replicate_result {
 int mc_fit_replicate(const mc_options *opt, const mc_data *dat, int device, const mc_rng *base, int b, int null_K, int alt_K,
 		     int n_init, int mle_K, const double *mle_q, const double *mle_p, mc_replicate_result *out, mc_model **models);
 
+/* ---- K-fold cross-validation of a fitted admixture model (mc_cv.c; an extension, the reference has no counterpart) ----
+ * `mod` holds the full-data estimate of its K in slot mod->pindex.  The folds are drawn on the device from a fresh stream seeded
+ * with opt->seed -- a stream of their own, the same for every K, so the K are compared on one partition; the run's rand()
+ * stream is not touched.  For each fold: hold it out (mchip_cv_hold_out), put the estimate into slot 0, run mc_em from that warm
+ * start with the run's own options (acceleration, tolerances, iteration cap, projection, bounds), score the held-out copies
+ * (mchip_cv_heldout_loglik).  Then the full data set is installed again and
+ *     cv = - sum_f sum_log_f / sum_f n_copies_f,
+ * the mean negative log predictive probability of a held-out allele copy.  floor: a prediction below it counts as the floor
+ * (a copy whose allele is absent from the retained data otherwise scores log 0 after the first M step); <= 0 takes the default
+ * 1 / (I ploidy + 1), below every non-zero sample frequency of an allele.
+ * A fold whose fit stops on NaN or on a decrease of the log likelihood is reported on stderr and makes cv NaN (fatal_fold = the
+ * first such fold); the call still returns 0.  On return the parameters of slot mod->pindex, mod->logL, mod->n_iter and the rest
+ * of the host state are what they were (the other two slots, the secants and the expected counts are the last fold fit's).
+ * Admixture models only (individual or shared mixing proportions), 2 <= n_folds <= MC_CV_MAX_FOLDS. */
+#define MC_CV_MAX_FOLDS 64
+typedef struct mc_cv_result {
+	double cv, sum_log, floor;
+	uint64_t n_copies, n_floored;
+	int n_folds, fatal_fold;	/* fatal_fold: -1 = none */
+	double fold_sum_log[MC_CV_MAX_FOLDS];
+	uint64_t fold_copies[MC_CV_MAX_FOLDS], fold_floored[MC_CV_MAX_FOLDS];
+	int fold_iter[MC_CV_MAX_FOLDS];	/* EM iterations of each fold's fit */
+} mc_cv_result;
+double mc_cv_default_floor(const mc_data *dat);
+int mc_cross_validate(const mc_options *opt, const mc_data *dat, mc_model *mod, int n_folds, double floor, mc_cv_result *out);
+
 /* ---- opt-in watchdog (mc_watchdog.c): nothing in the reference corresponds -- it has nothing to wait for ----
  * mc_watchdog_start(s): a detached thread that polls the library's event count (mchip_progress_report) and, when it has stood
  * still for s seconds, prints where every thread stands (library record + /proc/self/task) on stderr and leaves with _exit(3).

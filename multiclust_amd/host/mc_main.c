@@ -8,7 +8,8 @@
  * (618-627), print_model_state (718-793), run_bootstrap (675-708) and the -w repetition summary (201-347).
  * Deliberately absent (documented in DESIGN.md): -I/-I1 (allele-index mode gives different numbers from default
  * mode in the reference itself), --impute, --simulate, -x (not implemented in the reference either).
- * Extensions: --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
+ * Extensions: --cv <F> adds the F-fold cross-validation error of every K's best fit (one more stdout line per K, nothing else changes);
+ * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
  * the node (one host thread and one context per GPU, units u = d, d+n, ..., each starting from the serial program's
  * rand() position by jump-ahead), with a single RCCL all-reduce of the per-unit result table, after which the serial
  * bookkeeping is replayed in unit order (admixture model, fixed number of initialisations).  Bootstrap replicates (-b) are split
@@ -53,7 +54,9 @@ static void usage(FILE *fp, const char *prog)
 		"  --randem      Rand-EM initialisation: the best of -m <n> (50) candidates from random allele centers\n"
 		"  -A <file>     a partition of the individuals (labels 1, 2, ...): the adjusted Rand index of the fitted one is reported\n"
 		"  --bed <prefix>  read the PLINK 1 fileset <prefix>.bed/.bim/.fam instead of -f (diploid; not with -f, -R or -p other than 2;\n"
-		"                --missing is ignored); the 2-bit records are uploaded as they are and unpacked on the GPU\n", prog);
+		"                --missing is ignored); the 2-bit records are uploaded as they are and unpacked on the GPU\n"
+		"  --cv <F>      F-fold cross-validation (2..64) of the best fit of every K: one more line 'CV error (K=..)' per K; needs -a,\n"
+		"                not with -b, -w, -M or --gpus above 1        --cv-floor <x>  smallest prediction scored, in (0, 1] (1/(I*ploidy+1))\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -109,7 +112,11 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			else if (!strncmp(w, "bou", 3)) { if (arg_dbl(argc, argv, ++i, &d) || d < 0) BAD("--bound"); o->em.lower_bound = d; }
 			else { if (arg_int(argc, argv, ++i, &v) || v < 0) BAD("-b"); o->n_bootstrap = (int)v; }
 			break;
-		case 'c': o->em.eta_constrained = 1; break;
+		case 'c':
+			if (!strncmp(w, "cv-f", 4)) { if (arg_dbl(argc, argv, ++i, &d) || !(d > 0 && d <= 1)) BAD("--cv-floor"); o->cv_floor = d; }
+			else if (!strncmp(w, "cv", 2)) { if (arg_int(argc, argv, ++i, &v) || v < 2 || v > MC_CV_MAX_FOLDS) BAD("--cv"); o->cv_folds = (int)v; }
+			else o->em.eta_constrained = 1;
+			break;
 		case 'd':
 			if (!strncmp(w, "dev", 3)) { if (arg_int(argc, argv, ++i, &v) || v < 0) BAD("--device"); o->device = (int)v; }
 			else { if (++i >= argc) BAD("-d"); o->path = argv[i]; }
@@ -200,6 +207,17 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			return MC_EXIT_INVALID_CMD_OPTION;
 		}
 	}
+	if (o->cv_folds) {	/* extension: what cross-validation cannot be combined with is a usage error like a bad argument */
+		const char *why = NULL;
+		if (!o->em.admixture) why = "--cv needs the admixture model (-a)";
+		else if (o->n_bootstrap) why = "--cv cannot be combined with the bootstrap (-b)";
+		else if (o->n_gpus > 1) why = "--cv cannot be combined with --gpus above 1";
+		else if (!o->write_files || o->parallel) why = "--cv cannot be combined with -w or -M";
+		if (why) {
+			fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '--cv'); try -h\n", why);
+			return MC_EXIT_INVALID_CMD_ARGUMENT;
+		}
+	}
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -237,6 +255,9 @@ typedef struct run_state {
 	 * was partitioned (dat->I_K) and the adjusted Rand index of the two (model::arand: never reset, as in the reference) */
 	int *partition_from_file, pK, *I_K;
 	double arand;
+	/* --cv: the cross-validation of the K just fitted, printed by estimate_model behind the K's summary line */
+	mc_cv_result cv;
+	int cv_done;
 } run_state;
 
 /* sharded runs use n_gpus * n_streams workers (host thread + context + stream each); worker x sits on device
@@ -345,6 +366,31 @@ static int cli_initialize(const mc_cli_options *o, const mc_cli_data *d, const m
 	return rc;
 }
 
+/* --cv: F-fold cross-validation of the best fit of one K, whose parameters q, p the caller holds.  mod: the model that fitted
+ * it (its slots are free again), or NULL: a model is created on `device` for the purpose (the workers of a sharded fit are gone by
+ * the time the best unit is known). */
+static int cli_cross_validate(const mc_cli_options *o, const mc_data *md, run_state *st, mc_model *mod, int K, int device, const double *q,
+			      const double *p, double logL, int n_iter, int converged)
+{
+	mc_model *own = NULL;
+	int rc = 0;
+	mchip_progress_note("cross-validation");
+	if (!mod) {
+		if ((rc = mc_model_create(&own, &o->em, md, K, device))) return rc;
+		mod = own;
+	}
+	mc_reset_model_state(mod);
+	if (!(rc = mc_model_set_q(mod, mod->pindex, q)) && !(rc = mc_model_set_p(mod, mod->pindex, p))) {
+		mod->logL = logL;
+		mod->n_iter = n_iter;
+		mod->converged = converged;
+		rc = mc_cross_validate(&o->em, md, mod, o->cv_folds, o->cv_floor, &st->cv);
+		if (!rc) st->cv_done = 1;
+	}
+	mc_model_free(own);
+	return rc;
+}
+
 static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, mc_model *mod, run_state *st, int bootstrap)
 {
 	const int K = mod->K, nq = (o->em.admixture && !o->em.eta_constrained) ? d->I * K : K;
@@ -354,6 +400,10 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 	const double max_logL_keep = st->sum.max_logL, aic_keep = st->sum.aic, bic_keep = st->sum.bic;
 	double *q = NULL, *p = NULL, *sik = NULL;
 	int *count_K = NULL, rc = 0;
+	/* --cv: the best fit of THIS K (the files above follow the maximum over the K so far) */
+	const int cv = o->cv_folds && !bootstrap;
+	double *cv_q = NULL, *cv_p = NULL, cv_logL = -INFINITY;
+	int cv_iter = 0, cv_conv = 0;
 	mc_summary_reset(&st->sum);
 	st->sum.max_logL = max_logL_keep;
 	if (max_logL_keep > -INFINITY) { st->sum.aic = aic_keep; st->sum.bic = bic_keep; }
@@ -376,6 +426,12 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 		mc_unit_result r = { i, mod->logL, mod->converged, mod->n_iter, mod->time_stop, mod->iter_stop, mod->pindex, 0, mod->seconds_run };
 		const double prev_max = st->sum.max_logL;
 		mc_summary_add(&o->em, &st->sum, &r, npar, d->I);
+		if (cv && mod->logL > cv_logL) {
+			if (!cv_q) { cv_q = malloc(sizeof(double) * (size_t)nq); cv_p = malloc(sizeof(double) * (size_t)K * d->T); }
+			if (!cv_q || !cv_p) { rc = MCHIP_ERR_ALLOC; goto DONE; }
+			if ((rc = mc_model_get_q(mod, mod->pindex, cv_q)) || (rc = mc_model_get_p(mod, mod->pindex, cv_p))) goto DONE;
+			cv_logL = mod->logL; cv_iter = mod->n_iter; cv_conv = mod->converged;
+		}
 		if (mod->logL > prev_max) {
 			const int keep_mle = !bootstrap && o->n_bootstrap && K == st->null_K;
 			const int part_only = o->afile && !o->write_files;	/* nothing is written, but -A wants the partition */
@@ -428,8 +484,9 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 			}
 		}
 	}
+	if (cv && cv_q) rc = cli_cross_validate(o, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
 DONE:
-	free(q); free(p); free(sik); free(count_K);
+	free(q); free(p); free(sik); free(count_K); free(cv_q); free(cv_p);
 	return rc;
 }
 
@@ -515,7 +572,7 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 	}
 	for (int x = 0; x < n_dev; x++) {
 		w[x].o = o; w[x].d = d; w[x].md = md; w[x].K = K; w[x].index = x; w[x].n_dev = n_dev; w[x].n_units = n_units;
-		w[x].want_params = keep_mle || (!bootstrap && o->write_files) || o->afile != NULL;
+		w[x].want_params = keep_mle || (!bootstrap && o->write_files) || o->afile != NULL || (o->cv_folds && !bootstrap);
 		w[x].sim = sim;
 		w[x].starts = starts; w[x].draws = mc_draws_per_init(&o->em, md, K); w[x].res = res;
 		if (pthread_create(&th[x], NULL, shard_main, &w[x])) shard_main(&w[x]);	/* no thread to be had: in this one */
@@ -581,6 +638,13 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 			if (fits) st->arand = mc_adjusted_rand(d->I, st->pK, K, st->partition_from_file, st->I_K);
 		}
 	}
+	if (!rc && o->cv_folds && !bootstrap) {	/* --cv: the best unit of this K, on the device whose worker fitted it */
+		int ub = 0;
+		for (int u = 1; u < n_units; u++) if (res[u].logL > res[ub].logL) ub = u;
+		const shard_worker *own = &w[ub % n_dev];
+		if (own->best_unit != ub) { fprintf(stderr, "ERROR [mc_main.c]: owner of the best unit does not hold it\n"); rc = MCHIP_ERR_STATE; goto DONE; }
+		rc = cli_cross_validate(o, md, st, NULL, K, worker_device(o, ub % n_dev), own->q, own->p, res[ub].logL, res[ub].n_iter, res[ub].converged);
+	}
 DONE:
 	if (w) for (int x = 0; x < n_dev; x++) { free(w[x].q); free(w[x].p); free(w[x].sik); }
 	if (tab) for (int x = 0; x < n_gpus; x++) free(tab[x]);
@@ -636,6 +700,11 @@ static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const m
 		if (rc) return rc;
 		if (o->n_repeat == 1 && o->em.verbosity)
 			print_model_state(o, d, st, K, (int)(((double)clock() - start) / CLOCKS_PER_SEC), 1);
+		if (st->cv_done) {	/* --cv */
+			fprintf(st->out, "CV error (K=%d, %d folds): %.10f  [%llu held-out copies, %llu floored]\n", K, o->cv_folds, st->cv.cv,
+				(unsigned long long)st->cv.n_copies, (unsigned long long)st->cv.n_floored);
+			st->cv_done = 0;
+		}
 		if (total_iter) *total_iter += st->sum.n_total_iter;
 		if (o->n_bootstrap && K == st->null_K) st->max_logL_H0 = st->sum.max_logL;
 		if (min_aic > st->sum.aic) { min_aic = st->sum.aic; st->aic_K = K; }
