@@ -309,6 +309,26 @@ int mchip_cv_hold_out(mchip_context *ctx, int fold /* -1: the full data set agai
 int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor,
 			    double *sum_log, uint64_t *n_copies, uint64_t *n_floored);
 
+/* ---- a selection of loci with repeats: the data sets of the non-parametric bootstrap over loci (an extension) ----
+ * Let the base be the data set the context held when the first resample was asked for (I, L_base, ploidy, uniquealleles,
+ * genotypes).  After the call the context holds exactly what
+ *     mchip_set_genotypes(ctx, I, L2, ploidy, ua_base[src[.]], geno_base[:, src[.], :])
+ * would install, bit for bit: mchip_get_genotypes, mchip_data_counts, mchip_empty_individuals, mchip_copy_genotypes and every fit of
+ * every model.  The allele lists are the base's, gathered and not recounted: a locus keeps its phantom slot even when no missing
+ * copy of it survives, a locus without one gets none.  Like every call that installs a data set it drops the model, the init
+ * genotypes and the cross-validation state (folds, saved full data set).
+ * The first call saves the base once, in upload form, on the device (read back from the kernels' layout, so a base installed by
+ * mchip_set_genotypes_bed or generated on the device serves as well), with its allele lists and its individuals without an observed
+ * copy; every later call gathers from the saved base, never from the replicate installed before it.  src = NULL (L2 is ignored)
+ * installs the base again, bit-identical to the data set held before the first resample, and keeps it saved.  Any other call
+ * that installs a data set (mchip_set_genotypes, _bed, mchip_simulate_genotypes, _mixture, mchip_copy_genotypes) drops the saved
+ * base; mchip_cv_hold_out keeps it.
+ * MCHIP_ERR_STATE without a data set, with a cross-validation hold-out in force (fold >= 0), or for src = NULL without a saved
+ * base; MCHIP_ERR_INVALID for L2 < 1, for an index outside [0, L_base) or for a selection with more than 2 000 000 000 allele
+ * columns -- all checked before anything is touched: the data set, the model and the saved base stay as they were.
+ */
+int mchip_resample_loci(mchip_context *ctx, const int32_t *src /* [L2], each in [0, L_base); NULL: the base again */, int L2);
+
 /* ---- acceleration (accel_em.c, em_alg.c:1072-1211) ---- */
 /* u (which=0) or v (which=1) secant j := x[to] - x[from], for p and eta (em_alg.c:1104-1161). */
 int mchip_secant(mchip_context *ctx, int which, int j, int to, int from);

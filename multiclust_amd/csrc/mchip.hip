@@ -96,6 +96,13 @@ struct mchip_context {
 	double *d_cv_part;		/* the score's partial sums, one per workgroup */
 	size_t cv_part_cap;
 	unsigned long long *d_cv_out;	/* [0] the score's sum (a double), [1] copies, [2] floored copies */
+	/* selections of loci (mchip_resample_loci; kernel: mchip_resample.hip): the base they are gathered from, saved by the first one
+	 * and dropped by every other call that installs a data set */
+	uint8_t *d_rs_base;		/* the base in upload form [I][rs_L][ploidy]; null = none saved */
+	int rs_L;
+	std::vector<int32_t> rs_ua;	/* uniquealleles of the base */
+	std::vector<int> rs_empty;	/* empty_rows of the base */
+	int rs_installing;		/* mchip_resample_loci is installing a selection: set_shape and free_data leave the base alone */
 	/* Rand-EM candidates (mchip_init_from_allele_centers), kept from one candidate to the next and grown when needed: the
 	 * rand() % K values of a candidate's span of the stream, its center alleles [L][K], its per-locus draw offsets */
 	uint8_t *d_cand_span, *d_cand_centers;
@@ -1737,9 +1744,19 @@ static void drop_cv(mchip_context *ctx)
 	ctx->cv_full_empty.clear();
 }
 
+static void drop_resample(mchip_context *ctx)
+{
+	if (ctx->rs_installing) return;
+	dfree(ctx->d_rs_base);
+	ctx->rs_L = 0;
+	ctx->rs_ua.clear();
+	ctx->rs_empty.clear();
+}
+
 static void free_data(mchip_context *ctx)
 {
 	drop_cv(ctx);
+	drop_resample(ctx);
 	dfree(ctx->d_ua); dfree(ctx->d_toff); dfree(ctx->d_col_locus); dfree(ctx->d_col_allele);
 	dfree(ctx->d_gtA); dfree(ctx->d_gtS); dfree(ctx->d_gtC); dfree(ctx->d_asA); dfree(ctx->d_asS);
 	dfree(ctx->d_initA); dfree(ctx->d_initS);
@@ -1908,6 +1925,7 @@ static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const in
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	drop_cv(ctx);	/* folds, the saved full data set and a hold-out in force belong to the data set that goes */
+	drop_resample(ctx);	/* so does the base of its selections of loci (kept while mchip_resample_loci itself installs one) */
 	/* The same shape and allele lists as the data set held (the next bootstrap replicate, a re-upload): every buffer stays;
 	 * the model is dropped as the contract says, but its buffers are parked for an mchip_set_model with the same arguments.
 	 * Freeing and re-allocating ~10 GB per replicate costs little per call, but the runtime returns freed memory lazily and
@@ -2349,6 +2367,83 @@ int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor, double *
 
 static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_constrained, int do_projection,
 			  double eta_lb, double p_lb, int n_secants);
+
+/* ---- a selection of loci with repeats (kernel: mchip_resample.hip) ---- */
+int mchip_resample_loci(mchip_context *ctx, const int32_t *src, int L2)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
+	if (ctx->cv_fold >= 0) return fail(ctx, MCHIP_ERR_STATE, "resample_loci: a cross-validation fold is held out%s", nullptr);
+	if (!src && !ctx->d_rs_base) return fail(ctx, MCHIP_ERR_STATE, "resample_loci: no saved base to install again%s", nullptr);
+	const int I = ctx->I, pl = ctx->ploidy;
+	const int Lb = ctx->d_rs_base ? ctx->rs_L : ctx->L;
+	std::vector<int32_t> ua2;
+	if (src) {	/* everything that can be refused is refused before anything is touched */
+		if (L2 < 1) return fail(ctx, MCHIP_ERR_INVALID, "resample_loci: L2 must be at least 1%s", nullptr);
+		const std::vector<int32_t> &ua_base = ctx->d_rs_base ? ctx->rs_ua : ctx->h_ua;
+		long long T2 = 0;
+		ua2.resize((size_t)L2);
+		for (int j = 0; j < L2; j++) {
+			if (src[j] < 0 || src[j] >= Lb) return fail(ctx, MCHIP_ERR_INVALID, "resample_loci: locus index outside [0, L_base)%s", nullptr);
+			T2 += (ua2[j] = ua_base[src[j]]);
+		}
+		if (T2 > 2000000000LL) return fail(ctx, MCHIP_ERR_INVALID, "too many allele columns%s", nullptr);
+		if (T2 <= 0) return fail(ctx, MCHIP_ERR_INVALID, "no alleles%s", nullptr);
+	} else {
+		L2 = Lb;
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	if (!ctx->d_rs_base) {	/* the data set installed now is the base: keep it, in upload form */
+		const size_t n = (size_t)I * Lb * pl;
+		HIPCHK(hipMalloc((void **)&ctx->d_rs_base, n));
+		hipLaunchKernelGGL(k_unlayout, dim3(nblk_capped(n)), dim3(256), 0, ctx->stream, ctx->d_gtA, I, Lb, pl, ctx->d_rs_base);
+		if (MCHIP_WAIT(hipGetLastError()) != hipSuccess || MCHIP_WAIT(hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+			dfree(ctx->d_rs_base);
+			return fail(ctx, MCHIP_ERR_HIP, "resample_loci: saving the base failed%s", nullptr);
+		}
+		ctx->rs_L = Lb;
+		ctx->rs_ua = ctx->h_ua;
+		ctx->rs_empty = ctx->empty_rows;
+	}
+	/* the new shape: tables, buffers, no model, no init genotypes, no cross-validation state -- and the base stays */
+	ctx->rs_installing = 1;
+	int rc = set_shape(ctx, I, L2, pl, src ? ua2.data() : ctx->rs_ua.data());
+	ctx->rs_installing = 0;
+	if (!rc) {
+		if (!src) {
+			if (!(rc = install_raw(ctx, ctx->d_rs_base))) ctx->empty_rows = ctx->rs_empty;
+		} else {
+			rc = [&]() -> int {
+				int rc2 = stream_buffer(ctx);
+				if (rc2) return rc2;
+				scoped_dev<uint8_t> d_seen;
+				scoped_dev<int32_t> d_src;
+				HIPCHK(d_seen.alloc((size_t)I));
+				HIPCHK(d_src.alloc((size_t)L2));
+				HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
+				HIPCHK(hipMemcpyAsync(d_src.p, src, sizeof(int32_t) * (size_t)L2, hipMemcpyHostToDevice, ctx->stream));
+				mchip_resample_gather(ctx->stream, ctx->d_rs_base, d_src.p, I, Lb, L2, pl, ctx->d_draw, d_seen.p);
+				HIPCHK(hipGetLastError());
+				std::vector<uint8_t> seen((size_t)I);
+				HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
+				if ((rc2 = install_raw(ctx, ctx->d_draw))) return rc2;	/* (synchronises the stream) */
+				ctx->empty_rows.clear();
+				for (int i = 0; i < I; i++)
+					if (!seen[i]) ctx->empty_rows.push_back(i);
+				return MCHIP_OK;
+			}();
+		}
+	}
+	if (rc) {	/* a failure half way: no data set (set_shape), or one whose bytes are not what was asked for */
+		free_model(ctx);
+		free_data(ctx);
+		return rc;
+	}
+	ctx->first_empty = ctx->empty_rows.empty() ? -1 : ctx->empty_rows[0];
+	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
+	return MCHIP_OK;
+}
 
 int mchip_set_model(mchip_context *ctx, int K, int admixture, int eta_constrained, int do_projection,
 		    double eta_lb, double p_lb, int n_secants)

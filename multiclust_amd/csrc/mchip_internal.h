@@ -215,6 +215,12 @@ int mchip_cv_score(hipStream_t s, int I, int L, int ploidy, int K, int max_M, in
 		   int fold_id, const int32_t *toff, const double *P, const double *Q, int qstride, double floor, double *part,
 		   unsigned long long *counts);
 
+/* A selection of loci with repeats (mchip_resample.hip; mchip_resample_loci).  base: the saved data set in upload form
+ * [I][L_base][ploidy]; src: L2 locus indices, each in [0, L_base) (checked by the caller).  out[i][j][.] = base[i][src[j]][.] in
+ * upload form [I][L2][ploidy]; seen[i] (zeroed by the caller) = 1 for every individual that keeps an observed copy. */
+void mchip_resample_gather(hipStream_t s, const uint8_t *base, const int32_t *src, int I, int L_base, int L2, int ploidy, uint8_t *out,
+			   uint8_t *seen);
+
 inline int mchip_ind_waves(int K, int tile_cols)
 {
 	/* (a buffer is rounded up to whole 1 KiB pieces where tiles are copied straight into LDS) */

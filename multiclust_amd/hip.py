@@ -98,6 +98,7 @@ def load():
         "mchip_cv_get_folds": ([vp, vp], i32),
         "mchip_cv_hold_out": ([vp, i32], i32),
         "mchip_cv_heldout_loglik": ([vp, i32, C.c_double, dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], i32),
+        "mchip_resample_loci": ([vp, vp, i32], i32),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("MCHIP_ALLOW_PARTIAL_ABI") == "1" and not hasattr(lib, name):
@@ -121,6 +122,7 @@ ABI_SYMBOLS = [
     "mchip_comm_last_error", "mchip_comm_info", "mchip_progress_report", "mchip_progress_note",
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
+    "mchip_resample_loci",
 ]
 
 
@@ -135,6 +137,7 @@ class Context:
             raise HipError("mchip_create failed: %s (no GPU => no product path; nothing falls back to the CPU)" % STATUS.get(rc, rc))
         self.I = self.L = self.ploidy = self.T = self.K = 0
         self.indiv_q = True
+        self._ua = self._rs_ua = None   # allele lists of the data set held and of the base of its selections (resample_loci)
 
     def _chk(self, rc):
         if rc:
@@ -157,6 +160,7 @@ class Context:
         I, L, p = geno.shape
         self._chk(self.lib.mchip_set_genotypes(self.h, I, L, p, ua.ctypes.data, geno.ctypes.data))
         self.I, self.L, self.ploidy, self.T = I, L, p, int(ua.sum())
+        self._ua, self._rs_ua = ua.copy(), None
 
     def set_genotypes_bed(self, I, bed, record_bytes=None):
         """PLINK 1 packed records [L][record_bytes] (the .bed file behind its three header bytes; record_bytes defaults to the
@@ -170,6 +174,7 @@ class Context:
         ua = np.empty(L, dtype=np.int32)
         self._chk(self.lib.mchip_set_genotypes_bed(self.h, I, L, bed.ctypes.data, rb, ua.ctypes.data))
         self.I, self.L, self.ploidy, self.T = I, L, 2, int(ua.sum())
+        self._ua, self._rs_ua = ua.copy(), None
         return ua
 
     def data_counts(self):
@@ -182,6 +187,7 @@ class Context:
         """take the data set another context (same device) holds"""
         self._chk(self.lib.mchip_copy_genotypes(self.h, src.h))
         self.I, self.L, self.ploidy, self.T = src.I, src.L, src.ploidy, src.T
+        self._ua, self._rs_ua = src._ua, None
 
     def get_genotypes(self):
         g = np.empty((self.I, self.L, self.ploidy), dtype=np.uint8)
@@ -221,6 +227,25 @@ class Context:
         self._chk(self.lib.mchip_cv_heldout_loglik(self.h, slot, floor, C.byref(s), C.byref(n), C.byref(nf)))
         return s.value, n.value, nf.value
 
+    def resample_loci(self, src):
+        """install the selection `src` (locus indices into the base, repeats allowed) of the base: the data set held when the first
+        selection was asked for; None: the base again (include/multiclust_hip.h).  Drops the model; L and T follow."""
+        base = getattr(self, "_rs_ua", None)
+        if base is None:
+            base = getattr(self, "_ua", None)
+        if src is None:
+            self._chk(self.lib.mchip_resample_loci(self.h, None, 0))
+            ua = base
+        else:
+            s = np.ascontiguousarray(src, dtype=np.int32)
+            assert s.ndim == 1
+            if base is None and self.L:
+                raise HipError("resample_loci: this wrapper was not told the allele lists of the data set its context holds")
+            self._chk(self.lib.mchip_resample_loci(self.h, s.ctypes.data, s.size))
+            ua = base[s]
+        self._rs_ua, self._ua = base, ua
+        self.L, self.T, self.K = int(ua.size), int(ua.sum()), 0
+
     def set_init_genotypes(self, geno):
         """The data set hard-partition initialisations read instead of the current one (None: back to the current one)."""
         if geno is None:
@@ -241,6 +266,7 @@ class Context:
         self._chk(self.lib.mchip_simulate_genotypes(self.h, I, L, ploidy, ua.ctypes.data, w.ctypes.data, K,
                                                     eta_constrained, q.ctypes.data, p.ctypes.data))
         self.I, self.L, self.ploidy, self.T = I, L, ploidy, int(ua.sum())
+        self._ua, self._rs_ua = ua.copy(), None
 
     def simulate_genotypes_mixture(self, I, L, ploidy, ua, window, K, eta, p):
         """The mixture model's parametric-bootstrap data set drawn on the device (include/multiclust_hip.h); drops the model."""
@@ -252,6 +278,7 @@ class Context:
         self._chk(self.lib.mchip_simulate_genotypes_mixture(self.h, I, L, ploidy, ua.ctypes.data, w.ctypes.data, K,
                                                             eta.ctypes.data, p.ctypes.data))
         self.I, self.L, self.ploidy, self.T = I, L, ploidy, int(ua.sum())
+        self._ua, self._rs_ua = ua.copy(), None
 
     def init_from_individual_centers(self, centers, to=0):
         """Mixture model: assignment to the nearest of the K center individuals and the parameters initialised from it, into

@@ -72,6 +72,12 @@ class McCvResult(C.Structure):
                 ("fold_floored", C.c_uint64 * CV_MAX_FOLDS), ("fold_iter", C.c_int * CV_MAX_FOLDS)]
 
 
+class McSeResult(C.Structure):
+    """mc_se_result (multiclust_amd/host/mc_host.h)"""
+    _fields_ = [("n_replicates", C.c_int), ("block", C.c_int), ("n_failed", C.c_int), ("n_iter", C.c_uint64),
+                ("mean_se", C.c_double), ("max_se", C.c_double)]
+
+
 class CliOptions(C.Structure):
     """mc_cli_options (multiclust_amd/host/mc_cli.h)"""
     _fields_ = [("em", McOptions), ("filename", C.c_char_p), ("filename_file", C.c_char_p), ("path", C.c_char_p),
@@ -82,8 +88,8 @@ class CliOptions(C.Structure):
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
                 ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
-    # (the C struct ends with cv_folds / cv_floor, the command line's --cv: only mc_main.c reads them, the readers this mirror is
-    # handed to stop at bed_prefix)
+    # (the C struct ends with cv_folds / cv_floor and se_replicates / se_block, the command line's --cv and --se: only mc_main.c
+    # reads them, the readers this mirror is handed to stop at bed_prefix)
 
 
 class CliData(C.Structure):
@@ -243,6 +249,9 @@ def load():
     lib.mc_cross_validate.argtypes = [OP, DP, MP, C.c_int, C.c_double, C.POINTER(McCvResult)]
     lib.mc_cv_default_floor.argtypes = [DP]
     lib.mc_cv_default_floor.restype = C.c_double
+    lib.mc_locus_bootstrap.argtypes = [OP, DP, MP, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(McSeResult)]
+    lib.mc_se_list_capacity.argtypes = [C.c_int, C.c_int]
+    lib.mc_se_draw_lists.argtypes = [C.POINTER(McRng), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.mc_aic.restype = C.c_double
     lib.mc_aic.argtypes = [C.c_double, C.c_int]
     lib.mc_bic.restype = C.c_double
@@ -357,3 +366,30 @@ class Fit:
             raise hip.HipError("mc_cross_validate failed (%d)" % rc)
         folds = [(r.fold_sum_log[f], r.fold_copies[f], r.fold_floored[f], r.fold_iter[f]) for f in range(n_folds)]
         return r.cv, r.sum_log, r.n_copies, r.n_floored, folds
+
+    def locus_bootstrap(self, n_replicates, block=1):
+        """mc_locus_bootstrap on the estimate in slot mod.pindex: (mean, se, count, result) -- mean and standard error of every
+        entry of Q over the replicates (loci, or blocks of `block` neighbouring loci, drawn with replacement; each replicate fitted
+        from the estimate), the number of replicates each entry was observed in, and the mc_se_result.  Leaves the model as it
+        found it."""
+        shape = (self.I, self.K) if self.indiv_q else (self.K,)
+        mean, se, count = np.empty(shape), np.empty(shape), np.empty(shape, dtype=np.int32)
+        r = McSeResult()
+        rc = self.lib.mc_locus_bootstrap(C.byref(self.opt), C.byref(self.dat), self.mp, n_replicates, block, mean.ctypes.data,
+                                         se.ctypes.data, count.ctypes.data, C.byref(r))
+        if rc:
+            raise hip.HipError("mc_locus_bootstrap failed (%d)" % rc)
+        return mean, se, count, r
+
+    def locus_lists(self, n_replicates, block=1):
+        """the locus lists mc_locus_bootstrap installs for these arguments and the options' seed, one int32 array per replicate"""
+        L = self.dat.L
+        cap = self.lib.mc_se_list_capacity(L, block)
+        if not cap or n_replicates < 0:
+            raise hip.HipError("locus_lists: block must be in [1, L]")
+        rng = McRng()
+        self.lib.mc_srand(C.byref(rng), self.opt.seed)
+        src, n = np.empty((max(n_replicates, 1), cap), dtype=np.int32), np.empty(max(n_replicates, 1), dtype=np.int32)
+        if self.lib.mc_se_draw_lists(C.byref(rng), L, block, n_replicates, src.ctypes.data, n.ctypes.data):
+            raise hip.HipError("mc_se_draw_lists failed")
+        return [src[r, :n[r]].copy() for r in range(n_replicates)]

@@ -47,6 +47,9 @@ typedef struct mc_cli_options {
 	const char *bed_prefix;		/* --bed (extension): read <prefix>.bed / .bim / .fam instead of the STRUCTURE file of -f */
 	int cv_folds;			/* --cv <F> (extension): F-fold cross-validation of the best fit of every K (admixture model); 0 = off */
 	double cv_floor;		/* --cv-floor <x>: smallest prediction a held-out copy is scored with; 0 = the default of mc_cross_validate */
+	int se_replicates;		/* --se <B> (extension): bootstrap standard errors of the mixing proportions of the best fit of every K
+					 * from B resamples of the loci (mc_locus_bootstrap, either model); 0 = off */
+	int se_block;			/* --se-block <n>: blocks of n neighbouring loci are resampled; default 1 */
 } mc_cli_options;
 
 typedef struct mc_cli_data {
@@ -107,5 +110,10 @@ double mc_adjusted_rand(int n, int k1, int k2, const int *cl1, const int *cl2);
 void mc_partition(const mc_cli_data *dat, const mc_fit_view *fit, int *I_K, int *count_K);
 /* write_file_detail + popq_* + indivq_* (write_file.c:203-348, 398-475, 492-569, 618-732) */
 int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc_fit_view *fit, const int *count_K);
+/* --se (an extension): <stem>.<admix|mix>.K=<K>.se.txt, lines "i k eta se mean n" (tab-separated, one header line; without i under
+ * shared mixing proportions and the mixture model): the estimate q, and the standard error, mean and number of replicates of
+ * mc_locus_bootstrap for every entry */
+int mc_write_se(const mc_cli_options *opt, const mc_cli_data *dat, int K, const double *q, const double *mean, const double *se,
+		const int32_t *count);
 
 #endif

@@ -245,6 +245,38 @@ typedef struct mc_cv_result {
 double mc_cv_default_floor(const mc_data *dat);
 int mc_cross_validate(const mc_options *opt, const mc_data *dat, mc_model *mod, int n_folds, double floor, mc_cv_result *out);
 
+/* ---- standard errors of the mixing proportions: non-parametric bootstrap over loci (mc_se.c; an extension -- the reference's
+ * bootstrap is parametric, tests K - 1 against K and gives no standard errors) ----
+ * `mod` holds the full-data estimate of its K in slot mod->pindex; both models (individual or shared mixing proportions, and the
+ * mixture model's eta_k).  nq = mchip_q_length.
+ * Stream convention: a fresh mc_rng seeded with opt->seed -- a stream of their own, so the run's rand() stream is not advanced,
+ * and the lists do not depend on K.  The L loci form nb = ceil(L / block) blocks of consecutive loci (the last may be shorter).
+ * Replicate r takes the next nb draws of the stream; each draw b = rand() % nb appends the loci b block ... min(L, (b + 1) block) - 1
+ * to the replicate's list; L2 is what that adds up to.
+ * For each replicate: the list is installed (mchip_resample_loci), the model set again (mchip_set_model with mc_model_create's
+ * arguments), slot 0 takes the estimate -- q as it is (rows of empty individuals go up and come back as NaN), p with its columns
+ * following their loci -- and mc_em runs from that warm start with the run's own options.  The warm start stands in for matching
+ * cluster labels between replicates: a fit that starts at the estimate stays in its labelling unless the replicate moves it to a
+ * permuted solution, which then inflates the standard errors of the entries concerned.  A fit that stops on NaN or on a decrease
+ * of the log likelihood is reported on stderr, counted in n_failed and skipped; a device failure ends the call with its status.
+ * Accumulation is on the host, from mc_model_get_q(pindex), in replicate order, per entry x by Welford's update
+ *     n++; d = x - mean; mean += d / n; M2 += d (x - mean)
+ * where a NaN entry (the row of an individual without an observed copy in this replicate) is skipped and does not count.
+ * count[e] = the entry's n, se[e] = sqrt(M2 / (n - 1)) or NaN when n < 2, mean[e] NaN when n = 0; equal values give se = 0 exactly.
+ * mean_se / max_se: over the entries with n >= 2 (NaN when there is none); n_iter: EM iterations of all the fits.
+ * Afterwards, whatever happened, the base data set is installed again (mchip_resample_loci(NULL)), the model set, and the
+ * parameters of slot mod->pindex, mod->logL, mod->n_iter and the rest of the host state are what they were; the other two slots,
+ * the secants and the expected counts are unspecified.
+ * 2 <= n_replicates <= MC_SE_MAX_REPLICATES and 1 <= block <= L, else MCHIP_ERR_INVALID. */
+#define MC_SE_MAX_REPLICATES 10000
+typedef struct mc_se_result { int n_replicates, block, n_failed; uint64_t n_iter; double mean_se, max_se; } mc_se_result;
+int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod, int n_replicates, int block,
+		       double *mean /* [nq] */, double *se /* [nq] */, int32_t *count /* [nq] */, mc_se_result *out);
+/* The next n_lists lists of the stream convention above, drawn from `rng` (mc_srand(rng, opt->seed) before the first): list r is
+ * src[r * cap ... r * cap + len[r] - 1] with cap = mc_se_list_capacity(L, block) = nb * block (0 for a bad L or block). */
+int mc_se_list_capacity(int L, int block);
+int mc_se_draw_lists(mc_rng *rng, int L, int block, int n_lists, int32_t *src /* [n_lists][cap] */, int32_t *len /* [n_lists] */);
+
 /* ---- opt-in watchdog (mc_watchdog.c): nothing in the reference corresponds -- it has nothing to wait for ----
  * mc_watchdog_start(s): a detached thread that polls the library's event count (mchip_progress_report) and, when it has stood
  * still for s seconds, prints where every thread stands (library record + /proc/self/task) on stderr and leaves with _exit(3).

@@ -8,7 +8,8 @@
  * (618-627), print_model_state (718-793), run_bootstrap (675-708) and the -w repetition summary (201-347).
  * Deliberately absent (documented in DESIGN.md): -I/-I1 (allele-index mode gives different numbers from default
  * mode in the reference itself), --impute, --simulate, -x (not implemented in the reference either).
- * Extensions: --cv <F> adds the F-fold cross-validation error of every K's best fit (one more stdout line per K, nothing else changes);
+ * Extensions: --se <B> adds bootstrap standard errors of the mixing proportions of every K's best fit (B resamples of the loci, or of
+ * blocks of --se-block neighbouring loci: one more stdout line per K and one more file, nothing else changes); --cv <F> adds the F-fold cross-validation error of every K's best fit (one more stdout line per K, nothing else changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
  * the node (one host thread and one context per GPU, units u = d, d+n, ..., each starting from the serial program's
  * rand() position by jump-ahead), with a single RCCL all-reduce of the per-unit result table, after which the serial
@@ -56,7 +57,10 @@ static void usage(FILE *fp, const char *prog)
 		"  --bed <prefix>  read the PLINK 1 fileset <prefix>.bed/.bim/.fam instead of -f (diploid; not with -f, -R or -p other than 2;\n"
 		"                --missing is ignored); the 2-bit records are uploaded as they are and unpacked on the GPU\n"
 		"  --cv <F>      F-fold cross-validation (2..64) of the best fit of every K: one more line 'CV error (K=..)' per K; needs -a,\n"
-		"                not with -b, -w, -M or --gpus above 1        --cv-floor <x>  smallest prediction scored, in (0, 1] (1/(I*ploidy+1))\n", prog);
+		"                not with -b, -w, -M or --gpus above 1        --cv-floor <x>  smallest prediction scored, in (0, 1] (1/(I*ploidy+1))\n"
+		"  --se <B>      standard errors of the mixing proportions of the best fit of every K from B (2..10000) bootstrap resamples of\n"
+		"                the loci: one more line 'Bootstrap SE (K=..)' per K and a file <stem>.<admix|mix>.K=<K>.se.txt; either model; not with -b,\n"
+		"                -w, -M or --gpus above 1    --se-block <n>  resample blocks of n neighbouring loci (1)\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -91,6 +95,7 @@ static void defaults(mc_cli_options *o)
 	o->compact = 1;
 	o->n_gpus = 1;
 	o->n_streams = 1;
+	o->se_block = 1;
 }
 
 #define BAD(msg) do { fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '%s'); try -h\n", msg, i < argc ? argv[i] : ""); return MC_EXIT_INVALID_CMD_ARGUMENT; } while (0)
@@ -171,6 +176,8 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 		case 'x': BAD("-x (block relaxation) is not implemented, as in the reference");
 		case 's':
 			if (!strncmp(w, "si", 2)) BAD("--simulate is not supported by this build");
+			if (!strncmp(w, "se-b", 4)) { if (arg_int(argc, argv, ++i, &v) || v < 1 || v > 2147483647L) BAD("--se-block"); o->se_block = (int)v; break; }
+			if (!strncmp(w, "se", 2)) { if (arg_int(argc, argv, ++i, &v) || v < 2 || v > MC_SE_MAX_REPLICATES) BAD("--se"); o->se_replicates = (int)v; break; }
 			if (!strncmp(w, "st", 2)) { if (arg_int(argc, argv, ++i, &v) || v < 1 || v > 16) BAD("--streams"); o->n_streams = (int)v; break; }
 			if (arg_int(argc, argv, ++i, &v) || v < 0 || v > 6) BAD("-s");
 			o->em.accel_scheme = (int)v;
@@ -218,6 +225,16 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			return MC_EXIT_INVALID_CMD_ARGUMENT;
 		}
 	}
+	if (o->se_replicates) {	/* extension: the same for the bootstrap over loci (either model) */
+		const char *why = NULL;
+		if (o->n_bootstrap) why = "--se cannot be combined with the bootstrap (-b)";
+		else if (o->n_gpus > 1) why = "--se cannot be combined with --gpus above 1";
+		else if (!o->write_files || o->parallel) why = "--se cannot be combined with -w or -M";
+		if (why) {
+			fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '--se'); try -h\n", why);
+			return MC_EXIT_INVALID_CMD_ARGUMENT;
+		}
+	}
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -258,6 +275,9 @@ typedef struct run_state {
 	/* --cv: the cross-validation of the K just fitted, printed by estimate_model behind the K's summary line */
 	mc_cv_result cv;
 	int cv_done;
+	/* --se: the same for the bootstrap over loci */
+	mc_se_result se;
+	int se_done;
 } run_state;
 
 /* sharded runs use n_gpus * n_streams workers (host thread + context + stream each); worker x sits on device
@@ -391,6 +411,36 @@ static int cli_cross_validate(const mc_cli_options *o, const mc_data *md, run_st
 	return rc;
 }
 
+/* --se: bootstrap standard errors of the mixing proportions of the best fit of one K, under the same arrangement; with result
+ * files on they go to <stem>.<admix|mix>.K=<K>.se.txt */
+static int cli_locus_bootstrap(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, mc_model *mod, int K, int device,
+			       const double *q, const double *p, double logL, int n_iter, int converged)
+{
+	const size_t nq = (o->em.admixture && !o->em.eta_constrained) ? (size_t)d->I * K : (size_t)K;
+	mc_model *own = NULL;
+	double *mean = malloc(sizeof(double) * nq), *se = malloc(sizeof(double) * nq);
+	int32_t *count = malloc(sizeof(int32_t) * nq);
+	int rc = (mean && se && count) ? 0 : MCHIP_ERR_ALLOC;
+	mchip_progress_note("bootstrap over loci");
+	if (!rc && !mod) {
+		if (!(rc = mc_model_create(&own, &o->em, md, K, device))) mod = own;
+	}
+	if (!rc) {
+		mc_reset_model_state(mod);
+		if (!(rc = mc_model_set_q(mod, mod->pindex, q)) && !(rc = mc_model_set_p(mod, mod->pindex, p))) {
+			mod->logL = logL;
+			mod->n_iter = n_iter;
+			mod->converged = converged;
+			rc = mc_locus_bootstrap(&o->em, md, mod, o->se_replicates, o->se_block, mean, se, count, &st->se);
+			if (!rc) st->se_done = 1;
+			if (!rc && o->write_files) rc = mc_write_se(o, d, K, q, mean, se, count);
+		}
+	}
+	mc_model_free(own);
+	free(mean); free(se); free(count);
+	return rc;
+}
+
 static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, mc_model *mod, run_state *st, int bootstrap)
 {
 	const int K = mod->K, nq = (o->em.admixture && !o->em.eta_constrained) ? d->I * K : K;
@@ -401,7 +451,7 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 	double *q = NULL, *p = NULL, *sik = NULL;
 	int *count_K = NULL, rc = 0;
 	/* --cv: the best fit of THIS K (the files above follow the maximum over the K so far) */
-	const int cv = o->cv_folds && !bootstrap;
+	const int cv = (o->cv_folds || o->se_replicates) && !bootstrap;	/* (--se keeps the same fit) */
 	double *cv_q = NULL, *cv_p = NULL, cv_logL = -INFINITY;
 	int cv_iter = 0, cv_conv = 0;
 	mc_summary_reset(&st->sum);
@@ -484,7 +534,8 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 			}
 		}
 	}
-	if (cv && cv_q) rc = cli_cross_validate(o, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
+	if (cv && cv_q && o->cv_folds) rc = cli_cross_validate(o, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
+	if (!rc && cv && cv_q && o->se_replicates) rc = cli_locus_bootstrap(o, d, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
 DONE:
 	free(q); free(p); free(sik); free(count_K); free(cv_q); free(cv_p);
 	return rc;
@@ -572,7 +623,7 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 	}
 	for (int x = 0; x < n_dev; x++) {
 		w[x].o = o; w[x].d = d; w[x].md = md; w[x].K = K; w[x].index = x; w[x].n_dev = n_dev; w[x].n_units = n_units;
-		w[x].want_params = keep_mle || (!bootstrap && o->write_files) || o->afile != NULL || (o->cv_folds && !bootstrap);
+		w[x].want_params = keep_mle || (!bootstrap && o->write_files) || o->afile != NULL || ((o->cv_folds || o->se_replicates) && !bootstrap);
 		w[x].sim = sim;
 		w[x].starts = starts; w[x].draws = mc_draws_per_init(&o->em, md, K); w[x].res = res;
 		if (pthread_create(&th[x], NULL, shard_main, &w[x])) shard_main(&w[x]);	/* no thread to be had: in this one */
@@ -638,12 +689,16 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 			if (fits) st->arand = mc_adjusted_rand(d->I, st->pK, K, st->partition_from_file, st->I_K);
 		}
 	}
-	if (!rc && o->cv_folds && !bootstrap) {	/* --cv: the best unit of this K, on the device whose worker fitted it */
+	if (!rc && (o->cv_folds || o->se_replicates) && !bootstrap) {	/* --cv, --se: the best unit of this K, on the device whose worker fitted it */
 		int ub = 0;
 		for (int u = 1; u < n_units; u++) if (res[u].logL > res[ub].logL) ub = u;
 		const shard_worker *own = &w[ub % n_dev];
 		if (own->best_unit != ub) { fprintf(stderr, "ERROR [mc_main.c]: owner of the best unit does not hold it\n"); rc = MCHIP_ERR_STATE; goto DONE; }
-		rc = cli_cross_validate(o, md, st, NULL, K, worker_device(o, ub % n_dev), own->q, own->p, res[ub].logL, res[ub].n_iter, res[ub].converged);
+		if (o->cv_folds)
+			rc = cli_cross_validate(o, md, st, NULL, K, worker_device(o, ub % n_dev), own->q, own->p, res[ub].logL, res[ub].n_iter, res[ub].converged);
+		if (!rc && o->se_replicates)
+			rc = cli_locus_bootstrap(o, d, md, st, NULL, K, worker_device(o, ub % n_dev), own->q, own->p, res[ub].logL, res[ub].n_iter,
+						 res[ub].converged);
 	}
 DONE:
 	if (w) for (int x = 0; x < n_dev; x++) { free(w[x].q); free(w[x].p); free(w[x].sik); }
@@ -704,6 +759,11 @@ static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const m
 			fprintf(st->out, "CV error (K=%d, %d folds): %.10f  [%llu held-out copies, %llu floored]\n", K, o->cv_folds, st->cv.cv,
 				(unsigned long long)st->cv.n_copies, (unsigned long long)st->cv.n_floored);
 			st->cv_done = 0;
+		}
+		if (st->se_done) {	/* --se */
+			fprintf(st->out, "Bootstrap SE (K=%d, %d replicates, block %d): mean %.10f  max %.10f  [%d failed]\n", K, st->se.n_replicates,
+				st->se.block, st->se.mean_se, st->se.max_se, st->se.n_failed);
+			st->se_done = 0;
 		}
 		if (total_iter) *total_iter += st->sum.n_total_iter;
 		if (o->n_bootstrap && K == st->null_K) st->max_logL_H0 = st->sum.max_logL;
@@ -847,6 +907,7 @@ int main(int argc, const char **argv)
 	if (mc_synchronize(&o.em, &md)) return MC_EXIT_INVALID_USER_SETUP;
 	if (d.I < o.max_K) { fprintf(stderr, "ERROR: Maximum number of clusters (%d) (set with command-line argument -k) cannot exceed the number of individuals (%d)\n", o.max_K, d.I); return MC_EXIT_INVALID_USER_SETUP; }
 	if (o.n_bootstrap && o.max_K <= 1) { fprintf(stderr, "ERROR: When bootstrapping, maximum K (%d) (set with command-line argument -k) must exceed 1.\n", o.max_K); return MC_EXIT_INVALID_USER_SETUP; }
+	if (o.se_replicates && o.se_block > d.L) { fprintf(stderr, "ERROR: The block of --se-block (%d) cannot exceed the number of loci (%d).\n", o.se_block, d.L); return MC_EXIT_INVALID_USER_SETUP; }
 	if (o.min_K > o.max_K) { fprintf(stderr, "ERROR: Minimum K (%d) must not exceed maximum K (%d).\n", o.min_K, o.max_K); return MC_EXIT_INVALID_USER_SETUP; }
 	if (!o.target_ll && !o.target_revisit && !o.em.n_seconds && !o.n_init) o.n_init = 1;
 	if (!o.em.n_rand_em_init) o.em.initialization_procedure = MC_INIT_NOTHING;	/* -m 0 (multiclust.c:1549-1550) */

@@ -113,6 +113,26 @@ double mc_adjusted_rand(int n, int k1, int k2, const int *cl1, const int *cl2)
 	return index;
 }
 
+int mc_write_se(const mc_cli_options *opt, const mc_cli_data *dat, int K, const double *q, const double *mean, const double *se,
+		const int32_t *count)
+{
+	char base[4096], path[4200];
+	const int admix = opt->em.admixture, shared_eta = (!admix || opt->em.eta_constrained);
+	FILE *fp;
+	stem(opt, base, sizeof base);
+	snprintf(path, sizeof path, "%s.%s.K=%d.se.txt", base, admix ? "admix" : "mix", K);
+	if (!(fp = open_out(path))) return 1;
+	fprintf(fp, shared_eta ? "k\teta\tse\tmean\tn\n" : "i\tk\teta\tse\tmean\tn\n");
+	for (int i = 0; i < (shared_eta ? 1 : dat->I); i++)
+		for (int k = 0; k < K; k++) {
+			const size_t x = (size_t)i * K + k;
+			if (!shared_eta) fprintf(fp, "%d\t", i);
+			fprintf(fp, "%d\t%.10f\t%.10f\t%.10f\t%d\n", k, q[x], se[x], mean[x], (int)count[x]);
+		}
+	fclose(fp);
+	return 0;
+}
+
 int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc_fit_view *fit, const int *count_K)
 {
 	char base[4096], path[4200];
