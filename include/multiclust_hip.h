@@ -309,6 +309,37 @@ int mchip_cv_hold_out(mchip_context *ctx, int fold /* -1: the full data set agai
 int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor,
 			    double *sum_log, uint64_t *n_copies, uint64_t *n_floored);
 
+/* ---- mixing proportions of query individuals against fixed allele frequencies (an extension: the reference fits Q and P together
+ * and has nothing for individuals kept out of the panel) ----
+ * For every listed individual i = rows[r] (distinct, each in [0, I)) the admixture model's q_i. is fitted with P of `slot` held
+ * fixed, each row to its own convergence:
+ *   q(0)     1 / K, or row i of `slot` as the device stores it when from_slot != 0;
+ *   n = 0, 1, ...   one pass over the individual's observed copies (i, l, a), m the copy's allele:
+ *                   t = sum_k q_k p_klm,   l_n = sum log t,   S_k = q_k sum p_klm / t   (one term per copy);
+ *            if n >= 1 and a test is made and every test made holds, stop converged -- the tests are mc_converged's
+ *                   (em_alg.c:163-182): abs_error != 0: |l_n - l_(n-1)| <= abs_error; rel_error != 0: |l_n - l_(n-1)| / |l_(n-1)| <=
+ *                   rel_error; a zero error is a test not made.  Where that rule is degenerate this one is not: the difference is
+ *                   taken whichever test is made (there a relative test without an absolute one divides a zero), and with both
+ *                   errors zero no row converges, the loop runs to max_iter (there such a fit stops at its first check);
+ *            if n == max_iter, stop not converged;
+ *            else q(n+1) = S / sum_k S_k, then the simplex projection with the model's lower bound when the model has
+ *                   do_projection: the arithmetic of an EM step's Q side.
+ *   on stopping:    q_rows[r][.] = q(n), loglik_rows[r] = l_n, iter_rows[r] = n, converged_rows[r] = 1 or 0.
+ * An individual without an observed copy reports 1 / K, 0, n = 0, not converged.  A row whose l_n is not finite stops there and
+ * reports NaN proportions, that l_n, n, not converged (a copy whose allele has frequency 0 in every cluster the row has weight in).
+ * Reads the full data set: the saved one while a cross-validation hold-out is in force (as mchip_cv_heldout_loglik does), so
+ * individuals hidden from the fit of P by a hold-out are fitted on their genotypes; otherwise the installed one.
+ * Writes the four host arrays and nothing else: no parameter slot, secant, expected count, held S-side sum, data-set or hold-out
+ * state changes.  Sums are combined in an order fixed by the shape, no floating-point atomics: two calls on the same state return
+ * the same bits.  One workgroup per row, iterating inside one launch (mchip_query.hip).
+ * MCHIP_ERR_STATE without a data set or model; MCHIP_ERR_UNSUPPORTED for the mixture model and for shared mixing proportions;
+ * MCHIP_ERR_INVALID for a slot out of range, a null pointer, n_rows < 1, a row out of range or repeated, max_iter < 1 or an error
+ * that is negative or NaN -- all checked before anything runs, the arrays stay untouched.
+ */
+int mchip_fit_q_rows(mchip_context *ctx, int slot, const int32_t *rows, int n_rows, int from_slot,
+		     int max_iter, double abs_error, double rel_error,
+		     double *q_rows /* [n_rows][K] */, double *loglik_rows, int32_t *iter_rows, uint8_t *converged_rows);
+
 /* ---- a selection of loci with repeats: the data sets of the non-parametric bootstrap over loci (an extension) ----
  * Let the base be the data set the context held when the first resample was asked for (I, L_base, ploidy, uniquealleles,
  * genotypes).  After the call the context holds exactly what

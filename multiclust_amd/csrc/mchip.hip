@@ -2365,6 +2365,66 @@ int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor, double *
 	return MCHIP_OK;
 }
 
+/* ---- mixing proportions of query individuals against fixed allele frequencies (kernels: mchip_query.hip) ---- */
+int mchip_fit_q_rows(mchip_context *ctx, int slot, const int32_t *rows, int n_rows, int from_slot, int max_iter, double abs_error,
+		     double rel_error, double *q_rows, double *loglik_rows, int32_t *iter_rows, uint8_t *converged_rows)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 0);
+	if (rc) return rc;
+	if ((rc = check_slot(ctx, slot))) return rc;
+	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixture model has no mixing proportions per individual%s", nullptr);
+	if (!ctx->qstride) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixing proportions are shared by all individuals%s", nullptr);
+	if (!rows || !q_rows || !loglik_rows || !iter_rows || !converged_rows) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	if (n_rows < 1 || n_rows > ctx->I) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: n_rows must be in [1, I]%s", nullptr);
+	if (max_iter < 1) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: max_iter must be >= 1%s", nullptr);
+	if (!(abs_error >= 0) || !(rel_error >= 0)) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: an error must be >= 0%s", nullptr);
+	{
+		std::vector<uint8_t> listed((size_t)ctx->I, 0);
+		for (int r = 0; r < n_rows; r++) {
+			if (rows[r] < 0 || rows[r] >= ctx->I) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: a row outside [0, I)%s", nullptr);
+			if (listed[(size_t)rows[r]]) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: a row is listed twice%s", nullptr);
+			listed[(size_t)rows[r]] = 1;
+		}
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	const int L = ctx->L, pl = ctx->ploidy, K = ctx->K;
+	const size_t nr = (size_t)n_rows;
+	scoped_dev<int32_t> d_rows, d_iter;
+	scoped_dev<uint8_t> d_geno, d_conv;
+	scoped_dev<double> d_q, d_ll;
+	HIPCHK(d_rows.alloc(nr));
+	HIPCHK(d_iter.alloc(nr));
+	HIPCHK(d_geno.alloc(nr * L * pl));
+	HIPCHK(d_conv.alloc(nr));
+	HIPCHK(d_q.alloc(nr * K));
+	HIPCHK(d_ll.alloc(nr));
+	HIPCHK(hipMemcpyAsync(d_rows.p, rows, nr * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	/* the full data set: the saved one while a fold is held out of the installed one */
+	const bool saved = ctx->cv_fold >= 0 && ctx->d_cv_full;
+	mchip_query_gather(ctx->stream, saved ? ctx->d_cv_full : ctx->d_gtA, saved ? 1 : 0, d_rows.p, n_rows, L, pl, d_geno.p);
+	HIPCHK(hipGetLastError());
+	mchip_query_fit(ctx->stream, n_rows, L, pl, K, d_geno.p, ctx->d_toff, ctx->d_p[slot], from_slot ? ctx->d_q[slot] : nullptr, d_rows.p,
+			ctx->do_projection, ctx->eta_lb, max_iter, abs_error, rel_error, d_q.p, d_ll.p, d_iter.p, d_conv.p);
+	HIPCHK(hipGetLastError());
+	/* (the rows array and the results cross in pageable memory: the copies are done when the stream is) */
+	std::vector<double> h_q(nr * K), h_ll(nr);
+	std::vector<int32_t> h_iter(nr);
+	std::vector<uint8_t> h_conv(nr);
+	HIPCHK(hipMemcpyAsync(h_q.data(), d_q.p, nr * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(h_ll.data(), d_ll.p, nr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(h_iter.data(), d_iter.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(h_conv.data(), d_conv.p, nr, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	/* the caller's arrays are written once everything has succeeded */
+	memcpy(q_rows, h_q.data(), nr * K * sizeof(double));
+	memcpy(loglik_rows, h_ll.data(), nr * sizeof(double));
+	memcpy(iter_rows, h_iter.data(), nr * sizeof(int32_t));
+	memcpy(converged_rows, h_conv.data(), nr);
+	return MCHIP_OK;
+}
+
 static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_constrained, int do_projection,
 			  double eta_lb, double p_lb, int n_secants);
 

@@ -215,6 +215,15 @@ int mchip_cv_score(hipStream_t s, int I, int L, int ploidy, int K, int max_M, in
 		   int fold_id, const int32_t *toff, const double *P, const double *Q, int qstride, double floor, double *part,
 		   unsigned long long *counts);
 
+/* Mixing proportions of listed individuals against fixed allele frequencies (mchip_query.hip; mchip_fit_q_rows).
+ * Gather: out[r][l][a] = genotype byte (rows[r], l, a), from the upload form [I][L][ploidy] (upload_form != 0) or from gtA.
+ * Fit: one workgroup per row of geno [n_rows][L][ploidy]; P a slot's [T][K]; Q0 a slot's [I][K] (the row rows[r] is the start)
+ * or NULL (1 / K); the four outputs are device arrays ([n_rows][K], [n_rows], [n_rows], [n_rows]). */
+void mchip_query_gather(hipStream_t s, const uint8_t *src, int upload_form, const int32_t *rows, int n_rows, int L, int ploidy, uint8_t *out);
+void mchip_query_fit(hipStream_t s, int n_rows, int L, int ploidy, int K, const uint8_t *geno, const int32_t *toff, const double *P,
+		     const double *Q0, const int32_t *rows, int do_projection, double lb, int max_iter, double abs_error, double rel_error,
+		     double *q_out, double *ll_out, int32_t *iter_out, uint8_t *conv_out);
+
 /* A selection of loci with repeats (mchip_resample.hip; mchip_resample_loci).  base: the saved data set in upload form
  * [I][L_base][ploidy]; src: L2 locus indices, each in [0, L_base) (checked by the caller).  out[i][j][.] = base[i][src[j]][.] in
  * upload form [I][L2][ploidy]; seen[i] (zeroed by the caller) = 1 for every individual that keeps an observed copy. */

@@ -99,6 +99,7 @@ def load():
         "mchip_cv_hold_out": ([vp, i32], i32),
         "mchip_cv_heldout_loglik": ([vp, i32, C.c_double, dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], i32),
         "mchip_resample_loci": ([vp, vp, i32], i32),
+        "mchip_fit_q_rows": ([vp, i32, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("MCHIP_ALLOW_PARTIAL_ABI") == "1" and not hasattr(lib, name):
@@ -122,7 +123,7 @@ ABI_SYMBOLS = [
     "mchip_comm_last_error", "mchip_comm_info", "mchip_progress_report", "mchip_progress_note",
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
-    "mchip_resample_loci",
+    "mchip_resample_loci", "mchip_fit_q_rows",
 ]
 
 
@@ -226,6 +227,20 @@ class Context:
         s, n, nf = C.c_double(), C.c_uint64(), C.c_uint64()
         self._chk(self.lib.mchip_cv_heldout_loglik(self.h, slot, floor, C.byref(s), C.byref(n), C.byref(nf)))
         return s.value, n.value, nf.value
+
+    def fit_q_rows(self, slot, rows, max_iter, abs_error=0.0, rel_error=0.0, from_slot=False, out=None):
+        """mchip_fit_q_rows: the mixing proportions of the listed individuals fitted with P of `slot` held fixed, each row to its
+        own convergence (include/multiclust_hip.h): (q [n][K], logL [n], iterations [n] int32, converged [n] uint8).  out: the four
+        arrays to fill instead of new ones."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        assert r.ndim == 1
+        n = r.size
+        if out is None:
+            out = (np.empty((n, self.K)), np.empty(n), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint8))
+        q, ll, it, cv = out
+        self._chk(self.lib.mchip_fit_q_rows(self.h, slot, r.ctypes.data, n, int(bool(from_slot)), max_iter, abs_error, rel_error,
+                                            q.ctypes.data, ll.ctypes.data, it.ctypes.data, cv.ctypes.data))
+        return q, ll, it, cv
 
     def resample_loci(self, src):
         """install the selection `src` (locus indices into the base, repeats allowed) of the base: the data set held when the first

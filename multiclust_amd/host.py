@@ -78,6 +78,13 @@ class McSeResult(C.Structure):
                 ("mean_se", C.c_double), ("max_se", C.c_double)]
 
 
+class McQueryResult(C.Structure):
+    """mc_query_result (multiclust_amd/host/mc_host.h)"""
+    _fields_ = [("n", C.c_int), ("K", C.c_int), ("n_converged", C.c_int), ("n_failed", C.c_int), ("max_iter", C.c_int),
+                ("sum_logL", C.c_double), ("rows", C.POINTER(C.c_int32)), ("iter", C.POINTER(C.c_int32)),
+                ("q", C.POINTER(C.c_double)), ("logL", C.POINTER(C.c_double)), ("converged", C.POINTER(C.c_uint8))]
+
+
 class CliOptions(C.Structure):
     """mc_cli_options (multiclust_amd/host/mc_cli.h)"""
     _fields_ = [("em", McOptions), ("filename", C.c_char_p), ("filename_file", C.c_char_p), ("path", C.c_char_p),
@@ -88,8 +95,8 @@ class CliOptions(C.Structure):
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
                 ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
-    # (the C struct ends with cv_folds / cv_floor and se_replicates / se_block, the command line's --cv and --se: only mc_main.c
-    # reads them, the readers this mirror is handed to stop at bed_prefix)
+    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block and query_file, the command line's --cv, --se and
+    # --query: only mc_main.c reads them, the readers this mirror is handed to stop at bed_prefix)
 
 
 class CliData(C.Structure):
@@ -178,6 +185,25 @@ def read_bed(prefix, decode=True):
     return 0, out
 
 
+def query_read(path, I):
+    """mc_query_read (host/mc_query.c) on a query file: (status, None) on failure, else (0, mask [I] uint8)"""
+    lib = load()
+    m = C.POINTER(C.c_uint8)()
+    rc = lib.mc_query_read(path.encode(), I, C.byref(m))
+    if rc:
+        return rc, None
+    mask = np.ctypeslib.as_array(m, shape=(I,)).copy()
+    _libc_free(m)
+    return 0, mask
+
+
+def _libc_free(ptr):
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free.restype = None
+    libc.free(C.cast(ptr, C.c_void_p))
+
+
 def replicate_starts(opt, dat, base, n_replicates, null_K, alt_K, n_init):
     """mc_replicate_starts: the generator at the start of every bootstrap replicate, [n_replicates + 1] McRng"""
     starts = (McRng * (n_replicates + 1))()
@@ -252,6 +278,11 @@ def load():
     lib.mc_locus_bootstrap.argtypes = [OP, DP, MP, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(McSeResult)]
     lib.mc_se_list_capacity.argtypes = [C.c_int, C.c_int]
     lib.mc_se_draw_lists.argtypes = [C.POINTER(McRng), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mc_query_read.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.POINTER(C.c_uint8))]
+    lib.mc_query_hide.argtypes = [MP, DP, C.c_void_p]
+    lib.mc_query_fit.argtypes = [OP, DP, MP, C.c_void_p, C.POINTER(McQueryResult)]
+    lib.mc_query_result_free.argtypes = [C.POINTER(McQueryResult)]
+    lib.mc_query_result_free.restype = None
     lib.mc_aic.restype = C.c_double
     lib.mc_aic.argtypes = [C.c_double, C.c_int]
     lib.mc_bic.restype = C.c_double
@@ -380,6 +411,32 @@ class Fit:
         if rc:
             raise hip.HipError("mc_locus_bootstrap failed (%d)" % rc)
         return mean, se, count, r
+
+    def hide_queries(self, mask):
+        """mc_query_hide: the individuals with mask[i] != 0 become individuals without an observed copy for every fit that
+        follows (the device keeps their genotypes); call it right after the model is created, as the command line does"""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert m.shape == (self.I,)
+        rc = self.lib.mc_query_hide(self.mp, C.byref(self.dat), m.ctypes.data)
+        if rc:
+            raise hip.HipError("mc_query_hide failed (%d)" % rc)
+        self._query_mask = m
+
+    def fit_queries(self, mask=None):
+        """mc_query_fit on the estimate in slot mod.pindex: dict with rows, q [n][K], logL, iter, converged (one entry per query
+        individual in data order) and n_converged, n_failed, max_iter, sum_logL.  mask: the one hide_queries was given."""
+        m = self._query_mask if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        r = McQueryResult()
+        rc = self.lib.mc_query_fit(C.byref(self.opt), C.byref(self.dat), self.mp, m.ctypes.data, C.byref(r))
+        if rc:
+            raise hip.HipError("mc_query_fit failed (%d)" % rc)
+        n, K = r.n, r.K
+        out = dict(rows=np.ctypeslib.as_array(r.rows, shape=(n,)).copy(), q=np.ctypeslib.as_array(r.q, shape=(n, K)).copy(),
+                   logL=np.ctypeslib.as_array(r.logL, shape=(n,)).copy(), iter=np.ctypeslib.as_array(r.iter, shape=(n,)).copy(),
+                   converged=np.ctypeslib.as_array(r.converged, shape=(n,)).copy(), n_converged=r.n_converged,
+                   n_failed=r.n_failed, max_iter=r.max_iter, sum_logL=r.sum_logL)
+        self.lib.mc_query_result_free(C.byref(r))
+        return out
 
     def locus_lists(self, n_replicates, block=1):
         """the locus lists mc_locus_bootstrap installs for these arguments and the options' seed, one int32 array per replicate"""

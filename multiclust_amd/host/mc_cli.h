@@ -50,6 +50,8 @@ typedef struct mc_cli_options {
 	int se_replicates;		/* --se <B> (extension): bootstrap standard errors of the mixing proportions of the best fit of every K
 					 * from B resamples of the loci (mc_locus_bootstrap, either model); 0 = off */
 	int se_block;			/* --se-block <n>: blocks of n neighbouring loci are resampled; default 1 */
+	const char *query_file;		/* --query <file> (extension): I tokens 0 (panel) / 1 (query); the query individuals are hidden from every
+					 * fit and fitted against the best fit of every K afterwards (mc_query.c) */
 } mc_cli_options;
 
 typedef struct mc_cli_data {
@@ -115,5 +117,14 @@ int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc
  * mc_locus_bootstrap for every entry */
 int mc_write_se(const mc_cli_options *opt, const mc_cli_data *dat, int K, const double *q, const double *mean, const double *se,
 		const int32_t *count);
+
+/* --query (an extension, mc_query.c): the query file -- exactly I tokens separated by white space, each 0 (panel) or 1 (query), in
+ * the data set's individual order, at least one of each -> mask[I] (the caller frees it); returns 0 or the exit status mc_read_afile
+ * gives the failure (file cannot be opened 5, contents 7) */
+int mc_query_read(const char *path, int I, uint8_t **mask_out);
+/* <stem>.admix.K=<K>.query.txt: one header line, then one tab-separated line per query individual in data order: i, iter, converged,
+ * logL, and the K mixing proportions (%.10f, as .se.txt prints); arrays as mc_query_fit fills them */
+int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows, const int32_t *iter, const uint8_t *converged,
+		   const double *logL, const double *q);
 
 #endif

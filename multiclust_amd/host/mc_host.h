@@ -277,6 +277,32 @@ int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod,
 int mc_se_list_capacity(int L, int block);
 int mc_se_draw_lists(mc_rng *rng, int L, int block, int n_lists, int32_t *src /* [n_lists][cap] */, int32_t *len /* [n_lists] */);
 
+/* ---- query individuals: fitted against a panel's allele frequencies, not part of estimating them (mc_query.c; an extension) ----
+ * mask[i] != 0 marks individual i of the data set as a query individual; the others are the panel.
+ * mc_query_hide: call it right after mc_model_create.  It sets two folds on the device, fold(i, l) = mask[i], and holds fold 1
+ * out (mchip_cv_set_folds, mchip_cv_hold_out): the query individuals become individuals without an observed copy -- they add
+ * nothing to P, the log likelihood or the expected counts, their rows of Q are the NaN of mchip_empty_individuals, and the
+ * result files show them as they show such individuals -- while the device keeps their genotypes in the saved full data set.
+ * mc_query_fit: `mod` holds a fit of the panel in slot mod->pindex.  Every query individual's mixing proportions are fitted from
+ * 1 / K with that slot's P held fixed (mchip_fit_q_rows) under the run's opt->abs_error / rel_error and an iteration cap of
+ * opt->max_iter, or MC_QUERY_MAX_ITER when that is 0 (no limit): plain EM on K numbers takes tens of iterations, a row that
+ * creeps along a boundary a few thousand, and the cap bounds a launch that cannot be interrupted.  The context is left as it was
+ * found, the hold-out still in force.  out: one entry per query individual in data order -- rows[r] its index, q[r][K], logL[r],
+ * iter[r], converged[r] -- with n_converged, n_failed (rows whose log likelihood is not finite: their q is NaN), max_iter = the
+ * largest iter[r] and sum_logL over the finite rows; release it with mc_query_result_free.
+ * Admixture model with individual mixing proportions only, else MCHIP_ERR_UNSUPPORTED. */
+#define MC_QUERY_MAX_ITER 10000
+typedef struct mc_query_result {
+	int n, K, n_converged, n_failed, max_iter;
+	double sum_logL;
+	int32_t *rows, *iter;
+	double *q, *logL;
+	uint8_t *converged;
+} mc_query_result;
+int mc_query_hide(mc_model *mod, const mc_data *dat, const uint8_t *mask /* [I] */);
+int mc_query_fit(const mc_options *opt, const mc_data *dat, mc_model *mod, const uint8_t *mask /* [I] */, mc_query_result *out);
+void mc_query_result_free(mc_query_result *r);
+
 /* ---- opt-in watchdog (mc_watchdog.c): nothing in the reference corresponds -- it has nothing to wait for ----
  * mc_watchdog_start(s): a detached thread that polls the library's event count (mchip_progress_report) and, when it has stood
  * still for s seconds, prints where every thread stands (library record + /proc/self/task) on stderr and leaves with _exit(3).

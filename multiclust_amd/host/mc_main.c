@@ -10,6 +10,8 @@
  * mode in the reference itself), --impute, --simulate, -x (not implemented in the reference either).
  * Extensions: --se <B> adds bootstrap standard errors of the mixing proportions of every K's best fit (B resamples of the loci, or of
  * blocks of --se-block neighbouring loci: one more stdout line per K and one more file, nothing else changes); --cv <F> adds the F-fold cross-validation error of every K's best fit (one more stdout line per K, nothing else changes);
+ * --query <file> keeps the individuals the file marks out of every fit and fits their mixing proportions against the best fit of every K
+ * afterwards (one more stdout line per K and one more file; without it nothing changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
  * the node (one host thread and one context per GPU, units u = d, d+n, ..., each starting from the serial program's
  * rand() position by jump-ahead), with a single RCCL all-reduce of the per-unit result table, after which the serial
@@ -60,7 +62,12 @@ static void usage(FILE *fp, const char *prog)
 		"                not with -b, -w, -M or --gpus above 1        --cv-floor <x>  smallest prediction scored, in (0, 1] (1/(I*ploidy+1))\n"
 		"  --se <B>      standard errors of the mixing proportions of the best fit of every K from B (2..10000) bootstrap resamples of\n"
 		"                the loci: one more line 'Bootstrap SE (K=..)' per K and a file <stem>.<admix|mix>.K=<K>.se.txt; either model; not with -b,\n"
-		"                -w, -M or --gpus above 1    --se-block <n>  resample blocks of n neighbouring loci (1)\n", prog);
+		"                -w, -M or --gpus above 1    --se-block <n>  resample blocks of n neighbouring loci (1)\n"
+		"  --query <file>  I tokens, 0 (panel) or 1 (query), in the order of the individuals: the query individuals are hidden from every\n"
+		"                fit (the result files show them as individuals without data; AIC and BIC keep the data set's number of\n"
+		"                individuals) and their mixing proportions are then fitted to the allele frequencies of the best fit of every K:\n"
+		"                one more line 'Query fit (K=..)' per K and a file <stem>.admix.K=<K>.query.txt; needs -a, not with -c, -b, -w,\n"
+		"                -M, -A, --cv, --se, --randem, or --gpus / --streams above 1\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -163,6 +170,14 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			break;
 		case 'P': if (++i >= argc) BAD("-P"); o->pfile = argv[i]; break;
 		case 'Q': if (++i >= argc) BAD("-Q"); o->qfile = argv[i]; break;
+		case 'q':
+			if (strncmp(w, "qu", 2)) {
+				fprintf(stderr, "ERROR [mc_main.c::parse_options]: unknown option (argument '%s'); try -h\n", argv[i]);
+				return MC_EXIT_INVALID_CMD_OPTION;
+			}
+			if (++i >= argc) BAD("--query");
+			o->query_file = argv[i];
+			break;
 		case 'A': if (++i >= argc) BAD("-A"); o->afile = argv[i]; break;	/* multiclust.c:1416-1418 */
 		case 'R': o->R_format = 1; break;
 		case 'r':
@@ -235,6 +250,21 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			return MC_EXIT_INVALID_CMD_ARGUMENT;
 		}
 	}
+	if (o->query_file) {	/* extension: the same for query individuals */
+		const char *why = NULL;
+		if (!o->em.admixture) why = "--query needs the admixture model (-a)";
+		else if (o->em.eta_constrained) why = "--query cannot be combined with shared mixing proportions (-c)";
+		else if (o->n_bootstrap) why = "--query cannot be combined with the bootstrap (-b)";
+		else if (!o->write_files || o->parallel) why = "--query cannot be combined with -w or -M";
+		else if (o->afile) why = "--query cannot be combined with a partition to compare with (-A)";
+		else if (o->cv_folds || o->se_replicates) why = "--query cannot be combined with --cv or --se (they share the fold state of the device)";
+		else if (o->em.initialization_procedure == MC_RAND_EM) why = "--query cannot be combined with --randem (its centers are drawn from the genotypes on the host)";
+		else if (o->n_gpus > 1 || o->n_streams > 1) why = "--query cannot be combined with --gpus or --streams above 1";
+		if (why) {
+			fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '--query'); try -h\n", why);
+			return MC_EXIT_INVALID_CMD_ARGUMENT;
+		}
+	}
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -278,6 +308,10 @@ typedef struct run_state {
 	/* --se: the same for the bootstrap over loci */
 	mc_se_result se;
 	int se_done;
+	/* --query: which individuals are query individuals, and the query fit of the K just fitted */
+	uint8_t *query_mask;
+	mc_query_result query;
+	int query_done;
 } run_state;
 
 /* sharded runs use n_gpus * n_streams workers (host thread + context + stream each); worker x sits on device
@@ -441,6 +475,26 @@ static int cli_locus_bootstrap(const mc_cli_options *o, const mc_cli_data *d, co
 	return rc;
 }
 
+/* --query: the query individuals against the best fit of one K, under the same arrangement (`mod` is the model that fitted it: the
+ * hold-out that hides them is in force on its context); with result files on they go to <stem>.admix.K=<K>.query.txt */
+static int cli_query_fit(const mc_cli_options *o, const mc_data *md, run_state *st, mc_model *mod, int K, const double *q, const double *p,
+			 double logL, int n_iter, int converged)
+{
+	int rc;
+	mchip_progress_note("query fit");
+	mc_reset_model_state(mod);
+	if ((rc = mc_model_set_q(mod, mod->pindex, q)) || (rc = mc_model_set_p(mod, mod->pindex, p))) return rc;
+	mod->logL = logL;
+	mod->n_iter = n_iter;
+	mod->converged = converged;
+	mc_query_result_free(&st->query);
+	if ((rc = mc_query_fit(&o->em, md, mod, st->query_mask, &st->query))) return rc;
+	st->query_done = 1;
+	if (o->write_files)
+		rc = mc_write_query(o, K, st->query.n, st->query.rows, st->query.iter, st->query.converged, st->query.logL, st->query.q);
+	return rc;
+}
+
 static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, mc_model *mod, run_state *st, int bootstrap)
 {
 	const int K = mod->K, nq = (o->em.admixture && !o->em.eta_constrained) ? d->I * K : K;
@@ -451,7 +505,7 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 	double *q = NULL, *p = NULL, *sik = NULL;
 	int *count_K = NULL, rc = 0;
 	/* --cv: the best fit of THIS K (the files above follow the maximum over the K so far) */
-	const int cv = (o->cv_folds || o->se_replicates) && !bootstrap;	/* (--se keeps the same fit) */
+	const int cv = (o->cv_folds || o->se_replicates || o->query_file) && !bootstrap;	/* (--se and --query keep the same fit) */
 	double *cv_q = NULL, *cv_p = NULL, cv_logL = -INFINITY;
 	int cv_iter = 0, cv_conv = 0;
 	mc_summary_reset(&st->sum);
@@ -536,6 +590,7 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 	}
 	if (cv && cv_q && o->cv_folds) rc = cli_cross_validate(o, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
 	if (!rc && cv && cv_q && o->se_replicates) rc = cli_locus_bootstrap(o, d, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
+	if (!rc && cv && cv_q && o->query_file) rc = cli_query_fit(o, md, st, mod, K, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
 DONE:
 	free(q); free(p); free(sik); free(count_K); free(cv_q); free(cv_p);
 	return rc;
@@ -714,7 +769,8 @@ static int replicates_shardable(const mc_cli_options *o)
 	 * single-GPU rehearsal used by tests/test_gpu_cli.py */
 	const int force = getenv("MC_FORCE_SHARDED") != NULL;
 	return (o->n_gpus > 1 || o->n_streams > 1 || (force && o->n_gpus == 1)) && !o->target_revisit && !o->target_ll && !o->em.n_seconds &&
-	       !(o->pfile && o->qfile);	/* initial parameters from files: every unit would be the same fit */
+	       !(o->pfile && o->qfile) &&	/* initial parameters from files: every unit would be the same fit */
+	       !o->query_file;		/* query individuals: one model, one hold-out */
 }
 
 /* the initialisations of one fit can be handed to workers: the admixture model only */
@@ -748,6 +804,8 @@ static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const m
 				if ((rc = sim ? mc_model_create_simulated(&mod, &o->em, md, K, o->device, sim)
 					      : mc_model_create(&mod, &o->em, md, K, o->device))) return rc;
 				if (slot) { mc_model_free(*slot); *slot = mod; }
+				/* --query: every initialisation of this K sees the panel alone */
+				if (o->query_file && !sim && (rc = mc_query_hide(mod, md, st->query_mask))) { if (!slot) mc_model_free(mod); return rc; }
 			}
 			rc = maximize_likelihood(o, d, md, mod, st, bootstrap);
 			if (!slot) mc_model_free(mod);
@@ -764,6 +822,11 @@ static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const m
 			fprintf(st->out, "Bootstrap SE (K=%d, %d replicates, block %d): mean %.10f  max %.10f  [%d failed]\n", K, st->se.n_replicates,
 				st->se.block, st->se.mean_se, st->se.max_se, st->se.n_failed);
 			st->se_done = 0;
+		}
+		if (st->query_done) {	/* --query */
+			fprintf(st->out, "Query fit (K=%d): %d individuals, %d converged, %d failed, at most %d iterations, log likelihood %.6f\n", K,
+				st->query.n, st->query.n_converged, st->query.n_failed, st->query.max_iter, st->query.sum_logL);
+			st->query_done = 0;
 		}
 		if (total_iter) *total_iter += st->sum.n_total_iter;
 		if (o->n_bootstrap && K == st->null_K) st->max_logL_H0 = st->sum.max_logL;
@@ -914,6 +977,7 @@ int main(int argc, const char **argv)
 	memset(&st, 0, sizeof st);
 	if (!(st.I_K = calloc((size_t)d.I, sizeof *st.I_K))) return MC_EXIT_MEMORY_ALLOCATION;
 	if (o.afile && (rc = mc_read_afile(o.afile, d.I, &st.partition_from_file, &st.pK))) return rc;	/* synchronize's last step (multiclust.c:889-890) */
+	if (o.query_file && (rc = mc_query_read(o.query_file, d.I, &st.query_mask))) return rc;
 	st.out = stdout;
 	mchip_comm *run_comm = NULL;
 	st.comm = &run_comm;
@@ -1046,7 +1110,8 @@ int main(int argc, const char **argv)
 END:
 	mchip_progress_note("end of main: freeing");
 	if (run_comm) mchip_comm_destroy(run_comm);
-	free(st.mle_q); free(st.mle_p); free(st.I_K); free(st.partition_from_file);
+	free(st.mle_q); free(st.mle_p); free(st.I_K); free(st.partition_from_file); free(st.query_mask);
+	mc_query_result_free(&st.query);
 	mc_free_data(&d);
 	mchip_progress_note("returning from main: the HIP runtime's own teardown follows");
 	return rc;

@@ -133,6 +133,26 @@ int mc_write_se(const mc_cli_options *opt, const mc_cli_data *dat, int K, const 
 	return 0;
 }
 
+int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows, const int32_t *iter, const uint8_t *converged,
+		   const double *logL, const double *q)
+{
+	char base[4096], path[4200];
+	FILE *fp;
+	stem(opt, base, sizeof base);
+	snprintf(path, sizeof path, "%s.admix.K=%d.query.txt", base, K);
+	if (!(fp = open_out(path))) return 1;
+	fprintf(fp, "i\titer\tconverged\tlogL");
+	for (int k = 0; k < K; k++) fprintf(fp, "\teta%d", k);
+	fprintf(fp, "\n");
+	for (int r = 0; r < n; r++) {
+		fprintf(fp, "%d\t%d\t%d\t%.6f", (int)rows[r], (int)iter[r], (int)converged[r], logL[r]);
+		for (int k = 0; k < K; k++) fprintf(fp, "\t%.10f", q[(size_t)r * K + k]);
+		fprintf(fp, "\n");
+	}
+	fclose(fp);
+	return 0;
+}
+
 int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc_fit_view *fit, const int *count_K)
 {
 	char base[4096], path[4200];
