@@ -25,31 +25,15 @@ $(OBJ)/mchip_k%.o: multiclust_amd/csrc/mchip_kernels_k.hip multiclust_amd/csrc/m
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_K=$* -c $< -o $@
 
-$(OBJ)/mchip.o: multiclust_amd/csrc/mchip.hip multiclust_amd/csrc/mchip_internal.h multiclust_amd/csrc/mchip_finalize.h multiclust_amd/csrc/mchip_progress.h include/multiclust_hip.h
+# the K-independent units: a new one costs one word here
+HIPUNITS = mchip mchip_comm mchip_bed mchip_cv mchip_query mchip_resample
+HIPOBJ   = $(HIPUNITS:%=$(OBJ)/%.o)
+HIPHDRS  = $(wildcard multiclust_amd/csrc/*.h) include/multiclust_hip.h
+$(OBJ)/%.o: multiclust_amd/csrc/%.hip $(HIPHDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -c $< -o $@
 
-$(OBJ)/mchip_comm.o: multiclust_amd/csrc/mchip_comm.hip multiclust_amd/csrc/mchip_progress.h include/multiclust_hip.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -c $< -o $@
-
-$(OBJ)/mchip_bed.o: multiclust_amd/csrc/mchip_bed.hip multiclust_amd/csrc/mchip_internal.h include/multiclust_hip.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -c $< -o $@
-
-$(OBJ)/mchip_cv.o: multiclust_amd/csrc/mchip_cv.hip multiclust_amd/csrc/mchip_internal.h include/multiclust_hip.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -c $< -o $@
-
-$(OBJ)/mchip_query.o: multiclust_amd/csrc/mchip_query.hip multiclust_amd/csrc/mchip_internal.h multiclust_amd/csrc/mchip_finalize.h include/multiclust_hip.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -c $< -o $@
-
-$(OBJ)/mchip_resample.o: multiclust_amd/csrc/mchip_resample.hip multiclust_amd/csrc/mchip_internal.h include/multiclust_hip.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -c $< -o $@
-
-$(LIB)/libmulticlust_hip.so: $(OBJ)/mchip.o $(OBJ)/mchip_comm.o $(OBJ)/mchip_bed.o $(OBJ)/mchip_cv.o $(OBJ)/mchip_query.o $(OBJ)/mchip_resample.o $(KOBJ)
+$(LIB)/libmulticlust_hip.so: $(HIPOBJ) $(KOBJ)
 	@mkdir -p $(LIB)
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o $@ $^ -ldl
 
@@ -77,7 +61,7 @@ exp-scatter: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_EXP_SCATTER -DMCHIP_K=8 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k8.o
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_scatter.so \
-		$(filter-out $(OBJ)/mchip_k8.o,$(OBJ)/mchip.o $(OBJ)/mchip_comm.o $(OBJ)/mchip_bed.o $(OBJ)/mchip_cv.o $(OBJ)/mchip_query.o $(OBJ)/mchip_resample.o $(KOBJ)) build/exp/mchip_k8.o -ldl
+		$(filter-out $(OBJ)/mchip_k8.o,$(HIPOBJ) $(KOBJ)) build/exp/mchip_k8.o -ldl
 
 # diagnosis behind profiles/r03_k52_spill.md: the K = 52 kernels with one lane per individual (MCHIP_FORCE_SPLIT1: the instance
 # that returned -inf / NaN before the lane split) built with hipcc's default VGPR->AGPR spilling and with KFLAGS, each linked
@@ -88,7 +72,7 @@ exp-k52: $(LIB)/libmulticlust_hip.so
 	$(HIPCC) $(HIPFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k52_agpr.o
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k52_scratch.o
 	for v in agpr scratch; do $(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_k52$$v.so \
-		build/exp/mchip_split1.o $(OBJ)/mchip_comm.o $(OBJ)/mchip_bed.o $(OBJ)/mchip_cv.o $(OBJ)/mchip_query.o $(OBJ)/mchip_resample.o $(filter-out $(OBJ)/mchip_k52.o,$(KOBJ)) build/exp/mchip_k52_$$v.o -ldl; done
+		build/exp/mchip_split1.o $(filter-out $(OBJ)/mchip.o,$(HIPOBJ)) $(filter-out $(OBJ)/mchip_k52.o,$(KOBJ)) build/exp/mchip_k52_$$v.o -ldl; done
 
 # A/B builds of the K = 8 kernels: `make exp-k8 EXPNAME=w5 EXPFLAGS=-DMCHIP_SPARSE_WAVES=5` -> scripts/exp/libmulticlust_hip_w5.so
 # (the K = 8 object rebuilt with EXPFLAGS, everything else the product's); scripts/diag/ab.sh times variants against the shipped
@@ -98,7 +82,7 @@ exp-k8: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(EXPFLAGS) -DMCHIP_K=8 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k8_$(EXPNAME).o
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_$(EXPNAME).so \
-		$(filter-out $(OBJ)/mchip_k8.o,$(OBJ)/mchip.o $(OBJ)/mchip_comm.o $(OBJ)/mchip_bed.o $(OBJ)/mchip_cv.o $(OBJ)/mchip_query.o $(OBJ)/mchip_resample.o $(KOBJ)) build/exp/mchip_k8_$(EXPNAME).o -ldl
+		$(filter-out $(OBJ)/mchip_k8.o,$(HIPOBJ) $(KOBJ)) build/exp/mchip_k8_$(EXPNAME).o -ldl
 
 # the same for any K: `make exp-k EXPK=40 EXPNAME=k40s4 EXPFLAGS=-DMCHIP_COL_SPLIT4_ABOVE=24`
 EXPK ?= 8
@@ -106,7 +90,7 @@ exp-k: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(EXPFLAGS) -DMCHIP_K=$(EXPK) -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k$(EXPK)_$(EXPNAME).o
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_$(EXPNAME).so \
-		$(filter-out $(OBJ)/mchip_k$(EXPK).o,$(OBJ)/mchip.o $(OBJ)/mchip_comm.o $(OBJ)/mchip_bed.o $(OBJ)/mchip_cv.o $(OBJ)/mchip_query.o $(OBJ)/mchip_resample.o $(KOBJ)) build/exp/mchip_k$(EXPK)_$(EXPNAME).o -ldl
+		$(filter-out $(OBJ)/mchip_k$(EXPK).o,$(HIPOBJ) $(KOBJ)) build/exp/mchip_k$(EXPK)_$(EXPNAME).o -ldl
 
 clean:
 	rm -rf build $(LIB)/*.so $(BIN) scripts/micro/fp64_micro scripts/micro/op_cost scripts/micro/lds_valu scripts/micro/vgpr_banks scripts/micro/mfma_sustained scripts/exp/*.so

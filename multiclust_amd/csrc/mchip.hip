@@ -3,9 +3,8 @@
  * libmulticlust_hip.so (include/multiclust_hip.h).  gfx950 only; no CPU fallback: every entry point
  * fails with MCHIP_ERR_NO_DEVICE / MCHIP_ERR_HIP when the GPU path cannot run.
  */
-#include "mchip_internal.h"
+#include "mchip_context.h"
 #include "mchip_finalize.h"
-#include "mchip_progress.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -61,106 +60,6 @@ const mchip_ktable *mchip_get_ktable(int K)
 }
 
 /* ------------------------------------------------------------------ context */
-struct mchip_context {
-	int device;
-	hipStream_t stream;
-	char err[512];
-	int n_cu;
-	/* data set */
-	int I, L, ploidy, T, max_M, min_M;
-	std::vector<int32_t> h_ua;	/* host copy of uniquealleles: a data set of the same shape reuses every buffer */
-	int parked_K;			/* model buffers kept allocated for this K (and the signature below) while no model is set */
-	int sig_admixture, sig_constrained, sig_projection, sig_nsec;
-	double sig_eta_lb, sig_p_lb;
-	int init_geno_set;		/* d_initA / d_initS hold the observed haplotypes (mchip_set_init_genotypes) */
-	int32_t *d_ua, *d_toff, *d_col_locus;
-	uint8_t *d_col_allele;
-	uint8_t *d_gtA, *d_gtS, *d_gtC;
-	int count_bits, has_missing;
-	int first_empty;	/* first individual without a single observed copy, or -1 */
-	std::vector<int> empty_rows;	/* all of them: their mixing proportions are 0 / 0 in the reference (em_alg.c:685-690) */
-	int empty_rows_nan[3];	/* per slot: the slot's rows of such individuals stand for the reference's 0 / 0 (an M step wrote the slot, or
-				 * something computed from such a slot did, or NaN rows were uploaded): mchip_get_q reports them as NaN */
-	unsigned long long nnz_cells, n_copies;	/* cells with n_ic > 0, non-missing allele copies (mchip_data_counts) */
-	int counts_valid;
-	size_t geno_bytes_A, geno_bytes_S;
-	uint8_t *d_asA, *d_asS;		/* hard-partition scratch, allocated on first use */
-	uint8_t *d_initA, *d_initS;	/* genotype the hard-partition M step reads when it is not the data set itself (bootstrap) */
-	uint8_t *d_draw;		/* device-drawn partition in stream order [I][L][ploidy], padded to whole chunks */
-	/* K-fold cross-validation (mchip_cv_*; kernels: mchip_cv.hip): state of the data set, dropped with it */
-	uint8_t *d_cv_fold;		/* fold of every genotype [I][L], padded to whole generator chunks + MCHIP_CV_PAD; null = no folds */
-	int cv_n_folds;
-	uint8_t *d_cv_full;		/* the full data set in upload form [I][L][ploidy], saved by the first hold-out */
-	int cv_fold;			/* fold held out of the installed data set, -1 = none */
-	std::vector<int> cv_full_empty;	/* empty_rows of the full data set */
-	double *d_cv_part;		/* the score's partial sums, one per workgroup */
-	size_t cv_part_cap;
-	unsigned long long *d_cv_out;	/* [0] the score's sum (a double), [1] copies, [2] floored copies */
-	/* selections of loci (mchip_resample_loci; kernel: mchip_resample.hip): the base they are gathered from, saved by the first one
-	 * and dropped by every other call that installs a data set */
-	uint8_t *d_rs_base;		/* the base in upload form [I][rs_L][ploidy]; null = none saved */
-	int rs_L;
-	std::vector<int32_t> rs_ua;	/* uniquealleles of the base */
-	std::vector<int> rs_empty;	/* empty_rows of the base */
-	int rs_installing;		/* mchip_resample_loci is installing a selection: set_shape and free_data leave the base alone */
-	/* Rand-EM candidates (mchip_init_from_allele_centers), kept from one candidate to the next and grown when needed: the
-	 * rand() % K values of a candidate's span of the stream, its center alleles [L][K], its per-locus draw offsets */
-	uint8_t *d_cand_span, *d_cand_centers;
-	unsigned long long *d_cand_off;
-	size_t cand_span_bytes, cand_loci, cand_center_bytes;
-	uint32_t *d_jump_hi, *d_jump_lo;	/* jump polynomials of the rand() stream (mchip_mstep_from_rand_partition) */
-	size_t n_jump_hi;
-	/* jump polynomials of the tiled generators (0: bootstrap data set, 1: random partition): x^(A*i), i < nA, stored [31][nA]
-	 * (one per individual) and x^(B*r), r < nB, stored [nB][31] (one per locus tile); kept while A, nA, B, nB stay the same */
-	struct lattice { uint32_t *d_i, *d_r; uint64_t A, B; unsigned nA, nB; } lat[2];
-	uint32_t *d_part_slabs;		/* tiled random partition: packed 16-bit N-side counts per block of 256 individuals */
-	size_t part_slab_bytes;
-	/* mixture model on generated data: the cluster of every individual of the data set (mchip_simulate_genotypes_mixture), and the
-	 * workspaces of mchip_init_from_individual_centers (partial distances [chunk][K][I]; counts [T][K], n_k, centers, assignment) */
-	uint8_t *d_sim_cluster;
-	uint32_t *d_cen_part, *d_cen_work;
-	size_t cen_part_bytes, cen_work_bytes;
-	/* model */
-	int K, admixture, constrained, do_projection, nsec, nq, qstride;
-	double eta_lb, p_lb;
-	const mchip_ktable *kt;
-	double *d_p[3], *d_q[3];
-	double *d_up[MCHIP_MAX_SECANTS], *d_vp[MCHIP_MAX_SECANTS], *d_uq[MCHIP_MAX_SECANTS], *d_vq[MCHIP_MAX_SECANTS];
-	double *d_sik;			/* [I][K] expected counts / vik */
-	double *d_stage;		/* K*T staging for the [K][T] <-> [T][K] transposes */
-	double *d_logp;			/* mixture model: log P table [T][K] */
-	/* workspaces */
-	int ichunk, n_ichunks, lchunk, n_lchunks, n_llpart, flush_blocks, safe_rcp, sparse;
-	int ind_waves;			/* waves per workgroup of the cooperating individual-side kernels (mchip_internal.h) */
-	int xcd_rows;			/* their slab rows come in whole groups of eight: one row, one XCD */
-	/* testing / tuning knobs of the environment (README), read when a context is created and again with every data set and every
-	 * model -- never on a launch path */
-	struct {
-		int no_bial, no_counts, force_dense, force_safe, no_graph, no_dual, no_slab_sum, no_col_split, part_no_tile, sim_no_tile;
-		int no_fused_finalize;
-		int per_cu_col, per_cu_ind, geometry_given, no_roundup;
-		double slab_frac;
-	} knob;
-	double *d_Apart, *d_Spart, *d_llpart, *d_scalars;	/* d_scalars: [0]=logL, [1..3]=dots, [4..]=eta sums */
-	double *d_llpart2;		/* partial log likelihoods of the second parameter set of a dual individual pass */
-	double *d_redpart;		/* block partials of the dot products / column sums */
-	uint8_t *d_flags;		/* michelot "fixed" flags for loci with more than 64 alleles */
-	double *h_pinned;		/* 64 doubles */
-	mchip_run_state *d_run;		/* batched-run state (mchip_em_run) */
-	hipGraphExec_t step_graph[3];	/* one captured {EM step + stop check} per slot; rebuilt when the model changes */
-	hipGraphExec_t cycle_graph[3][5];	/* one captured accelerated cycle per (start slot, scheme) */
-	int *d_cyc;			/* batched accelerated runs: [0] no update this cycle, [1] extrapolation accepted */
-	int have_ll;
-	int ll_parts;			/* partial log likelihoods the last E step left in d_llpart */
-	int s_cache_slot;		/* slot whose S-side sums + logL are held in Spart / d_scalars[2] (mchip_loglik_prefetch), or -1 */
-	/* profiling */
-	int profiling;
-	hipEvent_t ev_begin, ev_end;
-	std::vector<hipEvent_t> ev_pool;
-	std::vector<int> ev_kind;	/* kernel kind of pair p = events 2p, 2p+1 */
-	size_t ev_used;
-};
-
 static void read_knobs(mchip_context *ctx)
 {
 	auto on = [](const char *name) { return getenv(name) != nullptr ? 1 : 0; };
@@ -184,39 +83,6 @@ static void read_knobs(mchip_context *ctx)
 	ctx->knob.no_roundup = on("MCHIP_NO_CHUNK_ROUNDUP");
 	ctx->knob.geometry_given = on("MCHIP_BLOCKS_PER_CU") || on("MCHIP_BLOCKS_PER_CU_COL") || on("MCHIP_SLAB_FRAC");
 }
-
-static int fail(mchip_context *ctx, int code, const char *fmt, const char *detail)
-{
-	if (ctx) snprintf(ctx->err, sizeof ctx->err, fmt, detail ? detail : "");
-	return code;
-}
-
-#define HIPCHK(call)                                                                                  \
-	do {                                                                                          \
-		hipError_t e_ = MCHIP_WAIT(call);                                                     \
-		if (e_ != hipSuccess) {                                                               \
-			snprintf(ctx->err, sizeof ctx->err, "%s failed: %s (%s:%d)", #call,           \
-				 hipGetErrorString(e_), __FILE__, __LINE__);                          \
-			return MCHIP_ERR_HIP;                                                         \
-		}                                                                                     \
-	} while (0)
-
-template <typename Tp> static void dfree(Tp *&p)
-{
-	if (p) (void)MCHIP_WAIT(hipFree(p));
-	p = nullptr;
-}
-
-/* temporary device allocation released on every exit path of the function that owns it */
-template <typename Tp> struct scoped_dev {
-	Tp *p = nullptr;
-	scoped_dev() = default;
-	scoped_dev(const scoped_dev &) = delete;
-	scoped_dev &operator=(const scoped_dev &) = delete;
-	~scoped_dev() { if (p) (void)MCHIP_WAIT(hipFree(p)); }
-	hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(Tp)); }
-	operator Tp *() const { return p; }
-};
 
 /* ------------------------------------------------------------------ K-independent kernels */
 
@@ -313,9 +179,6 @@ static int launch_relayout(hipStream_t stream, const uint8_t *raw, int I, int L,
  * ahead.  Thread c draws the RNG_CHUNK consecutive values that start RNG_CHUNK*c draws into the stream: its jump
  * polynomial is the product of two tabulated ones (hi = c / 256, lo = c % 256), so the stream is the serial one
  * whatever the launch geometry (random_allele_partition, rnd_init.c:456-467: one rand() % K per allele copy). */
-constexpr int RNG_LAG = 31;
-constexpr int RNG_CHUNK = 4 * RNG_LAG * 32;	/* draws (= bytes written) per thread: 32 rounds of 31 packed words */
-
 struct rng_window { uint32_t s[2 * RNG_LAG - 1]; };	/* x_{j-31} .. x_{j+29}: window, then its next 30 values */
 
 /* window (31 words behind the first draw) of a thread whose first draw lies n draws into the stream, x^n = hi(x) * lo(x)
@@ -1683,15 +1546,7 @@ __global__ void k_select_copy(double *qdst, const double *__restrict__ q_if_acce
 }
 
 /* ------------------------------------------------------------------ helpers */
-static inline unsigned nblk(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
-/* for the byte-per-thread layout kernels (grid-stride loops): at most 2^30 work-items per launch */
-static inline unsigned nblk_capped(size_t n, unsigned b = 256)
-{
-	const size_t blocks = (n + b - 1) / b, cap = ((size_t)1 << 30) / b;
-	return (unsigned)(blocks < cap ? blocks : cap);
-}
-
-static int check_slot(mchip_context *ctx, int slot)
+int check_slot(mchip_context *ctx, int slot)
 {
 	if (!ctx) return MCHIP_ERR_INVALID;
 	if (!ctx->K) return fail(ctx, MCHIP_ERR_STATE, "no model set%s", nullptr);
@@ -1721,7 +1576,7 @@ static void drop_graphs(mchip_context *ctx)
 			if (ctx->cycle_graph[s][m]) { (void)MCHIP_WAIT(hipGraphExecDestroy(ctx->cycle_graph[s][m])); ctx->cycle_graph[s][m] = nullptr; }
 }
 
-static void free_model(mchip_context *ctx)
+void free_model(mchip_context *ctx)
 {
 	drop_graphs(ctx);
 	for (int s = 0; s < 3; s++) { dfree(ctx->d_p[s]); dfree(ctx->d_q[s]); }
@@ -1735,28 +1590,18 @@ static void free_model(mchip_context *ctx)
 	ctx->s_cache_slot = -1;
 }
 
-static void drop_cv(mchip_context *ctx)
+void drop_saved(saved_set &set)
 {
-	dfree(ctx->d_cv_fold); dfree(ctx->d_cv_full); dfree(ctx->d_cv_part); dfree(ctx->d_cv_out);
-	ctx->cv_n_folds = 0;
-	ctx->cv_fold = -1;
-	ctx->cv_part_cap = 0;
-	ctx->cv_full_empty.clear();
+	dfree(set.d_raw);
+	set.L = 0;
+	set.ua.clear();
+	set.empty.clear();
 }
 
-static void drop_resample(mchip_context *ctx)
-{
-	if (ctx->rs_installing) return;
-	dfree(ctx->d_rs_base);
-	ctx->rs_L = 0;
-	ctx->rs_ua.clear();
-	ctx->rs_empty.clear();
-}
-
-static void free_data(mchip_context *ctx)
+void free_data(mchip_context *ctx, int keep)
 {
 	drop_cv(ctx);
-	drop_resample(ctx);
+	if (!(keep & KEEP_RS_BASE)) drop_saved(ctx->rs_base);
 	dfree(ctx->d_ua); dfree(ctx->d_toff); dfree(ctx->d_col_locus); dfree(ctx->d_col_allele);
 	dfree(ctx->d_gtA); dfree(ctx->d_gtS); dfree(ctx->d_gtC); dfree(ctx->d_asA); dfree(ctx->d_asS);
 	dfree(ctx->d_initA); dfree(ctx->d_initS);
@@ -1809,10 +1654,6 @@ static void launch_finalize_p(mchip_context *ctx, int n_slabs, const double *sla
 				   ctx->L, ctx->K, ctx->T, ctx->d_toff, n_slabs, slabs, ctx->d_p[from], ctx->d_p[to],
 				   weighted, add_lb, do_projection, ctx->p_lb, ctx->d_flags, stop);
 }
-
-/* the "bad input" word of the layout kernels: the last double of d_scalars (slots 0..47 are in use), so that an
- * initialisation allocates and frees nothing (hipFree waits for the whole device, i.e. for every other stream's fits) */
-static int *bad_flag(mchip_context *ctx) { return reinterpret_cast<int *>(ctx->d_scalars + 63); }
 
 /* ------------------------------------------------------------------ C-ABI */
 extern "C" {
@@ -1904,20 +1745,11 @@ int mchip_device_info(mchip_context *ctx, char *name, int name_len, int *compute
 	return MCHIP_OK;
 }
 
-/* shape of a data set: tables derived from uniquealleles, genotype buffers allocated but not filled */
-static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, int keep_init);
+}	/* extern "C" */
 
-static int set_shape(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, int keep_init = 0)
-{
-	const int rc = set_shape_impl(ctx, I, L, ploidy, ua, keep_init);
-	if (rc == MCHIP_ERR_HIP || rc == MCHIP_ERR_ALLOC) {	/* an allocation that failed half way: no data set, no model */
-		free_model(ctx);
-		free_data(ctx);
-	}
-	return rc;
-}
-
-static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, int keep_init)
+/* ------------------------------------------------------------------ installing a data set (mchip_context.h declares what the
+ * feature units call) */
+static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, int keep)
 {
 	if (I <= 0 || L <= 0 || ploidy <= 0 || ploidy > 64 || !ua)
 		return fail(ctx, MCHIP_ERR_INVALID, "set_genotypes: bad shape or null pointer%s", nullptr);
@@ -1925,7 +1757,7 @@ static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const in
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	drop_cv(ctx);	/* folds, the saved full data set and a hold-out in force belong to the data set that goes */
-	drop_resample(ctx);	/* so does the base of its selections of loci (kept while mchip_resample_loci itself installs one) */
+	if (!(keep & KEEP_RS_BASE)) drop_saved(ctx->rs_base);	/* so does the base of its selections of loci (a new selection keeps it) */
 	/* The same shape and allele lists as the data set held (the next bootstrap replicate, a re-upload): every buffer stays;
 	 * the model is dropped as the contract says, but its buffers are parked for an mchip_set_model with the same arguments.
 	 * Freeing and re-allocating ~10 GB per replicate costs little per call, but the runtime returns freed memory lazily and
@@ -1936,11 +1768,11 @@ static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const in
 		ctx->K = 0;
 		ctx->have_ll = 0;
 		ctx->s_cache_slot = -1;
-		if (!keep_init) ctx->init_geno_set = 0;
+		if (!(keep & KEEP_INIT)) ctx->init_geno_set = 0;
 		return MCHIP_OK;
 	}
 	free_model(ctx);	/* workspaces depend on T */
-	free_data(ctx);
+	free_data(ctx, keep);
 
 	std::vector<int32_t> toff(L + 25);	/* padded: kernels read the offsets of a block of 8 loci and of the two blocks behind it */
 	toff[0] = 0;
@@ -1980,6 +1812,16 @@ static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const in
 	return MCHIP_OK;
 }
 
+int set_shape(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, int keep)
+{
+	const int rc = set_shape_impl(ctx, I, L, ploidy, ua, keep);
+	if (rc == MCHIP_ERR_HIP || rc == MCHIP_ERR_ALLOC) {	/* an allocation that failed half way: no data set, no model */
+		free_model(ctx);
+		free_data(ctx, keep);
+	}
+	return rc;
+}
+
 /* one byte per allele copy in stream order, padded to whole generator chunks: the device-drawn partition, a generated data
  * set before it goes into the kernels' layouts, an uploaded genotype on its way there.  Kept for the life of the data set. */
 static int stream_buffer(mchip_context *ctx)
@@ -1990,8 +1832,7 @@ static int stream_buffer(mchip_context *ctx)
 	return MCHIP_OK;
 }
 
-/* gtA / gtS are in place: flags and the packed per-column allele counts of the column pass */
-static int install_layouts(mchip_context *ctx, int has_missing)
+int install_layouts(mchip_context *ctx, int has_missing)
 {
 	const int I = ctx->I, L = ctx->L, ploidy = ctx->ploidy, T = ctx->T;
 	if (ctx->has_missing != has_missing) drop_graphs(ctx);	/* parked model buffers: the kernel variant changes */
@@ -2034,6 +1875,69 @@ static int install_raw(mchip_context *ctx, const uint8_t *d_raw)
 	return install_layouts(ctx, (bad & 2) ? 1 : 0);
 }
 
+/* (a generated data set has no empty rows, and its call passes none: that the slots' NaN marks are reset there too cannot be
+ * observed, because they stand for rows of this list) */
+void set_empty_rows(mchip_context *ctx, std::vector<int> rows)
+{
+	ctx->empty_rows = std::move(rows);
+	ctx->first_empty = ctx->empty_rows.empty() ? -1 : ctx->empty_rows[0];
+	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
+}
+
+void set_empty_rows_unseen(mchip_context *ctx, const std::vector<uint8_t> &seen)
+{
+	std::vector<int> rows;
+	for (size_t i = 0; i < seen.size(); i++)
+		if (!seen[i]) rows.push_back((int)i);
+	set_empty_rows(ctx, std::move(rows));
+}
+
+static void launch_unlayout(mchip_context *ctx, uint8_t *d_raw)
+{
+	const size_t n = (size_t)ctx->I * ctx->L * ctx->ploidy;
+	hipLaunchKernelGGL(k_unlayout, dim3(nblk_capped(n)), dim3(256), 0, ctx->stream, ctx->d_gtA, ctx->I, ctx->L, ctx->ploidy, d_raw);
+}
+
+int save_installed(mchip_context *ctx, saved_set &set)
+{
+	HIPCHK(hipMalloc((void **)&set.d_raw, (size_t)ctx->I * ctx->L * ctx->ploidy));
+	launch_unlayout(ctx, set.d_raw);
+	if (MCHIP_WAIT(hipGetLastError()) != hipSuccess || MCHIP_WAIT(hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+		dfree(set.d_raw);
+		return fail(ctx, MCHIP_ERR_HIP, "saving the installed data set failed%s", nullptr);
+	}
+	set.L = ctx->L;
+	set.ua = ctx->h_ua;
+	set.empty = ctx->empty_rows;
+	return MCHIP_OK;
+}
+
+int install_saved(mchip_context *ctx, const saved_set &set)
+{
+	const int rc = install_raw(ctx, set.d_raw);
+	if (!rc) set_empty_rows(ctx, set.empty);
+	return rc;
+}
+
+int install_derived(mchip_context *ctx, const std::function<void(uint8_t *d_out, uint8_t *d_seen)> &fill)
+{
+	int rc = stream_buffer(ctx);
+	if (rc) return rc;
+	const size_t I = (size_t)ctx->I;
+	scoped_dev<uint8_t> d_seen;
+	HIPCHK(d_seen.alloc(I));
+	HIPCHK(hipMemsetAsync(d_seen.p, 0, I, ctx->stream));
+	fill(ctx->d_draw, d_seen.p);
+	HIPCHK(hipGetLastError());
+	std::vector<uint8_t> seen(I);
+	HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, I, hipMemcpyDeviceToHost, ctx->stream));
+	if ((rc = install_raw(ctx, ctx->d_draw))) return rc;	/* (synchronises the stream) */
+	set_empty_rows_unseen(ctx, seen);
+	return MCHIP_OK;
+}
+
+extern "C" {
+
 int mchip_set_genotypes(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, const uint8_t *geno)
 {
 	MCHIP_ENTRY();
@@ -2043,68 +1947,17 @@ int mchip_set_genotypes(mchip_context *ctx, int I, int L, int ploidy, const int3
 	if (rc) return rc;
 	const size_t raw_bytes = (size_t)I * L * ploidy;
 	/* an individual whose every copy is missing (one pass that stops at each individual's first observed copy: O(I) on real data) */
-	ctx->first_empty = -1;
-	ctx->empty_rows.clear();
-	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
+	std::vector<int> empty;
 	for (int i = 0; i < I; i++) {
 		const uint8_t *row = geno + (size_t)i * L * ploidy;
 		size_t x = 0;
 		while (x < (size_t)L * ploidy && row[x] == MCHIP_MISSING) x++;
-		if (x == (size_t)L * ploidy) ctx->empty_rows.push_back(i);
+		if (x == (size_t)L * ploidy) empty.push_back(i);
 	}
-	if (!ctx->empty_rows.empty()) ctx->first_empty = ctx->empty_rows[0];
+	set_empty_rows(ctx, std::move(empty));
 	if ((rc = stream_buffer(ctx))) return rc;
 	HIPCHK(hipMemcpyAsync(ctx->d_draw, geno, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
 	return install_raw(ctx, ctx->d_draw);
-}
-
-/* The packed records go up as they are; the locus pass tells the host the allele counts set_shape sizes the column tables from,
- * the expand pass fills gtA / gtS (kernels: mchip_bed.hip).  No stream buffer (d_draw) and no k_relayout on this route. */
-int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int32_t *uniquealleles_out)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	if (I <= 0 || L <= 0 || !bed || record_bytes < ((size_t)I + 3) / 4)
-		return fail(ctx, MCHIP_ERR_INVALID, "set_genotypes_bed: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
-	HIPCHK(hipSetDevice(ctx->device));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	const size_t bed_bytes = (size_t)L * record_bytes;
-	scoped_dev<uint8_t> d_bed, d_a1, d_seen;
-	scoped_dev<int32_t> d_ua;
-	HIPCHK(d_bed.alloc(bed_bytes + MCHIP_BED_PAD));
-	HIPCHK(d_a1.alloc((size_t)L));
-	HIPCHK(d_seen.alloc((size_t)I));
-	HIPCHK(d_ua.alloc((size_t)L));
-	int *d_bad = bad_flag(ctx);
-	HIPCHK(hipMemcpyAsync(d_bed.p, bed, bed_bytes, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(hipMemsetAsync(d_bed.p + bed_bytes, 0, MCHIP_BED_PAD, ctx->stream));
-	HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
-	HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
-	mchip_bed_locus_pass(ctx->stream, d_bed, record_bytes, I, L, d_ua, d_a1, d_bad);
-	HIPCHK(hipGetLastError());
-	std::vector<int32_t> ua((size_t)L);
-	int bad = 0;
-	HIPCHK(hipMemcpyAsync(ua.data(), d_ua.p, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	if (uniquealleles_out) memcpy(uniquealleles_out, ua.data(), sizeof(int32_t) * (size_t)L);
-	int rc = set_shape(ctx, I, L, 2, ua.data());
-	if (rc) return rc;
-	if (mchip_bed_expand(ctx->stream, d_bed, record_bytes, I, L, d_a1, ctx->d_gtA, ctx->d_gtS, d_seen)) {
-		free_data(ctx);
-		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "data set too large for the layout kernel%s", nullptr);
-	}
-	HIPCHK(hipGetLastError());
-	std::vector<uint8_t> seen((size_t)I);
-	HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	ctx->first_empty = -1;
-	ctx->empty_rows.clear();
-	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
-	for (int i = 0; i < I; i++)
-		if (!seen[i]) ctx->empty_rows.push_back(i);
-	if (!ctx->empty_rows.empty()) ctx->first_empty = ctx->empty_rows[0];
-	return install_layouts(ctx, (bad & 2) ? 1 : 0);
 }
 
 int mchip_copy_genotypes(mchip_context *ctx, const mchip_context *src)
@@ -2113,7 +1966,7 @@ int mchip_copy_genotypes(mchip_context *ctx, const mchip_context *src)
 	if (!ctx || !src || ctx == src) return MCHIP_ERR_INVALID;
 	if (!src->T) return fail(ctx, MCHIP_ERR_STATE, "copy_genotypes: the source holds no data set%s", nullptr);
 	if (src->device != ctx->device) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "copy_genotypes: contexts on different devices%s", nullptr);
-	int rc = set_shape(ctx, src->I, src->L, src->ploidy, src->h_ua.data(), 1);
+	int rc = set_shape(ctx, src->I, src->L, src->ploidy, src->h_ua.data(), KEEP_INIT);
 	if (rc) return rc;
 	HIPCHK(hipStreamSynchronize(src->stream));
 	HIPCHK(hipMemcpyAsync(ctx->d_gtA, src->d_gtA, ctx->geno_bytes_A, hipMemcpyDeviceToDevice, ctx->stream));
@@ -2126,9 +1979,7 @@ int mchip_copy_genotypes(mchip_context *ctx, const mchip_context *src)
 	}
 	if (ctx->has_missing != src->has_missing) drop_graphs(ctx);
 	ctx->has_missing = src->has_missing;
-	ctx->first_empty = src->first_empty;
-	ctx->empty_rows = src->empty_rows;
-	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
+	set_empty_rows(ctx, src->empty_rows);
 	ctx->count_bits = src->count_bits;
 	ctx->counts_valid = src->counts_valid;
 	ctx->nnz_cells = src->nnz_cells;
@@ -2207,312 +2058,11 @@ int mchip_get_genotypes(mchip_context *ctx, uint8_t *geno)
 	const size_t n = (size_t)ctx->I * ctx->L * ctx->ploidy;
 	scoped_dev<uint8_t> d_raw;
 	HIPCHK(d_raw.alloc(n));
-	hipLaunchKernelGGL(k_unlayout, dim3(nblk_capped(n)), dim3(256), 0, ctx->stream, ctx->d_gtA, ctx->I, ctx->L, ctx->ploidy, d_raw.p);
+	launch_unlayout(ctx, d_raw.p);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(geno, d_raw, n, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	return MCHIP_OK;
-}
-
-/* ---- K-fold cross-validation: folds, hold-out, held-out score (kernels: mchip_cv.hip) ---- */
-static int rng_stream_setup(mchip_context *ctx, const uint32_t *window, size_t n_draws, rng_window *base, size_t *n_chunks, size_t *n_blocks);
-static void mod_k_magic(int K, uint32_t *magic, uint32_t *shift);
-
-static int cv_check_data(mchip_context *ctx, int need_folds)
-{
-	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
-	if (need_folds && !ctx->d_cv_fold) return fail(ctx, MCHIP_ERR_STATE, "no folds: mchip_cv_draw_folds or mchip_cv_set_folds first%s", nullptr);
-	return MCHIP_OK;
-}
-
-/* one byte per genotype, whole generator chunks (k_draw_partition writes whole chunks) and the padding the score's reads want */
-static int cv_fold_buffer(mchip_context *ctx)
-{
-	if (ctx->d_cv_fold) return MCHIP_OK;
-	const size_t n = (size_t)ctx->I * ctx->L, bytes = ((n + RNG_CHUNK - 1) / RNG_CHUNK) * RNG_CHUNK + MCHIP_CV_PAD;
-	HIPCHK(hipMalloc((void **)&ctx->d_cv_fold, bytes));
-	HIPCHK(hipMemsetAsync(ctx->d_cv_fold, 0, bytes, ctx->stream));
-	return MCHIP_OK;
-}
-
-int mchip_cv_draw_folds(mchip_context *ctx, const uint32_t *window, int n_folds)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	int rc = cv_check_data(ctx, 0);
-	if (rc) return rc;
-	if (!window) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
-	if (n_folds < 2 || n_folds > 64) return fail(ctx, MCHIP_ERR_INVALID, "cv: n_folds must be in [2, 64]%s", nullptr);
-	HIPCHK(hipSetDevice(ctx->device));
-	rng_window base;
-	size_t n_chunks, n_blocks;
-	if ((rc = rng_stream_setup(ctx, window, (size_t)ctx->I * ctx->L, &base, &n_chunks, &n_blocks))) return rc;
-	if ((rc = cv_fold_buffer(ctx))) return rc;
-	uint32_t magic, shift;
-	mod_k_magic(n_folds, &magic, &shift);
-	hipLaunchKernelGGL(k_draw_partition, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, base, ctx->d_jump_hi, ctx->d_jump_lo,
-			   n_chunks, (uint32_t)n_folds, magic, shift, (uint32_t *)ctx->d_cv_fold);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	ctx->cv_n_folds = n_folds;
-	return MCHIP_OK;
-}
-
-int mchip_cv_set_folds(mchip_context *ctx, const uint8_t *folds, int n_folds)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	int rc = cv_check_data(ctx, 0);
-	if (rc) return rc;
-	if (!folds) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
-	if (n_folds < 2 || n_folds > 64) return fail(ctx, MCHIP_ERR_INVALID, "cv: n_folds must be in [2, 64]%s", nullptr);
-	const size_t n = (size_t)ctx->I * ctx->L;
-	for (size_t x = 0; x < n; x++)
-		if (folds[x] >= n_folds) return fail(ctx, MCHIP_ERR_INVALID, "cv: fold byte >= n_folds%s", nullptr);
-	HIPCHK(hipSetDevice(ctx->device));
-	if ((rc = cv_fold_buffer(ctx))) return rc;
-	HIPCHK(hipMemcpyAsync(ctx->d_cv_fold, folds, n, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	ctx->cv_n_folds = n_folds;
-	return MCHIP_OK;
-}
-
-int mchip_cv_get_folds(mchip_context *ctx, uint8_t *folds)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	int rc = cv_check_data(ctx, 1);
-	if (rc) return rc;
-	if (!folds) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
-	HIPCHK(hipSetDevice(ctx->device));
-	HIPCHK(hipMemcpyAsync(folds, ctx->d_cv_fold, (size_t)ctx->I * ctx->L, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	return MCHIP_OK;
-}
-
-int mchip_cv_hold_out(mchip_context *ctx, int fold)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	int rc = cv_check_data(ctx, 1);
-	if (rc) return rc;
-	if (fold < -1 || fold >= ctx->cv_n_folds) return fail(ctx, MCHIP_ERR_INVALID, "cv: fold outside [-1, n_folds)%s", nullptr);
-	HIPCHK(hipSetDevice(ctx->device));
-	const int I = ctx->I, L = ctx->L, pl = ctx->ploidy;
-	const size_t n = (size_t)I * L * pl;
-	if (!ctx->d_cv_full) {	/* the data set installed now is the full one: keep it, in upload form */
-		HIPCHK(hipMalloc((void **)&ctx->d_cv_full, n));
-		hipLaunchKernelGGL(k_unlayout, dim3(nblk_capped(n)), dim3(256), 0, ctx->stream, ctx->d_gtA, I, L, pl, ctx->d_cv_full);
-		HIPCHK(hipGetLastError());
-		ctx->cv_full_empty = ctx->empty_rows;
-	}
-	if (!ctx->d_cv_out) HIPCHK(hipMalloc((void **)&ctx->d_cv_out, 4 * sizeof(unsigned long long)));
-	if (fold < 0) {
-		if ((rc = install_raw(ctx, ctx->d_cv_full))) return rc;
-		ctx->empty_rows = ctx->cv_full_empty;
-	} else {
-		if ((rc = stream_buffer(ctx))) return rc;
-		scoped_dev<uint8_t> d_seen;
-		HIPCHK(d_seen.alloc((size_t)I));
-		HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
-		mchip_cv_mask(ctx->stream, ctx->d_cv_full, ctx->d_cv_fold, fold, I, L, pl, ctx->d_draw, d_seen.p);
-		HIPCHK(hipGetLastError());
-		std::vector<uint8_t> seen((size_t)I);
-		HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
-		if ((rc = install_raw(ctx, ctx->d_draw))) return rc;	/* (synchronises the stream) */
-		ctx->empty_rows.clear();
-		for (int i = 0; i < I; i++)
-			if (!seen[i]) ctx->empty_rows.push_back(i);
-	}
-	ctx->first_empty = ctx->empty_rows.empty() ? -1 : ctx->empty_rows[0];
-	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
-	ctx->s_cache_slot = -1;
-	ctx->cv_fold = fold;
-	return MCHIP_OK;
-}
-
-int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor, double *sum_log, uint64_t *n_copies, uint64_t *n_floored)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	int rc = cv_check_data(ctx, 1);
-	if (rc) return rc;
-	if ((rc = check_slot(ctx, slot))) return rc;
-	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "cv: the held-out score is the admixture model's%s", nullptr);
-	if (ctx->cv_fold < 0 || !ctx->d_cv_full) return fail(ctx, MCHIP_ERR_STATE, "cv: no fold is held out%s", nullptr);
-	if (!(floor > 0.0 && floor <= 1.0)) return fail(ctx, MCHIP_ERR_INVALID, "cv: floor must be in (0, 1]%s", nullptr);
-	HIPCHK(hipSetDevice(ctx->device));
-	const size_t parts = (size_t)mchip_cv_score_parts(ctx->I, ctx->L, ctx->K, ctx->max_M, ctx->n_cu);
-	if (ctx->cv_part_cap < parts) {
-		dfree(ctx->d_cv_part);
-		ctx->cv_part_cap = 0;
-		HIPCHK(hipMalloc((void **)&ctx->d_cv_part, parts * sizeof(double)));
-		ctx->cv_part_cap = parts;
-	}
-	HIPCHK(hipMemsetAsync(ctx->d_cv_out, 0, 4 * sizeof(unsigned long long), ctx->stream));
-	mchip_cv_score(ctx->stream, ctx->I, ctx->L, ctx->ploidy, ctx->K, ctx->max_M, ctx->n_cu, ctx->d_cv_full, ctx->d_cv_fold, ctx->cv_fold,
-		       ctx->d_toff, ctx->d_p[slot], ctx->d_q[slot], ctx->qstride, floor, ctx->d_cv_part, ctx->d_cv_out + 1);
-	HIPCHK(hipGetLastError());
-	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_cv_part, (int)parts,
-			   reinterpret_cast<double *>(ctx->d_cv_out), (const int *)nullptr);
-	HIPCHK(hipGetLastError());
-	unsigned long long h[3];
-	HIPCHK(hipMemcpyAsync(h, ctx->d_cv_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	if (sum_log) memcpy(sum_log, &h[0], sizeof(double));
-	if (n_copies) *n_copies = h[1];
-	if (n_floored) *n_floored = h[2];
-	return MCHIP_OK;
-}
-
-/* ---- mixing proportions of query individuals against fixed allele frequencies (kernels: mchip_query.hip) ---- */
-int mchip_fit_q_rows(mchip_context *ctx, int slot, const int32_t *rows, int n_rows, int from_slot, int max_iter, double abs_error,
-		     double rel_error, double *q_rows, double *loglik_rows, int32_t *iter_rows, uint8_t *converged_rows)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	int rc = cv_check_data(ctx, 0);
-	if (rc) return rc;
-	if ((rc = check_slot(ctx, slot))) return rc;
-	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixture model has no mixing proportions per individual%s", nullptr);
-	if (!ctx->qstride) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixing proportions are shared by all individuals%s", nullptr);
-	if (!rows || !q_rows || !loglik_rows || !iter_rows || !converged_rows) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
-	if (n_rows < 1 || n_rows > ctx->I) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: n_rows must be in [1, I]%s", nullptr);
-	if (max_iter < 1) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: max_iter must be >= 1%s", nullptr);
-	if (!(abs_error >= 0) || !(rel_error >= 0)) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: an error must be >= 0%s", nullptr);
-	{
-		std::vector<uint8_t> listed((size_t)ctx->I, 0);
-		for (int r = 0; r < n_rows; r++) {
-			if (rows[r] < 0 || rows[r] >= ctx->I) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: a row outside [0, I)%s", nullptr);
-			if (listed[(size_t)rows[r]]) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: a row is listed twice%s", nullptr);
-			listed[(size_t)rows[r]] = 1;
-		}
-	}
-	HIPCHK(hipSetDevice(ctx->device));
-	const int L = ctx->L, pl = ctx->ploidy, K = ctx->K;
-	const size_t nr = (size_t)n_rows;
-	scoped_dev<int32_t> d_rows, d_iter;
-	scoped_dev<uint8_t> d_geno, d_conv;
-	scoped_dev<double> d_q, d_ll;
-	HIPCHK(d_rows.alloc(nr));
-	HIPCHK(d_iter.alloc(nr));
-	HIPCHK(d_geno.alloc(nr * L * pl));
-	HIPCHK(d_conv.alloc(nr));
-	HIPCHK(d_q.alloc(nr * K));
-	HIPCHK(d_ll.alloc(nr));
-	HIPCHK(hipMemcpyAsync(d_rows.p, rows, nr * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-	/* the full data set: the saved one while a fold is held out of the installed one */
-	const bool saved = ctx->cv_fold >= 0 && ctx->d_cv_full;
-	mchip_query_gather(ctx->stream, saved ? ctx->d_cv_full : ctx->d_gtA, saved ? 1 : 0, d_rows.p, n_rows, L, pl, d_geno.p);
-	HIPCHK(hipGetLastError());
-	mchip_query_fit(ctx->stream, n_rows, L, pl, K, d_geno.p, ctx->d_toff, ctx->d_p[slot], from_slot ? ctx->d_q[slot] : nullptr, d_rows.p,
-			ctx->do_projection, ctx->eta_lb, max_iter, abs_error, rel_error, d_q.p, d_ll.p, d_iter.p, d_conv.p);
-	HIPCHK(hipGetLastError());
-	/* (the rows array and the results cross in pageable memory: the copies are done when the stream is) */
-	std::vector<double> h_q(nr * K), h_ll(nr);
-	std::vector<int32_t> h_iter(nr);
-	std::vector<uint8_t> h_conv(nr);
-	HIPCHK(hipMemcpyAsync(h_q.data(), d_q.p, nr * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipMemcpyAsync(h_ll.data(), d_ll.p, nr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipMemcpyAsync(h_iter.data(), d_iter.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipMemcpyAsync(h_conv.data(), d_conv.p, nr, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	/* the caller's arrays are written once everything has succeeded */
-	memcpy(q_rows, h_q.data(), nr * K * sizeof(double));
-	memcpy(loglik_rows, h_ll.data(), nr * sizeof(double));
-	memcpy(iter_rows, h_iter.data(), nr * sizeof(int32_t));
-	memcpy(converged_rows, h_conv.data(), nr);
-	return MCHIP_OK;
-}
-
-static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_constrained, int do_projection,
-			  double eta_lb, double p_lb, int n_secants);
-
-/* ---- a selection of loci with repeats (kernel: mchip_resample.hip) ---- */
-int mchip_resample_loci(mchip_context *ctx, const int32_t *src, int L2)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
-	if (ctx->cv_fold >= 0) return fail(ctx, MCHIP_ERR_STATE, "resample_loci: a cross-validation fold is held out%s", nullptr);
-	if (!src && !ctx->d_rs_base) return fail(ctx, MCHIP_ERR_STATE, "resample_loci: no saved base to install again%s", nullptr);
-	const int I = ctx->I, pl = ctx->ploidy;
-	const int Lb = ctx->d_rs_base ? ctx->rs_L : ctx->L;
-	std::vector<int32_t> ua2;
-	if (src) {	/* everything that can be refused is refused before anything is touched */
-		if (L2 < 1) return fail(ctx, MCHIP_ERR_INVALID, "resample_loci: L2 must be at least 1%s", nullptr);
-		const std::vector<int32_t> &ua_base = ctx->d_rs_base ? ctx->rs_ua : ctx->h_ua;
-		long long T2 = 0;
-		ua2.resize((size_t)L2);
-		for (int j = 0; j < L2; j++) {
-			if (src[j] < 0 || src[j] >= Lb) return fail(ctx, MCHIP_ERR_INVALID, "resample_loci: locus index outside [0, L_base)%s", nullptr);
-			T2 += (ua2[j] = ua_base[src[j]]);
-		}
-		if (T2 > 2000000000LL) return fail(ctx, MCHIP_ERR_INVALID, "too many allele columns%s", nullptr);
-		if (T2 <= 0) return fail(ctx, MCHIP_ERR_INVALID, "no alleles%s", nullptr);
-	} else {
-		L2 = Lb;
-	}
-	HIPCHK(hipSetDevice(ctx->device));
-	if (!ctx->d_rs_base) {	/* the data set installed now is the base: keep it, in upload form */
-		const size_t n = (size_t)I * Lb * pl;
-		HIPCHK(hipMalloc((void **)&ctx->d_rs_base, n));
-		hipLaunchKernelGGL(k_unlayout, dim3(nblk_capped(n)), dim3(256), 0, ctx->stream, ctx->d_gtA, I, Lb, pl, ctx->d_rs_base);
-		if (MCHIP_WAIT(hipGetLastError()) != hipSuccess || MCHIP_WAIT(hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-			dfree(ctx->d_rs_base);
-			return fail(ctx, MCHIP_ERR_HIP, "resample_loci: saving the base failed%s", nullptr);
-		}
-		ctx->rs_L = Lb;
-		ctx->rs_ua = ctx->h_ua;
-		ctx->rs_empty = ctx->empty_rows;
-	}
-	/* the new shape: tables, buffers, no model, no init genotypes, no cross-validation state -- and the base stays */
-	ctx->rs_installing = 1;
-	int rc = set_shape(ctx, I, L2, pl, src ? ua2.data() : ctx->rs_ua.data());
-	ctx->rs_installing = 0;
-	if (!rc) {
-		if (!src) {
-			if (!(rc = install_raw(ctx, ctx->d_rs_base))) ctx->empty_rows = ctx->rs_empty;
-		} else {
-			rc = [&]() -> int {
-				int rc2 = stream_buffer(ctx);
-				if (rc2) return rc2;
-				scoped_dev<uint8_t> d_seen;
-				scoped_dev<int32_t> d_src;
-				HIPCHK(d_seen.alloc((size_t)I));
-				HIPCHK(d_src.alloc((size_t)L2));
-				HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
-				HIPCHK(hipMemcpyAsync(d_src.p, src, sizeof(int32_t) * (size_t)L2, hipMemcpyHostToDevice, ctx->stream));
-				mchip_resample_gather(ctx->stream, ctx->d_rs_base, d_src.p, I, Lb, L2, pl, ctx->d_draw, d_seen.p);
-				HIPCHK(hipGetLastError());
-				std::vector<uint8_t> seen((size_t)I);
-				HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
-				if ((rc2 = install_raw(ctx, ctx->d_draw))) return rc2;	/* (synchronises the stream) */
-				ctx->empty_rows.clear();
-				for (int i = 0; i < I; i++)
-					if (!seen[i]) ctx->empty_rows.push_back(i);
-				return MCHIP_OK;
-			}();
-		}
-	}
-	if (rc) {	/* a failure half way: no data set (set_shape), or one whose bytes are not what was asked for */
-		free_model(ctx);
-		free_data(ctx);
-		return rc;
-	}
-	ctx->first_empty = ctx->empty_rows.empty() ? -1 : ctx->empty_rows[0];
-	for (int sl = 0; sl < 3; sl++) ctx->empty_rows_nan[sl] = 0;
-	return MCHIP_OK;
-}
-
-int mchip_set_model(mchip_context *ctx, int K, int admixture, int eta_constrained, int do_projection,
-		    double eta_lb, double p_lb, int n_secants)
-{
-	MCHIP_ENTRY();
-	if (!ctx) return MCHIP_ERR_INVALID;
-	const int rc = set_model_impl(ctx, K, admixture, eta_constrained, do_projection, eta_lb, p_lb, n_secants);
-	if (rc == MCHIP_ERR_HIP || rc == MCHIP_ERR_ALLOC) free_model(ctx);	/* an allocation that failed half way leaves no model, not a partial one */
-	return rc;
 }
 
 static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_constrained, int do_projection,
@@ -2680,6 +2230,16 @@ static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_cons
 	}
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	return MCHIP_OK;
+}
+
+int mchip_set_model(mchip_context *ctx, int K, int admixture, int eta_constrained, int do_projection,
+		    double eta_lb, double p_lb, int n_secants)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	const int rc = set_model_impl(ctx, K, admixture, eta_constrained, do_projection, eta_lb, p_lb, n_secants);
+	if (rc == MCHIP_ERR_HIP || rc == MCHIP_ERR_ALLOC) free_model(ctx);	/* an allocation that failed half way leaves no model, not a partial one */
+	return rc;
 }
 
 int mchip_q_length(const mchip_context *ctx, int *n)
@@ -3205,6 +2765,33 @@ static void mod_k_magic(int K, uint32_t *magic, uint32_t *shift)
 	*shift = l - 1;
 }
 
+}	/* extern "C" */
+
+int draw_mod_stream(mchip_context *ctx, const uint32_t *window, size_t n_draws, int m, uint8_t *d_out)
+{
+	rng_window base;
+	size_t n_chunks, n_blocks;
+	const int rc = rng_stream_setup(ctx, window, n_draws, &base, &n_chunks, &n_blocks);
+	if (rc) return rc;
+	if (m == 1) {
+		HIPCHK(hipMemsetAsync(d_out, 0, n_chunks * RNG_CHUNK, ctx->stream));	/* rand() % 1 */
+		return MCHIP_OK;
+	}
+	uint32_t magic, shift;
+	mod_k_magic(m, &magic, &shift);
+	hipLaunchKernelGGL(k_draw_partition, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, base, ctx->d_jump_hi, ctx->d_jump_lo,
+			   n_chunks, (uint32_t)m, magic, shift, (uint32_t *)d_out);
+	HIPCHK(hipGetLastError());
+	return MCHIP_OK;
+}
+
+void launch_reduce_sum(mchip_context *ctx, const double *in, int n, double *out)
+{
+	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, in, n, out, (const int *)nullptr);
+}
+
+extern "C" {
+
 /* the tiled form of the random partition + first M step (k_partition_tile); returns -1 when the shape does not fit it */
 static int rand_partition_tiled(mchip_context *ctx, const uint32_t *window, int to)
 {
@@ -3256,19 +2843,8 @@ int mchip_mstep_from_rand_partition(mchip_context *ctx, const uint32_t *window, 
 	HIPCHK(hipSetDevice(ctx->device));
 	if ((rc = rand_partition_tiled(ctx, window, to)) >= 0) return rc;
 	const size_t n = (size_t)ctx->I * ctx->L * ctx->ploidy;
-	rng_window base;
-	size_t n_chunks, n_blocks;
-	if ((rc = rng_stream_setup(ctx, window, n, &base, &n_chunks, &n_blocks))) return rc;
 	if ((rc = stream_buffer(ctx))) return rc;
-	if (ctx->K == 1) {
-		HIPCHK(hipMemsetAsync(ctx->d_draw, 0, n, ctx->stream));	/* rand() % 1 */
-	} else {
-		uint32_t magic, shift;
-		mod_k_magic(ctx->K, &magic, &shift);
-		hipLaunchKernelGGL(k_draw_partition, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, base, ctx->d_jump_hi,
-				   ctx->d_jump_lo, n_chunks, (uint32_t)ctx->K, magic, shift, (uint32_t *)ctx->d_draw);
-		HIPCHK(hipGetLastError());
-	}
+	if ((rc = draw_mod_stream(ctx, window, n, ctx->K, ctx->d_draw))) return rc;
 	return partition_mstep(ctx, ctx->d_draw, to);
 }
 
@@ -3286,8 +2862,6 @@ int mchip_init_from_allele_centers(mchip_context *ctx, const uint8_t *centers, c
 	 * --streams workers, n_rand_em_init times per initialisation */
 	if ((rc = stream_buffer(ctx))) return rc;
 	uint8_t *d_raw = ctx->d_draw;
-	rng_window base;
-	size_t n_chunks = 0, n_blocks = 0;
 	auto grow = [&](void **p, size_t *have, size_t want) -> hipError_t {
 		if (*have >= want) return hipSuccess;
 		if (*p) { (void)MCHIP_WAIT(hipStreamSynchronize(ctx->stream)); (void)MCHIP_WAIT(hipFree(*p)); *p = nullptr; *have = 0; }
@@ -3296,16 +2870,9 @@ int mchip_init_from_allele_centers(mchip_context *ctx, const uint8_t *centers, c
 		return e;
 	};
 	if (n_draws) {
-		if ((rc = rng_stream_setup(ctx, window, (size_t)n_draws, &base, &n_chunks, &n_blocks))) return rc;
-		HIPCHK(grow((void **)&ctx->d_cand_span, &ctx->cand_span_bytes, n_chunks * RNG_CHUNK + n_chunks * RNG_CHUNK / 8));
-		if (ctx->K == 1) {
-			HIPCHK(hipMemsetAsync(ctx->d_cand_span, 0, n_chunks * RNG_CHUNK, ctx->stream));
-		} else {
-			uint32_t magic, shift;
-			mod_k_magic(ctx->K, &magic, &shift);
-			hipLaunchKernelGGL(k_draw_partition, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, base, ctx->d_jump_hi,
-					   ctx->d_jump_lo, n_chunks, (uint32_t)ctx->K, magic, shift, (uint32_t *)ctx->d_cand_span);
-		}
+		const size_t span = (((size_t)n_draws + RNG_CHUNK - 1) / RNG_CHUNK) * RNG_CHUNK;	/* whole chunks are written */
+		HIPCHK(grow((void **)&ctx->d_cand_span, &ctx->cand_span_bytes, span + span / 8));
+		if ((rc = draw_mod_stream(ctx, window, (size_t)n_draws, ctx->K, ctx->d_cand_span))) return rc;
 	} else {
 		HIPCHK(grow((void **)&ctx->d_cand_span, &ctx->cand_span_bytes, 16));	/* no copy draws: never read */
 	}
@@ -3359,10 +2926,9 @@ int mchip_simulate_genotypes(mchip_context *ctx, int I, int L, int ploidy, const
 	if (!window || !q || !p || K < 1) return fail(ctx, MCHIP_ERR_INVALID, "simulate_genotypes: null pointer or K < 1%s", nullptr);
 	/* a replicate of the same observed data: the observed haplotypes installed by mchip_set_init_genotypes stay in force
 	 * (the reference's dat->IL stays in place across parametric_bootstrap calls, bootstrap.c:35-41) */
-	int rc = set_shape(ctx, I, L, ploidy, ua, 1);
+	int rc = set_shape(ctx, I, L, ploidy, ua, KEEP_INIT);
 	if (rc) return rc;
-	ctx->first_empty = -1;		/* every copy of a generated data set is drawn */
-	ctx->empty_rows.clear();
+	set_empty_rows(ctx, {});	/* every copy of a generated data set is drawn */
 	const size_t n_copies = (size_t)I * L * ploidy;
 	rng_window base;
 	size_t n_chunks, n_blocks;
@@ -3435,10 +3001,9 @@ int mchip_simulate_genotypes_mixture(mchip_context *ctx, int I, int L, int ploid
 	if (!ctx) return MCHIP_ERR_INVALID;
 	if (!window || !eta || !p || K < 1) return fail(ctx, MCHIP_ERR_INVALID, "simulate_genotypes_mixture: null pointer or K < 1%s", nullptr);
 	if (K > 256) return fail(ctx, MCHIP_ERR_INVALID, "simulate_genotypes_mixture: more than 256 clusters%s", nullptr);
-	int rc = set_shape(ctx, I, L, ploidy, ua, 1);
+	int rc = set_shape(ctx, I, L, ploidy, ua, KEEP_INIT);
 	if (rc) return rc;
-	ctx->first_empty = -1;		/* every copy of a generated data set is drawn */
-	ctx->empty_rows.clear();
+	set_empty_rows(ctx, {});	/* every copy of a generated data set is drawn */
 	rng_window base, base1;		/* at the first draw (the first individual's cluster); one draw on (its first copy) */
 	for (int t = 0; t < RNG_LAG; t++) base.s[t] = window[t];
 	for (int t = 0; t < RNG_LAG - 1; t++) base.s[RNG_LAG + t] = base.s[t] + base.s[RNG_LAG - 3 + t];

@@ -1,6 +1,6 @@
 /*
- * mchip_bed.hip -- PLINK 1 .bed records (2 bits per genotype, variant-major) unpacked on the device: the kernels behind
- * mchip_set_genotypes_bed (include/multiclust_hip.h has the format and the contract; mchip.hip has the entry point).
+ * mchip_bed.hip -- PLINK 1 .bed records (2 bits per genotype, variant-major) unpacked on the device: mchip_set_genotypes_bed
+ * and its kernels (include/multiclust_hip.h has the format and the contract; mchip_context.h the context and the install path).
  *
  * Two passes over the packed records, I * L / 4 bytes each:
  *   k_bed_locus   one wave per locus: which of A1, A2 and "missing" occur among the I samples of the record -> uniquealleles[l]
@@ -11,15 +11,16 @@
  *                 either side, and marks the individuals that have an observed call.
  * The upload form [I][L][2] never exists.
  */
-#include "mchip_internal.h"
+#include "mchip_context.h"
 
+constexpr int BED_PAD = 8;	/* bytes allocated behind the last record: records are read as dwords from any byte offset */
 constexpr int BT_L = 64;	/* loci per tile */
 constexpr int BT_I = 256;	/* individuals per tile: 64 staged bytes of each record */
 constexpr int BT_ROW = 17;	/* dwords between staged records: 16 of data and one of padding, so that the 64 lanes that read the
 				 * same byte pair of 64 consecutive records (gtA side) fall on 64 different banks */
 
 /* four packed bytes from any byte offset of the buffer: records are record_bytes apart, whatever that is modulo 4.  Two aligned
- * loads; the second may reach MCHIP_BED_PAD - 1 bytes behind the last record */
+ * loads; the second may reach BED_PAD - 1 bytes behind the last record */
 __device__ __forceinline__ uint32_t bed_word(const uint8_t *__restrict__ bed, size_t off)
 {
 	const uint32_t *w = reinterpret_cast<const uint32_t *>(bed + (off & ~(size_t)3));
@@ -28,6 +29,8 @@ __device__ __forceinline__ uint32_t bed_word(const uint8_t *__restrict__ bed, si
 	return sh ? (lo >> sh) | (w[1] << (32u - sh)) : lo;
 }
 
+/* locus pass: ua[l] as the STRUCTURE reader counts it, a1[l] = 1 when allele A1 is observed at locus l (the one thing the recoding
+ * of a locus depends on), bit 1 of *flags set when any call is missing */
 __global__ __launch_bounds__(256) void k_bed_locus(const uint8_t *__restrict__ bed, size_t rb, int I, int L, int32_t *__restrict__ ua,
 						   uint8_t *__restrict__ a1_out, int *flags)
 {
@@ -59,6 +62,8 @@ __device__ __forceinline__ uint64_t bed_pairs(uint32_t hom2)
 	return 0xFFFF0000ull | (0x0100ull << 32) | ((uint64_t)hom2 << 48);
 }
 
+/* expand pass: gtA and gtS of the ploidy-2 data set, padded with 0xFF like k_relayout's; seen[i] (zeroed by the caller) = 1 for
+ * every individual with an observed call */
 __global__ __launch_bounds__(256) void k_bed_expand(const uint8_t *__restrict__ bed, size_t rb, int I, int L, const uint8_t *__restrict__ a1,
 						    uint8_t *__restrict__ gtA, uint8_t *__restrict__ gtS, uint8_t *seen, int n_ltiles)
 {
@@ -110,17 +115,50 @@ __global__ __launch_bounds__(256) void k_bed_expand(const uint8_t *__restrict__ 
 	if (any) seen[i0 + threadIdx.x] = 1;	/* (every writer stores the same value) */
 }
 
-void mchip_bed_locus_pass(hipStream_t s, const uint8_t *d_bed, size_t record_bytes, int I, int L, int32_t *ua, uint8_t *a1, int *flags)
+/* The packed records go up as they are; the locus pass tells the host the allele counts set_shape sizes the column tables from,
+ * the expand pass fills gtA / gtS.  No stream buffer (d_draw) and no k_relayout on this route. */
+extern "C" int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int32_t *uniquealleles_out)
 {
-	hipLaunchKernelGGL(k_bed_locus, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, s, d_bed, record_bytes, I, L, ua, a1, flags);
-}
-
-int mchip_bed_expand(hipStream_t s, const uint8_t *d_bed, size_t record_bytes, int I, int L, const uint8_t *a1, uint8_t *gtA,
-		     uint8_t *gtS, uint8_t *seen)
-{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (I <= 0 || L <= 0 || !bed || record_bytes < ((size_t)I + 3) / 4)
+		return fail(ctx, MCHIP_ERR_INVALID, "set_genotypes_bed: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	const size_t bed_bytes = (size_t)L * record_bytes;
+	scoped_dev<uint8_t> d_bed, d_a1, d_seen;
+	scoped_dev<int32_t> d_ua;
+	HIPCHK(d_bed.alloc(bed_bytes + BED_PAD));
+	HIPCHK(d_a1.alloc((size_t)L));
+	HIPCHK(d_seen.alloc((size_t)I));
+	HIPCHK(d_ua.alloc((size_t)L));
+	int *d_bad = bad_flag(ctx);
+	HIPCHK(hipMemcpyAsync(d_bed.p, bed, bed_bytes, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_bed.p + bed_bytes, 0, BED_PAD, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
+	hipLaunchKernelGGL(k_bed_locus, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, ctx->stream, d_bed.p, record_bytes, I, L, d_ua.p, d_a1.p, d_bad);
+	HIPCHK(hipGetLastError());
+	std::vector<int32_t> ua((size_t)L);
+	int bad = 0;
+	HIPCHK(hipMemcpyAsync(ua.data(), d_ua.p, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	if (uniquealleles_out) memcpy(uniquealleles_out, ua.data(), sizeof(int32_t) * (size_t)L);
+	int rc = set_shape(ctx, I, L, 2, ua.data());
+	if (rc) return rc;
 	const int n_ltiles = (L + BT_L - 1) / BT_L, n_itiles = (I + BT_I - 1) / BT_I;
 	const size_t blocks = (size_t)n_ltiles * n_itiles;
-	if (blocks >= ((size_t)1 << 31)) return -1;
-	hipLaunchKernelGGL(k_bed_expand, dim3((unsigned)blocks), dim3(256), 0, s, d_bed, record_bytes, I, L, a1, gtA, gtS, seen, n_ltiles);
-	return 0;
+	if (blocks >= ((size_t)1 << 31)) {
+		free_data(ctx);
+		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "data set too large for the layout kernel%s", nullptr);
+	}
+	hipLaunchKernelGGL(k_bed_expand, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_bed.p, record_bytes, I, L, d_a1.p, ctx->d_gtA,
+			   ctx->d_gtS, d_seen.p, n_ltiles);
+	HIPCHK(hipGetLastError());
+	std::vector<uint8_t> seen((size_t)I);
+	HIPCHK(hipMemcpyAsync(seen.data(), d_seen.p, (size_t)I, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	set_empty_rows_unseen(ctx, seen);
+	return install_layouts(ctx, (bad & 2) ? 1 : 0);
 }

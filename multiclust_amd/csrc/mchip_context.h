@@ -1,0 +1,204 @@
+/*
+ * mchip_context.h -- the per-context state of libmulticlust_hip.so and the few helpers of mchip.hip that the units holding a
+ * data-set feature's kernels and entry points call (mchip_bed.hip, mchip_cv.hip, mchip_query.hip, mchip_resample.hip).
+ * Private to the library's host-side units; not part of the C-ABI, and mchip_kernels_k.hip does not include it.
+ */
+#ifndef MCHIP_CONTEXT_H
+#define MCHIP_CONTEXT_H
+
+#include "mchip_internal.h"
+#include "mchip_progress.h"
+
+#include <functional>
+#include <stdio.h>
+#include <string.h>
+
+constexpr int RNG_LAG = 31;
+constexpr int RNG_CHUNK = 4 * RNG_LAG * 32;	/* draws (= bytes written) per thread: 32 rounds of 31 packed words */
+
+/* a data set kept beside the installed one, in upload form [I][L][ploidy] (I and ploidy are the installed data set's) */
+struct saved_set {
+	uint8_t *d_raw = nullptr;	/* null = none saved */
+	int L = 0;
+	std::vector<int32_t> ua;	/* its uniquealleles */
+	std::vector<int> empty;		/* its empty_rows */
+};
+
+struct mchip_context {
+	int device;
+	hipStream_t stream;
+	char err[512];
+	int n_cu;
+	/* data set */
+	int I, L, ploidy, T, max_M, min_M;
+	std::vector<int32_t> h_ua;	/* host copy of uniquealleles: a data set of the same shape reuses every buffer */
+	int parked_K;			/* model buffers kept allocated for this K (and the signature below) while no model is set */
+	int sig_admixture, sig_constrained, sig_projection, sig_nsec;
+	double sig_eta_lb, sig_p_lb;
+	int init_geno_set;		/* d_initA / d_initS hold the observed haplotypes (mchip_set_init_genotypes) */
+	int32_t *d_ua, *d_toff, *d_col_locus;
+	uint8_t *d_col_allele;
+	uint8_t *d_gtA, *d_gtS, *d_gtC;
+	int count_bits, has_missing;
+	int first_empty;	/* first individual without a single observed copy, or -1 */
+	std::vector<int> empty_rows;	/* all of them: their mixing proportions are 0 / 0 in the reference (em_alg.c:685-690) */
+	int empty_rows_nan[3];	/* per slot: the slot's rows of such individuals stand for the reference's 0 / 0 (an M step wrote the slot, or
+				 * something computed from such a slot did, or NaN rows were uploaded): mchip_get_q reports them as NaN */
+	unsigned long long nnz_cells, n_copies;	/* cells with n_ic > 0, non-missing allele copies (mchip_data_counts) */
+	int counts_valid;
+	size_t geno_bytes_A, geno_bytes_S;
+	uint8_t *d_asA, *d_asS;		/* hard-partition scratch, allocated on first use */
+	uint8_t *d_initA, *d_initS;	/* genotype the hard-partition M step reads when it is not the data set itself (bootstrap) */
+	uint8_t *d_draw;		/* device-drawn partition in stream order [I][L][ploidy], padded to whole chunks */
+	/* K-fold cross-validation (mchip_cv.hip): state of the data set, dropped with it */
+	uint8_t *d_cv_fold;		/* fold of every genotype [I][L], padded to whole generator chunks + CV_PAD; null = no folds */
+	int cv_n_folds;
+	saved_set cv_full;		/* the full data set, saved by the first hold-out */
+	int cv_fold;			/* fold held out of the installed data set, -1 = none */
+	double *d_cv_part;		/* the score's partial sums, one per workgroup */
+	size_t cv_part_cap;
+	unsigned long long *d_cv_out;	/* [0] the score's sum (a double), [1] copies, [2] floored copies */
+	/* selections of loci (mchip_resample.hip): the base they are gathered from, saved by the first one and dropped by every other
+	 * call that installs a data set */
+	saved_set rs_base;
+	/* Rand-EM candidates (mchip_init_from_allele_centers), kept from one candidate to the next and grown when needed: the
+	 * rand() % K values of a candidate's span of the stream, its center alleles [L][K], its per-locus draw offsets */
+	uint8_t *d_cand_span, *d_cand_centers;
+	unsigned long long *d_cand_off;
+	size_t cand_span_bytes, cand_loci, cand_center_bytes;
+	uint32_t *d_jump_hi, *d_jump_lo;	/* jump polynomials of the rand() stream (mchip_mstep_from_rand_partition) */
+	size_t n_jump_hi;
+	/* jump polynomials of the tiled generators (0: bootstrap data set, 1: random partition): x^(A*i), i < nA, stored [31][nA]
+	 * (one per individual) and x^(B*r), r < nB, stored [nB][31] (one per locus tile); kept while A, nA, B, nB stay the same */
+	struct lattice { uint32_t *d_i, *d_r; uint64_t A, B; unsigned nA, nB; } lat[2];
+	uint32_t *d_part_slabs;		/* tiled random partition: packed 16-bit N-side counts per block of 256 individuals */
+	size_t part_slab_bytes;
+	/* mixture model on generated data: the cluster of every individual of the data set (mchip_simulate_genotypes_mixture), and the
+	 * workspaces of mchip_init_from_individual_centers (partial distances [chunk][K][I]; counts [T][K], n_k, centers, assignment) */
+	uint8_t *d_sim_cluster;
+	uint32_t *d_cen_part, *d_cen_work;
+	size_t cen_part_bytes, cen_work_bytes;
+	/* model */
+	int K, admixture, constrained, do_projection, nsec, nq, qstride;
+	double eta_lb, p_lb;
+	const mchip_ktable *kt;
+	double *d_p[3], *d_q[3];
+	double *d_up[MCHIP_MAX_SECANTS], *d_vp[MCHIP_MAX_SECANTS], *d_uq[MCHIP_MAX_SECANTS], *d_vq[MCHIP_MAX_SECANTS];
+	double *d_sik;			/* [I][K] expected counts / vik */
+	double *d_stage;		/* K*T staging for the [K][T] <-> [T][K] transposes */
+	double *d_logp;			/* mixture model: log P table [T][K] */
+	/* workspaces */
+	int ichunk, n_ichunks, lchunk, n_lchunks, n_llpart, flush_blocks, safe_rcp, sparse;
+	int ind_waves;			/* waves per workgroup of the cooperating individual-side kernels (mchip_internal.h) */
+	int xcd_rows;			/* their slab rows come in whole groups of eight: one row, one XCD */
+	/* testing / tuning knobs of the environment (README), read when a context is created and again with every data set and every
+	 * model -- never on a launch path */
+	struct {
+		int no_bial, no_counts, force_dense, force_safe, no_graph, no_dual, no_slab_sum, no_col_split, part_no_tile, sim_no_tile;
+		int no_fused_finalize;
+		int per_cu_col, per_cu_ind, geometry_given, no_roundup;
+		double slab_frac;
+	} knob;
+	double *d_Apart, *d_Spart, *d_llpart, *d_scalars;	/* d_scalars: [0]=logL, [1..3]=dots, [4..]=eta sums */
+	double *d_llpart2;		/* partial log likelihoods of the second parameter set of a dual individual pass */
+	double *d_redpart;		/* block partials of the dot products / column sums */
+	uint8_t *d_flags;		/* michelot "fixed" flags for loci with more than 64 alleles */
+	double *h_pinned;		/* 64 doubles */
+	mchip_run_state *d_run;		/* batched-run state (mchip_em_run) */
+	hipGraphExec_t step_graph[3];	/* one captured {EM step + stop check} per slot; rebuilt when the model changes */
+	hipGraphExec_t cycle_graph[3][5];	/* one captured accelerated cycle per (start slot, scheme) */
+	int *d_cyc;			/* batched accelerated runs: [0] no update this cycle, [1] extrapolation accepted */
+	int have_ll;
+	int ll_parts;			/* partial log likelihoods the last E step left in d_llpart */
+	int s_cache_slot;		/* slot whose S-side sums + logL are held in Spart / d_scalars[2] (mchip_loglik_prefetch), or -1 */
+	/* profiling */
+	int profiling;
+	hipEvent_t ev_begin, ev_end;
+	std::vector<hipEvent_t> ev_pool;
+	std::vector<int> ev_kind;	/* kernel kind of pair p = events 2p, 2p+1 */
+	size_t ev_used;
+};
+
+static int fail(mchip_context *ctx, int code, const char *fmt, const char *detail)
+{
+	if (ctx) snprintf(ctx->err, sizeof ctx->err, fmt, detail ? detail : "");
+	return code;
+}
+
+#define HIPCHK(call)                                                                                  \
+	do {                                                                                          \
+		hipError_t e_ = MCHIP_WAIT(call);                                                     \
+		if (e_ != hipSuccess) {                                                               \
+			snprintf(ctx->err, sizeof ctx->err, "%s failed: %s (%s:%d)", #call,           \
+				 hipGetErrorString(e_), __FILE__, __LINE__);                          \
+			return MCHIP_ERR_HIP;                                                         \
+		}                                                                                     \
+	} while (0)
+
+template <typename Tp> static void dfree(Tp *&p)
+{
+	if (p) (void)MCHIP_WAIT(hipFree(p));
+	p = nullptr;
+}
+
+/* temporary device allocation released on every exit path of the function that owns it */
+template <typename Tp> struct scoped_dev {
+	Tp *p = nullptr;
+	scoped_dev() = default;
+	scoped_dev(const scoped_dev &) = delete;
+	scoped_dev &operator=(const scoped_dev &) = delete;
+	~scoped_dev() { if (p) (void)MCHIP_WAIT(hipFree(p)); }
+	hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(Tp)); }
+	operator Tp *() const { return p; }
+};
+
+static inline unsigned nblk(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
+/* for the byte-per-thread layout kernels (grid-stride loops): at most 2^30 work-items per launch */
+static inline unsigned nblk_capped(size_t n, unsigned b = 256)
+{
+	const size_t blocks = (n + b - 1) / b, cap = ((size_t)1 << 30) / b;
+	return (unsigned)(blocks < cap ? blocks : cap);
+}
+
+/* the "bad input" word of the layout kernels: the last double of d_scalars (slots 0..47 are in use), so that an
+ * initialisation allocates and frees nothing (hipFree waits for the whole device, i.e. for every other stream's fits) */
+static int *bad_flag(mchip_context *ctx) { return reinterpret_cast<int *>(ctx->d_scalars + 63); }
+
+/* ---- what the feature units call; defined in mchip.hip unless noted, never exported from the library ---- */
+#pragma GCC visibility push(hidden)
+
+int check_slot(mchip_context *ctx, int slot);
+void free_model(mchip_context *ctx);
+/* free_data and set_shape drop both saved sets with the data set that goes, unless told to keep the base of the selections */
+enum { KEEP_INIT = 1, KEEP_RS_BASE = 2 };
+void free_data(mchip_context *ctx, int keep = 0);
+/* shape of a data set: tables derived from uniquealleles, genotype buffers allocated but not filled; no model afterwards.
+ * KEEP_INIT: the observed haplotypes of mchip_set_init_genotypes stay in force when the shape is the one held. */
+int set_shape(mchip_context *ctx, int I, int L, int ploidy, const int32_t *ua, int keep = 0);
+/* gtA / gtS are in place: flags and the packed per-column allele counts of the column pass */
+int install_layouts(mchip_context *ctx, int has_missing);
+
+/* the only writer of empty_rows, first_empty and empty_rows_nan; the second form lists the individuals with seen[i] == 0 */
+void set_empty_rows(mchip_context *ctx, std::vector<int> rows);
+void set_empty_rows_unseen(mchip_context *ctx, const std::vector<uint8_t> &seen);
+/* The installed data set -> `set`, in upload form, with its L, uniquealleles and empty rows; synchronises the stream.  On any
+ * failure the buffer is freed and the set stays empty. */
+int save_installed(mchip_context *ctx, saved_set &set);
+void drop_saved(saved_set &set);
+/* A saved set of the installed shape -> the kernels' layouts, with its empty rows. */
+int install_saved(mchip_context *ctx, const saved_set &set);
+/* A data set made on the device -> the kernels' layouts.  fill(d_out, d_seen) launches the kernel that writes the upload form
+ * [I][L][ploidy] of the installed shape to d_out and sets d_seen[i] (zeroed here) = 1 for every individual that keeps an observed
+ * copy. */
+int install_derived(mchip_context *ctx, const std::function<void(uint8_t *d_out, uint8_t *d_seen)> &fill);
+/* rand() % m for the n_draws draws that follow `window`, one byte each, to d_out: whole chunks of RNG_CHUNK bytes are written */
+int draw_mod_stream(mchip_context *ctx, const uint32_t *window, size_t n_draws, int m, uint8_t *d_out);
+/* out[0] = in[0] + ... + in[n - 1] in k_reduce_sum's fixed order, one workgroup */
+void launch_reduce_sum(mchip_context *ctx, const double *in, int n, double *out);
+
+/* mchip_cv.hip: folds, the saved full data set and a hold-out in force belong to the data set that goes */
+void drop_cv(mchip_context *ctx);
+
+#pragma GCC visibility pop
+
+#endif

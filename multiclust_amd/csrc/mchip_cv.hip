@@ -1,7 +1,7 @@
 /*
- * mchip_cv.hip -- K-fold cross-validation of the admixture model: the kernels behind mchip_cv_hold_out and
- * mchip_cv_heldout_loglik (include/multiclust_hip.h has the contract; mchip.hip has the entry points and the per-context state;
- * the fold draw is k_draw_partition with K := n_folds and lives there with the generator).
+ * mchip_cv.hip -- K-fold cross-validation of the admixture model: the mchip_cv_* entry points and the kernels behind
+ * mchip_cv_hold_out and mchip_cv_heldout_loglik (include/multiclust_hip.h has the contract; mchip_context.h the per-context
+ * state and the install path; the fold draw is draw_mod_stream with m := n_folds and lives in mchip.hip with the generator).
  *
  *   k_cv_mask    a thread per genotype: copies its `ploidy` bytes of the saved full data set into the stream buffer, or 0xFF when
  *                the genotype's fold is the one held out; marks the individuals that keep an observed copy.
@@ -22,7 +22,12 @@
  *                per workgroup, k_reduce_sum (mchip.hip) adds the partials.  No floating-point atomics: the same state gives the
  *                same bits.  The two counts are integers and go through atomics.
  */
-#include "mchip_internal.h"
+#include "mchip_context.h"
+
+constexpr int CV_PAD = 16;	/* bytes allocated behind the fold bytes [I][L]: they are read eight at a time from any byte offset */
+
+/* out = full (the saved data set in upload form [I][L][ploidy]) with every copy of the genotypes of fold `fold_id` turned into
+ * 0xFF; seen[i] (zeroed by the caller) = 1 for every individual that keeps an observed copy */
 
 __global__ __launch_bounds__(256) void k_cv_mask(const uint8_t *__restrict__ full, const uint8_t *__restrict__ fold, int fold_id, int I,
 						 int L, int pl, uint8_t *__restrict__ out, uint8_t *seen)
@@ -40,14 +45,7 @@ __global__ __launch_bounds__(256) void k_cv_mask(const uint8_t *__restrict__ ful
 	}
 }
 
-void mchip_cv_mask(hipStream_t s, const uint8_t *full, const uint8_t *fold, int fold_id, int I, int L, int ploidy, uint8_t *out,
-		   uint8_t *seen)
-{
-	const size_t n = (size_t)I * L, blocks = (n + 255) / 256, cap = (size_t)1 << 20;
-	hipLaunchKernelGGL(k_cv_mask, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, s, full, fold, fold_id, I, L, ploidy, out, seen);
-}
-
-/* eight bytes from any byte offset: two aligned loads (the second may reach 15 bytes behind `off`: MCHIP_CV_PAD) */
+/* eight bytes from any byte offset: two aligned loads (the second may reach 15 bytes behind `off`: CV_PAD) */
 __device__ __forceinline__ uint64_t cv_load8(const uint8_t *__restrict__ base, size_t off)
 {
 	const uint64_t *w = reinterpret_cast<const uint64_t *>(base + (off & ~(size_t)7));
@@ -90,6 +88,9 @@ static cv_geometry cv_score_geometry(int I, int L, int K, int max_M, int n_cu)
 	return g;
 }
 
+/* sum of log max(t, floor) over the observed copies of the fold, one partial per workgroup in part[] (n_itiles * n_lchunks of
+ * them); counts[0] += copies, counts[1] += floored copies (zeroed by the caller).  P is a slot's [T][K], Q its [I][K]
+ * (qstride = K) or [K] (qstride = 0). */
 __global__ __launch_bounds__(256) void k_cv_score(int I, int L, int pl, int K, int KS, int stage, int lchunk,
 						  const uint8_t *__restrict__ full, const uint8_t *__restrict__ fold, int fold_id,
 						  const int32_t *__restrict__ toff, const double *__restrict__ P, const double *__restrict__ Q,
@@ -173,18 +174,142 @@ __global__ __launch_bounds__(256) void k_cv_score(int I, int L, int pl, int K, i
 	}
 }
 
-int mchip_cv_score_parts(int I, int L, int K, int max_M, int n_cu)
+/* folds, the saved full data set and a hold-out in force belong to the data set that goes */
+void drop_cv(mchip_context *ctx)
 {
-	const cv_geometry g = cv_score_geometry(I, L, K, max_M, n_cu);
-	return g.n_itiles * g.n_lchunks;
+	dfree(ctx->d_cv_fold);
+	drop_saved(ctx->cv_full);
+	dfree(ctx->d_cv_part); dfree(ctx->d_cv_out);
+	ctx->cv_n_folds = 0;
+	ctx->cv_fold = -1;
+	ctx->cv_part_cap = 0;
 }
 
-int mchip_cv_score(hipStream_t s, int I, int L, int ploidy, int K, int max_M, int n_cu, const uint8_t *full, const uint8_t *fold,
-		   int fold_id, const int32_t *toff, const double *P, const double *Q, int qstride, double floor, double *part,
-		   unsigned long long *counts)
+static int cv_check_data(mchip_context *ctx, int need_folds)
 {
-	const cv_geometry g = cv_score_geometry(I, L, K, max_M, n_cu);
-	hipLaunchKernelGGL(k_cv_score, dim3((unsigned)g.n_itiles, (unsigned)g.n_lchunks), dim3((unsigned)g.threads), g.lds, s, I, L, ploidy, K,
-			   cv_ks(K), g.stage, g.lchunk, full, fold, fold_id, toff, P, Q, qstride, floor, part, counts);
-	return g.n_itiles * g.n_lchunks;
+	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
+	if (need_folds && !ctx->d_cv_fold) return fail(ctx, MCHIP_ERR_STATE, "no folds: mchip_cv_draw_folds or mchip_cv_set_folds first%s", nullptr);
+	return MCHIP_OK;
+}
+
+/* one byte per genotype, whole generator chunks (draw_mod_stream writes whole chunks) and the padding the score's reads want */
+static int cv_fold_buffer(mchip_context *ctx)
+{
+	if (ctx->d_cv_fold) return MCHIP_OK;
+	const size_t n = (size_t)ctx->I * ctx->L, bytes = ((n + RNG_CHUNK - 1) / RNG_CHUNK) * RNG_CHUNK + CV_PAD;
+	HIPCHK(hipMalloc((void **)&ctx->d_cv_fold, bytes));
+	HIPCHK(hipMemsetAsync(ctx->d_cv_fold, 0, bytes, ctx->stream));
+	return MCHIP_OK;
+}
+
+extern "C" {
+
+int mchip_cv_draw_folds(mchip_context *ctx, const uint32_t *window, int n_folds)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 0);
+	if (rc) return rc;
+	if (!window) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	if (n_folds < 2 || n_folds > 64) return fail(ctx, MCHIP_ERR_INVALID, "cv: n_folds must be in [2, 64]%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	if ((rc = cv_fold_buffer(ctx))) return rc;
+	if ((rc = draw_mod_stream(ctx, window, (size_t)ctx->I * ctx->L, n_folds, ctx->d_cv_fold))) return rc;
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	ctx->cv_n_folds = n_folds;
+	return MCHIP_OK;
+}
+
+int mchip_cv_set_folds(mchip_context *ctx, const uint8_t *folds, int n_folds)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 0);
+	if (rc) return rc;
+	if (!folds) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	if (n_folds < 2 || n_folds > 64) return fail(ctx, MCHIP_ERR_INVALID, "cv: n_folds must be in [2, 64]%s", nullptr);
+	const size_t n = (size_t)ctx->I * ctx->L;
+	for (size_t x = 0; x < n; x++)
+		if (folds[x] >= n_folds) return fail(ctx, MCHIP_ERR_INVALID, "cv: fold byte >= n_folds%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	if ((rc = cv_fold_buffer(ctx))) return rc;
+	HIPCHK(hipMemcpyAsync(ctx->d_cv_fold, folds, n, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	ctx->cv_n_folds = n_folds;
+	return MCHIP_OK;
+}
+
+int mchip_cv_get_folds(mchip_context *ctx, uint8_t *folds)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 1);
+	if (rc) return rc;
+	if (!folds) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	HIPCHK(hipMemcpyAsync(folds, ctx->d_cv_fold, (size_t)ctx->I * ctx->L, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	return MCHIP_OK;
+}
+
+int mchip_cv_hold_out(mchip_context *ctx, int fold)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 1);
+	if (rc) return rc;
+	if (fold < -1 || fold >= ctx->cv_n_folds) return fail(ctx, MCHIP_ERR_INVALID, "cv: fold outside [-1, n_folds)%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	/* the data set installed now is the full one: keep it */
+	if (!ctx->cv_full.d_raw && (rc = save_installed(ctx, ctx->cv_full))) return rc;
+	if (!ctx->d_cv_out) HIPCHK(hipMalloc((void **)&ctx->d_cv_out, 4 * sizeof(unsigned long long)));
+	if (fold < 0)
+		rc = install_saved(ctx, ctx->cv_full);
+	else
+		rc = install_derived(ctx, [&](uint8_t *d_out, uint8_t *d_seen) {
+			const size_t n = (size_t)ctx->I * ctx->L, blocks = (n + 255) / 256, cap = (size_t)1 << 20;
+			hipLaunchKernelGGL(k_cv_mask, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, ctx->stream, ctx->cv_full.d_raw,
+					   ctx->d_cv_fold, fold, ctx->I, ctx->L, ctx->ploidy, d_out, d_seen);
+		});
+	if (rc) return rc;
+	ctx->s_cache_slot = -1;
+	ctx->cv_fold = fold;
+	return MCHIP_OK;
+}
+
+int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor, double *sum_log, uint64_t *n_copies, uint64_t *n_floored)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	int rc = cv_check_data(ctx, 1);
+	if (rc) return rc;
+	if ((rc = check_slot(ctx, slot))) return rc;
+	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "cv: the held-out score is the admixture model's%s", nullptr);
+	if (ctx->cv_fold < 0 || !ctx->cv_full.d_raw) return fail(ctx, MCHIP_ERR_STATE, "cv: no fold is held out%s", nullptr);
+	if (!(floor > 0.0 && floor <= 1.0)) return fail(ctx, MCHIP_ERR_INVALID, "cv: floor must be in (0, 1]%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	const cv_geometry g = cv_score_geometry(ctx->I, ctx->L, ctx->K, ctx->max_M, ctx->n_cu);
+	const size_t parts = (size_t)g.n_itiles * g.n_lchunks;
+	if (ctx->cv_part_cap < parts) {
+		dfree(ctx->d_cv_part);
+		ctx->cv_part_cap = 0;
+		HIPCHK(hipMalloc((void **)&ctx->d_cv_part, parts * sizeof(double)));
+		ctx->cv_part_cap = parts;
+	}
+	HIPCHK(hipMemsetAsync(ctx->d_cv_out, 0, 4 * sizeof(unsigned long long), ctx->stream));
+	hipLaunchKernelGGL(k_cv_score, dim3((unsigned)g.n_itiles, (unsigned)g.n_lchunks), dim3((unsigned)g.threads), g.lds, ctx->stream, ctx->I,
+			   ctx->L, ctx->ploidy, ctx->K, cv_ks(ctx->K), g.stage, g.lchunk, ctx->cv_full.d_raw, ctx->d_cv_fold, ctx->cv_fold, ctx->d_toff,
+			   ctx->d_p[slot], ctx->d_q[slot], ctx->qstride, floor, ctx->d_cv_part, ctx->d_cv_out + 1);
+	HIPCHK(hipGetLastError());
+	launch_reduce_sum(ctx, ctx->d_cv_part, (int)parts, reinterpret_cast<double *>(ctx->d_cv_out));
+	HIPCHK(hipGetLastError());
+	unsigned long long h[3];
+	HIPCHK(hipMemcpyAsync(h, ctx->d_cv_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	if (sum_log) memcpy(sum_log, &h[0], sizeof(double));
+	if (n_copies) *n_copies = h[1];
+	if (n_floored) *n_floored = h[2];
+	return MCHIP_OK;
+}
+
 }

@@ -188,48 +188,6 @@ struct mchip_ktable {
 
 const mchip_ktable *mchip_get_ktable(int K);
 
-/* PLINK .bed records on the device (mchip_bed.hip; mchip_set_genotypes_bed).  d_bed: L records of record_bytes bytes, the
- * allocation at least MCHIP_BED_PAD bytes longer than that (records are read as dwords from any byte offset).
- * Locus pass: ua[l] as the STRUCTURE reader counts it, a1[l] = 1 when allele A1 is observed at locus l (the one thing the recoding
- * of a locus depends on), bit 1 of *flags set when any call is missing.  Expand pass: gtA and gtS of the ploidy-2 data set, padded
- * with 0xFF like k_relayout's; seen[i] (zeroed by the caller) = 1 for every individual with an observed call.  Returns non-zero
- * when the data set has too many tiles for one launch. */
-#define MCHIP_BED_PAD 8
-void mchip_bed_locus_pass(hipStream_t s, const uint8_t *d_bed, size_t record_bytes, int I, int L, int32_t *ua, uint8_t *a1, int *flags);
-int mchip_bed_expand(hipStream_t s, const uint8_t *d_bed, size_t record_bytes, int I, int L, const uint8_t *a1, uint8_t *gtA,
-		     uint8_t *gtS, uint8_t *seen);
-
-/* K-fold cross-validation (mchip_cv.hip; mchip_cv_hold_out, mchip_cv_heldout_loglik).  full: the saved data set in upload form
- * [I][L][ploidy]; fold: one byte per genotype [I][L], the allocation MCHIP_CV_PAD bytes longer than that (fold bytes are read
- * eight at a time from any byte offset).
- * Mask: out = full with every copy of the genotypes of fold `fold_id` turned into 0xFF; seen[i] (zeroed by the caller) = 1 for
- * every individual that keeps an observed copy.
- * Score: sum of log max(t, floor) over the observed copies of the fold, one partial per workgroup in part[] (the return value
- * says how many; mchip_cv_score_parts() is the same number, for sizing part[]), counts[0] += copies, counts[1] += floored copies
- * (zeroed by the caller).  P is a slot's [T][K], Q its [I][K] (qstride = K) or [K] (qstride = 0). */
-#define MCHIP_CV_PAD 16
-void mchip_cv_mask(hipStream_t s, const uint8_t *full, const uint8_t *fold, int fold_id, int I, int L, int ploidy, uint8_t *out,
-		   uint8_t *seen);
-int mchip_cv_score_parts(int I, int L, int K, int max_M, int n_cu);
-int mchip_cv_score(hipStream_t s, int I, int L, int ploidy, int K, int max_M, int n_cu, const uint8_t *full, const uint8_t *fold,
-		   int fold_id, const int32_t *toff, const double *P, const double *Q, int qstride, double floor, double *part,
-		   unsigned long long *counts);
-
-/* Mixing proportions of listed individuals against fixed allele frequencies (mchip_query.hip; mchip_fit_q_rows).
- * Gather: out[r][l][a] = genotype byte (rows[r], l, a), from the upload form [I][L][ploidy] (upload_form != 0) or from gtA.
- * Fit: one workgroup per row of geno [n_rows][L][ploidy]; P a slot's [T][K]; Q0 a slot's [I][K] (the row rows[r] is the start)
- * or NULL (1 / K); the four outputs are device arrays ([n_rows][K], [n_rows], [n_rows], [n_rows]). */
-void mchip_query_gather(hipStream_t s, const uint8_t *src, int upload_form, const int32_t *rows, int n_rows, int L, int ploidy, uint8_t *out);
-void mchip_query_fit(hipStream_t s, int n_rows, int L, int ploidy, int K, const uint8_t *geno, const int32_t *toff, const double *P,
-		     const double *Q0, const int32_t *rows, int do_projection, double lb, int max_iter, double abs_error, double rel_error,
-		     double *q_out, double *ll_out, int32_t *iter_out, uint8_t *conv_out);
-
-/* A selection of loci with repeats (mchip_resample.hip; mchip_resample_loci).  base: the saved data set in upload form
- * [I][L_base][ploidy]; src: L2 locus indices, each in [0, L_base) (checked by the caller).  out[i][j][.] = base[i][src[j]][.] in
- * upload form [I][L2][ploidy]; seen[i] (zeroed by the caller) = 1 for every individual that keeps an observed copy. */
-void mchip_resample_gather(hipStream_t s, const uint8_t *base, const int32_t *src, int I, int L_base, int L2, int ploidy, uint8_t *out,
-			   uint8_t *seen);
-
 inline int mchip_ind_waves(int K, int tile_cols)
 {
 	/* (a buffer is rounded up to whole 1 KiB pieces where tiles are copied straight into LDS) */

@@ -1,6 +1,6 @@
 /*
- * mchip_query.hip -- mixing proportions of listed individuals with the allele frequencies held fixed: the kernels behind
- * mchip_fit_q_rows (include/multiclust_hip.h has the contract; mchip.hip has the entry point).  Given P the individuals are
+ * mchip_query.hip -- mixing proportions of listed individuals with the allele frequencies held fixed: mchip_fit_q_rows and
+ * its kernels (include/multiclust_hip.h has the contract; mchip_context.h the per-context state).  Given P the individuals are
  * independent concave problems in K numbers each, so a row is fitted to its own convergence inside one launch.
  *
  *   k_query_gather   a thread per byte: the listed individuals' genotype bytes into a contiguous [n_rows][L][ploidy], read from
@@ -18,9 +18,10 @@
  *                    No floating-point atomics, every sum in an order fixed by (L, ploidy, K): the same state gives the same bits.
  *                    Not yet timed on a device (profiles/query_fit.txt, scripts/query_fit_bench.py).
  */
-#include "mchip_internal.h"
+#include "mchip_context.h"
 #include "mchip_finalize.h"
 
+/* out[r][l][a] = genotype byte (rows[r], l, a), from the upload form [I][L][ploidy] (upload_form != 0) or from gtA */
 __global__ __launch_bounds__(256) void k_query_gather(const uint8_t *__restrict__ src, int upload_form, const int32_t *__restrict__ rows,
 						      int n_rows, int L, int pl, uint8_t *__restrict__ out)
 {
@@ -30,12 +31,6 @@ __global__ __launch_bounds__(256) void k_query_gather(const uint8_t *__restrict_
 		const size_t i = (size_t)rows[r], l = rem / pl, a = rem % pl;
 		out[idx] = upload_form ? src[i * per_row + rem] : src[(((i >> 3) * L + l) * 8 + (i & 7)) * (size_t)pl + a];
 	}
-}
-
-void mchip_query_gather(hipStream_t s, const uint8_t *src, int upload_form, const int32_t *rows, int n_rows, int L, int ploidy, uint8_t *out)
-{
-	const size_t n = (size_t)n_rows * L * ploidy, blocks = (n + 255) / 256, cap = (size_t)1 << 20;
-	hipLaunchKernelGGL(k_query_gather, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, s, src, upload_form, rows, n_rows, L, ploidy, out);
 }
 
 constexpr int FQR_THREADS = 256, FQR_WAVES = FQR_THREADS / 64;
@@ -54,6 +49,8 @@ __device__ __forceinline__ int fqr_wave_sum(int v)
 	return v;
 }
 
+/* one workgroup per row of geno [n_rows][L][ploidy]; P a slot's [T][K]; Q0 a slot's [I][K] (the row rows[r] is the start) or NULL
+ * (1 / K); the four outputs are device arrays ([n_rows][K], [n_rows], [n_rows], [n_rows]) */
 template <int KB>
 __global__ __launch_bounds__(FQR_THREADS) void k_fit_q_rows(int L, int pl, int K, const uint8_t *__restrict__ geno, const int32_t *__restrict__ toff,
 		const double *__restrict__ P, const double *__restrict__ Q0, const int32_t *__restrict__ rows, int do_projection, double lb,
@@ -169,16 +166,73 @@ __global__ __launch_bounds__(FQR_THREADS) void k_fit_q_rows(int L, int pl, int K
 	}
 }
 
-void mchip_query_fit(hipStream_t s, int n_rows, int L, int ploidy, int K, const uint8_t *geno, const int32_t *toff, const double *P,
-		     const double *Q0, const int32_t *rows, int do_projection, double lb, int max_iter, double abs_error, double rel_error,
-		     double *q_out, double *ll_out, int32_t *iter_out, uint8_t *conv_out)
+extern "C" int mchip_fit_q_rows(mchip_context *ctx, int slot, const int32_t *rows, int n_rows, int from_slot, int max_iter, double abs_error,
+		     double rel_error, double *q_rows, double *loglik_rows, int32_t *iter_rows, uint8_t *converged_rows)
 {
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
+	int rc = check_slot(ctx, slot);
+	if (rc) return rc;
+	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixture model has no mixing proportions per individual%s", nullptr);
+	if (!ctx->qstride) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixing proportions are shared by all individuals%s", nullptr);
+	if (!rows || !q_rows || !loglik_rows || !iter_rows || !converged_rows) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
+	if (n_rows < 1 || n_rows > ctx->I) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: n_rows must be in [1, I]%s", nullptr);
+	if (max_iter < 1) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: max_iter must be >= 1%s", nullptr);
+	if (!(abs_error >= 0) || !(rel_error >= 0)) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: an error must be >= 0%s", nullptr);
+	{
+		std::vector<uint8_t> listed((size_t)ctx->I, 0);
+		for (int r = 0; r < n_rows; r++) {
+			if (rows[r] < 0 || rows[r] >= ctx->I) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: a row outside [0, I)%s", nullptr);
+			if (listed[(size_t)rows[r]]) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: a row is listed twice%s", nullptr);
+			listed[(size_t)rows[r]] = 1;
+		}
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	const int L = ctx->L, pl = ctx->ploidy, K = ctx->K;
+	const size_t nr = (size_t)n_rows;
+	scoped_dev<int32_t> d_rows, d_iter;
+	scoped_dev<uint8_t> d_geno, d_conv;
+	scoped_dev<double> d_q, d_ll;
+	HIPCHK(d_rows.alloc(nr));
+	HIPCHK(d_iter.alloc(nr));
+	HIPCHK(d_geno.alloc(nr * L * pl));
+	HIPCHK(d_conv.alloc(nr));
+	HIPCHK(d_q.alloc(nr * K));
+	HIPCHK(d_ll.alloc(nr));
+	HIPCHK(hipMemcpyAsync(d_rows.p, rows, nr * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	/* the full data set: the saved one while a fold is held out of the installed one */
+	const bool saved = ctx->cv_fold >= 0 && ctx->cv_full.d_raw;
+	{
+		const size_t n = nr * L * pl, blocks = (n + 255) / 256, cap = (size_t)1 << 20;
+		hipLaunchKernelGGL(k_query_gather, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, ctx->stream,
+				   saved ? ctx->cv_full.d_raw : ctx->d_gtA, saved ? 1 : 0, d_rows.p, n_rows, L, pl, d_geno.p);
+	}
+	HIPCHK(hipGetLastError());
+	const double *Q0 = from_slot ? ctx->d_q[slot] : nullptr;
 #define FQR_LAUNCH(KB)                                                                                                                   \
-	hipLaunchKernelGGL(k_fit_q_rows<KB>, dim3((unsigned)n_rows), dim3(FQR_THREADS), 0, s, L, ploidy, K, geno, toff, P, Q0, rows, \
-			   do_projection, lb, max_iter, abs_error, rel_error, q_out, ll_out, iter_out, conv_out)
+	hipLaunchKernelGGL(k_fit_q_rows<KB>, dim3((unsigned)n_rows), dim3(FQR_THREADS), 0, ctx->stream, L, pl, K, d_geno.p, ctx->d_toff, \
+			   ctx->d_p[slot], Q0, d_rows.p, ctx->do_projection, ctx->eta_lb, max_iter, abs_error, rel_error, d_q.p, d_ll.p, \
+			   d_iter.p, d_conv.p)
 	if (K <= 8) FQR_LAUNCH(8);
 	else if (K <= 16) FQR_LAUNCH(16);
 	else if (K <= 32) FQR_LAUNCH(32);
 	else FQR_LAUNCH(64);
 #undef FQR_LAUNCH
+	HIPCHK(hipGetLastError());
+	/* (the rows array and the results cross in pageable memory: the copies are done when the stream is) */
+	std::vector<double> h_q(nr * K), h_ll(nr);
+	std::vector<int32_t> h_iter(nr);
+	std::vector<uint8_t> h_conv(nr);
+	HIPCHK(hipMemcpyAsync(h_q.data(), d_q.p, nr * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(h_ll.data(), d_ll.p, nr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(h_iter.data(), d_iter.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(h_conv.data(), d_conv.p, nr, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	/* the caller's arrays are written once everything has succeeded */
+	memcpy(q_rows, h_q.data(), nr * K * sizeof(double));
+	memcpy(loglik_rows, h_ll.data(), nr * sizeof(double));
+	memcpy(iter_rows, h_iter.data(), nr * sizeof(int32_t));
+	memcpy(converged_rows, h_conv.data(), nr);
+	return MCHIP_OK;
 }

@@ -32,7 +32,7 @@ RAND_MAX = rw.RAND_MAX
 
 # ---------------------------------------------------------------------------------------------------------------- DISPATCH RULE
 SIM_QW, SIM_PW = 8, 4        # mchip.hip: widths of the FAST form's threshold rows
-RNG_CHUNK = 4 * 31 * 32      # mchip.hip: draws per thread of the chunked generators
+RNG_CHUNK = 4 * 31 * 32      # mchip_context.h: draws per thread of the chunked generators
 SIM_COPIES = RNG_CHUNK // 2  # copies per thread of k_simulate_admixture
 
 

@@ -36,7 +36,7 @@ IND_WAVES_MAX = 4           # MCHIP_IND_WAVES_MAX
 COL_SPLIT2_ABOVE = 36       # MCHIP_COL_SPLIT2_ABOVE
 FP_TILE = 1024              # mchip_finalize.h
 N_CU = 256
-# the knobs read_knobs() takes (mchip.hip:143-165); every test starts from none of them
+# the knobs read_knobs() takes (mchip.hip); every test starts from none of them
 KNOBS = ("MCHIP_NO_BIAL", "MCHIP_NO_COUNTS", "MCHIP_FORCE_DENSE", "MCHIP_FORCE_SAFE", "MCHIP_NO_GRAPH", "MCHIP_NO_DUAL",
          "MCHIP_NO_SLAB_SUM", "MCHIP_NO_FUSED_FINALIZE", "MCHIP_NO_COL_SPLIT", "MCHIP_PART_NO_TILE", "MCHIP_SIM_NO_TILE",
          "MCHIP_BLOCKS_PER_CU", "MCHIP_BLOCKS_PER_CU_COL", "MCHIP_BLOCKS_PER_CU_IND", "MCHIP_SLAB_FRAC", "MCHIP_NO_CHUNK_ROUNDUP")
@@ -84,7 +84,7 @@ def ind_waves_for(K, tile_cols):     # mchip_ind_waves (mchip_internal.h)
     return 1
 
 
-def lds_sparse(K, max_M):    # ctx->sparse (mchip.hip:1889-1893): two staged tiles of 8 loci fit 64 KiB
+def lds_sparse(K, max_M):    # ctx->sparse (mchip.hip): two staged tiles of 8 loci fit 64 KiB
     return max_M <= SPARSE_MAX_M and (2 * 8 * max_M * kp(K) + qblock(K)) * 8 <= 65536
 
 
@@ -92,13 +92,13 @@ def sparse_edge(K):          # the largest max_M that still takes the sparse pas
     return max(m for m in range(1, SPARSE_MAX_M + 1) if lds_sparse(K, m))
 
 
-def count_bits(ploidy, knobs):       # install_layouts (mchip.hip:1603-1604)
+def count_bits(ploidy, knobs):       # install_layouts (mchip.hip)
     if "MCHIP_NO_COUNTS" in knobs:
         return 0
     return 2 if ploidy <= 3 else (4 if ploidy <= 15 else 0)
 
 
-def finalize_p_loci(K, max_M):       # finalize_p_loci (mchip.hip:1027-1032)
+def finalize_p_loci(K, max_M):       # finalize_p_loci (mchip.hip)
     if max_M > 64 or max_M < 1:
         return 0
     n = FP_TILE // (max_M * K)
@@ -106,7 +106,7 @@ def finalize_p_loci(K, max_M):       # finalize_p_loci (mchip.hip:1027-1032)
 
 
 def flush_blocks(K, ploidy, projection, p_lb):
-    """(safe_rcp, flush_blocks) of set_model_impl (mchip.hip:1924-1945).  The column passes on packed counts take the
+    """(safe_rcp, flush_blocks) of set_model_impl (mchip.hip).  The column passes on packed counts take the
     reciprocal per cell where safe_rcp; the individual-side passes and the dense pair wherever flush_blocks < 1 (launch_sparse:
     `safe = a.flush_blocks < 1`), which a lower bound such as 1e-40 gives without safe_rcp."""
     safe = (not projection) or not (p_lb >= 1e-75)
@@ -119,7 +119,7 @@ def flush_blocks(K, ploidy, projection, p_lb):
 
 
 def geometry(K, I, L, T, ploidy, max_M, admixture, cbits, knobs, n_cu=N_CU):
-    """set_model_impl's launch geometry (mchip.hip:1849-1908): chunks of either pass, waves of the cooperating sparse pass"""
+    """set_model_impl's launch geometry (mchip.hip): chunks of either pass, waves of the cooperating sparse pass"""
     def num(name, dflt):
         v = int(knobs.get(name, "0"))
         return v if v > 0 else dflt
@@ -207,7 +207,7 @@ def reach(case):
     if "MCHIP_FORCE_SAFE" in knobs:
         safe, flush = True, 0
     ind_safe = flush < 1
-    biallelic = min_M == 2 and max_M == 2 and "MCHIP_NO_BIAL" not in knobs      # pass_args (mchip.hip:1397)
+    biallelic = min_M == 2 and max_M == 2 and "MCHIP_NO_BIAL" not in knobs      # pass_args (mchip.hip)
     nomiss = not missing
     out = set()
     if not admixture:
@@ -235,7 +235,7 @@ def reach(case):
     else:
         out.add("k_individual_pass<%d>" % (2 if pl == 2 else 0))
         out.add("k_column_pass<2,false,%s,true>" % B(flush < 1) if pl == 2 else "k_column_pass<0,false,true,true>")
-    # run_estep's finalisers (mchip.hip:2136-2166) and col_slabs / ind_slabs (mchip_kernels_k.hip)
+    # run_estep's finalisers (mchip.hip) and col_slabs / ind_slabs (mchip_kernels_k.hip)
     n_slabs = cdiv(g["n_ichunks"], COL_WAVES) if (sparse and cbits and not split_ok) else g["n_ichunks"]
     s_slabs = cdiv(g["n_lchunks"], g["waves"]) if (sparse and ind_split(K) == 1) else g["n_lchunks"]
     p_loci = finalize_p_loci(K, max_M)
@@ -250,7 +250,7 @@ def reach(case):
             out.add("k_sum_slabs")
         out.add("k_finalize_p_tile" if p_loci else "k_finalize_p")
     if max_M > 64:
-        out.add("byte_flag_projection")          # k_finalize_p / k_project_p with d_flags (mchip.hip:1919-1921)
+        out.add("byte_flag_projection")          # k_finalize_p / k_project_p with d_flags (mchip.hip)
     if n_slabs > 8:
         out.add("col_slabs>8")
     if s_slabs > 8:
@@ -258,7 +258,7 @@ def reach(case):
     if g["xcd_rows"]:
         out.add("xcd_rows")
     if case.get("accel") and admixture and "MCHIP_NO_DUAL" not in knobs and \
-            dual_available(K, sparse, ind_safe, pl, biallelic, g["waves"], max_M):     # mchip.hip:2855
+            dual_available(K, sparse, ind_safe, pl, biallelic, g["waves"], max_M):     # accel_cycle_enqueue (mchip.hip)
         out.add("k_individual_sparse_w<2,true,false,%s,true>" % B(nomiss))
     return out
 

@@ -242,3 +242,62 @@ def test_refusals_and_state(contexts):
     assert bits(ctx.get_genotypes()) == bits(geno[:, src[[4, 4]], :])
     fresh.copy_genotypes(ctx)
     assert resample(fresh, None) == "STATE"                               # a copy is a data set of its own, without a base
+
+
+# ---------------------------------------------------------------- 5. every installer drops both saved sets
+
+INSTALLERS = ["same_shape", "other_shape", "bed", "simulate", "simulate_mixture", "copy"]
+
+
+@pytest.mark.parametrize("installer", INSTALLERS)
+def test_every_installer_drops_the_folds_the_hold_out_and_the_base(installer, contexts):
+    """a selection with a fold held out of it (the base of the selections and the full selection both saved), then a call that
+    installs a data set: no folds, no hold-out and no base afterwards, and the data set is the one a fresh context gets from the
+    same call, one EM step included, bit for bit"""
+    ctx, source, _ = contexts
+    lib = ctx.lib
+    I, L, pl, K = 67, 61, 2, 3
+    ua, geno = su.resample_dataset(I, L, pl, seed=4)
+    src = np.array([5, 5, 0, 60, 17], np.int32)
+    window = ob.glibc_window(11)[0]
+    ctx.set_genotypes(ua, geno)
+    ctx.resample_loci(src)
+    ctx.cv_draw_folds(window, 2)
+    ctx.cv_hold_out(1)
+
+    sel_ua, sel = ua[src], np.ascontiguousarray(geno[:, src, :])
+    sim_q, sim_p = random_params(I, ua, K, seed=2)
+    packed = bf.pack(bf.draw_codes(I, L, missing=0.03, seed=5))
+    source.set_genotypes(ua, geno)
+    install = {
+        "same_shape": lambda c: c.set_genotypes(sel_ua, sel),          # the shape held: set_shape keeps every buffer
+        "other_shape": lambda c: c.set_genotypes(ua, geno),
+        "bed": lambda c: c.set_genotypes_bed(I, packed),
+        "simulate": lambda c: c.simulate_genotypes(I, L, pl, ua, window, K, sim_q, sim_p),
+        "simulate_mixture": lambda c: c.simulate_genotypes_mixture(I, L, pl, ua, window, K, sim_q.mean(axis=0), sim_p),
+        "copy": lambda c: c.copy_genotypes(source),
+    }[installer]
+    fresh = hip.Context(0)
+    try:
+        install(ctx)
+        install(fresh)
+        out = np.empty((ctx.I, ctx.L), np.uint8)
+        assert status_of(lib.mchip_cv_get_folds(ctx.h, out.ctypes.data)) == "STATE"
+        assert status_of(lib.mchip_cv_hold_out(ctx.h, 0)) == "STATE"
+        assert status_of(lib.mchip_resample_loci(ctx.h, None, 0)) == "STATE"
+        assert (ctx.I, ctx.L, ctx.ploidy, ctx.T) == (fresh.I, fresh.L, fresh.ploidy, fresh.T)
+        assert bits(ctx.get_genotypes()) == bits(fresh.get_genotypes())
+        assert ctx.data_counts() == fresh.data_counts()
+        assert ctx.empty_individuals() == fresh.empty_individuals()
+        if installer == "same_shape":
+            assert bits(ctx.get_genotypes()) == bits(sel)
+        q0, p0 = random_params(I, ctx._ua, K, seed=1)
+        for c in (ctx, fresh):
+            c.set_model(K)
+            c.set_q(0, q0)
+            c.set_p(0, p0)
+        a, b = ctx.em_step(0, 0), fresh.em_step(0, 0)
+        assert np.isfinite(b) and bits(np.float64(a)) == bits(np.float64(b)), (installer, a, b)
+        assert bits(ctx.get_q(0)) == bits(fresh.get_q(0)) and bits(ctx.get_p(0)) == bits(fresh.get_p(0)), installer
+    finally:
+        fresh.close()
