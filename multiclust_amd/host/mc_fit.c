@@ -109,6 +109,11 @@ uint64_t mc_draws_per_init(const mc_options *opt, const mc_data *dat, int K)
 	return (uint64_t)dat->I * dat->L * dat->ploidy;
 }
 
+void mc_unit_result_from_model(mc_unit_result *r, int unit, const mc_model *mod)
+{
+	*r = (mc_unit_result){ unit, mod->logL, mod->converged, mod->n_iter, mod->time_stop, mod->iter_stop, mod->pindex, mod->fatal, mod->seconds_run };
+}
+
 int mc_fit_unit(const mc_options *opt, const mc_data *dat, mc_model *mod, unsigned int seed, int unit, mc_unit_result *out)
 {
 	mc_rng rng;
@@ -120,15 +125,7 @@ int mc_fit_unit(const mc_options *opt, const mc_data *dat, mc_model *mod, unsign
 	mod->delta_index = delta_keep;
 	if ((rc = mc_initialize_model(opt, dat, mod, &rng))) return rc;
 	mc_em(opt, dat, mod);
-	out->unit = unit;
-	out->logL = mod->logL;
-	out->converged = mod->converged;
-	out->n_iter = mod->n_iter;
-	out->time_stop = mod->time_stop;
-	out->iter_stop = mod->iter_stop;
-	out->pindex = mod->pindex;
-	out->fatal = mod->fatal;
-	out->seconds_run = mod->seconds_run;
+	mc_unit_result_from_model(out, unit, mod);
 	return 0;
 }
 

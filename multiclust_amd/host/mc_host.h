@@ -203,6 +203,8 @@ void mc_summary_reset(mc_summary *s);						/* multiclust.c:477-486 */
 void mc_summary_add(const mc_options *opt, mc_summary *s, const mc_unit_result *r, int no_parameters, int I);
 /* rand() draws one admixture initialisation consumes (rnd_init.c:460-467: one per allele copy, missing included) */
 uint64_t mc_draws_per_init(const mc_options *opt, const mc_data *dat, int K);
+/* what initialisation `unit` left behind in the model that just ran it */
+void mc_unit_result_from_model(mc_unit_result *r, int unit, const mc_model *mod);
 /* initialisation `unit` of a run seeded with `seed`: jump the stream to unit * draws_per_init, initialise, em() */
 int mc_fit_unit(const mc_options *opt, const mc_data *dat, mc_model *mod, unsigned int seed, int unit, mc_unit_result *out);
 
@@ -218,6 +220,23 @@ typedef struct mc_replicate_result {
  * (free them with mc_model_free when the replicates are done); NULL: models are created and freed inside the call */
 int mc_fit_replicate(const mc_options *opt, const mc_data *dat, int device, const mc_rng *base, int b, int null_K, int alt_K,
 		     int n_init, int mle_K, const double *mle_q, const double *mle_p, mc_replicate_result *out, mc_model **models);
+
+/* ---- refits of a fitted model to data sets derived from its own, from the estimate as a warm start (mc_refit.c): the part
+ * mc_cross_validate and mc_locus_bootstrap below have in common.  `mod` holds the estimate in slot mod->pindex.
+ * mc_refit_begin: the estimate and the host state of the model are kept in *h (on failure nothing is held); where = "file::function"
+ * in front of every stderr line.  mc_refit_check: reports a failed device call `what` under that prefix and hands rc on.
+ * mc_refit_warm_start, once the derived data set is installed: mc_reset_model_state, then q and p (NULL: the estimate's; else the
+ * estimate rearranged for the data set) into slot 0; mc_em follows.  mc_refit_fitted, after mc_em: MCHIP_ERR_HIP on a device failure
+ * (the call ends); *skipped on NaN or a decrease of the log likelihood ("WARNING ... K = <K>, <unit> <index>: the fit stopped on
+ * ...; <then>" is printed and the run goes on).  mc_refit_end, whatever happened and after the
+ * caller has installed the base data set again with status rc_base: the estimate back into its slot (unless rc_base), *mod as
+ * it was but for dev and init_cache, the buffers freed; returns rc, or else what giving back failed with. */
+typedef struct mc_refit { const char *where; mc_model *mod, keep; int nq, np; double *q, *p; } mc_refit;
+int mc_refit_check(const mc_refit *h, int rc, const char *what);
+int mc_refit_begin(mc_refit *h, mc_model *mod, const char *where);
+int mc_refit_warm_start(mc_refit *h, const double *p);
+int mc_refit_fitted(const mc_refit *h, const char *unit, int index, const char *then, int *skipped);
+int mc_refit_end(mc_refit *h, int rc, int rc_base);
 
 /* ---- K-fold cross-validation of a fitted admixture model (mc_cv.c; an extension, the reference has no counterpart) ----
  * `mod` holds the full-data estimate of its K in slot mod->pindex.  The folds are drawn on the device from a fresh stream seeded

@@ -17,6 +17,10 @@
  * rand() position by jump-ahead), with a single RCCL all-reduce of the per-unit result table, after which the serial
  * bookkeeping is replayed in unit order (admixture model, fixed number of initialisations).  Bootstrap replicates (-b) are split
  * over the same workers as whole units for both models; the mixture model's initialisations are not sharded.
+ * Where a post-fit analysis plugs in: the serial and the sharded path differ in who fits which unit and share the rest.  Both keep
+ * the best fit of a K in a fit_record, hand it to new_maximum() when it improved on the K before (H0 estimate, result files, -A) and
+ * end in post_fit(), which puts the record back into a model once and runs --cv, --se, --query; an analysis that refits derived
+ * data sets builds on mc_refit_* (mc_refit.c), adds its line to post_fit()'s text and its refusals to parse_options' refuse().
  */
 #include "mc_cli.h"
 
@@ -106,6 +110,14 @@ static void defaults(mc_cli_options *o)
 }
 
 #define BAD(msg) do { fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '%s'); try -h\n", msg, i < argc ? argv[i] : ""); return MC_EXIT_INVALID_CMD_ARGUMENT; } while (0)
+
+/* "option X cannot be combined with ...": why = NULL when it can */
+static int refuse(const char *option, const char *why)
+{
+	if (!why) return 0;
+	fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '%s'); try -h\n", why, option);
+	return MC_EXIT_INVALID_CMD_ARGUMENT;
+}
 
 static int parse_options(mc_cli_options *o, int argc, const char **argv)
 {
@@ -229,42 +241,28 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			return MC_EXIT_INVALID_CMD_OPTION;
 		}
 	}
-	if (o->cv_folds) {	/* extension: what cross-validation cannot be combined with is a usage error like a bad argument */
-		const char *why = NULL;
-		if (!o->em.admixture) why = "--cv needs the admixture model (-a)";
-		else if (o->n_bootstrap) why = "--cv cannot be combined with the bootstrap (-b)";
-		else if (o->n_gpus > 1) why = "--cv cannot be combined with --gpus above 1";
-		else if (!o->write_files || o->parallel) why = "--cv cannot be combined with -w or -M";
-		if (why) {
-			fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '--cv'); try -h\n", why);
-			return MC_EXIT_INVALID_CMD_ARGUMENT;
-		}
-	}
-	if (o->se_replicates) {	/* extension: the same for the bootstrap over loci (either model) */
-		const char *why = NULL;
-		if (o->n_bootstrap) why = "--se cannot be combined with the bootstrap (-b)";
-		else if (o->n_gpus > 1) why = "--se cannot be combined with --gpus above 1";
-		else if (!o->write_files || o->parallel) why = "--se cannot be combined with -w or -M";
-		if (why) {
-			fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '--se'); try -h\n", why);
-			return MC_EXIT_INVALID_CMD_ARGUMENT;
-		}
-	}
-	if (o->query_file) {	/* extension: the same for query individuals */
-		const char *why = NULL;
-		if (!o->em.admixture) why = "--query needs the admixture model (-a)";
-		else if (o->em.eta_constrained) why = "--query cannot be combined with shared mixing proportions (-c)";
-		else if (o->n_bootstrap) why = "--query cannot be combined with the bootstrap (-b)";
-		else if (!o->write_files || o->parallel) why = "--query cannot be combined with -w or -M";
-		else if (o->afile) why = "--query cannot be combined with a partition to compare with (-A)";
-		else if (o->cv_folds || o->se_replicates) why = "--query cannot be combined with --cv or --se (they share the fold state of the device)";
-		else if (o->em.initialization_procedure == MC_RAND_EM) why = "--query cannot be combined with --randem (its centers are drawn from the genotypes on the host)";
-		else if (o->n_gpus > 1 || o->n_streams > 1) why = "--query cannot be combined with --gpus or --streams above 1";
-		if (why) {
-			fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '--query'); try -h\n", why);
-			return MC_EXIT_INVALID_CMD_ARGUMENT;
-		}
-	}
+	/* extensions: what cross-validation, the bootstrap over loci (either model) and query individuals cannot be combined with is a
+	 * usage error like a bad argument */
+	const int timed = !o->write_files || o->parallel;
+	int rc;
+	if (o->cv_folds && (rc = refuse("--cv",
+			!o->em.admixture ? "--cv needs the admixture model (-a)" :
+			o->n_bootstrap ? "--cv cannot be combined with the bootstrap (-b)" :
+			o->n_gpus > 1 ? "--cv cannot be combined with --gpus above 1" :
+			timed ? "--cv cannot be combined with -w or -M" : NULL))) return rc;
+	if (o->se_replicates && (rc = refuse("--se",
+			o->n_bootstrap ? "--se cannot be combined with the bootstrap (-b)" :
+			o->n_gpus > 1 ? "--se cannot be combined with --gpus above 1" :
+			timed ? "--se cannot be combined with -w or -M" : NULL))) return rc;
+	if (o->query_file && (rc = refuse("--query",
+			!o->em.admixture ? "--query needs the admixture model (-a)" :
+			o->em.eta_constrained ? "--query cannot be combined with shared mixing proportions (-c)" :
+			o->n_bootstrap ? "--query cannot be combined with the bootstrap (-b)" :
+			timed ? "--query cannot be combined with -w or -M" :
+			o->afile ? "--query cannot be combined with a partition to compare with (-A)" :
+			o->cv_folds || o->se_replicates ? "--query cannot be combined with --cv or --se (they share the fold state of the device)" :
+			o->em.initialization_procedure == MC_RAND_EM ? "--query cannot be combined with --randem (its centers are drawn from the genotypes on the host)" :
+			o->n_gpus > 1 || o->n_streams > 1 ? "--query cannot be combined with --gpus or --streams above 1" : NULL))) return rc;
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -285,14 +283,43 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 	return 0;
 }
 
+/* ---- one record of a fit: what the command line keeps of an initialisation once its model has moved on ---- */
+typedef struct fit_record {
+	int K, unit, n_iter, converged;	/* unit: the initialisation, -1 = nothing recorded yet */
+	double logL;
+	double *q, *p, *sik;		/* owned copies of slot pindex and of the expected counts (the layouts of mc_fit_view); NULL when not asked for */
+} fit_record;
+#define FIT_RECORD_NONE { 0, -1, 0, 0, -INFINITY, NULL, NULL, NULL }
+
+static size_t n_q(const mc_cli_options *o, const mc_cli_data *d, int K) { return (o->em.admixture && !o->em.eta_constrained) ? (size_t)d->I * K : (size_t)K; }
+
+/* fills the record from the model that just fitted initialisation `unit`; the parameters only when asked for (a record is used for
+ * one K: its buffers are allocated on first need and written over afterwards) */
+static int record_take(fit_record *r, const mc_cli_options *o, const mc_cli_data *d, mc_model *mod, int unit, int params, int sik)
+{
+	int rc;
+	if (params && !r->q) { r->q = malloc(sizeof(double) * n_q(o, d, mod->K)); r->p = malloc(sizeof(double) * (size_t)mod->K * d->T); }
+	if (sik && !r->sik) r->sik = malloc(sizeof(double) * (size_t)d->I * mod->K);
+	if ((params && (!r->q || !r->p)) || (sik && !r->sik)) return MCHIP_ERR_ALLOC;
+	if (params && ((rc = mc_model_get_q(mod, mod->pindex, r->q)) || (rc = mc_model_get_p(mod, mod->pindex, r->p)))) return rc;
+	if (sik && (rc = mc_model_get_expected_counts(mod, r->sik))) return rc;
+	r->K = mod->K; r->unit = unit; r->logL = mod->logL; r->n_iter = mod->n_iter; r->converged = mod->converged;
+	return 0;
+}
+
+static void record_free(fit_record *r)
+{
+	free(r->q); free(r->p); free(r->sik);
+	*r = (fit_record)FIT_RECORD_NONE;
+}
+
 /* ---- state across initialisations / models (reference struct _model, multiclust.h:337-360) ---- */
 typedef struct run_state {
 	mc_summary sum;
 	double max_logL_H0, ts_obs, ts_bs;
 	int n_targetll_times, n_targetll_init, time_stop;
 	int aic_K, bic_K, null_K, alt_K;
-	double *mle_q, *mle_p;		/* H0 MLEs for the bootstrap (multiclust.c:562-581) */
-	int mle_K;
+	fit_record h0;			/* H0 MLEs for the bootstrap (multiclust.c:562-581): K, q, p */
 	mc_rng rng;
 	FILE *out;			/* stdout, or a replicate's buffer when bootstrap replicates run on several devices */
 	mchip_comm **comm;		/* the run's RCCL communicator over devices device..device+n_gpus-1, created on first use */
@@ -302,16 +329,8 @@ typedef struct run_state {
 	 * was partitioned (dat->I_K) and the adjusted Rand index of the two (model::arand: never reset, as in the reference) */
 	int *partition_from_file, pK, *I_K;
 	double arand;
-	/* --cv: the cross-validation of the K just fitted, printed by estimate_model behind the K's summary line */
-	mc_cv_result cv;
-	int cv_done;
-	/* --se: the same for the bootstrap over loci */
-	mc_se_result se;
-	int se_done;
-	/* --query: which individuals are query individuals, and the query fit of the K just fitted */
-	uint8_t *query_mask;
-	mc_query_result query;
-	int query_done;
+	uint8_t *query_mask;		/* --query: which individuals are query individuals */
+	char *post_lines;		/* what post_fit has to say about the K just fitted: estimate_model prints it behind the K's summary line */
 } run_state;
 
 /* sharded runs use n_gpus * n_streams workers (host thread + context + stream each); worker x sits on device
@@ -381,7 +400,6 @@ static void print_model_state(const mc_cli_options *o, const mc_cli_data *d, con
 	}
 }
 
-/* maximize_likelihood (multiclust.c:471-656) for one K */
 /* initialize_model (rnd_init.c:54-89).  With -P and -Q the admixture model starts from the parameters in those files instead
  * of a random partition (rnd_init.c:74-76): read_qfile (read_file.c:880-922: I*K numbers in i, k order, or K with -c) and
  * read_pfile (924-959: "assumes biallelic locus": L*K numbers p[k][l][0] in l, k order, p[k][l][1] = 1 - p[k][l][0], any further
@@ -420,94 +438,127 @@ static int cli_initialize(const mc_cli_options *o, const mc_cli_data *d, const m
 	return rc;
 }
 
-/* --cv: F-fold cross-validation of the best fit of one K, whose parameters q, p the caller holds.  mod: the model that fitted
- * it (its slots are free again), or NULL: a model is created on `device` for the purpose (the workers of a sharded fit are gone by
- * the time the best unit is known). */
-static int cli_cross_validate(const mc_cli_options *o, const mc_data *md, run_state *st, mc_model *mod, int K, int device, const double *q,
-			      const double *p, double logL, int n_iter, int converged)
+/* the per-initialisation stdout line (multiclust.c:618-627) */
+static void print_unit_line(const mc_cli_options *o, const run_state *st, int K, const mc_unit_result *r, int bootstrap)
 {
-	mc_model *own = NULL;
+	if (bootstrap || o->em.verbosity <= MC_QUIET || !o->write_files) return;
+	fprintf(st->out, "K = %d, initialization = %d: %f (%s) in %3d iterations, %02d:%02d:%02d (%f; %d), seed: %u\n", K, r->unit, r->logL,
+	       r->converged ? "converged" : "not converged", r->n_iter, (int)(r->seconds_run / 3600),
+	       (int)((((int)r->seconds_run) % 3600) / 60), ((int)r->seconds_run) % 60, st->sum.max_logL, st->sum.n_maxll_times, o->em.seed);
+}
+
+/* what new_maximum() below reads of the fit: the parameters (and the expected counts, which only the partition needs) */
+static int max_wants_partition(const mc_cli_options *o, int bootstrap) { return (!bootstrap && o->write_files) || (o->afile && !o->write_files); }
+static int max_wants_params(const mc_cli_options *o, const run_state *st, int K, int bootstrap)
+{
+	return (!bootstrap && o->n_bootstrap && K == st->null_K) || max_wants_partition(o, bootstrap);
+}
+
+/* A fit improved on the maximum so far (st->sum holds it already): the serial loop comes here at every improvement, the sharded
+ * path once per K for its best unit, the last improvement of the serial loop */
+static int new_maximum(const mc_cli_options *o, const mc_cli_data *d, run_state *st, const fit_record *fit, int bootstrap)
+{
+	const int K = fit->K;
 	int rc = 0;
-	mchip_progress_note("cross-validation");
+	if (!bootstrap && o->n_bootstrap && K == st->null_K) {	/* multiclust.c:562-581 */
+		const size_t nq = n_q(o, d, K), np = (size_t)K * d->T;
+		record_free(&st->h0);
+		st->h0 = *fit;			/* a copy of its own: the caller's record moves on */
+		st->h0.sik = NULL;
+		st->h0.q = malloc(sizeof(double) * nq);
+		st->h0.p = malloc(sizeof(double) * np);
+		if (!st->h0.q || !st->h0.p) return MCHIP_ERR_ALLOC;
+		memcpy(st->h0.q, fit->q, sizeof(double) * nq);
+		memcpy(st->h0.p, fit->p, sizeof(double) * np);
+	}
+	if (max_wants_partition(o, bootstrap)) {	/* multiclust.c:584-600; nothing is written with -w, but -A wants the partition */
+		const mc_fit_view fv = { K, fit->converged, fit->logL, st->sum.aic, st->sum.bic, fit->q, fit->p, fit->sik };
+		int *count_K = malloc(sizeof(int) * (size_t)K);
+		if (!count_K) return MCHIP_ERR_ALLOC;
+		mc_partition(d, &fv, st->I_K, count_K);
+		if (o->write_files) rc = mc_write_results(o, d, &fv, count_K);
+		free(count_K);
+	}
+	if (!rc && o->afile) {		/* multiclust.c:602-612 */
+		/* (a bootstrap fit with result files on is not partitioned in the reference: dat->I_K is then the partition
+		 * of an earlier fit, possibly with a cluster index this K does not have -- it indexes past its table there;
+		 * the index is left as it was here) */
+		int fits = 1;
+		for (int x = 0; x < d->I; x++) if (st->I_K[x] >= K) fits = 0;
+		if (fits) st->arand = mc_adjusted_rand(d->I, st->pK, K, st->partition_from_file, st->I_K);
+	}
+	return rc;
+}
+
+/* ---- the post-fit stage: --cv, --se and --query, in that order, on the best fit of one K ----
+ * fit: that fit, with its parameters.  mod: the model that fitted it (its slots are free again; --query needs this one: the
+ * hold-out that hides the query individuals is in force on its context), or NULL: a model is created on `device` for the purpose
+ * (the workers of a sharded fit are gone by the time the best unit is known).  The fit goes back into the model once: every
+ * analysis leaves slot pindex and the host state of the model as it found them (mc_host.h).  Each analysis writes its file
+ * (result files on) and adds its stdout line to st->post_lines. */
+static int wants_post_fit(const mc_cli_options *o, int bootstrap) { return (o->cv_folds || o->se_replicates || o->query_file) && !bootstrap; }
+
+static int post_fit(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, const fit_record *fit, mc_model *mod, int device)
+{
+	const int K = fit->K;
+	mc_model *own = NULL;
+	size_t len = 0;
+	int rc;
 	if (!mod) {
 		if ((rc = mc_model_create(&own, &o->em, md, K, device))) return rc;
 		mod = own;
 	}
+	FILE *say = open_memstream(&st->post_lines, &len);
+	if (!say) { mc_model_free(own); return MCHIP_ERR_ALLOC; }
 	mc_reset_model_state(mod);
-	if (!(rc = mc_model_set_q(mod, mod->pindex, q)) && !(rc = mc_model_set_p(mod, mod->pindex, p))) {
-		mod->logL = logL;
-		mod->n_iter = n_iter;
-		mod->converged = converged;
-		rc = mc_cross_validate(&o->em, md, mod, o->cv_folds, o->cv_floor, &st->cv);
-		if (!rc) st->cv_done = 1;
+	if (!(rc = mc_model_set_q(mod, mod->pindex, fit->q))) rc = mc_model_set_p(mod, mod->pindex, fit->p);
+	mod->logL = fit->logL; mod->n_iter = fit->n_iter; mod->converged = fit->converged;
+	if (!rc && o->cv_folds) {
+		mc_cv_result cv;
+		mchip_progress_note("cross-validation");
+		if (!(rc = mc_cross_validate(&o->em, md, mod, o->cv_folds, o->cv_floor, &cv)))
+			fprintf(say, "CV error (K=%d, %d folds): %.10f  [%llu held-out copies, %llu floored]\n", K, o->cv_folds, cv.cv,
+				(unsigned long long)cv.n_copies, (unsigned long long)cv.n_floored);
 	}
+	if (!rc && o->se_replicates) {	/* with result files on: <stem>.<admix|mix>.K=<K>.se.txt */
+		const size_t nq = n_q(o, d, K);
+		double *mean = malloc(sizeof(double) * nq), *se = malloc(sizeof(double) * nq);
+		int32_t *count = malloc(sizeof(int32_t) * nq);
+		mc_se_result res;
+		mchip_progress_note("bootstrap over loci");
+		rc = (mean && se && count) ? mc_locus_bootstrap(&o->em, md, mod, o->se_replicates, o->se_block, mean, se, count, &res) : MCHIP_ERR_ALLOC;
+		if (!rc) fprintf(say, "Bootstrap SE (K=%d, %d replicates, block %d): mean %.10f  max %.10f  [%d failed]\n", K, res.n_replicates,
+				 res.block, res.mean_se, res.max_se, res.n_failed);
+		if (!rc && o->write_files) rc = mc_write_se(o, d, K, fit->q, mean, se, count);
+		free(mean); free(se); free(count);
+	}
+	if (!rc && o->query_file) {	/* with result files on: <stem>.admix.K=<K>.query.txt */
+		mc_query_result res;
+		memset(&res, 0, sizeof res);
+		mchip_progress_note("query fit");
+		if (!(rc = mc_query_fit(&o->em, md, mod, st->query_mask, &res)))
+			fprintf(say, "Query fit (K=%d): %d individuals, %d converged, %d failed, at most %d iterations, log likelihood %.6f\n", K,
+				res.n, res.n_converged, res.n_failed, res.max_iter, res.sum_logL);
+		if (!rc && o->write_files) rc = mc_write_query(o, K, res.n, res.rows, res.iter, res.converged, res.logL, res.q);
+		mc_query_result_free(&res);
+	}
+	fclose(say);
 	mc_model_free(own);
 	return rc;
 }
 
-/* --se: bootstrap standard errors of the mixing proportions of the best fit of one K, under the same arrangement; with result
- * files on they go to <stem>.<admix|mix>.K=<K>.se.txt */
-static int cli_locus_bootstrap(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, mc_model *mod, int K, int device,
-			       const double *q, const double *p, double logL, int n_iter, int converged)
-{
-	const size_t nq = (o->em.admixture && !o->em.eta_constrained) ? (size_t)d->I * K : (size_t)K;
-	mc_model *own = NULL;
-	double *mean = malloc(sizeof(double) * nq), *se = malloc(sizeof(double) * nq);
-	int32_t *count = malloc(sizeof(int32_t) * nq);
-	int rc = (mean && se && count) ? 0 : MCHIP_ERR_ALLOC;
-	mchip_progress_note("bootstrap over loci");
-	if (!rc && !mod) {
-		if (!(rc = mc_model_create(&own, &o->em, md, K, device))) mod = own;
-	}
-	if (!rc) {
-		mc_reset_model_state(mod);
-		if (!(rc = mc_model_set_q(mod, mod->pindex, q)) && !(rc = mc_model_set_p(mod, mod->pindex, p))) {
-			mod->logL = logL;
-			mod->n_iter = n_iter;
-			mod->converged = converged;
-			rc = mc_locus_bootstrap(&o->em, md, mod, o->se_replicates, o->se_block, mean, se, count, &st->se);
-			if (!rc) st->se_done = 1;
-			if (!rc && o->write_files) rc = mc_write_se(o, d, K, q, mean, se, count);
-		}
-	}
-	mc_model_free(own);
-	free(mean); free(se); free(count);
-	return rc;
-}
-
-/* --query: the query individuals against the best fit of one K, under the same arrangement (`mod` is the model that fitted it: the
- * hold-out that hides them is in force on its context); with result files on they go to <stem>.admix.K=<K>.query.txt */
-static int cli_query_fit(const mc_cli_options *o, const mc_data *md, run_state *st, mc_model *mod, int K, const double *q, const double *p,
-			 double logL, int n_iter, int converged)
-{
-	int rc;
-	mchip_progress_note("query fit");
-	mc_reset_model_state(mod);
-	if ((rc = mc_model_set_q(mod, mod->pindex, q)) || (rc = mc_model_set_p(mod, mod->pindex, p))) return rc;
-	mod->logL = logL;
-	mod->n_iter = n_iter;
-	mod->converged = converged;
-	mc_query_result_free(&st->query);
-	if ((rc = mc_query_fit(&o->em, md, mod, st->query_mask, &st->query))) return rc;
-	st->query_done = 1;
-	if (o->write_files)
-		rc = mc_write_query(o, K, st->query.n, st->query.rows, st->query.iter, st->query.converged, st->query.logL, st->query.q);
-	return rc;
-}
-
+/* maximize_likelihood (multiclust.c:471-656) for one K */
 static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, mc_model *mod, run_state *st, int bootstrap)
 {
-	const int K = mod->K, nq = (o->em.admixture && !o->em.eta_constrained) ? d->I * K : K;
-	const int npar = mc_no_parameters(&o->em, md, K);
+	const int K = mod->K, npar = mc_no_parameters(&o->em, md, K);
 	/* estimate_model resets the maximum per call, not per K (multiclust.c:377), and nothing resets AIC / BIC: a K whose fits do
 	 * not beat the previous K's maximum reports that K's figures (and writes no files) */
 	const double max_logL_keep = st->sum.max_logL, aic_keep = st->sum.aic, bic_keep = st->sum.bic;
-	double *q = NULL, *p = NULL, *sik = NULL;
-	int *count_K = NULL, rc = 0;
-	/* --cv: the best fit of THIS K (the files above follow the maximum over the K so far) */
-	const int cv = (o->cv_folds || o->se_replicates || o->query_file) && !bootstrap;	/* (--se and --query keep the same fit) */
-	double *cv_q = NULL, *cv_p = NULL, cv_logL = -INFINITY;
-	int cv_iter = 0, cv_conv = 0;
+	/* the best fit of THIS K: what the post-fit stage sees.  The files follow the maximum over the K so far, and a fit that
+	 * improves on that maximum is the best of this K too, so new_maximum() reads the same record */
+	const int post = wants_post_fit(o, bootstrap), max_params = max_wants_params(o, st, K, bootstrap);
+	fit_record best = FIT_RECORD_NONE;
+	int rc = 0;
 	mc_summary_reset(&st->sum);
 	st->sum.max_logL = max_logL_keep;
 	if (max_logL_keep > -INFINITY) { st->sum.aic = aic_keep; st->sum.bic = bic_keep; }
@@ -517,6 +568,7 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 	const clock_t start = mod->start;
 	for (int i = 0; o->target_revisit || o->target_ll || o->em.n_seconds || i < o->n_init; i++) {
 		const int delta_keep = mod->delta_index;
+		mc_unit_result r;
 		mc_reset_model_state(mod);
 		mod->delta_index = delta_keep;
 		mod->start = start;			/* the time limit spans all initialisations (multiclust.c:488) */
@@ -527,55 +579,15 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 		mchip_progress_note("maximize_likelihood: bookkeeping and result files");
 		if (mod->fatal == MC_FATAL_DEVICE) { rc = MCHIP_ERR_HIP; goto DONE; }
 		if (mod->fatal) exit(0);		/* the reference's reaction to NaN / decreasing logL (em_alg.c:106-120) */
-		mc_unit_result r = { i, mod->logL, mod->converged, mod->n_iter, mod->time_stop, mod->iter_stop, mod->pindex, 0, mod->seconds_run };
-		const double prev_max = st->sum.max_logL;
+		mc_unit_result_from_model(&r, i, mod);
+		const int new_max = mod->logL > st->sum.max_logL;
 		mc_summary_add(&o->em, &st->sum, &r, npar, d->I);
-		if (cv && mod->logL > cv_logL) {
-			if (!cv_q) { cv_q = malloc(sizeof(double) * (size_t)nq); cv_p = malloc(sizeof(double) * (size_t)K * d->T); }
-			if (!cv_q || !cv_p) { rc = MCHIP_ERR_ALLOC; goto DONE; }
-			if ((rc = mc_model_get_q(mod, mod->pindex, cv_q)) || (rc = mc_model_get_p(mod, mod->pindex, cv_p))) goto DONE;
-			cv_logL = mod->logL; cv_iter = mod->n_iter; cv_conv = mod->converged;
+		if (mod->logL > best.logL) {
+			const int params = post || (new_max && max_params);
+			if ((rc = record_take(&best, o, d, mod, i, params, new_max && max_wants_partition(o, bootstrap)))) goto DONE;
 		}
-		if (mod->logL > prev_max) {
-			const int keep_mle = !bootstrap && o->n_bootstrap && K == st->null_K;
-			const int part_only = o->afile && !o->write_files;	/* nothing is written, but -A wants the partition */
-			if (keep_mle || (!bootstrap && o->write_files) || part_only) {
-				if (!q) { q = malloc(sizeof(double) * (size_t)nq); p = malloc(sizeof(double) * (size_t)K * d->T);
-					  sik = malloc(sizeof(double) * (size_t)d->I * K); count_K = malloc(sizeof(int) * (size_t)K); }
-				if (!q || !p || !sik || !count_K) { rc = MCHIP_ERR_ALLOC; goto DONE; }
-				if ((rc = mc_model_get_q(mod, mod->pindex, q)) || (rc = mc_model_get_p(mod, mod->pindex, p)) ||
-				    (rc = mc_model_get_expected_counts(mod, sik))) goto DONE;
-			}
-			if (keep_mle) {		/* multiclust.c:562-581 */
-				free(st->mle_q); free(st->mle_p);
-				st->mle_q = malloc(sizeof(double) * (size_t)nq); st->mle_p = malloc(sizeof(double) * (size_t)K * d->T);
-				memcpy(st->mle_q, q, sizeof(double) * (size_t)nq);
-				memcpy(st->mle_p, p, sizeof(double) * (size_t)K * d->T);
-				st->mle_K = K;
-			}
-			if (!bootstrap && o->write_files) {	/* multiclust.c:584-600 */
-				mc_fit_view fv = { K, mod->converged, mod->logL, st->sum.aic, st->sum.bic, q, p, sik };
-				mc_partition(d, &fv, st->I_K, count_K);
-				if ((rc = mc_write_results(o, d, &fv, count_K))) goto DONE;
-			}
-			if (o->afile) {		/* multiclust.c:602-612 */
-				if (part_only) {
-					mc_fit_view fv = { K, mod->converged, mod->logL, st->sum.aic, st->sum.bic, q, p, sik };
-					mc_partition(d, &fv, st->I_K, count_K);
-				}
-				/* (a bootstrap fit with result files on is not partitioned in the reference: dat->I_K is then the partition
-				 * of an earlier fit, possibly with a cluster index this K does not have -- it indexes past its table there;
-				 * the index is left as it was here) */
-				int fits = 1;
-				for (int x = 0; x < d->I; x++) if (st->I_K[x] >= K) fits = 0;
-				if (fits) st->arand = mc_adjusted_rand(d->I, st->pK, K, st->partition_from_file, st->I_K);
-			}
-		}
-		if (!bootstrap && o->em.verbosity > MC_QUIET && o->write_files)	/* multiclust.c:618-627 */
-			fprintf(st->out, "K = %d, initialization = %d: %f (%s) in %3d iterations, %02d:%02d:%02d (%f; %d), seed: %u\n", K, i, mod->logL,
-			       mod->converged ? "converged" : "not converged", mod->n_iter, (int)(mod->seconds_run / 3600),
-			       (int)((((int)mod->seconds_run) % 3600) / 60), ((int)mod->seconds_run) % 60, st->sum.max_logL,
-			       st->sum.n_maxll_times, o->em.seed);
+		if (new_max && (rc = new_maximum(o, d, st, &best, bootstrap))) goto DONE;
+		print_unit_line(o, st, K, &r, bootstrap);
 		if (K == 1) break;
 		if (mod->time_stop) { st->time_stop = 1; break; }
 		if (o->target_revisit && st->sum.n_maxll_times >= o->target_revisit) break;
@@ -588,14 +600,11 @@ static int maximize_likelihood(const mc_cli_options *o, const mc_cli_data *d, co
 			}
 		}
 	}
-	if (cv && cv_q && o->cv_folds) rc = cli_cross_validate(o, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
-	if (!rc && cv && cv_q && o->se_replicates) rc = cli_locus_bootstrap(o, d, md, st, mod, K, o->device, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
-	if (!rc && cv && cv_q && o->query_file) rc = cli_query_fit(o, md, st, mod, K, cv_q, cv_p, cv_logL, cv_iter, cv_conv);
+	if (post && best.q) rc = post_fit(o, d, md, st, &best, mod, o->device);
 DONE:
-	free(q); free(p); free(sik); free(count_K); free(cv_q); free(cv_p);
+	record_free(&best);
 	return rc;
 }
-
 
 /* ---- initialisations sharded over several GPUs of the node ---- */
 typedef struct shard_worker {
@@ -607,18 +616,15 @@ typedef struct shard_worker {
 	const mc_rng *starts;		/* [n_units + 1]: the serial stream's state at the start of every unit (and after the last) */
 	uint64_t draws;
 	mc_unit_result *res;		/* [n_units], shared: worker d writes rows u = d, d + n_dev, ... */
-	double best_logL;
-	int best_unit, rc;
-	double *q, *p, *sik;		/* parameters of this worker's best unit */
+	int rc;
+	fit_record best;		/* this worker's best unit, with its parameters when want_params */
 } shard_worker;
 
 static void *shard_main(void *arg)
 {
 	shard_worker *w = arg;
-	const int nq = (w->o->em.admixture && !w->o->em.eta_constrained) ? w->d->I * w->K : w->K;
 	mc_model *mod = NULL;
-	w->best_logL = -INFINITY;
-	w->best_unit = -1;
+	w->best = (fit_record)FIT_RECORD_NONE;
 	const int device = worker_device(w->o, w->index);
 	if ((w->rc = w->sim ? mc_model_create_simulated(&mod, &w->o->em, w->md, w->K, device, w->sim)
 			    : mc_model_create(&mod, &w->o->em, w->md, w->K, device))) return NULL;
@@ -631,42 +637,42 @@ static void *shard_main(void *arg)
 		if ((w->rc = mc_initialize_model(&w->o->em, w->md, mod, &rng))) break;
 		mc_em(&w->o->em, w->md, mod);
 		if (mod->fatal == MC_FATAL_DEVICE) { w->rc = MCHIP_ERR_HIP; break; }
-		mc_unit_result *r = &w->res[u];
-		r->unit = u; r->logL = mod->logL; r->converged = mod->converged; r->n_iter = mod->n_iter;
-		r->time_stop = mod->time_stop; r->iter_stop = mod->iter_stop; r->pindex = mod->pindex; r->fatal = mod->fatal;
-		r->seconds_run = mod->seconds_run;
+		mc_unit_result_from_model(&w->res[u], u, mod);
 		if (mod->fatal) break;
-		if (w->want_params && mod->logL > w->best_logL) {	/* strict: the earliest of equal units wins, as in the serial loop */
-			if (!w->q) { w->q = malloc(sizeof(double) * (size_t)nq); w->p = malloc(sizeof(double) * (size_t)w->K * w->d->T);
-				     w->sik = malloc(sizeof(double) * (size_t)w->d->I * w->K); }
-			if (!w->q || !w->p || !w->sik) { w->rc = MCHIP_ERR_ALLOC; break; }
-			if ((w->rc = mc_model_get_q(mod, mod->pindex, w->q)) || (w->rc = mc_model_get_p(mod, mod->pindex, w->p)) ||
-			    (w->rc = mc_model_get_expected_counts(mod, w->sik))) break;
-			w->best_logL = mod->logL;
-			w->best_unit = u;
-		}
+		/* strict: the earliest of equal units wins, as in the serial loop */
+		if (w->want_params && mod->logL > w->best.logL && (w->rc = record_take(&w->best, w->o, w->d, mod, u, 1, 1))) break;
 	}
 	mc_model_free(mod);
 	return NULL;
 }
 
+/* a unit's result as a row of the exchange table: the last field counts how often the unit was fitted */
 #define RES_FIELDS 9
+static void pack_result(double *row, const mc_unit_result *r)
+{
+	row[0] = r->logL; row[1] = r->converged; row[2] = r->n_iter; row[3] = r->time_stop;
+	row[4] = r->iter_stop; row[5] = r->pindex; row[6] = r->fatal; row[7] = r->seconds_run; row[8] = 1.0;
+}
+static void unpack_result(const double *row, int unit, mc_unit_result *r)
+{
+	*r = (mc_unit_result){ unit, row[0], (int)row[1], (int)row[2], (int)row[3], (int)row[4], (int)row[5], (int)row[6], row[7] };
+}
+
 static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, int K, run_state *st, int bootstrap,
 				       const mc_simulation *sim)
 {
 	const int n_dev = n_workers(o), n_gpus = o->n_gpus < 1 ? 1 : o->n_gpus, n_units = (K == 1) ? 1 : o->n_init;
-	const int nq = (o->em.admixture && !o->em.eta_constrained) ? d->I * K : K;
 	const int npar = mc_no_parameters(&o->em, md, K);
-	const int keep_mle = !bootstrap && o->n_bootstrap && K == st->null_K;
+	const int want_params = (!bootstrap && (o->write_files || o->cv_folds || o->se_replicates || (o->n_bootstrap && K == st->null_K))) || o->afile != NULL;
 	const double max_logL_keep = st->sum.max_logL, aic_keep = st->sum.aic, bic_keep = st->sum.bic;
 	shard_worker *w = calloc((size_t)n_dev, sizeof *w);
 	pthread_t *th = calloc((size_t)n_dev, sizeof *th);
 	int *joinable = calloc((size_t)n_dev, sizeof *joinable);	/* (a pthread_t has no "none" value) */
 	mc_unit_result *res = calloc((size_t)n_units, sizeof *res);
 	double **tab = calloc((size_t)n_gpus, sizeof *tab);
-	int *count_K = calloc((size_t)K, sizeof *count_K), rc = 0;
+	int rc = 0;
 	mc_rng *starts = calloc((size_t)n_units + 1, sizeof *starts);
-	if (!w || !th || !joinable || !res || !tab || !count_K || !starts) { rc = MCHIP_ERR_ALLOC; goto DONE; }
+	if (!w || !th || !joinable || !res || !tab || !starts) { rc = MCHIP_ERR_ALLOC; goto DONE; }
 	{	/* where each unit starts in the rand() stream: one walk (a jump per unit for the random allele partition, the host-side
 		 * replay of the center draws for Rand-EM), instead of every worker replaying the units before its own */
 		mc_model walker;
@@ -678,7 +684,7 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 	}
 	for (int x = 0; x < n_dev; x++) {
 		w[x].o = o; w[x].d = d; w[x].md = md; w[x].K = K; w[x].index = x; w[x].n_dev = n_dev; w[x].n_units = n_units;
-		w[x].want_params = keep_mle || (!bootstrap && o->write_files) || o->afile != NULL || ((o->cv_folds || o->se_replicates) && !bootstrap);
+		w[x].want_params = want_params;
 		w[x].sim = sim;
 		w[x].starts = starts; w[x].draws = mc_draws_per_init(&o->em, md, K); w[x].res = res;
 		if (pthread_create(&th[x], NULL, shard_main, &w[x])) shard_main(&w[x]);	/* no thread to be had: in this one */
@@ -693,11 +699,7 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 	 * completes them all */
 	for (int g = 0; g < n_gpus; g++)
 		if (!(tab[g] = calloc((size_t)n_units * RES_FIELDS, sizeof(double)))) { rc = MCHIP_ERR_ALLOC; goto DONE; }
-	for (int u = 0; u < n_units; u++) {
-		double *row = tab[(u % n_dev) % n_gpus] + (size_t)u * RES_FIELDS;
-		row[0] = res[u].logL; row[1] = res[u].converged; row[2] = res[u].n_iter; row[3] = res[u].time_stop;
-		row[4] = res[u].iter_stop; row[5] = res[u].pindex; row[6] = res[u].fatal; row[7] = res[u].seconds_run; row[8] = 1.0;
-	}
+	for (int u = 0; u < n_units; u++) pack_result(tab[(u % n_dev) % n_gpus] + (size_t)u * RES_FIELDS, &res[u]);
 	if (exchange_needed(o) && (rc = exchange_table(o, st, tab, n_units * RES_FIELDS, "per-initialisation results"))) goto DONE;
 	for (int x = 1; x < n_gpus; x++)
 		if (memcmp(tab[0], tab[x], sizeof(double) * (size_t)n_units * RES_FIELDS)) { fprintf(stderr, "ERROR [mc_main.c]: devices disagree after the all-reduce\n"); rc = MCHIP_ERR_STATE; goto DONE; }
@@ -707,58 +709,28 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 	st->sum.max_logL = max_logL_keep;
 	if (max_logL_keep > -INFINITY) { st->sum.aic = aic_keep; st->sum.bic = bic_keep; }	/* as in maximize_likelihood above */
 	st->time_stop = 0;
+	int ub = 0;		/* the best unit of this K; where it improved on the maximum so far, st->sum.best_unit as well */
 	for (int u = 0; u < n_units; u++) {
 		const double *row = tab[0] + (size_t)u * RES_FIELDS;
+		mc_unit_result r;
 		if (row[8] != 1.0) { fprintf(stderr, "ERROR [mc_main.c]: unit %d was fitted %g times\n", u, row[8]); rc = MCHIP_ERR_STATE; goto DONE; }
-		if ((int)row[6]) exit(0);		/* NaN / decreasing logL: the reference's reaction (em_alg.c:106-120) */
-		mc_unit_result r = { u, row[0], (int)row[1], (int)row[2], (int)row[3], (int)row[4], (int)row[5], 0, row[7] };
+		unpack_result(row, u, &r);
+		if (r.fatal) exit(0);		/* NaN / decreasing logL: the reference's reaction (em_alg.c:106-120) */
 		mc_summary_add(&o->em, &st->sum, &r, npar, d->I);
-		if (!bootstrap && o->em.verbosity > MC_QUIET && o->write_files)
-			fprintf(st->out, "K = %d, initialization = %d: %f (%s) in %3d iterations, %02d:%02d:%02d (%f; %d), seed: %u\n", K, u, r.logL,
-			       r.converged ? "converged" : "not converged", r.n_iter, (int)(r.seconds_run / 3600),
-			       (int)((((int)r.seconds_run) % 3600) / 60), ((int)r.seconds_run) % 60, st->sum.max_logL, st->sum.n_maxll_times, o->em.seed);
+		print_unit_line(o, st, K, &r, bootstrap);
+		if (r.logL > res[ub].logL) ub = u;
 	}
-	/* the winner's parameters live on the device that fitted it */
-	if (st->sum.best_unit >= 0 && (keep_mle || (!bootstrap && o->write_files) || o->afile)) {
-		const shard_worker *own = &w[st->sum.best_unit % n_dev];
-		if (own->best_unit != st->sum.best_unit) { fprintf(stderr, "ERROR [mc_main.c]: owner of the best unit does not hold it\n"); rc = MCHIP_ERR_STATE; goto DONE; }
-		if (keep_mle) {
-			free(st->mle_q); free(st->mle_p);
-			st->mle_q = malloc(sizeof(double) * (size_t)nq); st->mle_p = malloc(sizeof(double) * (size_t)K * d->T);
-			memcpy(st->mle_q, own->q, sizeof(double) * (size_t)nq);
-			memcpy(st->mle_p, own->p, sizeof(double) * (size_t)K * d->T);
-			st->mle_K = K;
-		}
-		if (!bootstrap && o->write_files) {
-			mc_fit_view fv = { K, res[st->sum.best_unit].converged, st->sum.max_logL, st->sum.aic, st->sum.bic, own->q, own->p, own->sik };
-			mc_partition(d, &fv, st->I_K, count_K);
-			rc = mc_write_results(o, d, &fv, count_K);
-		}
-		if (!rc && o->afile) {	/* multiclust.c:602-612: the index of the serial loop's last improvement = the best unit's */
-			if (!o->write_files) {
-				mc_fit_view fv = { K, res[st->sum.best_unit].converged, st->sum.max_logL, st->sum.aic, st->sum.bic, own->q, own->p, own->sik };
-				mc_partition(d, &fv, st->I_K, count_K);
-			}
-			int fits = 1;
-			for (int x = 0; x < d->I; x++) if (st->I_K[x] >= K) fits = 0;
-			if (fits) st->arand = mc_adjusted_rand(d->I, st->pK, K, st->partition_from_file, st->I_K);
-		}
-	}
-	if (!rc && (o->cv_folds || o->se_replicates) && !bootstrap) {	/* --cv, --se: the best unit of this K, on the device whose worker fitted it */
-		int ub = 0;
-		for (int u = 1; u < n_units; u++) if (res[u].logL > res[ub].logL) ub = u;
-		const shard_worker *own = &w[ub % n_dev];
-		if (own->best_unit != ub) { fprintf(stderr, "ERROR [mc_main.c]: owner of the best unit does not hold it\n"); rc = MCHIP_ERR_STATE; goto DONE; }
-		if (o->cv_folds)
-			rc = cli_cross_validate(o, md, st, NULL, K, worker_device(o, ub % n_dev), own->q, own->p, res[ub].logL, res[ub].n_iter, res[ub].converged);
-		if (!rc && o->se_replicates)
-			rc = cli_locus_bootstrap(o, d, md, st, NULL, K, worker_device(o, ub % n_dev), own->q, own->p, res[ub].logL, res[ub].n_iter,
-						 res[ub].converged);
+	if (want_params) {	/* the winner's parameters came from the device that fitted it */
+		const fit_record *fit = &w[ub % n_dev].best;
+		if (fit->unit != ub) { fprintf(stderr, "ERROR [mc_main.c]: owner of the best unit does not hold it\n"); rc = MCHIP_ERR_STATE; goto DONE; }
+		/* the serial loop's last improvement on the maximum, if it had one in this K, is the best unit */
+		if (st->sum.best_unit >= 0) rc = new_maximum(o, d, st, fit, bootstrap);
+		if (!rc && wants_post_fit(o, bootstrap)) rc = post_fit(o, d, md, st, fit, NULL, worker_device(o, ub % n_dev));
 	}
 DONE:
-	if (w) for (int x = 0; x < n_dev; x++) { free(w[x].q); free(w[x].p); free(w[x].sik); }
+	if (w) for (int x = 0; x < n_dev; x++) record_free(&w[x].best);
 	if (tab) for (int x = 0; x < n_gpus; x++) free(tab[x]);
-	free(w); free(th); free(joinable); free(res); free(tab); free(count_K); free(starts);
+	free(w); free(th); free(joinable); free(res); free(tab); free(starts);
 	return rc;
 }
 
@@ -813,20 +785,10 @@ static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const m
 		if (rc) return rc;
 		if (o->n_repeat == 1 && o->em.verbosity)
 			print_model_state(o, d, st, K, (int)(((double)clock() - start) / CLOCKS_PER_SEC), 1);
-		if (st->cv_done) {	/* --cv */
-			fprintf(st->out, "CV error (K=%d, %d folds): %.10f  [%llu held-out copies, %llu floored]\n", K, o->cv_folds, st->cv.cv,
-				(unsigned long long)st->cv.n_copies, (unsigned long long)st->cv.n_floored);
-			st->cv_done = 0;
-		}
-		if (st->se_done) {	/* --se */
-			fprintf(st->out, "Bootstrap SE (K=%d, %d replicates, block %d): mean %.10f  max %.10f  [%d failed]\n", K, st->se.n_replicates,
-				st->se.block, st->se.mean_se, st->se.max_se, st->se.n_failed);
-			st->se_done = 0;
-		}
-		if (st->query_done) {	/* --query */
-			fprintf(st->out, "Query fit (K=%d): %d individuals, %d converged, %d failed, at most %d iterations, log likelihood %.6f\n", K,
-				st->query.n, st->query.n_converged, st->query.n_failed, st->query.max_iter, st->query.sum_logL);
-			st->query_done = 0;
+		if (st->post_lines) {	/* --cv, --se, --query (post_fit) */
+			fputs(st->post_lines, st->out);
+			free(st->post_lines);
+			st->post_lines = NULL;
 		}
 		if (total_iter) *total_iter += st->sum.n_total_iter;
 		if (o->n_bootstrap && K == st->null_K) st->max_logL_H0 = st->sum.max_logL;
@@ -858,7 +820,7 @@ typedef struct bs_worker {
 	const mc_cli_options *o;
 	const mc_cli_data *d;
 	const mc_data *md;
-	const run_state *st;		/* observed-data results: null_K, alt_K, H0 MLEs, ts_obs */
+	const run_state *st;		/* observed-data results: null_K, alt_K, H0 MLEs (read only), ts_obs */
 	int index, n_dev;
 	const mc_rng *starts;		/* [n_bootstrap + 1]: the serial stream's state at the start of every replicate */
 	double *ts;			/* [n_bootstrap], shared: worker x writes entries b = x, x + n_dev, ... */
@@ -883,11 +845,10 @@ static void *bs_main(void *arg)
 		ls.I_K = own_I_K;
 		mc_simulation gen;
 		size_t len = 0;
-		ls.mle_q = w->st->mle_q; ls.mle_p = w->st->mle_p;	/* read only */
 		ls.rng = w->starts[b];
 		if (!(ls.out = open_memstream(&w->text[b], &len))) { w->rc = MCHIP_ERR_ALLOC; free(own_I_K); return NULL; }
 		fprintf(ls.out, "Bootstrap dataset %d (of %d):", b + 1, w->o->n_bootstrap);
-		mc_simulation_begin(&gen, &ow.em, w->md, ls.mle_K, ls.mle_q, ls.mle_p, &ls.rng);
+		mc_simulation_begin(&gen, &ow.em, w->md, ls.h0.K, ls.h0.q, ls.h0.p, &ls.rng);
 		w->rc = estimate_model(&ow, w->d, w->md, &ls, 1, NULL, &gen);
 		fclose(ls.out);
 		if (w->rc) break;
@@ -1074,7 +1035,7 @@ int main(int argc, const char **argv)
 		/* the observed haplotypes the fits to an uploaded replicate initialise from (decoded here when the data set is held packed) */
 		const uint8_t *observed = on_device ? NULL : mc_data_geno(&md);
 		int ntime = 0;
-		if ((!on_device && (!sim || !observed)) || !st.mle_q) { rc = MCHIP_ERR_ALLOC; goto END; }
+		if ((!on_device && (!sim || !observed)) || !st.h0.q) { rc = MCHIP_ERR_ALLOC; goto END; }
 		/* whole replicates per device when there is at least one for each; otherwise (or on one device) the replicates run in
 		 * turn and --gpus shards the initialisations inside each */
 		/* (Rand-EM draws a data-dependent number of values per initialisation: replicate b's place in the stream has no closed form) */
@@ -1086,10 +1047,10 @@ int main(int argc, const char **argv)
 			printf("Bootstrap dataset %d (of %d):", b + 1, o.n_bootstrap);
 			if (on_device) {
 				mc_simulation gen;
-				mc_simulation_begin(&gen, &o.em, &md, st.mle_K, st.mle_q, st.mle_p, &st.rng);
+				mc_simulation_begin(&gen, &o.em, &md, st.h0.K, st.h0.q, st.h0.p, &st.rng);
 				rc = estimate_model(&o, &d, &md, &st, 1, NULL, &gen);
 			} else {
-				mc_bootstrap_genotypes(&o.em, &md, st.mle_K, st.mle_q, st.mle_p, &st.rng, sim);
+				mc_bootstrap_genotypes(&o.em, &md, st.h0.K, st.h0.q, st.h0.p, &st.rng, sim);
 				md.geno = d.geno = sim;
 				md.init_geno = observed;
 				rc = estimate_model(&o, &d, &md, &st, 1, NULL, NULL);
@@ -1110,8 +1071,8 @@ int main(int argc, const char **argv)
 END:
 	mchip_progress_note("end of main: freeing");
 	if (run_comm) mchip_comm_destroy(run_comm);
-	free(st.mle_q); free(st.mle_p); free(st.I_K); free(st.partition_from_file); free(st.query_mask);
-	mc_query_result_free(&st.query);
+	record_free(&st.h0);
+	free(st.I_K); free(st.partition_from_file); free(st.query_mask); free(st.post_lines);
 	mc_free_data(&d);
 	mchip_progress_note("returning from main: the HIP runtime's own teardown follows");
 	return rc;

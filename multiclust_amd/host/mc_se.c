@@ -10,12 +10,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-static int se_fail(mc_model *mod, int rc, const char *what)
-{
-	if (rc) fprintf(stderr, "ERROR [mc_se.c::mc_locus_bootstrap]: %s failed (%d): %s\n", what, rc, mchip_last_error(mod->dev));
-	return rc;
-}
-
 /* Welford's update of one entry, each operation rounded on its own (a fused multiply-add would change M2's bits from one build to
  * the next; equal values must give M2 = 0 exactly) */
 #if defined(__GNUC__) && !defined(__clang__)
@@ -63,10 +57,10 @@ static int set_model(const mc_options *opt, mc_model *mod)
 int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod, int n_replicates, int block, double *mean, double *se,
 		       int32_t *count, mc_se_result *out)
 {
-	const int K = mod->K, mle = mod->pindex, L = dat->L;
-	const mc_model keep = *mod;	/* logL, n_iter, ring indices, ...: given back as they were */
-	int nq = 0, np = 0, rc, T = 0, installed = 0;
-	double *q = NULL, *p = NULL, *x = NULL, *m2 = NULL;
+	const int K = mod->K, L = dat->L;
+	mc_refit est;
+	int rc, rc2, skipped, T = 0;
+	double *x = NULL, *m2 = NULL;
 	int32_t *src = NULL, *ua2 = NULL, *toff = NULL;
 	mc_rng rng;
 	if (out) memset(out, 0, sizeof *out);
@@ -77,22 +71,19 @@ int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod,
 	if (n_replicates < 2 || n_replicates > MC_SE_MAX_REPLICATES || block < 1 || block > L) return MCHIP_ERR_INVALID;
 	const int cap = mc_se_list_capacity(L, block);
 	if (!cap) return MCHIP_ERR_INVALID;
-	if ((rc = se_fail(mod, mchip_q_length(mod->dev, &nq), "mchip_q_length")) || (rc = se_fail(mod, mchip_p_length(mod->dev, &np), "mchip_p_length")))
-		return rc;
-	q = malloc(sizeof(double) * (size_t)nq);
-	p = malloc(sizeof(double) * (size_t)np);
+	/* the full-data estimate waits on the host: the replicates have other shapes */
+	if ((rc = mc_refit_begin(&est, mod, "mc_se.c::mc_locus_bootstrap"))) return rc;
+	const int nq = est.nq;
+	const double *p = est.p;
 	x = malloc(sizeof(double) * (size_t)nq);
 	m2 = calloc((size_t)nq, sizeof(double));
 	src = malloc(sizeof(int32_t) * (size_t)cap);
 	ua2 = malloc(sizeof(int32_t) * (size_t)cap);
 	toff = malloc(sizeof(int32_t) * ((size_t)L + 1));
-	if (!q || !p || !x || !m2 || !src || !ua2 || !toff) { rc = MCHIP_ERR_ALLOC; goto DONE; }
+	if (!x || !m2 || !src || !ua2 || !toff) { rc = mc_refit_end(&est, MCHIP_ERR_ALLOC, MCHIP_ERR_ALLOC); goto DONE; }	/* (nothing installed yet) */
 	for (int e = 0; e < nq; e++) { mean[e] = 0; se[e] = NAN; count[e] = 0; }
 	for (int l = 0; l < L; l++) { toff[l] = T; T += dat->uniquealleles[l]; }
 	toff[L] = T;
-	/* the full-data estimate waits on the host: the replicates have other shapes, and an accelerated fit uses all three slots */
-	if ((rc = se_fail(mod, mchip_get_q(mod->dev, mle, q), "mchip_get_q")) || (rc = se_fail(mod, mchip_get_p(mod->dev, mle, p), "mchip_get_p")))
-		goto DONE;
 	/* the lists: a stream of their own from the run's seed, the same for every K; the run's main rand() stream stays where it is */
 	mc_srand(&rng, opt->seed);
 	for (int r = 0; r < n_replicates; r++) {
@@ -101,10 +92,8 @@ int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod,
 		double *p2;
 		mc_data rep = *dat;
 		mc_se_draw_lists(&rng, L, block, 1, src, &L2);
-		installed = 1;
-		if ((rc = se_fail(mod, mchip_resample_loci(mod->dev, src, L2), "mchip_resample_loci"))) break;
-		if ((rc = se_fail(mod, set_model(opt, mod), "mchip_set_model"))) break;
-		mc_reset_model_state(mod);	/* slot 0, iteration 0, logL = -inf: em() from the warm start */
+		if ((rc = mc_refit_check(&est, mchip_resample_loci(mod->dev, src, L2), "mchip_resample_loci"))) break;
+		if ((rc = mc_refit_check(&est, set_model(opt, mod), "mchip_set_model"))) break;
 		for (int j = 0; j < L2; j++) T2 += (ua2[j] = dat->uniquealleles[src[j]]);
 		if (!(p2 = malloc(sizeof(double) * (size_t)K * (size_t)T2))) { rc = MCHIP_ERR_ALLOC; break; }
 		for (int k = 0; k < K; k++) {	/* the columns of the estimate follow their loci */
@@ -114,7 +103,7 @@ int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod,
 				to += ua2[j];
 			}
 		}
-		if (!(rc = se_fail(mod, mchip_set_q(mod->dev, 0, q), "mchip_set_q"))) rc = se_fail(mod, mchip_set_p(mod->dev, 0, p2), "mchip_set_p");
+		rc = mc_refit_warm_start(&est, p2);
 		free(p2);
 		if (rc) break;
 		rep.L = L2;
@@ -123,33 +112,20 @@ int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod,
 		rep.bed_record_bytes = 0;
 		rep.lazy = NULL;
 		mc_em(opt, &rep, mod);
-		if (mod->fatal == MC_FATAL_DEVICE) { rc = MCHIP_ERR_HIP; break; }
+		if ((rc = mc_refit_fitted(&est, "replicate", r, "replicate skipped", &skipped))) break;
 		out->n_iter += (uint64_t)mod->n_iter;
-		if (mod->fatal) {	/* NaN or a decrease of the log likelihood: the replicate does not count, the run goes on */
-			fprintf(stderr, "WARNING [mc_se.c::mc_locus_bootstrap]: K = %d, replicate %d: the fit stopped on %s; replicate skipped\n", K, r,
-				mod->fatal == MC_FATAL_NAN ? "a NaN log likelihood" : "a decrease of the log likelihood");
+		if (skipped) {	/* the replicate does not count, the run goes on */
 			out->n_failed++;
 			continue;
 		}
-		if ((rc = se_fail(mod, mc_model_get_q(mod, mod->pindex, x), "mchip_get_q"))) break;
+		if ((rc = mc_refit_check(&est, mc_model_get_q(mod, mod->pindex, x), "mchip_get_q"))) break;
 		for (int e = 0; e < nq; e++) {	/* Welford; a NaN entry (an individual without an observed copy in this replicate) does not count */
 			if (x[e] == x[e]) welford(x[e], &mean[e], &m2[e], &count[e]);
 		}
 	}
-	if (installed) {	/* the base and the estimate again, whatever happened */
-		int rc2 = se_fail(mod, mchip_resample_loci(mod->dev, NULL, 0), "mchip_resample_loci");
-		if (!rc2) rc2 = se_fail(mod, set_model(opt, mod), "mchip_set_model");
-		if (!rc2) rc2 = se_fail(mod, mchip_set_q(mod->dev, mle, q), "mchip_set_q");
-		if (!rc2) rc2 = se_fail(mod, mchip_set_p(mod->dev, mle, p), "mchip_set_p");
-		if (!rc) rc = rc2;
-	}
-	{
-		mchip_context *dev = mod->dev;
-		void *cache = mod->init_cache;	/* (may have been built meanwhile: it belongs to the model) */
-		*mod = keep;
-		mod->dev = dev;
-		mod->init_cache = cache;
-	}
+	/* the base and the estimate again, whatever happened */
+	rc2 = mc_refit_check(&est, mchip_resample_loci(mod->dev, NULL, 0), "mchip_resample_loci");
+	rc = mc_refit_end(&est, rc, rc2 ? rc2 : mc_refit_check(&est, set_model(opt, mod), "mchip_set_model"));
 	if (!rc) {
 		double sum = 0;
 		int n = 0;
@@ -164,6 +140,6 @@ int mc_locus_bootstrap(const mc_options *opt, const mc_data *dat, mc_model *mod,
 		if (n) out->mean_se = sum / n;
 	}
 DONE:
-	free(q); free(p); free(x); free(m2); free(src); free(ua2); free(toff);
+	free(x); free(m2); free(src); free(ua2); free(toff);
 	return rc;
 }
