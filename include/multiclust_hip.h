@@ -340,6 +340,36 @@ int mchip_fit_q_rows(mchip_context *ctx, int slot, const int32_t *rows, int n_ro
 		     int max_iter, double abs_error, double rel_error,
 		     double *q_rows /* [n_rows][K] */, double *loglik_rows, int32_t *iter_rows, uint8_t *converged_rows);
 
+/* ---- missing allele copies filled from the fitted admixture model (an extension: the reference's --impute puts one allele per
+ * locus into every missing copy before any fit) ----
+ * For every genotype (i, l) of the INSTALLED data set with r >= 1 missing copies (under a cross-validation hold-out the hidden
+ * copies are missing copies like any other), with the parameters of `slot`:
+ *   candidates    the first n_real[l] allele slots of the locus (the reader's L_alleles[l]: uniquealleles[l] without the phantom
+ *                 trailing slot);
+ *   t_m           = sum_k q_ik p_klm, an fma chain in k order (q_k when the mixing proportions are shared); x_m = t_m / sum_cand t.
+ *                 Q is read as the device stores it: an individual without an observed copy holds 1 / K (the slot section above);
+ *   the r copies  together take the mode of the multinomial(r; x), found greedily: copy j = 1 .. r goes to argmax_m t_m / (c_m + 1),
+ *                 c_m the earlier copies of this genotype given to m, ties to the lowest m.  r = 1: argmax t; a fully missing
+ *                 diploid genotype becomes heterozygous when the larger x is below 2 / 3.  Observed copies of the genotype play no
+ *                 part (copies are independent given q);
+ *   written       the multiset, ascending by allele index, into the missing positions in copy order;
+ *   confidence    c = r! / prod_m c_m! prod_m x_m^c_m, the probability of the filled multiset;
+ *   left missing  all r copies when n_real[l] = 0 or no candidate has t > 0 (NaN is not > 0): they stay MCHIP_MISSING.
+ * geno_out [I][L][ploidy] = mchip_get_genotypes byte for byte outside the filled copies.  conf_out: NULL, or [I][L] receiving c where
+ * a genotype was filled and 0 elsewhere.  *n_filled / *n_left count copies, *n_genotypes the genotypes filled, *sum_conf is the sum
+ * of their c; any of the four may be NULL.  The sum is combined in an order fixed by the shape, no floating-point atomics: two
+ * calls on the same state return the same bits.
+ * Writes its host arrays and nothing else: no parameter slot, secant, expected count, held S-side sum, data set, fold or saved set
+ * changes.  The filled genotype is the most probable one given Q and P, not a draw: filled data understate the variance of
+ * heterozygosity.
+ * MCHIP_ERR_STATE without a data set or model; MCHIP_ERR_UNSUPPORTED for the mixture model (admixture = 0); MCHIP_ERR_INVALID for a
+ * slot out of range, a null n_real or geno_out, or an n_real[l] outside [0, uniquealleles[l]] -- all checked before anything runs,
+ * the arrays stay untouched.
+ */
+int mchip_impute_missing(mchip_context *ctx, int slot, const int32_t *n_real /* [L] */,
+			 uint8_t *geno_out /* [I][L][ploidy] */, double *conf_out /* [I][L] or NULL */,
+			 uint64_t *n_filled, uint64_t *n_left, uint64_t *n_genotypes, double *sum_conf);
+
 /* ---- a selection of loci with repeats: the data sets of the non-parametric bootstrap over loci (an extension) ----
  * Let the base be the data set the context held when the first resample was asked for (I, L_base, ploidy, uniquealleles,
  * genotypes).  After the call the context holds exactly what

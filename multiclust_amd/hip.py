@@ -100,6 +100,7 @@ def load():
         "mchip_cv_heldout_loglik": ([vp, i32, C.c_double, dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], i32),
         "mchip_resample_loci": ([vp, vp, i32], i32),
         "mchip_fit_q_rows": ([vp, i32, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp], i32),
+        "mchip_impute_missing": ([vp, i32, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp], i32),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("MCHIP_ALLOW_PARTIAL_ABI") == "1" and not hasattr(lib, name):
@@ -123,7 +124,7 @@ ABI_SYMBOLS = [
     "mchip_comm_last_error", "mchip_comm_info", "mchip_progress_report", "mchip_progress_note",
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
-    "mchip_resample_loci", "mchip_fit_q_rows",
+    "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing",
 ]
 
 
@@ -241,6 +242,20 @@ class Context:
         self._chk(self.lib.mchip_fit_q_rows(self.h, slot, r.ctypes.data, n, int(bool(from_slot)), max_iter, abs_error, rel_error,
                                             q.ctypes.data, ll.ctypes.data, it.ctypes.data, cv.ctypes.data))
         return q, ll, it, cv
+
+    def impute_missing(self, slot, n_real, conf=True, out=None):
+        """mchip_impute_missing: the missing copies of the installed data set filled from the parameters of `slot`
+        (include/multiclust_hip.h): (geno [I][L][ploidy], conf [I][L] or None, copies filled, copies left missing, genotypes
+        filled, sum of the confidences).  out: (geno, conf) arrays to fill instead of new ones."""
+        nr = np.ascontiguousarray(n_real, dtype=np.int32)
+        assert nr.shape == (self.L,)
+        if out is None:
+            out = (np.empty((self.I, self.L, self.ploidy), dtype=np.uint8), np.empty((self.I, self.L)) if conf else None)
+        g, c = out
+        nf, nl, ng, sc = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        self._chk(self.lib.mchip_impute_missing(self.h, slot, nr.ctypes.data, g.ctypes.data, None if c is None else c.ctypes.data,
+                                                C.byref(nf), C.byref(nl), C.byref(ng), C.byref(sc)))
+        return g, c, nf.value, nl.value, ng.value, sc.value
 
     def resample_loci(self, src):
         """install the selection `src` (locus indices into the base, repeats allowed) of the base: the data set held when the first

@@ -85,6 +85,12 @@ class McQueryResult(C.Structure):
                 ("q", C.POINTER(C.c_double)), ("logL", C.POINTER(C.c_double)), ("converged", C.POINTER(C.c_uint8))]
 
 
+class McImputeResult(C.Structure):
+    """mc_impute_result (multiclust_amd/host/mc_host.h)"""
+    _fields_ = [("n_filled", C.c_uint64), ("n_left", C.c_uint64), ("n_genotypes", C.c_uint64), ("sum_conf", C.c_double),
+                ("mean_conf", C.c_double)]
+
+
 class CliOptions(C.Structure):
     """mc_cli_options (multiclust_amd/host/mc_cli.h)"""
     _fields_ = [("em", McOptions), ("filename", C.c_char_p), ("filename_file", C.c_char_p), ("path", C.c_char_p),
@@ -95,8 +101,8 @@ class CliOptions(C.Structure):
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
                 ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
-    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block and query_file, the command line's --cv, --se and
-    # --query: only mc_main.c reads them, the readers this mirror is handed to stop at bed_prefix)
+    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block, query_file and fill, the command line's --cv, --se,
+    # --query and --fill: only mc_main.c reads them, the readers and writers this mirror is handed to stop at bed_prefix)
 
 
 class CliData(C.Structure):
@@ -183,6 +189,60 @@ def read_bed(prefix, decode=True):
         out.update(geno=geno, ua_decoded=ua_dec)
     lib.mc_free_data(C.byref(d))
     return 0, out
+
+
+def write_filled_structure(path, out_path, filled, ploidy=2, missing=-9, r_format=0):
+    """mc_write_filled_structure (host/mc_impute.c): the STRUCTURE file `path`, read with these reader options, copied to out_path
+    with every missing allele token whose copy is not 0xFF in filled [I][L][ploidy] replaced by that allele's label; returns the
+    status (0 = written)."""
+    lib = load()
+    o = CliOptions()
+    o.filename = path.encode()
+    o.ploidy, o.missing_value, o.R_format = ploidy, missing, r_format
+    d = CliData()
+    rc = lib.mc_read_structure(C.byref(o), C.byref(d))
+    if rc:
+        return rc
+    f = np.ascontiguousarray(filled, dtype=np.uint8)
+    assert f.shape == (d.I, d.L, d.ploidy)
+    rc = lib.mc_write_filled_structure(C.byref(o), C.byref(d), f.ctypes.data, out_path.encode())
+    lib.mc_free_data(C.byref(d))
+    return rc
+
+
+def write_filled_bed(prefix, out_prefix, filled):
+    """mc_write_filled_bed (host/mc_impute.c): the PLINK fileset `prefix` copied to out_prefix.bed/.bim/.fam with every missing
+    record whose two copies are not 0xFF in filled [I][L][2] replaced by the genotype they spell; returns the status."""
+    lib = load()
+    o = CliOptions()
+    o.bed_prefix = prefix.encode()
+    o.ploidy = 2
+    d = CliData()
+    rc = lib.mc_read_bed(C.byref(o), C.byref(d))
+    if rc:
+        return rc
+    f = np.ascontiguousarray(filled, dtype=np.uint8)
+    assert f.shape == (d.I, d.L, 2)
+    rc = lib.mc_write_filled_bed(C.byref(o), C.byref(d), f.ctypes.data, out_prefix.encode())
+    lib.mc_free_data(C.byref(d))
+    return rc
+
+
+def impute_n_real(ua, geno=None, bed=None, I=None):
+    """mc_impute_n_real (host/mc_impute.c): the candidate alleles of every locus, uniquealleles[l] without the phantom slot, from
+    the genotype [I][L][ploidy] or from packed PLINK records [L][record_bytes] of I individuals"""
+    lib = load()
+    ua = np.ascontiguousarray(ua, dtype=np.int32)
+    if geno is not None:
+        g = np.ascontiguousarray(geno, dtype=np.uint8)
+        dat = McData(g.shape[0], g.shape[1], g.shape[2], ua.ctypes.data, g.ctypes.data)
+    else:
+        b = np.ascontiguousarray(bed, dtype=np.uint8)
+        dat = McData(I, b.shape[0], 2, ua.ctypes.data, None, None, b.ctypes.data, b.shape[1])
+    out = np.empty(ua.size, dtype=np.int32)
+    if lib.mc_impute_n_real(C.byref(dat), out.ctypes.data):
+        raise hip.HipError("mc_impute_n_real failed")
+    return out
 
 
 def query_read(path, I):
@@ -283,6 +343,13 @@ def load():
     lib.mc_query_fit.argtypes = [OP, DP, MP, C.c_void_p, C.POINTER(McQueryResult)]
     lib.mc_query_result_free.argtypes = [C.POINTER(McQueryResult)]
     lib.mc_query_result_free.restype = None
+    lib.mc_impute.argtypes = [OP, DP, MP, C.c_void_p, C.POINTER(McImputeResult)]
+    lib.mc_impute_n_real.argtypes = [DP, C.c_void_p]
+    lib.mc_read_structure.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
+    lib.mc_read_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
+    lib.mc_free_data.argtypes = [C.POINTER(CliData)]
+    lib.mc_write_filled_structure.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData), C.c_void_p, C.c_char_p]
+    lib.mc_write_filled_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData), C.c_void_p, C.c_char_p]
     lib.mc_aic.restype = C.c_double
     lib.mc_aic.argtypes = [C.c_double, C.c_int]
     lib.mc_bic.restype = C.c_double
@@ -437,6 +504,17 @@ class Fit:
                    n_failed=r.n_failed, max_iter=r.max_iter, sum_logL=r.sum_logL)
         self.lib.mc_query_result_free(C.byref(r))
         return out
+
+    def impute(self):
+        """mc_impute on the estimate in slot mod.pindex: (geno [I][L][ploidy] with the missing copies of the data set installed on
+        the device filled in, dict with n_filled, n_left (copies), n_genotypes, sum_conf, mean_conf).  Leaves the model as it found
+        it."""
+        g = np.empty(self.geno.shape, dtype=np.uint8)
+        r = McImputeResult()
+        rc = self.lib.mc_impute(C.byref(self.opt), C.byref(self.dat), self.mp, g.ctypes.data, C.byref(r))
+        if rc:
+            raise hip.HipError("mc_impute failed (%d)" % rc)
+        return g, dict(n_filled=r.n_filled, n_left=r.n_left, n_genotypes=r.n_genotypes, sum_conf=r.sum_conf, mean_conf=r.mean_conf)
 
     def locus_lists(self, n_replicates, block=1):
         """the locus lists mc_locus_bootstrap installs for these arguments and the options' seed, one int32 array per replicate"""

@@ -52,6 +52,7 @@ typedef struct mc_cli_options {
 	int se_block;			/* --se-block <n>: blocks of n neighbouring loci are resampled; default 1 */
 	const char *query_file;		/* --query <file> (extension): I tokens 0 (panel) / 1 (query); the query individuals are hidden from every
 					 * fit and fitted against the best fit of every K afterwards (mc_query.c) */
+	int fill;			/* --fill (extension): the missing genotypes filled from the best fit of every K (mc_impute.c) */
 } mc_cli_options;
 
 typedef struct mc_cli_data {
@@ -126,5 +127,18 @@ int mc_query_read(const char *path, int I, uint8_t **mask_out);
  * logL, and the K mixing proportions (%.10f, as .se.txt prints); arrays as mc_query_fit fills them */
 int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows, const int32_t *iter, const uint8_t *converged,
 		   const double *logL, const double *q);
+
+
+/* --fill (an extension, mc_impute.c): the data set with its missing copies filled (filled [I][L][ploidy], as mc_impute gives it),
+ * written as a copy of the file it was read from.
+ * mc_write_filled_structure: opt->filename byte for byte -- header, "-1" line, both layouts, label columns, white space, line ends --
+ * except that each token the reader took for a missing allele copy and that was filled is the decimal label L_alleles[l][m].
+ * mc_write_filled_bed: <out_prefix>.bed with each missing record that was filled replaced by homozygous A1 / heterozygous /
+ * homozygous A2 (magic bytes and padding bits kept), .bim and .fam of opt->bed_prefix copied byte for byte.
+ * mc_write_filled: the one the input calls for, to <stem>.admix.K=<K>.filled.stru or <stem>.admix.K=<K>.filled.bed / .bim / .fam.
+ * Return 0 or an exit status of the enum above. */
+int mc_write_filled_structure(const mc_cli_options *opt, const mc_cli_data *dat, const uint8_t *filled, const char *out_path);
+int mc_write_filled_bed(const mc_cli_options *opt, const mc_cli_data *dat, const uint8_t *filled, const char *out_prefix);
+int mc_write_filled(const mc_cli_options *opt, const mc_cli_data *dat, int K, const uint8_t *filled);
 
 #endif

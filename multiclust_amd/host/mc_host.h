@@ -322,6 +322,21 @@ int mc_query_hide(mc_model *mod, const mc_data *dat, const uint8_t *mask /* [I] 
 int mc_query_fit(const mc_options *opt, const mc_data *dat, mc_model *mod, const uint8_t *mask /* [I] */, mc_query_result *out);
 void mc_query_result_free(mc_query_result *r);
 
+/* ---- missing genotypes filled from a fitted admixture model (mc_impute.c; an extension) ----
+ * `mod` holds a fit in slot mod->pindex.  Every missing copy of the data set installed on its context takes the most probable allele
+ * given that slot's Q and P -- the r missing copies of a genotype together the mode of the multinomial(r; x), x_m proportional to
+ * sum_k q_ik p_klm over the locus's real alleles (mchip_impute_missing, include/multiclust_hip.h) -- and geno_out [I][L][ploidy]
+ * receives the data set with them filled in.  mc_impute_n_real: the candidates of every locus, uniquealleles[l] without the phantom
+ * slot of a locus that has a missing copy, from the genotype or from the packed records of a PLINK fileset.  Counts are per copy
+ * (n_filled, n_left: the locus has no observed allele, or no allele has a positive probability) and per filled genotype
+ * (n_genotypes); sum_conf adds the probabilities of the filled genotypes, mean_conf = sum_conf / n_genotypes (0 without one).
+ * A filled genotype is the most probable one, not a draw: filled data understate the variance of heterozygosity.
+ * Nothing of the model or the context changes.  Admixture model only (individual or shared mixing proportions), else
+ * MCHIP_ERR_UNSUPPORTED. */
+typedef struct mc_impute_result { uint64_t n_filled, n_left, n_genotypes; double sum_conf, mean_conf; } mc_impute_result;
+int mc_impute_n_real(const mc_data *dat, int32_t *n_real /* [L] */);
+int mc_impute(const mc_options *opt, const mc_data *dat, mc_model *mod, uint8_t *geno_out /* [I][L][ploidy] */, mc_impute_result *out);
+
 /* ---- opt-in watchdog (mc_watchdog.c): nothing in the reference corresponds -- it has nothing to wait for ----
  * mc_watchdog_start(s): a detached thread that polls the library's event count (mchip_progress_report) and, when it has stood
  * still for s seconds, prints where every thread stands (library record + /proc/self/task) on stderr and leaves with _exit(3).

@@ -10,6 +10,7 @@
  * mode in the reference itself), --impute, --simulate, -x (not implemented in the reference either).
  * Extensions: --se <B> adds bootstrap standard errors of the mixing proportions of every K's best fit (B resamples of the loci, or of
  * blocks of --se-block neighbouring loci: one more stdout line per K and one more file, nothing else changes); --cv <F> adds the F-fold cross-validation error of every K's best fit (one more stdout line per K, nothing else changes);
+ * --fill fills the missing genotypes from the best fit of every K (one more stdout line per K and a filled copy of the data file; without it nothing changes);
  * --query <file> keeps the individuals the file marks out of every fit and fits their mixing proportions against the best fit of every K
  * afterwards (one more stdout line per K and one more file; without it nothing changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
@@ -19,7 +20,7 @@
  * over the same workers as whole units for both models; the mixture model's initialisations are not sharded.
  * Where a post-fit analysis plugs in: the serial and the sharded path differ in who fits which unit and share the rest.  Both keep
  * the best fit of a K in a fit_record, hand it to new_maximum() when it improved on the K before (H0 estimate, result files, -A) and
- * end in post_fit(), which puts the record back into a model once and runs --cv, --se, --query; an analysis that refits derived
+ * end in post_fit(), which puts the record back into a model once and runs --cv, --se, --query, --fill; an analysis that refits derived
  * data sets builds on mc_refit_* (mc_refit.c), adds its line to post_fit()'s text and its refusals to parse_options' refuse().
  */
 #include "mc_cli.h"
@@ -71,7 +72,10 @@ static void usage(FILE *fp, const char *prog)
 		"                fit (the result files show them as individuals without data; AIC and BIC keep the data set's number of\n"
 		"                individuals) and their mixing proportions are then fitted to the allele frequencies of the best fit of every K:\n"
 		"                one more line 'Query fit (K=..)' per K and a file <stem>.admix.K=<K>.query.txt; needs -a, not with -c, -b, -w,\n"
-		"                -M, -A, --cv, --se, --randem, or --gpus / --streams above 1\n", prog);
+		"                -M, -A, --cv, --se, --randem, or --gpus / --streams above 1\n"
+		"  --fill        fill every missing allele copy with the most probable alleles under the best fit of every K: one more line\n"
+		"                'Imputation (K=..)' per K and the data file with the copies filled in, <stem>.admix.K=<K>.filled.stru (or .filled.bed /\n"
+		"                .bim / .fam with --bed); needs -a, not with -b, -w, -M, --query or --gpus above 1\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -148,6 +152,7 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 		case 'e': if (arg_dbl(argc, argv, ++i, &d) || d < 0) BAD("-e"); o->em.rel_error = d; break;
 		case 'E': if (arg_dbl(argc, argv, ++i, &d) || d < 0) BAD("-E"); o->em.abs_error = d; break;
 		case 'f':
+			if (!strcmp(argv[i], "--fill")) { o->fill = 1; break; }	/* (in full: -f... is the data file) */
 			if (!strncmp(w, "fo", 2)) { ++i; break; }	/* --format only matters to the data writer */
 			if (++i >= argc) BAD("-f");
 			o->filename = o->filename_file = argv[i];
@@ -263,6 +268,12 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			o->cv_folds || o->se_replicates ? "--query cannot be combined with --cv or --se (they share the fold state of the device)" :
 			o->em.initialization_procedure == MC_RAND_EM ? "--query cannot be combined with --randem (its centers are drawn from the genotypes on the host)" :
 			o->n_gpus > 1 || o->n_streams > 1 ? "--query cannot be combined with --gpus or --streams above 1" : NULL))) return rc;
+	if (o->fill && (rc = refuse("--fill",
+			!o->em.admixture ? "--fill needs the admixture model (-a)" :
+			o->n_bootstrap ? "--fill cannot be combined with the bootstrap (-b)" :
+			o->n_gpus > 1 ? "--fill cannot be combined with --gpus above 1" :
+			timed ? "--fill cannot be combined with -w or -M" :
+			o->query_file ? "--fill cannot be combined with --query (the query individuals are hidden on the device)" : NULL))) return rc;
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -490,13 +501,13 @@ static int new_maximum(const mc_cli_options *o, const mc_cli_data *d, run_state 
 	return rc;
 }
 
-/* ---- the post-fit stage: --cv, --se and --query, in that order, on the best fit of one K ----
+/* ---- the post-fit stage: --cv, --se, --query and --fill, in that order, on the best fit of one K ----
  * fit: that fit, with its parameters.  mod: the model that fitted it (its slots are free again; --query needs this one: the
  * hold-out that hides the query individuals is in force on its context), or NULL: a model is created on `device` for the purpose
  * (the workers of a sharded fit are gone by the time the best unit is known).  The fit goes back into the model once: every
  * analysis leaves slot pindex and the host state of the model as it found them (mc_host.h).  Each analysis writes its file
  * (result files on) and adds its stdout line to st->post_lines. */
-static int wants_post_fit(const mc_cli_options *o, int bootstrap) { return (o->cv_folds || o->se_replicates || o->query_file) && !bootstrap; }
+static int wants_post_fit(const mc_cli_options *o, int bootstrap) { return (o->cv_folds || o->se_replicates || o->query_file || o->fill) && !bootstrap; }
 
 static int post_fit(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, const fit_record *fit, mc_model *mod, int device)
 {
@@ -541,6 +552,16 @@ static int post_fit(const mc_cli_options *o, const mc_cli_data *d, const mc_data
 				res.n, res.n_converged, res.n_failed, res.max_iter, res.sum_logL);
 		if (!rc && o->write_files) rc = mc_write_query(o, K, res.n, res.rows, res.iter, res.converged, res.logL, res.q);
 		mc_query_result_free(&res);
+	}
+	if (!rc && o->fill) {	/* last: --cv and --se have installed the data set again.  With result files on: <stem>.admix.K=<K>.filled.* */
+		uint8_t *filled = malloc((size_t)d->I * d->L * d->ploidy);
+		mc_impute_result res;
+		mchip_progress_note("filling missing genotypes");
+		rc = filled ? mc_impute(&o->em, md, mod, filled, &res) : MCHIP_ERR_ALLOC;
+		if (!rc) fprintf(say, "Imputation (K=%d): %llu copies filled in %llu genotypes, %llu left missing, mean confidence %.6f\n", K,
+				 (unsigned long long)res.n_filled, (unsigned long long)res.n_genotypes, (unsigned long long)res.n_left, res.mean_conf);
+		if (!rc && o->write_files) rc = mc_write_filled(o, d, K, filled);
+		free(filled);
 	}
 	fclose(say);
 	mc_model_free(own);
@@ -663,7 +684,7 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 {
 	const int n_dev = n_workers(o), n_gpus = o->n_gpus < 1 ? 1 : o->n_gpus, n_units = (K == 1) ? 1 : o->n_init;
 	const int npar = mc_no_parameters(&o->em, md, K);
-	const int want_params = (!bootstrap && (o->write_files || o->cv_folds || o->se_replicates || (o->n_bootstrap && K == st->null_K))) || o->afile != NULL;
+	const int want_params = (!bootstrap && (o->write_files || o->cv_folds || o->se_replicates || o->fill || (o->n_bootstrap && K == st->null_K))) || o->afile != NULL;
 	const double max_logL_keep = st->sum.max_logL, aic_keep = st->sum.aic, bic_keep = st->sum.bic;
 	shard_worker *w = calloc((size_t)n_dev, sizeof *w);
 	pthread_t *th = calloc((size_t)n_dev, sizeof *th);
