@@ -408,6 +408,31 @@ class Context:
     def accel_update(self, to, base, j, s, qn_form=0):
         self._chk(self.lib.mchip_accel_update(self.h, to, base, j, s, qn_form))
 
+    def set_secant(self, which, j, p_part, q_part):
+        """secant buffer j (which = 0: u, 1: v) written whole, in the boundary's flat order: P part [K][T], Q part [I][K] or [K]"""
+        p = np.ascontiguousarray(p_part, dtype=np.float64)
+        q = np.ascontiguousarray(q_part, dtype=np.float64)
+        assert p.size == self.K * self.T and q.size == (self.I * self.K if self.indiv_q else self.K)
+        self._chk(self.lib.mchip_set_secant(self.h, which, j, p.ctypes.data, q.ctypes.data))
+
+    def get_secant(self, which, j):
+        """(P part [K][T], Q part [I][K] or [K]) of secant buffer j (which = 0: u, 1: v)"""
+        p = np.empty((self.K, self.T), dtype=np.float64)
+        q = np.empty((self.I, self.K) if self.indiv_q else (self.K,), dtype=np.float64)
+        self._chk(self.lib.mchip_get_secant(self.h, which, j, p.ctypes.data, q.ctypes.data))
+        return p, q
+
+    def multisecant_update(self, to, base, u_index, v_index=(), coef_a=(), coef_b=()):
+        """x[to] = x[base] + u[u_index], then += v[v_index[t]] * coef_a[t] * coef_b[t] term by term, projected"""
+        vi = np.ascontiguousarray(v_index, dtype=np.int32)
+        ca = np.ascontiguousarray(coef_a, dtype=np.float64)
+        cb = np.ascontiguousarray(coef_b, dtype=np.float64)
+        assert vi.ndim == 1 and vi.size == ca.size == cb.size
+        n = int(vi.size)
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._chk(self.lib.mchip_multisecant_update(self.h, to, base, u_index, n, vi.ctypes.data_as(ip) if n else None,
+                                                    ca.ctypes.data_as(dp) if n else None, cb.ctypes.data_as(dp) if n else None))
+
     def synchronize(self):
         self._chk(self.lib.mchip_synchronize(self.h))
 

@@ -881,24 +881,50 @@ int mco_em_2_steps(const mco_data *d, const mco_options *o, mco_model *m)
 	return 0;
 }
 
+/* the three sums of accel_em.c:143-184 over one secant pair, one serial chain each: the eta part, then the p part */
+void mco_step_dots(const double *uq, const double *vq, size_t nq, const double *up, const double *vp, size_t np, double *out3)
+{
+	double utu = 0, utvu = 0, vutvu = 0;
+	for (size_t x = 0; x < nq; x++) {
+		utu += uq[x] * uq[x];
+		utvu += uq[x] * (vq[x] - uq[x]);
+		vutvu += (vq[x] - uq[x]) * (vq[x] - uq[x]);
+	}
+	for (size_t x = 0; x < np; x++) {
+		utu += up[x] * up[x];
+		utvu += up[x] * (vp[x] - up[x]);
+		vutvu += (vp[x] - up[x]) * (vp[x] - up[x]);
+	}
+	out3[0] = utu; out3[1] = utvu; out3[2] = vutvu;
+}
+
+/* u1.u2 and u1.v2 of accel_em.c:291-310 as one serial chain each over flat arrays, the eta part first (qn_accelerated_update below
+ * walks the same terms cluster by cluster, as the reference does; this is the plain order the tests hold to their error bound) */
+void mco_secant_dots(const double *u1q, const double *u2q, const double *v2q, size_t nq,
+		     const double *u1p, const double *u2p, const double *v2p, size_t np, double *out2)
+{
+	double utu = 0, utv = 0;
+	for (size_t x = 0; x < nq; x++) {
+		utu += u1q[x] * u2q[x];
+		utv += u1q[x] * v2q[x];
+	}
+	for (size_t x = 0; x < np; x++) {
+		utu += u1p[x] * u2p[x];
+		utv += u1p[x] * v2p[x];
+	}
+	out2[0] = utu; out2[1] = utv;
+}
+
 double mco_step_size(const mco_data *d, const mco_options *o, mco_model *m)
 {
 	/* accel_em.c:130-243: eta terms first, then p in k,l,m order (flat [K][T] order is the same) */
 	const size_t KT = (size_t)m->K * m->dat->T;
 	const double *uq = m->u_q[m->delta_index], *vq = m->v_q[m->delta_index];
 	const double *up = m->u_p[m->delta_index], *vp = m->v_p[m->delta_index];
-	double utu = 0, utvu = 0, vutvu = 0, s;
+	double dots[3], utu, utvu, vutvu, s;
 	(void)d;
-	for (int x = 0; x < m->nq; x++) {
-		utu += uq[x] * uq[x];
-		utvu += uq[x] * (vq[x] - uq[x]);
-		vutvu += (vq[x] - uq[x]) * (vq[x] - uq[x]);
-	}
-	for (size_t x = 0; x < KT; x++) {
-		utu += up[x] * up[x];
-		utvu += up[x] * (vp[x] - up[x]);
-		vutvu += (vp[x] - up[x]) * (vp[x] - up[x]);
-	}
+	mco_step_dots(uq, vq, (size_t)m->nq, up, vp, KT, dots);
+	utu = dots[0]; utvu = dots[1]; vutvu = dots[2];
 	if (o->accel_scheme == MCO_SQS1) s = utu / utvu;
 	else if (o->accel_scheme == MCO_SQS2) s = utvu / vutvu;
 	else if (o->accel_scheme == MCO_SQS3) {

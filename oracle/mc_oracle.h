@@ -12,6 +12,7 @@
  */
 #ifndef MC_ORACLE_H
 #define MC_ORACLE_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -104,6 +105,9 @@ double mco_log_likelihood(const mco_data *d, const mco_options *o, mco_model *m,
 /* em_alg.c:1072-1211 */
 int mco_em_2_steps(const mco_data *d, const mco_options *o, mco_model *m);
 /* accel_em.c:130-243 */
+void mco_step_dots(const double *uq, const double *vq, size_t nq, const double *up, const double *vp, size_t np, double *out3);
+void mco_secant_dots(const double *u1q, const double *u2q, const double *v2q, size_t nq,
+		     const double *u1p, const double *u2p, const double *v2p, size_t np, double *out2);
 double mco_step_size(const mco_data *d, const mco_options *o, mco_model *m);
 /* accel_em.c:422-551 */
 double mco_accelerated_update(const mco_data *d, const mco_options *o, mco_model *m, double s);

@@ -77,6 +77,10 @@ def _load():
     lib.mco_log_likelihood.argtypes = [vp, C.POINTER(Options), vp, i32]
     lib.mco_log_likelihood.restype = C.c_double
     lib.mco_em_2_steps.argtypes = [vp, C.POINTER(Options), vp]
+    lib.mco_step_dots.argtypes = [dp, dp, C.c_size_t, dp, dp, C.c_size_t, dp]
+    lib.mco_step_dots.restype = None
+    lib.mco_secant_dots.argtypes = [dp, dp, dp, C.c_size_t, dp, dp, dp, C.c_size_t, dp]
+    lib.mco_secant_dots.restype = None
     lib.mco_step_size.argtypes = [vp, C.POINTER(Options), vp]
     lib.mco_step_size.restype = C.c_double
     lib.mco_accelerated_update.argtypes = [vp, C.POINTER(Options), vp, C.c_double]
@@ -219,6 +223,27 @@ def michelot(x, minimum, total=1.0):
     x = np.array(x, dtype=np.float64)
     lib.mco_michelot_project(x.ctypes.data_as(C.POINTER(C.c_double)), len(x), total, minimum)
     return x
+
+
+def _flat(a):
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def step_dots(uq, vq, up, vp):
+    """[u.u, u.(v - u), (v - u).(v - u)] as mco_step_size adds them up: one serial chain each, the eta part and then the p part"""
+    (uq, a), (vq, b), (up, c), (vp, d) = _flat(uq), _flat(vq), _flat(up), _flat(vp)
+    out = (C.c_double * 3)()
+    lib.mco_step_dots(a, b, uq.size, c, d, up.size, out)
+    return list(out)
+
+
+def secant_dots(u1q, u2q, v2q, u1p, u2p, v2p):
+    """[u1.u2, u1.v2], one serial chain each over the flat arrays, the eta part and then the p part"""
+    (u1q, a), (u2q, b), (v2q, c), (u1p, d), (u2p, e), (v2p, f) = (_flat(x) for x in (u1q, u2q, v2q, u1p, u2p, v2p))
+    out = (C.c_double * 2)()
+    lib.mco_secant_dots(a, b, c, u1q.size, d, e, f, u1p.size, out)
+    return list(out)
 
 
 def glibc_window(seed, skip=0):
