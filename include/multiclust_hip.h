@@ -201,7 +201,12 @@ int mchip_accel_run(mchip_context *ctx, int slot, int scheme, int n_cycles, mchi
 
 /* E step only (em_e_step's trailing E step, em_alg.c:226,230): refreshes the expected counts, returns logL. */
 int mchip_e_step(mchip_context *ctx, int slot, double *loglik);
-/* log_likelihood(): logL_admixture / logL_mixture (log_likelihood.c:96-147, 157-232). */
+/* log_likelihood(): logL_admixture / logL_mixture (log_likelihood.c:96-147, 157-232).  Two departures from logL_mixture,
+ * both where the reference gives no usable number: an individual without one ordinary log-sum (all NaN or -inf, or one
+ * +inf) makes the result NaN where the reference's rescaling loop never ends; and where the reference's rescaled sum
+ * overflows (exp(max) == 0, the halved maximum within ln S of log DBL_MAX, clusters of total weight S >= 1.32 relative to
+ * the best) and its result is +inf, the individual's term is log sum_k exp(v_k - max) + max, e_step_mixture's form.
+ * Every result that is finite in the reference's arithmetic keeps its bits. */
 int mchip_loglik(mchip_context *ctx, int slot, double *loglik);
 /* The same value, computed by the pass that also accumulates the E step's per-individual sums and keeps them: an
  * mchip_em_step from this slot that follows (no parameter write in between) skips that pass.  accelerated_update's

@@ -1471,7 +1471,20 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_mix_finalize(int I, int n_lchun
 				temp_exp = 0.0;
 #pragma unroll
 				for (int k = 0; k < K; k++) temp_exp = temp_exp + exp(v[k]);
-				ll = log(temp_exp) + scale_exp;
+				if (temp_exp == HUGE_VAL) {
+					/* NOT the reference.  Its halving leaves the shifted maximum anywhere in (354.9, 709.78]; within ln S of
+					 * the upper end, with clusters of total weight S relative to the best one (two tied ones are enough), the
+					 * sum above overflows and the reference's term is +inf: a log likelihood that passes stop()'s NaN exit and
+					 * wins every `ll > emll`.  Such a term is taken in mode 0's form instead, log sum_k exp(v_k - max) + max.
+					 * Taken only where the reference's arithmetic gives +inf: every finite result keeps its bits. */
+					const double top = mx - scale_exp;	/* the shifted maximum */
+					temp_exp = 0.0;
+#pragma unroll
+					for (int k = 0; k < K; k++) temp_exp = temp_exp + exp(v[k] - top);
+					ll = log(temp_exp) + mx;
+				} else {
+					ll = log(temp_exp) + scale_exp;
+				}
 			}
 		}
 	}
