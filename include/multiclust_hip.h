@@ -375,6 +375,34 @@ int mchip_impute_missing(mchip_context *ctx, int slot, const int32_t *n_real /* 
 			 uint8_t *geno_out /* [I][L][ploidy] */, double *conf_out /* [I][L] or NULL */,
 			 uint64_t *n_filled, uint64_t *n_left, uint64_t *n_genotypes, double *sum_conf);
 
+/* ---- divergence of the fitted clusters (an extension: the tables STRUCTURE and ADMIXTURE end a fit with) ----
+ * P is the table of `slot`: p_klm for cluster k, locus l and column m over ALL uniquealleles[l] columns of the locus, the phantom
+ * slot included, whatever the M step left there; T columns in all.  L1 = the loci with at least one column; a locus with
+ * uniquealleles[l] = 0 contributes nothing and is not counted.  Every quantity is a sum of non-negative terms: none is formed by
+ * subtracting Gram-matrix entries, so two nearly equal clusters get their distance to full relative precision.
+ * Per cluster and pair, over the T columns:
+ *   het[a]          h_a = sum_c p_a (1 - p_a); the expected heterozygosity is H_a = h_a / L1;
+ *   sqdiff[a*K+b]   s_ab = sum_c (p_a - p_b)^2, symmetric, 0 on the diagonal; the net distance (STRUCTURE's table) is
+ *                   D_ab = s_ab / (2 L1), and Hudson's F_ST as a ratio of sums F_ab = D_ab / (D_ab + (H_a + H_b) / 2), NaN when the
+ *                   denominator is 0.
+ * Among the K clusters with weights[k] >= 0 (they are used as given: the caller makes them sum to 1), per locus:
+ *   pbar_lm         = sum_k w_k p_klm as an fma chain in k order from 0 -- this double IS pbar in what follows;
+ *   locus_ht[l]     HT_l = sum_m pbar_lm (1 - pbar_lm);
+ *   locus_v[l]      V_l = sum_m sum_k w_k (p_klm - pbar_lm)^2, which is H_T - H_S in its non-negative form; both are 0 for a locus
+ *                   without a column.  F_l = V_l / HT_l, NaN when HT_l = 0 or the locus has no column;
+ *   *sum_v, *sum_ht sum_l V_l and sum_l HT_l: overall F = sum_v / sum_ht;   *n_loci = L1.
+ * locus_v and locus_ht may be NULL; the other pointers are required.  Both models (the mixture model's P as well).  Every sum is
+ * combined in an order fixed by T, L and K alone, without floating-point atomics: the same state gives the same bits on any device
+ * and under any geometry knob of the environment.
+ * Writes its host arrays and nothing else: no parameter slot, secant, expected count, held S-side sum, data set, fold or saved set
+ * changes.
+ * MCHIP_ERR_STATE without a data set or model; MCHIP_ERR_INVALID for a slot out of range, a null required pointer, a weight that is
+ * negative, infinite or NaN, or weights that are all zero -- all checked before anything runs, the arrays stay untouched.
+ */
+int mchip_divergence(mchip_context *ctx, int slot, const double *weights /* [K] */, double *het /* [K] */,
+		     double *sqdiff /* [K][K] */, double *locus_v /* [L] or NULL */, double *locus_ht /* [L] or NULL */,
+		     double *sum_v, double *sum_ht, int32_t *n_loci);
+
 /* ---- a selection of loci with repeats: the data sets of the non-parametric bootstrap over loci (an extension) ----
  * Let the base be the data set the context held when the first resample was asked for (I, L_base, ploidy, uniquealleles,
  * genotypes).  After the call the context holds exactly what

@@ -101,6 +101,7 @@ def load():
         "mchip_resample_loci": ([vp, vp, i32], i32),
         "mchip_fit_q_rows": ([vp, i32, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp], i32),
         "mchip_impute_missing": ([vp, i32, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp], i32),
+        "mchip_divergence": ([vp, i32, vp, vp, vp, vp, vp, dp, dp, ip], i32),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("MCHIP_ALLOW_PARTIAL_ABI") == "1" and not hasattr(lib, name):
@@ -124,7 +125,7 @@ ABI_SYMBOLS = [
     "mchip_comm_last_error", "mchip_comm_info", "mchip_progress_report", "mchip_progress_note",
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
-    "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing",
+    "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
 ]
 
 
@@ -256,6 +257,19 @@ class Context:
         self._chk(self.lib.mchip_impute_missing(self.h, slot, nr.ctypes.data, g.ctypes.data, None if c is None else c.ctypes.data,
                                                 C.byref(nf), C.byref(nl), C.byref(ng), C.byref(sc)))
         return g, c, nf.value, nl.value, ng.value, sc.value
+
+    def divergence(self, slot, weights, loci=True):
+        """mchip_divergence: the divergence of the clusters of `slot` (include/multiclust_hip.h): dict with het [K], sqdiff [K][K],
+        locus_v and locus_ht [L] (None without `loci`), sum_v, sum_ht, n_loci."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.shape == (self.K,)
+        het, sq = np.empty(self.K), np.empty((self.K, self.K))
+        lv, lht = (np.empty(self.L), np.empty(self.L)) if loci else (None, None)
+        sv, sht, n1 = C.c_double(), C.c_double(), C.c_int()
+        self._chk(self.lib.mchip_divergence(self.h, slot, w.ctypes.data, het.ctypes.data, sq.ctypes.data,
+                                            None if lv is None else lv.ctypes.data, None if lht is None else lht.ctypes.data,
+                                            C.byref(sv), C.byref(sht), C.byref(n1)))
+        return dict(het=het, sqdiff=sq, locus_v=lv, locus_ht=lht, sum_v=sv.value, sum_ht=sht.value, n_loci=n1.value)
 
     def resample_loci(self, src):
         """install the selection `src` (locus indices into the base, repeats allowed) of the base: the data set held when the first

@@ -91,6 +91,14 @@ class McImputeResult(C.Structure):
                 ("mean_conf", C.c_double)]
 
 
+class McDivergenceResult(C.Structure):
+    """mc_divergence_result (multiclust_amd/host/mc_host.h)"""
+    _fields_ = [("K", C.c_int), ("L", C.c_int), ("n_loci", C.c_int), ("n_pairs", C.c_int), ("f_mean", C.c_double),
+                ("f_min", C.c_double), ("f_max", C.c_double), ("sum_v", C.c_double), ("sum_ht", C.c_double), ("f_all", C.c_double),
+                ("w", C.POINTER(C.c_double)), ("H", C.POINTER(C.c_double)), ("D", C.POINTER(C.c_double)),
+                ("F", C.POINTER(C.c_double)), ("locus_ht", C.POINTER(C.c_double)), ("locus_f", C.POINTER(C.c_double))]
+
+
 class CliOptions(C.Structure):
     """mc_cli_options (multiclust_amd/host/mc_cli.h)"""
     _fields_ = [("em", McOptions), ("filename", C.c_char_p), ("filename_file", C.c_char_p), ("path", C.c_char_p),
@@ -101,8 +109,8 @@ class CliOptions(C.Structure):
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
                 ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
-    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block, query_file and fill, the command line's --cv, --se,
-    # --query and --fill: only mc_main.c reads them, the readers and writers this mirror is handed to stop at bed_prefix)
+    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block, query_file, fill and fst, the command line's --cv, --se,
+    # --query, --fill and --fst: only mc_main.c reads them, the readers and writers this mirror is handed to stop at bed_prefix)
 
 
 class CliData(C.Structure):
@@ -245,6 +253,29 @@ def impute_n_real(ua, geno=None, bed=None, I=None):
     return out
 
 
+def divergence_weights(q, K):
+    """mc_divergence_weights (host/mc_diverge.c): the weights --fst gives the clusters from a fit's Q: the column means of q [I][K]
+    over the rows without a NaN (1 / K when there is none), or q [K] itself"""
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    w = np.empty(K)
+    load().mc_divergence_weights(K, q.shape[0] if q.ndim == 2 else 0, q.ctypes.data, w.ctypes.data)
+    return w
+
+
+def divergence_tables(het, sqdiff, n_loci):
+    """mc_divergence_tables and mc_divergence_summary (host/mc_diverge.c): (H [K], D [K][K], F [K][K], (pairs with a number,
+    their mean, smallest, largest F)) from the device's sums"""
+    het = np.ascontiguousarray(het, dtype=np.float64)
+    sq = np.ascontiguousarray(sqdiff, dtype=np.float64)
+    K = het.size
+    H, D, F = np.empty(K), np.empty((K, K)), np.empty((K, K))
+    lib = load()
+    lib.mc_divergence_tables(K, n_loci, het.ctypes.data, sq.ctypes.data, H.ctypes.data, D.ctypes.data, F.ctypes.data)
+    n, mean, lo, hi = C.c_int(), C.c_double(), C.c_double(), C.c_double()
+    lib.mc_divergence_summary(K, F.ctypes.data, C.byref(n), C.byref(mean), C.byref(lo), C.byref(hi))
+    return H, D, F, (n.value, mean.value, lo.value, hi.value)
+
+
 def query_read(path, I):
     """mc_query_read (host/mc_query.c) on a query file: (status, None) on failure, else (0, mask [I] uint8)"""
     lib = load()
@@ -345,6 +376,15 @@ def load():
     lib.mc_query_result_free.restype = None
     lib.mc_impute.argtypes = [OP, DP, MP, C.c_void_p, C.POINTER(McImputeResult)]
     lib.mc_impute_n_real.argtypes = [DP, C.c_void_p]
+    lib.mc_divergence.argtypes = [OP, DP, MP, C.POINTER(McDivergenceResult)]
+    lib.mc_divergence_result_free.argtypes = [C.POINTER(McDivergenceResult)]
+    lib.mc_divergence_result_free.restype = None
+    lib.mc_divergence_weights.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mc_divergence_weights.restype = None
+    lib.mc_divergence_tables.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.mc_divergence_tables.restype = None
+    lib.mc_divergence_summary.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 3
+    lib.mc_divergence_summary.restype = None
     lib.mc_read_structure.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
     lib.mc_read_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
     lib.mc_free_data.argtypes = [C.POINTER(CliData)]
@@ -515,6 +555,22 @@ class Fit:
         if rc:
             raise hip.HipError("mc_impute failed (%d)" % rc)
         return g, dict(n_filled=r.n_filled, n_left=r.n_left, n_genotypes=r.n_genotypes, sum_conf=r.sum_conf, mean_conf=r.mean_conf)
+
+    def divergence(self):
+        """mc_divergence on the estimate in slot mod.pindex: dict with w, H [K], D, F [K][K], locus_ht, locus_f [L], n_loci, n_pairs,
+        f_mean, f_min, f_max, sum_v, sum_ht, f_all (multiclust_amd/host/mc_host.h).  Leaves the model as it found it."""
+        r = McDivergenceResult()
+        rc = self.lib.mc_divergence(C.byref(self.opt), C.byref(self.dat), self.mp, C.byref(r))
+        if rc:
+            raise hip.HipError("mc_divergence failed (%d)" % rc)
+        K, L = r.K, r.L
+        out = dict(w=np.ctypeslib.as_array(r.w, shape=(K,)).copy(), H=np.ctypeslib.as_array(r.H, shape=(K,)).copy(),
+                   D=np.ctypeslib.as_array(r.D, shape=(K, K)).copy(), F=np.ctypeslib.as_array(r.F, shape=(K, K)).copy(),
+                   locus_ht=np.ctypeslib.as_array(r.locus_ht, shape=(L,)).copy(),
+                   locus_f=np.ctypeslib.as_array(r.locus_f, shape=(L,)).copy(), n_loci=r.n_loci, n_pairs=r.n_pairs,
+                   f_mean=r.f_mean, f_min=r.f_min, f_max=r.f_max, sum_v=r.sum_v, sum_ht=r.sum_ht, f_all=r.f_all)
+        self.lib.mc_divergence_result_free(C.byref(r))
+        return out
 
     def locus_lists(self, n_replicates, block=1):
         """the locus lists mc_locus_bootstrap installs for these arguments and the options' seed, one int32 array per replicate"""

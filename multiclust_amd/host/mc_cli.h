@@ -53,6 +53,7 @@ typedef struct mc_cli_options {
 	const char *query_file;		/* --query <file> (extension): I tokens 0 (panel) / 1 (query); the query individuals are hidden from every
 					 * fit and fitted against the best fit of every K afterwards (mc_query.c) */
 	int fill;			/* --fill (extension): the missing genotypes filled from the best fit of every K (mc_impute.c) */
+	int fst;			/* --fst (extension): divergence of the clusters of the best fit of every K (mc_diverge.c) */
 } mc_cli_options;
 
 typedef struct mc_cli_data {
@@ -140,5 +141,11 @@ int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows,
 int mc_write_filled_structure(const mc_cli_options *opt, const mc_cli_data *dat, const uint8_t *filled, const char *out_path);
 int mc_write_filled_bed(const mc_cli_options *opt, const mc_cli_data *dat, const uint8_t *filled, const char *out_prefix);
 int mc_write_filled(const mc_cli_options *opt, const mc_cli_data *dat, int K, const uint8_t *filled);
+
+/* --fst (an extension, mc_diverge.c): <stem>.<admix|mix>.K=<K>.fst.txt -- per cluster its weight and expected heterozygosity, then
+ * the K x K net-distance matrix and the K x K F_ST matrix -- and <stem>.<admix|mix>.K=<K>.fst.loci.txt -- per locus its index, its
+ * number of columns, HT_l and F_l; the formats are in the header comment of mc_diverge.c.  Returns 0 or an exit status of the enum
+ * above. */
+int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const mc_divergence_result *r);
 
 #endif

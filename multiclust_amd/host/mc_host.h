@@ -337,6 +337,30 @@ typedef struct mc_impute_result { uint64_t n_filled, n_left, n_genotypes; double
 int mc_impute_n_real(const mc_data *dat, int32_t *n_real /* [L] */);
 int mc_impute(const mc_options *opt, const mc_data *dat, mc_model *mod, uint8_t *geno_out /* [I][L][ploidy] */, mc_impute_result *out);
 
+/* ---- divergence of the fitted clusters (mc_diverge.c; an extension) ----
+ * `mod` holds a fit in slot mod->pindex; either model.  The weights of the clusters come from that slot's Q (mc_model_get_q): the
+ * column means over the rows that are not NaN under the admixture model with individual mixing proportions -- individuals without
+ * an observed copy and query individuals drop out; 1 / K when no row is left -- and eta itself under shared mixing proportions and
+ * the mixture model (mc_divergence_weights: n_rows = I or 0).  mchip_divergence (include/multiclust_hip.h has every definition)
+ * gives the sums over the slot's P; from them w [K], H [K] the expected heterozygosity of every cluster, D [K][K] the net distance
+ * and F [K][K] Hudson's F_ST of every pair (mc_divergence_tables), locus_ht [L] and locus_f [L] = V_l / HT_l (NaN where HT_l = 0
+ * or the locus has no column), sum_v, sum_ht and f_all = sum_v / sum_ht, and over the pairs a < b whose F_ab is a number their count
+ * n_pairs, f_mean, f_min and f_max (mc_divergence_summary; NaN without such a pair).  n_loci: the loci with a column.
+ * Nothing of the model or the context changes.  Release the arrays with mc_divergence_result_free; on failure nothing is held. */
+typedef struct mc_divergence_result {
+	int K, L, n_loci, n_pairs;
+	double f_mean, f_min, f_max, sum_v, sum_ht, f_all;
+	double *w, *H, *D, *F, *locus_ht, *locus_f;
+} mc_divergence_result;
+void mc_divergence_weights(int K, int n_rows, const double *q, double *w /* [K] */);
+void mc_divergence_tables(int K, int n_loci, const double *het /* [K] */, const double *sqdiff /* [K][K] */, double *H, double *D, double *F);
+void mc_divergence_summary(int K, const double *F /* [K][K] */, int *n_pairs, double *mean, double *min, double *max);
+int mc_divergence(const mc_options *opt, const mc_data *dat, mc_model *mod, mc_divergence_result *out);
+void mc_divergence_result_free(mc_divergence_result *r);
+/* "Divergence (K=<K>): pairwise Fst mean <%.6f> min <%.6f> max <%.6f> over <n> pairs; among clusters <%.6f> [<L1> loci]", with
+ * "no pairs" for the pairwise part when there is none (K = 1); no line end */
+void mc_divergence_line(FILE *fp, const mc_divergence_result *r);
+
 /* ---- opt-in watchdog (mc_watchdog.c): nothing in the reference corresponds -- it has nothing to wait for ----
  * mc_watchdog_start(s): a detached thread that polls the library's event count (mchip_progress_report) and, when it has stood
  * still for s seconds, prints where every thread stands (library record + /proc/self/task) on stderr and leaves with _exit(3).
