@@ -1,6 +1,6 @@
 /*
  * mchip_context.h -- the per-context state of libmulticlust_hip.so and the few helpers of mchip.hip that the units holding a
- * data-set feature's kernels and entry points call (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_impute.hip, mchip_query.hip, mchip_resample.hip).
+ * data-set feature's kernels and entry points call (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_generators.hip, mchip_impute.hip, mchip_query.hip, mchip_resample.hip).
  * Private to the library's host-side units; not part of the C-ABI, and mchip_kernels_k.hip does not include it.
  */
 #ifndef MCHIP_CONTEXT_H
@@ -10,6 +10,7 @@
 #include "mchip_progress.h"
 
 #include <functional>
+#include <type_traits>
 #include <stdio.h>
 #include <string.h>
 
@@ -152,6 +153,33 @@ template <typename Tp> struct scoped_dev {
 	operator Tp *() const { return p; }
 };
 
+/* a buffer kept in the context from one call to the next, grown when a call needs more: nothing happens while it is large enough
+ * (a hipFree waits for the whole device, i.e. for every other stream's fits); otherwise the stream is drained, the buffer freed
+ * and one of want_bytes allocated.  On failure the buffer is gone and *have_bytes is 0. */
+template <typename Tp> static hipError_t grow_dev(mchip_context *ctx, Tp **p, size_t *have_bytes, size_t want_bytes)
+{
+	if (*have_bytes >= want_bytes) return hipSuccess;
+	if (*p) { (void)MCHIP_WAIT(hipStreamSynchronize(ctx->stream)); (void)MCHIP_WAIT(hipFree(*p)); *p = nullptr; *have_bytes = 0; }
+	const hipError_t e = hipMalloc((void **)p, want_bytes);
+	if (e == hipSuccess) *have_bytes = want_bytes;
+	return e;
+}
+
+/* f(std::integral_constant<int, PL>) for the kernels instantiated per ploidy 1..8 (the callers have checked pl <= 8) */
+template <typename F> static void with_ploidy(int pl, F &&f)
+{
+	switch (pl) {
+	case 1: f(std::integral_constant<int, 1>()); break;
+	case 2: f(std::integral_constant<int, 2>()); break;
+	case 3: f(std::integral_constant<int, 3>()); break;
+	case 4: f(std::integral_constant<int, 4>()); break;
+	case 5: f(std::integral_constant<int, 5>()); break;
+	case 6: f(std::integral_constant<int, 6>()); break;
+	case 7: f(std::integral_constant<int, 7>()); break;
+	default: f(std::integral_constant<int, 8>()); break;
+	}
+}
+
 static inline unsigned nblk(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
 /* for the byte-per-thread layout kernels (grid-stride loops): at most 2^30 work-items per launch */
 static inline unsigned nblk_capped(size_t n, unsigned b = 256)
@@ -191,10 +219,23 @@ int install_saved(mchip_context *ctx, const saved_set &set);
  * [I][L][ploidy] of the installed shape to d_out and sets d_seen[i] (zeroed here) = 1 for every individual that keeps an observed
  * copy. */
 int install_derived(mchip_context *ctx, const std::function<void(uint8_t *d_out, uint8_t *d_seen)> &fill);
-/* rand() % m for the n_draws draws that follow `window`, one byte each, to d_out: whole chunks of RNG_CHUNK bytes are written */
-int draw_mod_stream(mchip_context *ctx, const uint32_t *window, size_t n_draws, int m, uint8_t *d_out);
+/* one byte per allele copy in stream order, padded to whole generator chunks (ctx->d_draw), allocated on first use */
+int stream_buffer(mchip_context *ctx);
+/* genotype held on the device as [I][L][ploidy] bytes -> the kernels' layouts (validated), packed counts */
+int install_raw(mchip_context *ctx, const uint8_t *d_raw);
+/* the hard partition: argument checks of its entry points; relayout of a partition held in stream order + M step into slot `to`;
+ * normalisation of counts already in Spart and n_aslabs slabs of Apart */
+int check_partition_call(mchip_context *ctx, const void *arg, int to);
+int partition_mstep(mchip_context *ctx, const uint8_t *d_raw, int to, int counts = 0);
+int partition_finalize(mchip_context *ctx, int to, int counts, int n_aslabs);
 /* out[0] = in[0] + ... + in[n - 1] in k_reduce_sum's fixed order, one workgroup */
 void launch_reduce_sum(mchip_context *ctx, const double *in, int n, double *out);
+
+/* mchip_generators.hip */
+/* rand() % m for the n_draws draws that follow `window`, one byte each, to d_out: whole chunks of RNG_CHUNK bytes are written */
+int draw_mod_stream(mchip_context *ctx, const uint32_t *window, size_t n_draws, int m, uint8_t *d_out);
+/* the jump tables of the rand() stream, the tiled partition's slabs and the generated individuals' clusters go with the data set */
+void drop_generators(mchip_context *ctx);
 
 /* mchip_cv.hip: folds, the saved full data set and a hold-out in force belong to the data set that goes */
 void drop_cv(mchip_context *ctx);

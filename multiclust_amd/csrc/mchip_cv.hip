@@ -1,7 +1,7 @@
 /*
  * mchip_cv.hip -- K-fold cross-validation of the admixture model: the mchip_cv_* entry points and the kernels behind
  * mchip_cv_hold_out and mchip_cv_heldout_loglik (include/multiclust_hip.h has the contract; mchip_context.h the per-context
- * state and the install path; the fold draw is draw_mod_stream with m := n_folds and lives in mchip.hip with the generator).
+ * state and the install path; the fold draw is draw_mod_stream with m := n_folds and lives in mchip_generators.hip with the generator).
  *
  *   k_cv_mask    a thread per genotype: copies its `ploidy` bytes of the saved full data set into the stream buffer, or 0xFF when
  *                the genotype's fold is the one held out; marks the individuals that keep an observed copy.

@@ -65,7 +65,7 @@ if os.environ.get("INITBENCH_BOOTSTRAP", "1") != "0":
         d = rs.dirichlet(np.full(M, 0.5), (Kb, cols.size))
         for m in range(M):
             p[:, cols + m] = d[:, :, m]
-    for rep in range(3):
+    for rep in range(a.reps):
         t0 = time.perf_counter()
         ctx.simulate_genotypes(a.I, a.L, a.ploidy, ua, window, Kb, q, p)
         ctx.synchronize()
@@ -87,3 +87,11 @@ if os.environ.get("INITBENCH_BOOTSTRAP", "1") != "0":
     print("host bootstrap data set: %.2f s for %d of %d individuals -> %.1f s for all (one core), + upload" %
           (t1 - t0, sub, a.I, (t1 - t0) * a.I / sub), flush=True)
     print("first individuals identical:", bool(np.array_equal(ctx.get_genotypes()[:sub], out)))
+    # the mixture model's replicate: one eta shared by all individuals, the same p
+    eta = rs.dirichlet(np.full(Kb, 0.3))
+    for rep in range(a.reps):
+        t0 = time.perf_counter()
+        ctx.simulate_genotypes_mixture(a.I, a.L, a.ploidy, ua, window, Kb, eta, p)
+        ctx.synchronize()
+        t1 = time.perf_counter()
+        print("device mixture bootstrap data set (generate + layouts + counts): %.1f ms" % ((t1 - t0) * 1e3), flush=True)

@@ -1,6 +1,6 @@
 """Windows of the libc rand() stream chosen by the draws they lead to (TEST INFRASTRUCTURE).
 
-glibc's rand() is x_j = x_{j-31} + x_{j-3} (mod 2^32), rand() = x_j >> 1 (oracle_bind.glibc_window, mchip.hip).  The recurrence
+glibc's rand() is x_j = x_{j-31} + x_{j-3} (mod 2^32), rand() = x_j >> 1 (oracle_bind.glibc_window, mchip_generators.hip).  The recurrence
 runs backwards as well, x_{j-31} = x_j - x_{j-3}, so any 31 consecutive words fix the whole stream: `window_placing` puts
 chosen draws at draw P..P+30 (the low bit of each word is free) and steps back to the 31 words behind draw 0, the form
 mchip_simulate_genotypes, mchip_mstep_from_rand_partition and `ref_time --bootstrap` take.  `draws` runs a window forwards."""

@@ -57,7 +57,7 @@ def test_host_bootstrap_equals_reference(name):
 
 
 def walk_threshold(c):
-    """k_walk_tables' rule (multiclust_amd/csrc/mchip.hip: walk_threshold), restated: the smallest v in [0, 2^31] with
+    """k_walk_tables' rule (multiclust_amd/csrc/mchip_generators.hip: walk_threshold), restated: the smallest v in [0, 2^31] with
     float64(v) / RAND_MAX > c."""
     D = 2147483647.0
     if not (c < 2.0):

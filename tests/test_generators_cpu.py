@@ -10,7 +10,7 @@
     = host = device holds on adversarial inputs, not only on the natural ones of the golden fixtures;
   * the device's integer form of the inverse-CDF walk (k_walk_tables: thresholds of the running maximum of the partial sums),
     restated, against the reference's walk on rows with negative entries, zeros and NaN;
-  * mod_k_magic (mchip.hip), restated: the multiply-shift remainder the partition kernels take is exact for every K <= 64."""
+  * mod_k_magic (mchip_generators.hip), restated: the multiply-shift remainder the partition kernels take is exact for every K <= 64."""
 import ctypes as C
 import os
 import subprocess
@@ -317,7 +317,7 @@ def fixed_thresholds(w):
 
 
 def search(tab, v):
-    """walk_search (mchip.hip), restated"""
+    """walk_search (mchip_generators.hip), restated"""
     lo, n = 0, len(tab)
     while n > 1:
         half = n >> 1

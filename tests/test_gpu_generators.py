@@ -31,7 +31,7 @@ from test_gpu_kernel_matrix import count_bits, geometry
 RAND_MAX = rw.RAND_MAX
 
 # ---------------------------------------------------------------------------------------------------------------- DISPATCH RULE
-SIM_QW, SIM_PW = 8, 4        # mchip.hip: widths of the FAST form's threshold rows
+SIM_QW, SIM_PW = 8, 4        # mchip_generators.hip: widths of the FAST form's threshold rows
 RNG_CHUNK = 4 * 31 * 32      # mchip_context.h: draws per thread of the chunked generators
 SIM_COPIES = RNG_CHUNK // 2  # copies per thread of k_simulate_admixture
 

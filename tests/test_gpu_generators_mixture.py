@@ -26,8 +26,8 @@ from test_generators_cpu import (EDGE_DRAWS, FAMILIES, TIE_P, TIE_Q, counts_of, 
 from test_gpu_generators import NO_SIM_TILE, context_for, contexts, sim_ua  # noqa: F401 (contexts is a fixture)
 
 # ---------------------------------------------------------------------------------------------------------------- DISPATCH RULE
-SIM_PW = 4                   # mchip.hip: width of the padded allele rows
-MIX_GENERAL_CHUNK = 64       # mchip.hip: loci per workgroup of the general form
+SIM_PW = 4                   # mchip_generators.hip: width of the padded allele rows
+MIX_GENERAL_CHUNK = 64       # mchip_generators.hip: loci per workgroup of the general form
 
 
 def mix_form(max_M, ploidy, knobs):
