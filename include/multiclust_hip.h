@@ -475,7 +475,13 @@ int mchip_profile_begin(mchip_context *ctx);
  * sums of the extrapolated point and the log likelihood of the second EM iterate in one pass; then [2] has no launches).
  * Launches that returned at once (batched runs: after the stopping
  * rule fired, or the S-side pass whose sums were already in place) took under 5 % of the kind's longest launch and are
- * left out of both figures. */
+ * left out of both figures.
+ * Where an E step runs its column pass and its individual pass as ONE launch (the paired E step: diploid data on packed
+ * counts, K <= 12; MCHIP_NO_PAIR=1 turns it off) no event pair can bracket either pass.  [0] and [1] then take, per launch,
+ * the span from the first start to the last end of that pass's workgroups, read from the device's constant-rate clock, and
+ * still count one launch each.  The two spans of a launch OVERLAP -- both run for nearly the whole launch -- so [0] + [1]
+ * exceeds the time the E steps took; total_ms is unaffected.  A pass whose workgroups all returned at once (cached sums,
+ * stopped run) has no span and is left out, as above. */
 #define MCHIP_PROF_KINDS 4
 int mchip_profile_end(mchip_context *ctx, double *total_ms, double *kernel_ms, int *launches);
 /* device properties the bench reports (name, CU count, memory) */

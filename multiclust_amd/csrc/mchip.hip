@@ -72,6 +72,7 @@ static void read_knobs(mchip_context *ctx)
 	ctx->knob.no_dual = on("MCHIP_NO_DUAL");
 	ctx->knob.no_slab_sum = on("MCHIP_NO_SLAB_SUM");
 	ctx->knob.no_fused_finalize = on("MCHIP_NO_FUSED_FINALIZE");
+	ctx->knob.no_pair = on("MCHIP_NO_PAIR");
 	ctx->knob.no_col_split = on("MCHIP_NO_COL_SPLIT");
 	ctx->knob.part_no_tile = on("MCHIP_PART_NO_TILE");
 	ctx->knob.sim_no_tile = on("MCHIP_SIM_NO_TILE");
@@ -954,6 +955,68 @@ static void prof_mark(mchip_context *ctx, int kind, bool start)
 	if (start) ctx->ev_kind.push_back(kind);
 }
 
+/* Profiled paired E steps (k_estep_pair).  The two kinds of block of such a launch overlap, so no pair of events brackets either
+ * pass: every block leaves two clock readings in d_pair_marks, and this one-block launch behind it takes, per kind, the first
+ * start and the last end of the blocks that worked (mchip_pair_span; start > end where none did).  mchip_profile_end turns the
+ * spans into the two passes' durations. */
+constexpr size_t PAIR_SPAN_CHUNK = 1024;	/* spans per device allocation */
+constexpr int PAIR_SPAN_THREADS = 1024;		/* one thread per run of MCHIP_PAIR_RUN blocks: the kind is worked out once per run */
+__global__ __launch_bounds__(PAIR_SPAN_THREADS) void k_pair_spans(const unsigned long long *__restrict__ marks, unsigned n_blocks, mchip_pair_runs runs,
+								  mchip_pair_span *out)
+{
+	__shared__ unsigned long long red[4][PAIR_SPAN_THREADS];
+	unsigned long long lo[2] = { ~0ull, ~0ull }, hi[2] = { 0ull, 0ull };
+	for (unsigned r = threadIdx.x; r < n_blocks / MCHIP_PAIR_RUN; r += PAIR_SPAN_THREADS) {	/* (n_blocks: whole runs, pair_blocks()) */
+		unsigned logical;
+		const int kind = mchip_pair_is_ind(r * MCHIP_PAIR_RUN, runs, &logical) ? 1 : 0;
+#pragma unroll
+		for (int x = 0; x < MCHIP_PAIR_RUN; x++) {
+			const size_t b = (size_t)r * MCHIP_PAIR_RUN + x;
+			const unsigned long long t0 = marks[2 * b], t1 = marks[2 * b + 1];
+			if (t0 > t1) continue;		/* the block returned at once */
+			lo[kind] = t0 < lo[kind] ? t0 : lo[kind];
+			hi[kind] = t1 > hi[kind] ? t1 : hi[kind];
+		}
+	}
+	red[0][threadIdx.x] = lo[0]; red[1][threadIdx.x] = lo[1]; red[2][threadIdx.x] = hi[0]; red[3][threadIdx.x] = hi[1];
+	__syncthreads();
+	for (int s = PAIR_SPAN_THREADS / 2; s > 0; s >>= 1) {
+		if ((int)threadIdx.x < s) {
+			for (int x = 0; x < 2; x++) {
+				const unsigned long long l2 = red[x][threadIdx.x + s], h2 = red[2 + x][threadIdx.x + s];
+				if (l2 < red[x][threadIdx.x]) red[x][threadIdx.x] = l2;
+				if (h2 > red[2 + x][threadIdx.x]) red[2 + x][threadIdx.x] = h2;
+			}
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		out->start[0] = red[0][0]; out->start[1] = red[1][0];
+		out->end[0] = red[2][0]; out->end[1] = red[3][0];
+	}
+}
+
+/* room for the next profiled paired launch: its blocks' clock readings and its span */
+static int pair_profile_slot(mchip_context *ctx, const mchip_pass_args &a, unsigned long long **marks)
+{
+	mchip_pair_runs runs;
+	const size_t n_blocks = ctx->kt->pair_blocks(a, &runs);
+	if (n_blocks > ctx->pair_marks_cap) {
+		HIPCHK(hipStreamSynchronize(ctx->stream));	/* (an earlier launch may still be writing the smaller buffer) */
+		dfree(ctx->d_pair_marks);
+		ctx->pair_marks_cap = 0;
+		HIPCHK(hipMalloc((void **)&ctx->d_pair_marks, 2 * n_blocks * sizeof(unsigned long long)));
+		ctx->pair_marks_cap = n_blocks;
+	}
+	if (ctx->pair_used / PAIR_SPAN_CHUNK >= ctx->pair_spans.size()) {
+		mchip_pair_span *chunk = nullptr;
+		HIPCHK(hipMalloc((void **)&chunk, PAIR_SPAN_CHUNK * sizeof(mchip_pair_span)));
+		ctx->pair_spans.push_back(chunk);
+	}
+	*marks = ctx->d_pair_marks;
+	return MCHIP_OK;
+}
+
 /* the captured steps carry their kernel arguments by value (buffer addresses, the data set's has_missing flag) */
 static void drop_graphs(mchip_context *ctx)
 {
@@ -1101,6 +1164,8 @@ int mchip_destroy(mchip_context *ctx)
 	dfree(ctx->d_run);
 	if (ctx->h_pinned) (void)MCHIP_WAIT(hipHostFree(ctx->h_pinned));
 	for (hipEvent_t e : ctx->ev_pool) (void)MCHIP_WAIT(hipEventDestroy(e));
+	dfree(ctx->d_pair_marks);
+	for (mchip_pair_span *&chunk : ctx->pair_spans) dfree(chunk);
 	(void)MCHIP_WAIT(hipEventDestroy(ctx->ev_begin));
 	(void)MCHIP_WAIT(hipEventDestroy(ctx->ev_end));
 	(void)MCHIP_WAIT(hipStreamDestroy(ctx->stream));
@@ -1793,12 +1858,36 @@ static int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const i
 	mchip_pass_args a = pass_args(ctx, from);
 	a.stop = stop;
 	a.skip_ind = skip_ind;
-	if (do_mstep || !ctx->sparse) {
+	const bool s_cached = ctx->sparse && do_mstep && !stop && ctx->s_cache_slot == from;
+	/* both passes of this E step as one launch (k_estep_pair: the same bodies, the same bits).  The choice depends on the model and
+	 * the data set alone: captured, eager and call-by-call steps take it alike */
+	const bool paired = do_mstep && !s_cached && !ctx->knob.no_pair && ctx->kt->pair_available(a);
+	if (paired) {
+		unsigned long long *marks = nullptr;
+		if (ctx->profiling) {
+			int rc = pair_profile_slot(ctx, a, &marks);
+			if (rc) return rc;
+		}
+		ctx->kt->estep_pair(a, marks, ctx->stream);
+		if (marks) {
+			mchip_pair_runs runs;
+			const unsigned n_blocks = ctx->kt->pair_blocks(a, &runs);
+			hipLaunchKernelGGL(k_pair_spans, dim3(1), dim3(PAIR_SPAN_THREADS), 0, ctx->stream, marks, n_blocks, runs,
+					   ctx->pair_spans[ctx->pair_used / PAIR_SPAN_CHUNK] + ctx->pair_used % PAIR_SPAN_CHUNK);
+			ctx->pair_used++;
+		}
+		ctx->ll_parts = ctx->kt->ind_ll_parts(a);
+		if (!defer_ll)
+			hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, ctx->ll_parts, ctx->d_scalars, stop);
+	}
+	if (!paired && (do_mstep || !ctx->sparse)) {
 		prof_mark(ctx, MCHIP_KERN_ACCUM_P, true);
 		if (do_mstep) ctx->kt->accum_p(a, ctx->stream); else ctx->kt->loglik(a, ctx->stream);
 		prof_mark(ctx, MCHIP_KERN_ACCUM_P, false);
 	}
-	if (ctx->sparse && do_mstep && !stop && ctx->s_cache_slot == from) {
+	if (paired) {
+		/* (done above) */
+	} else if (s_cached) {
 		/* the individual pass over these very parameters already ran (mchip_loglik_prefetch): its sums are in Spart,
 		 * its log likelihood in d_scalars[2] */
 		HIPCHK(hipMemcpyAsync(ctx->d_scalars, ctx->d_scalars + 2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -2477,6 +2566,7 @@ int mchip_profile_begin(mchip_context *ctx)
 	ctx->profiling = 1;
 	ctx->ev_used = 0;
 	ctx->ev_kind.clear();
+	ctx->pair_used = 0;
 	HIPCHK(hipEventRecord(ctx->ev_begin, ctx->stream));
 	return MCHIP_OK;
 }
@@ -2496,15 +2586,33 @@ int mchip_profile_end(mchip_context *ctx, double *total_ms, double *kernel_ms, i
 	double km[MCHIP_KERN_COUNT] = {0}, longest[MCHIP_KERN_COUNT] = {0};
 	int kl[MCHIP_KERN_COUNT] = {0};
 	std::vector<float> each(ctx->ev_kind.size(), 0.0f);
-	for (size_t p = 0; 2 * p + 1 < ctx->ev_used && p < ctx->ev_kind.size(); p++) {
+	std::vector<int> kind_of(ctx->ev_kind);
+	for (size_t p = 0; 2 * p + 1 < ctx->ev_used && p < ctx->ev_kind.size(); p++)
 		HIPCHK(hipEventElapsedTime(&each[p], ctx->ev_pool[2 * p], ctx->ev_pool[2 * p + 1]));
-		if (each[p] > longest[ctx->ev_kind[p]]) longest[ctx->ev_kind[p]] = each[p];
+	/* paired E steps: each kind's blocks' span inside the launch, from the device's constant-rate clock, is that pass's launch.
+	 * The two spans of a launch overlap (that is the point of the pair), so their sum exceeds the time the launch took */
+	if (ctx->pair_used) {
+		int khz = 0;
+		if (MCHIP_WAIT(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device)) != hipSuccess || khz <= 0) khz = 100000;
+		std::vector<mchip_pair_span> spans(ctx->pair_used);
+		for (size_t p = 0; p < ctx->pair_used; p += PAIR_SPAN_CHUNK) {
+			const size_t n = ctx->pair_used - p < PAIR_SPAN_CHUNK ? ctx->pair_used - p : PAIR_SPAN_CHUNK;
+			HIPCHK(hipMemcpy(&spans[p], ctx->pair_spans[p / PAIR_SPAN_CHUNK], n * sizeof(mchip_pair_span), hipMemcpyDeviceToHost));
+		}
+		for (const mchip_pair_span &sp : spans)
+			for (int x = 0; x < 2; x++) {
+				each.push_back(sp.end[x] > sp.start[x] ? (float)((double)(sp.end[x] - sp.start[x]) / khz) : 0.0f);
+				kind_of.push_back(x ? MCHIP_KERN_ACCUM_Q : MCHIP_KERN_ACCUM_P);
+			}
+		ctx->pair_used = 0;
 	}
+	for (size_t p = 0; p < each.size(); p++)
+		if (each[p] > longest[kind_of[p]]) longest[kind_of[p]] = each[p];
 	/* a launch that returned at once (the S-side pass of a batched accelerated cycle whose sums were already in place, any
 	 * kernel after the stopping rule fired) did no pass over the data: it is not a launch of that kernel for these figures */
-	for (size_t p = 0; 2 * p + 1 < ctx->ev_used && p < ctx->ev_kind.size(); p++) {
-		const int kind = ctx->ev_kind[p];
-		if (each[p] < 0.05 * longest[kind]) continue;
+	for (size_t p = 0; p < each.size(); p++) {
+		const int kind = kind_of[p];
+		if (each[p] <= 0.0f || each[p] < 0.05 * longest[kind]) continue;	/* (a kind's blocks of a paired launch that all returned: exactly 0) */
 		km[kind] += each[p];
 		kl[kind]++;
 	}

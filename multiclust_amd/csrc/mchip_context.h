@@ -96,7 +96,7 @@ struct mchip_context {
 	 * model -- never on a launch path */
 	struct {
 		int no_bial, no_counts, force_dense, force_safe, no_graph, no_dual, no_slab_sum, no_col_split, part_no_tile, sim_no_tile;
-		int no_fused_finalize;
+		int no_fused_finalize, no_pair;
 		int per_cu_col, per_cu_ind, geometry_given, no_roundup;
 		double slab_frac;
 	} knob;
@@ -118,6 +118,12 @@ struct mchip_context {
 	std::vector<hipEvent_t> ev_pool;
 	std::vector<int> ev_kind;	/* kernel kind of pair p = events 2p, 2p+1 */
 	size_t ev_used;
+	/* profiled paired E steps (k_estep_pair; mchip.hip: k_pair_spans): two clock readings per block of the latest such launch, and
+	 * one span per launch since mchip_profile_begin, in allocations of a fixed number of spans */
+	unsigned long long *d_pair_marks;
+	size_t pair_marks_cap;		/* blocks d_pair_marks has room for */
+	std::vector<mchip_pair_span *> pair_spans;
+	size_t pair_used;
 };
 
 static int fail(mchip_context *ctx, int code, const char *fmt, const char *detail)

@@ -147,6 +147,26 @@ struct mchip_pass_args {
 					 * 1: one count per copy, missing copies count for the individual (initialize_parameters_admixture) */
 };
 
+/* Paired E step (k_estep_pair): the column pass's and the S-side pass's workgroups in one one-dimensional grid.  Block ids are dealt
+ * out in runs of MCHIP_PAIR_RUN ids of one kind (the individual body's xcd_rows mapping reads id mod 8 as the XCD: a kind's logical
+ * id keeps its low three bits), and the runs of the two kinds alternate in the proportion of their counts, Bresenham-style: of the
+ * first r runs, r * ind_runs / (col_runs + ind_runs) are individual runs.  Both kinds therefore start and end together and sit side
+ * by side on every CU.  A kind's last run may hold ids past its workgroup count: those blocks return. */
+#define MCHIP_PAIR_RUN 8
+struct mchip_pair_runs { unsigned col_runs, ind_runs; };
+/* block -> (kind, logical block id of that kind); col_runs + ind_runs runs in all, (col_runs + ind_runs) * ind_runs < 2^32 */
+__host__ __device__ inline bool mchip_pair_is_ind(unsigned block, mchip_pair_runs r, unsigned *logical)
+{
+	const unsigned run = block / MCHIP_PAIR_RUN, total = r.col_runs + r.ind_runs;
+	const unsigned before = run * r.ind_runs / total, upto = (run + 1) * r.ind_runs / total;	/* individual runs among the first run, run + 1 */
+	const bool ind = upto > before;
+	*logical = (ind ? before : run - before) * MCHIP_PAIR_RUN + block % MCHIP_PAIR_RUN;
+	return ind;
+}
+/* what a profiled paired launch leaves per kind (0 column, 1 individual): first start and last end of that kind's working blocks on
+ * the device's constant-rate clock; start > end where no block of the kind worked (cached sums, stopped run) */
+struct mchip_pair_span { unsigned long long start[2], end[2]; };
+
 /* what the P-side part of a launch needs (k_finalize_qp takes it by value beside the Q side's arguments; mchip_finalize.h has the code) */
 struct mchip_finalize_p_args {
 	int L, K, T, loci_per_block, n_slabs, weighted, do_projection;
@@ -184,6 +204,11 @@ struct mchip_ktable {
 	/* both finalisers of an EM step in one launch (k_finalize_qp): individual mixing proportions, tiled P side */
 	void (*finalize_qp)(int I, int n_slabs_q, const double *Spart, const double *Qfrom, int qstride_from, double *Qto, double *sik,
 			    int do_projection_q, double lb_q, const mchip_finalize_p_args &p, const int *stop, hipStream_t s);
+	/* accum_p and accum_q of one E step as one launch (k_estep_pair), where pair_available() says so: the same bodies, the same
+	 * bits.  marks (profiled runs; else NULL): two clock readings per block of the launch, pair_blocks() blocks */
+	int (*pair_available)(const mchip_pass_args &a);
+	unsigned (*pair_blocks)(const mchip_pass_args &a, mchip_pair_runs *runs);
+	void (*estep_pair)(const mchip_pass_args &a, unsigned long long *marks, hipStream_t s);
 };
 
 const mchip_ktable *mchip_get_ktable(int K);

@@ -262,10 +262,11 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_column_pass(mchip_pass_args a)
  * n_ic = ILM[i][l][m] (BITS = 2 for ploidy <= 3, 4 for ploidy <= 15).  One coalesced 16-byte load per lane serves G
  * individuals and the count is a single v_bfe_u32, instead of two byte compares, a select and an add per cell.
  * MIX = false: admixture N-side sums  acc_k += q_ik * n / t;   MIX = true: mixture M step  acc_k += vik * n. */
-template <int BITS, bool MIX, bool SAFE = false>
-__global__ __launch_bounds__(MCHIP_BLOCK) void k_column_counts(mchip_pass_args a)
+/* The body: workgroup (bx, by) of counts_grid(); wsum is [K][64] doubles of LDS.  k_column_counts runs it on its own grid,
+ * k_estep_pair beside the S-side pass's body. */
+template <int BITS, bool MIX, bool SAFE>
+__device__ __forceinline__ void column_counts_body(const mchip_pass_args &a, const int bx, const int by, double (*wsum)[64])
 {
-	if (a.stop && *a.stop) return;		/* batched run already stopped (wave-uniform) */
 	constexpr int PERWORD = 32 / BITS;		/* individuals per dword */
 	constexpr int G = 4 * PERWORD;			/* individuals per 16-byte word */
 	constexpr unsigned MASK = (1u << BITS) - 1u;
@@ -273,9 +274,8 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_column_counts(mchip_pass_args a
 	constexpr int NJ = K <= 12 ? 4 : (K <= 20 ? 2 : 1);
 	/* the workgroup's MCHIP_COL_WAVES waves take the same 64 allele columns and consecutive sub-chunks of a.ichunk individuals;
 	 * their sums meet in LDS below, in wave order, and wave 0 stores the slab (mchip_internal.h: cooperating waves) */
-	__shared__ double wsum[K][64];
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;	/* wv is wave-uniform */
-	const int c_raw = blockIdx.x * 64 + lane;
+	const int c_raw = bx * 64 + lane;
 	const bool valid = c_raw < a.T;
 	const int c = valid ? c_raw : a.T - 1;
 	double p[K], acc[K];
@@ -284,10 +284,15 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_column_counts(mchip_pass_args a
 		p[k] = MIX ? 0.0 : a.P[(size_t)c * K + k];
 		acc[k] = 0.0;
 	}
-	const int i0 = __builtin_amdgcn_readfirstlane((blockIdx.y * MCHIP_COL_WAVES + wv) * a.ichunk);	/* multiple of G */
+	const int i0 = __builtin_amdgcn_readfirstlane((by * MCHIP_COL_WAVES + wv) * a.ichunk);	/* multiple of G */
 	const int i1 = min(a.I, i0 + a.ichunk);
 	const int g_end = (i1 + G - 1) / G;		/* (a wave whose sub-chunk starts behind the last individual has no groups) */
 	const uint4 *gt = reinterpret_cast<const uint4 *>(a.gtC);
+	/* (the q rows are read through the constant address space: Q does not change while a kernel runs, and in k_estep_pair the
+	 * clock reading in front of this body is opaque to hipcc -- it would otherwise assume that it may have written Q and read
+	 * the rows through the vector memory path into 64 more registers at K = 8) */
+	typedef __attribute__((address_space(4))) double const_double;
+	const const_double *Qc = (const const_double *)a.Q;
 	uint4 w = gt[(size_t)min(i0 / G, (a.I - 1) / G) * a.T + c];
 	for (int g = i0 / G; g < g_end; g++) {
 		const uint4 wn = gt[(size_t)min(g + 1, g_end - 1) * a.T + c];	/* prefetch (clamped) */
@@ -299,11 +304,11 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_column_counts(mchip_pass_args a
 				const int ibase = g * G + wi * PERWORD + h * NJ;
 				if (ibase >= i1) break;		/* wave-uniform; padded individuals have zero counts anyway */
 				/* NJ individuals at a time: their q rows are wave-uniform (scalar loads, used as SGPR operands) */
-				const double *__restrict__ q[NJ];
+				const const_double *q[NJ];
 				double n[NJ], t[NJ], rc[NJ];
 #pragma unroll
 				for (int j = 0; j < NJ; j++) {
-					q[j] = a.Q + (size_t)min(ibase + j, a.I - 1) * a.qstride;
+					q[j] = Qc + (size_t)min(ibase + j, a.I - 1) * a.qstride;
 					n[j] = (double)((word >> (BITS * j)) & MASK);
 				}
 				if (!MIX) {
@@ -351,12 +356,20 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_column_counts(mchip_pass_args a
 		}
 		__syncthreads();
 	}
-	const int c2 = (int)blockIdx.x * 64 + lane2;
+	const int c2 = bx * 64 + lane2;
 	if (wv2 == 0 && c2 < a.T) {
-		double *out = a.Apart + ((size_t)blockIdx.y * a.T + c2) * K;
+		double *out = a.Apart + ((size_t)by * a.T + c2) * K;
 #pragma unroll
 		for (int k = 0; k < K; k++) out[k] = acc[k];
 	}
+}
+
+template <int BITS, bool MIX, bool SAFE = false>
+__global__ __launch_bounds__(MCHIP_BLOCK) void k_column_counts(mchip_pass_args a)
+{
+	if (a.stop && *a.stop) return;		/* batched run already stopped (wave-uniform) */
+	__shared__ double wsum[K][64];
+	column_counts_body<BITS, MIX, SAFE>(a, (int)blockIdx.x, (int)blockIdx.y, wsum);
 }
 
 /* ---------------------------------------------------------------- column pass on packed counts, k range split over CSPLIT lanes
@@ -952,22 +965,22 @@ __device__ __forceinline__ void glds_wait()
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int PL, bool ACCUM, bool SAFE, bool NOMISS, bool DUAL = false>
-__global__ __launch_bounds__(64 * MCHIP_IND_WAVES_MAX) void k_individual_sparse_w(mchip_pass_args a)
+/* The body: workgroup `bid` of coop_rows(); lds is the launch's dynamic LDS, coop_lds_bytes() of it.  k_individual_sparse_w runs
+ * it on its own grid, k_estep_pair beside the column pass's body. */
+template <int PL, bool ACCUM, bool SAFE, bool NOMISS, bool DUAL>
+__device__ __forceinline__ void individual_sparse_w_body(const mchip_pass_args &a, const unsigned bid, double *lds)
 {
 	static_assert(SPLIT == 1, "wave-private tiles: one lane per individual");
 	static_assert(!DUAL || (ACCUM && !SAFE && PL == 2), "dual pass: ACCUM, shared reciprocals, diploid");
-	if (a.stop && *a.stop) return;		/* batched run already stopped (uniform over the grid) */
-	if (ACCUM && !DUAL && a.skip_ind && *a.skip_ind) return;	/* sums + logL partials of these parameters are already there */
-	extern __shared__ __attribute__((aligned(16))) double lds[];	/* [wave][buffer][set][tile_cols][KP]; after the loop: [K + 2][64] hand-over */
+	/* lds: [wave][buffer][set][tile_cols][KP]; after the loop: [K + 2][64] hand-over */
 	constexpr int SETS = DUAL ? 2 : 1;
 	const int lane = threadIdx.x & 63;
 	const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const int W = a.ind_waves;
 	/* which (tile of 64 individuals, slab row) this workgroup is: coop_rows() */
 	const int n_tiles = (a.I + 63) / 64;
-	const int slot = a.xcd_rows ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-	const int bx = slot % n_tiles, by = a.xcd_rows ? (slot / n_tiles) * 8 + (int)(blockIdx.x & 7) : slot / n_tiles;
+	const int slot = a.xcd_rows ? (int)(bid >> 3) : (int)bid;
+	const int bx = slot % n_tiles, by = a.xcd_rows ? (slot / n_tiles) * 8 + (int)(bid & 7) : slot / n_tiles;
 	const size_t tile_doubles = tile_stride(a.tile_cols);
 	double *mine = lds + (size_t)wv * 2 * SETS * tile_doubles;
 	const int i_raw = bx * 64 + lane;
@@ -1238,6 +1251,72 @@ __global__ __launch_bounds__(64 * MCHIP_IND_WAVES_MAX) void k_individual_sparse_
 		if (DUAL) {
 			const double tot2 = wave_total(active ? ll2 : 0.0);
 			if (lane == 0) a.llpart2[(size_t)by * n_tiles + bx] = tot2;
+		}
+	}
+}
+
+template <int PL, bool ACCUM, bool SAFE, bool NOMISS, bool DUAL = false>
+__global__ __launch_bounds__(64 * MCHIP_IND_WAVES_MAX) void k_individual_sparse_w(mchip_pass_args a)
+{
+	if (a.stop && *a.stop) return;		/* batched run already stopped (uniform over the grid) */
+	if (ACCUM && !DUAL && a.skip_ind && *a.skip_ind) return;	/* sums + logL partials of these parameters are already there */
+	extern __shared__ __attribute__((aligned(16))) double lds[];
+	individual_sparse_w_body<PL, ACCUM, SAFE, NOMISS, DUAL>(a, blockIdx.x, lds);
+}
+
+/* ---------------------------------------------------------------- paired E step: column pass and S-side pass in one launch
+ * The two passes of an E step read the same parameters and write disjoint workspaces (Apart; Spart + llpart), and each leaves idle
+ * what the other uses: the column body has no LDS traffic and waits on scalar loads, the individual body waits on LDS gathers.
+ * Here their workgroups share one grid (mchip_internal.h: block ids in runs of eight of one kind, the kinds interleaved in the
+ * proportion of their counts) and so every CU; each block runs one of the two bodies above unchanged, so every result is the two
+ * launches' bit for bit.  256 threads (a.ind_waves = 4); dynamic LDS: the larger of the individual body's tiles and the column
+ * body's [K][64] hand-over.
+ * a.skip_ind: the individual blocks return at once (the sums are cached), the column blocks work.
+ * marks (profiled runs): overlapping kinds have no event-to-event duration, so each working block leaves its first wave start and
+ * last wave end (s_memrealtime) in marks[2 * block], [2 * block + 1]; a block that returned leaves start > end.  One lane stores
+ * them after the waves' readings met in LDS; mchip.hip's k_pair_spans takes each kind's minimum and maximum.
+ * Registers (-Rpass-analysis=kernel-resource-usage): the function takes what the S-side body takes and runs at its waves per
+ * SIMD -- K = 8: 93 VGPRs, five waves (S-side instance 90-92, column instance 68 and seven waves); K = 12: 123-125, four waves
+ * (122-124).  No vector register spills; the column body's scalar registers are all taken (99 at K = 8), so a few of the
+ * launch's own scalars (the marks pointer, the start reading) wait in lanes of one vector register, outside the loops. */
+template <int BITS, int PL, bool SAFE, bool NOMISS>
+__global__ __launch_bounds__(MCHIP_BLOCK) void k_estep_pair(mchip_pass_args a, mchip_pair_runs runs, unsigned long long *marks)
+{
+	static_assert(64 * MCHIP_IND_WAVES_MAX == MCHIP_BLOCK, "both bodies at 256 threads");
+	extern __shared__ __attribute__((aligned(16))) double lds[];
+	unsigned logical;
+	const bool ind = mchip_pair_is_ind(blockIdx.x, runs, &logical);	/* uniform over the workgroup */
+	const unsigned n_col = (unsigned)((a.T + 63) / 64), n_mine = ind ? (unsigned)(((a.I + 63) / 64) * mchip_ind_slabs(a)) : n_col * (unsigned)mchip_col_slabs(a);
+	const bool idle = logical >= n_mine || (a.stop && *a.stop) || (ind && a.skip_ind && *a.skip_ind);
+	if (idle) {
+		if (marks && threadIdx.x == 0) {
+			marks[2 * (size_t)blockIdx.x] = ~0ull;
+			marks[2 * (size_t)blockIdx.x + 1] = 0ull;
+		}
+		return;
+	}
+	/* (the wave's start waits in registers until the body is done: a store in front of the bodies would be one more thing hipcc
+	 * has to assume about memory) */
+	const unsigned long long t_start = marks ? __builtin_amdgcn_s_memrealtime() : 0ull;
+	if (ind) individual_sparse_w_body<PL, true, SAFE, NOMISS, false>(a, logical, lds);
+	else column_counts_body<BITS, false, SAFE>(a, (int)(logical % n_col), (int)(logical / n_col), reinterpret_cast<double (*)[64]>(lds));
+	if (marks) {
+		/* (the waves' readings meet at the head of the dynamic array: both bodies end behind a barrier that follows their last
+		 * LDS read, and a static array beside the tiles would cost config 3 its fifth workgroup per CU -- 5 x 32 KiB fill it) */
+		unsigned long long (*wave_mark)[MCHIP_COL_WAVES] = reinterpret_cast<unsigned long long (*)[MCHIP_COL_WAVES]>(lds);
+		if ((threadIdx.x & 63) == 0) {
+			wave_mark[0][threadIdx.x >> 6] = t_start;
+			wave_mark[1][threadIdx.x >> 6] = __builtin_amdgcn_s_memrealtime();
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			unsigned long long t0 = wave_mark[0][0], t1 = wave_mark[1][0];
+			for (int w = 1; w < MCHIP_COL_WAVES; w++) {
+				t0 = wave_mark[0][w] < t0 ? wave_mark[0][w] : t0;
+				t1 = wave_mark[1][w] > t1 ? wave_mark[1][w] : t1;
+			}
+			marks[2 * (size_t)blockIdx.x] = t0;
+			marks[2 * (size_t)blockIdx.x + 1] = t1;
 		}
 	}
 }
@@ -1874,6 +1953,40 @@ void launch_accum_q_dual(const mchip_pass_args &a, hipStream_t s)
 		else hipLaunchKernelGGL((k_individual_sparse_w<2, true, false, false, true>), coop_rows(a), dim3(64 * a.ind_waves), lds, s, a);
 	}
 }
+/* the paired E step exists where launch_accum_p would run k_column_counts<2, false, SAFE> and launch_sparse<true> would run
+ * k_individual_sparse_w<2, true, SAFE, NOMISS> with four waves (so that its results are theirs bit for bit), at the K where both
+ * bodies fit a 256-thread workgroup's registers */
+unsigned pair_blocks(const mchip_pass_args &a, mchip_pair_runs *runs)
+{
+	const dim3 cg = counts_grid(a);
+	const unsigned n_col = cg.x * cg.y, n_ind = coop_rows(a).x;
+	runs->col_runs = (n_col + MCHIP_PAIR_RUN - 1) / MCHIP_PAIR_RUN;
+	runs->ind_runs = (n_ind + MCHIP_PAIR_RUN - 1) / MCHIP_PAIR_RUN;
+	return (runs->col_runs + runs->ind_runs) * MCHIP_PAIR_RUN;
+}
+int pair_available(const mchip_pass_args &a)
+{
+	if (K > 12 || SPLIT != 1 || CSPLIT != 1) return 0;
+	if (!a.sparse || a.count_bits != 2 || a.ploidy != 2 || a.ind_waves * 64 != MCHIP_BLOCK) return 0;
+	if ((a.safe_rcp != 0) != (a.flush_blocks < 1)) return 0;	/* (one SAFE for both bodies; mchip_set_model keeps them together) */
+	if (a.biallelic && K >= 10 && a.flush_blocks >= 1) return 0;	/* launch_sparse<true> takes k_individual_bial */
+	mchip_pair_runs r;
+	pair_blocks(a, &r);
+	if (r.col_runs == 0 || r.ind_runs == 0) return 0;
+	return (unsigned long long)(r.col_runs + r.ind_runs) * r.ind_runs < (1ull << 32);	/* mchip_pair_is_ind's 32-bit products */
+}
+void launch_estep_pair(const mchip_pass_args &a, unsigned long long *marks, hipStream_t s)
+{
+	if constexpr (K <= 12 && SPLIT == 1 && CSPLIT == 1) {
+		mchip_pair_runs r;
+		const dim3 grid(pair_blocks(a, &r)), block(MCHIP_BLOCK);
+		const size_t ind_lds = coop_lds_bytes(a, 1), col_lds = (size_t)K * 64 * sizeof(double);
+		const size_t lds = ind_lds > col_lds ? ind_lds : col_lds;
+		if (a.flush_blocks < 1) hipLaunchKernelGGL((k_estep_pair<2, 2, true, false>), grid, block, lds, s, a, r, marks);
+		else if (!a.has_missing) hipLaunchKernelGGL((k_estep_pair<2, 2, false, true>), grid, block, lds, s, a, r, marks);
+		else hipLaunchKernelGGL((k_estep_pair<2, 2, false, false>), grid, block, lds, s, a, r, marks);
+	}
+}
 /* what the launchers leave behind (mchip_ktable) */
 int col_slabs(const mchip_pass_args &a, int mix)
 {
@@ -1963,7 +2076,7 @@ const mchip_ktable *MCHIP_CAT(mchip_ktable_get_, MCHIP_K)()
 	static mchip_ktable t = {
 		launch_accum_p, launch_loglik, launch_accum_q, launch_part_p, launch_part_q, launch_finalize_q, launch_project_q,
 		launch_mix_gather, launch_mix_finalize, launch_mix_column, dual_available, launch_accum_q_dual,
-		col_slabs, ind_slabs, ind_ll_parts, launch_finalize_qp,
+		col_slabs, ind_slabs, ind_ll_parts, launch_finalize_qp, pair_available, pair_blocks, launch_estep_pair,
 	};
 	return &t;
 }
