@@ -403,6 +403,36 @@ int mchip_divergence(mchip_context *ctx, int slot, const double *weights /* [K] 
 		     double *sqdiff /* [K][K] */, double *locus_v /* [L] or NULL */, double *locus_ht /* [L] or NULL */,
 		     double *sum_v, double *sum_ht, int32_t *n_loci);
 
+/* ---- products of the fit's residuals between individuals (an extension: evalAdmix's check of an admixture fit, Garcia-Erill and
+ * Albrechtsen 2020, for multi-allelic data of any ploidy) ----
+ * The admixture model with individual or shared mixing proportions, the parameters of `slot`, the INSTALLED data set (under a
+ * cross-validation hold-out the hidden copies are missing copies like any other).  For individual i, locus l and column c = (l, m)
+ * over ALL uniquealleles[l] columns of the locus, the phantom slot included (T columns in all):
+ *   a_il    the observed (not MCHIP_MISSING) copies of the genotype;   n_ic   how many of them carry allele m;
+ *   t_ic    = sum_k q_ik p_kc, an fma chain in k order from 0 (q_k when the mixing proportions are shared).  Q is read as the
+ *           device stores it: an individual without an observed copy holds 1 / K (the slot section above);
+ *   r_ic    = fma(-a_il, t_ic, n_ic): the observed count minus the count the fit predicts -- this double IS the residual.  It is 0
+ *           where a_il = 0;
+ *   s_il    = sum_m r_ilm^2, by fma in m order from 0;   o_il = 1 if a_il > 0, else 0.
+ * Returned are the sums; the caller forms cor_ij = G_ij / sqrt(D_ij D_ji):
+ *   gram[i*I+j]    G_ij = sum_c r_ic r_jc over the T columns; symmetric bit for bit (the entries on and above the diagonal are
+ *                  computed, the others are copies);
+ *   norms[i*I+j]   D_ij = sum_l s_il o_jl: the squared norm of i's residuals over the loci at which j has data -- the
+ *                  pairwise-complete denominators; NOT symmetric.  Where the data set has no missing copy D_ij is G_ii, bit for
+ *                  bit.  norms = NULL: not computed.
+ * An element's terms are added in the order of the columns (of the loci), four to an instruction of the FP64 matrix unit, the order
+ * inside an instruction being the hardware's: at most two roundings per term.  The chunks the work is cut into depend on
+ * uniquealleles alone; no floating-point atomics; no order of addition depends on the number of compute units: the same state gives
+ * the same bits on any device and under every geometry knob of the environment.
+ * Cost: I^2 T + 2 I^2 L multiply-adds and two I x I arrays of doubles on the device (one without norms) -- quadratic in I.
+ * Writes its host arrays and nothing else: no parameter slot, secant, expected count, held S-side sum, data set, fold or saved set
+ * changes.
+ * MCHIP_ERR_STATE without a data set or model; MCHIP_ERR_UNSUPPORTED for the mixture model (admixture = 0); MCHIP_ERR_INVALID for a
+ * slot out of range or a null gram -- all checked before anything runs, the arrays stay untouched; MCHIP_ERR_ALLOC when the I x I
+ * sums or the chunk buffers do not fit on the device.
+ */
+int mchip_residual_products(mchip_context *ctx, int slot, double *gram /* [I][I] */, double *norms /* [I][I] or NULL */);
+
 /* ---- a selection of loci with repeats: the data sets of the non-parametric bootstrap over loci (an extension) ----
  * Let the base be the data set the context held when the first resample was asked for (I, L_base, ploidy, uniquealleles,
  * genotypes).  After the call the context holds exactly what

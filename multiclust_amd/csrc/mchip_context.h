@@ -1,6 +1,6 @@
 /*
  * mchip_context.h -- the per-context state of libmulticlust_hip.so and the few helpers of mchip.hip that the units holding a
- * data-set feature's kernels and entry points call (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_generators.hip, mchip_impute.hip, mchip_query.hip, mchip_resample.hip).
+ * data-set feature's kernels and entry points call (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_generators.hip, mchip_impute.hip, mchip_query.hip, mchip_resample.hip, mchip_residuals.hip).
  * Private to the library's host-side units; not part of the C-ABI, and mchip_kernels_k.hip does not include it.
  */
 #ifndef MCHIP_CONTEXT_H

@@ -102,6 +102,7 @@ def load():
         "mchip_fit_q_rows": ([vp, i32, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp], i32),
         "mchip_impute_missing": ([vp, i32, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp], i32),
         "mchip_divergence": ([vp, i32, vp, vp, vp, vp, vp, dp, dp, ip], i32),
+        "mchip_residual_products": ([vp, i32, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("MCHIP_ALLOW_PARTIAL_ABI") == "1" and not hasattr(lib, name):
@@ -126,6 +127,7 @@ ABI_SYMBOLS = [
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
     "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
+    "mchip_residual_products",
 ]
 
 
@@ -270,6 +272,14 @@ class Context:
                                             None if lv is None else lv.ctypes.data, None if lht is None else lht.ctypes.data,
                                             C.byref(sv), C.byref(sht), C.byref(n1)))
         return dict(het=het, sqdiff=sq, locus_v=lv, locus_ht=lht, sum_v=sv.value, sum_ht=sht.value, n_loci=n1.value)
+
+    def residual_products(self, slot, want_norms=True):
+        """mchip_residual_products: the products of the admixture fit's residuals between individuals for the parameters of `slot`
+        (include/multiclust_hip.h): (gram [I][I], norms [I][I] or None without `want_norms`)."""
+        G = np.empty((self.I, self.I))
+        D = np.empty((self.I, self.I)) if want_norms else None
+        self._chk(self.lib.mchip_residual_products(self.h, slot, G.ctypes.data, None if D is None else D.ctypes.data))
+        return G, D
 
     def resample_loci(self, src):
         """install the selection `src` (locus indices into the base, repeats allowed) of the base: the data set held when the first

@@ -99,6 +99,13 @@ class McDivergenceResult(C.Structure):
                 ("F", C.POINTER(C.c_double)), ("locus_ht", C.POINTER(C.c_double)), ("locus_f", C.POINTER(C.c_double))]
 
 
+class McResidResult(C.Structure):
+    """mc_resid_result (multiclust_amd/host/mc_host.h)"""
+    _fields_ = [("K", C.c_int), ("I", C.c_int), ("max_i", C.c_int), ("max_j", C.c_int), ("n_pairs", C.c_longlong),
+                ("mean", C.c_double), ("mean_abs", C.c_double), ("max", C.c_double), ("cor", C.POINTER(C.c_double)),
+                ("ind_mean", C.POINTER(C.c_double)), ("ind_max", C.POINTER(C.c_double)), ("ind_partner", C.POINTER(C.c_int32))]
+
+
 class CliOptions(C.Structure):
     """mc_cli_options (multiclust_amd/host/mc_cli.h)"""
     _fields_ = [("em", McOptions), ("filename", C.c_char_p), ("filename_file", C.c_char_p), ("path", C.c_char_p),
@@ -109,8 +116,8 @@ class CliOptions(C.Structure):
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
                 ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
-    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block, query_file, fill and fst, the command line's --cv, --se,
-    # --query, --fill and --fst: only mc_main.c reads them, the readers and writers this mirror is handed to stop at bed_prefix)
+    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block, query_file, fill, fst and resid, the command line's --cv, --se,
+    # --query, --fill, --fst and --resid: only mc_main.c reads them, the readers and writers this mirror is handed to stop at bed_prefix)
 
 
 class CliData(C.Structure):
@@ -276,6 +283,36 @@ def divergence_tables(het, sqdiff, n_loci):
     return H, D, F, (n.value, mean.value, lo.value, hi.value)
 
 
+def residual_ratios(G, D):
+    """mc_residual_ratios (host/mc_resid.c): cor [I][I] = G_ij / sqrt(D_ij D_ji), NaN on the diagonal and where either D is 0"""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    I = G.shape[0]
+    assert G.shape == D.shape == (I, I)
+    cor = np.empty((I, I))
+    load().mc_residual_ratios(I, G.ctypes.data, D.ctypes.data, cor.ctypes.data)
+    return cor
+
+
+def _resid_dict(r):
+    I = r.I
+    return dict(cor=np.ctypeslib.as_array(r.cor, shape=(I, I)).copy(), ind_mean=np.ctypeslib.as_array(r.ind_mean, shape=(I,)).copy(),
+                ind_max=np.ctypeslib.as_array(r.ind_max, shape=(I,)).copy(),
+                ind_partner=np.ctypeslib.as_array(r.ind_partner, shape=(I,)).copy(), n_pairs=r.n_pairs, mean=r.mean,
+                mean_abs=r.mean_abs, max=r.max, max_pair=(r.max_i, r.max_j))
+
+
+def residual_summary(cor):
+    """mc_residual_summary (host/mc_resid.c) of a correlation matrix: dict as Fit.residual_correlation gives it"""
+    cor = np.ascontiguousarray(cor, dtype=np.float64)
+    I = cor.shape[0]
+    im, ix, ip = np.empty(I), np.empty(I), np.empty(I, dtype=np.int32)
+    r = McResidResult(I=I, cor=cor.ctypes.data_as(C.POINTER(C.c_double)), ind_mean=im.ctypes.data_as(C.POINTER(C.c_double)),
+                      ind_max=ix.ctypes.data_as(C.POINTER(C.c_double)), ind_partner=ip.ctypes.data_as(C.POINTER(C.c_int32)))
+    load().mc_residual_summary(I, cor.ctypes.data, C.byref(r))
+    return _resid_dict(r)
+
+
 def query_read(path, I):
     """mc_query_read (host/mc_query.c) on a query file: (status, None) on failure, else (0, mask [I] uint8)"""
     lib = load()
@@ -385,6 +422,13 @@ def load():
     lib.mc_divergence_tables.restype = None
     lib.mc_divergence_summary.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 3
     lib.mc_divergence_summary.restype = None
+    lib.mc_residual_correlation.argtypes = [DP, MP, C.POINTER(McResidResult)]
+    lib.mc_resid_result_free.argtypes = [C.POINTER(McResidResult)]
+    lib.mc_resid_result_free.restype = None
+    lib.mc_residual_ratios.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mc_residual_ratios.restype = None
+    lib.mc_residual_summary.argtypes = [C.c_int, C.c_void_p, C.POINTER(McResidResult)]
+    lib.mc_residual_summary.restype = None
     lib.mc_read_structure.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
     lib.mc_read_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
     lib.mc_free_data.argtypes = [C.POINTER(CliData)]
@@ -570,6 +614,17 @@ class Fit:
                    locus_f=np.ctypeslib.as_array(r.locus_f, shape=(L,)).copy(), n_loci=r.n_loci, n_pairs=r.n_pairs,
                    f_mean=r.f_mean, f_min=r.f_min, f_max=r.f_max, sum_v=r.sum_v, sum_ht=r.sum_ht, f_all=r.f_all)
         self.lib.mc_divergence_result_free(C.byref(r))
+        return out
+
+    def residual_correlation(self):
+        """mc_residual_correlation on the estimate in slot mod.pindex: dict with cor [I][I], ind_mean, ind_max, ind_partner [I],
+        n_pairs, mean, mean_abs, max, max_pair (multiclust_amd/host/mc_host.h).  Leaves the model as it found it."""
+        r = McResidResult()
+        rc = self.lib.mc_residual_correlation(C.byref(self.dat), self.mp, C.byref(r))
+        if rc:
+            raise hip.HipError("mc_residual_correlation failed (%d)" % rc)
+        out = _resid_dict(r)
+        self.lib.mc_resid_result_free(C.byref(r))
         return out
 
     def locus_lists(self, n_replicates, block=1):

@@ -54,6 +54,7 @@ typedef struct mc_cli_options {
 					 * fit and fitted against the best fit of every K afterwards (mc_query.c) */
 	int fill;			/* --fill (extension): the missing genotypes filled from the best fit of every K (mc_impute.c) */
 	int fst;			/* --fst (extension): divergence of the clusters of the best fit of every K (mc_diverge.c) */
+	int resid;			/* --resid (extension): residual correlation between the individuals under the best fit of every K (mc_resid.c) */
 } mc_cli_options;
 
 typedef struct mc_cli_data {
@@ -147,5 +148,10 @@ int mc_write_filled(const mc_cli_options *opt, const mc_cli_data *dat, int K, co
  * number of columns, HT_l and F_l; the formats are in the header comment of mc_diverge.c.  Returns 0 or an exit status of the enum
  * above. */
 int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const mc_divergence_result *r);
+
+/* --resid (an extension, mc_resid.c): <stem>.admix.K=<K>.resid.txt -- the I x I matrix of residual correlations, I^2 numbers -- and
+ * <stem>.admix.K=<K>.resid.ind.txt -- per individual its index, mean and largest correlation and the partner of that; the formats are
+ * in the header comment of mc_resid.c.  Returns 0 or an exit status of the enum above. */
+int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r);
 
 #endif

@@ -361,6 +361,35 @@ void mc_divergence_result_free(mc_divergence_result *r);
  * "no pairs" for the pairwise part when there is none (K = 1); no line end */
 void mc_divergence_line(FILE *fp, const mc_divergence_result *r);
 
+/* ---- residual correlation of the admixture fit between individuals (mc_resid.c; an extension: evalAdmix's check of a fit) ----
+ * `mod` holds a fit of the admixture model (individual or shared mixing proportions) in slot mod->pindex; dat gives I.
+ * mchip_residual_products (include/multiclust_hip.h has every definition) gives, over the data set installed on the context, G_ij =
+ * sum_c r_ic r_jc of the residuals r = observed allele count - predicted count and the pairwise-complete D_ij = squared norm of i's
+ * residuals over the loci at which j has data; from them cor [I][I], cor_ij = G_ij / sqrt(D_ij D_ji), NaN on the diagonal and
+ * where either D is 0 -- an individual without an observed copy, a query individual -- symmetric bit for bit (mc_residual_ratios).
+ * mc_residual_summary, over the finite off-diagonal entries: per individual ind_mean, ind_max and ind_partner (the first
+ * individual it has its largest correlation with; NaN, NaN, -1 without a finite entry), and over the pairs i < j n_pairs, mean,
+ * mean_abs = mean |cor|, max with its pair (max_i, max_j); NaN and -1 without a pair.
+ * Limit: P was estimated with individual i in the data, so under a correct model the expected correlation is slightly negative, of
+ * the order -1 / (size of i's cluster), not zero; evalAdmix's leave-one-out refit of the frequencies, which removes that, is not done.
+ * Cost: quadratic in I -- I^2 T + 2 I^2 L multiply-adds on the device, three I x I arrays of doubles on the host.
+ * Nothing of the model or the context changes.  Mixture model: MCHIP_ERR_UNSUPPORTED.  Release the arrays with
+ * mc_resid_result_free; on failure nothing is held. */
+typedef struct mc_resid_result {
+	int K, I, max_i, max_j;
+	long long n_pairs;
+	double mean, mean_abs, max;
+	double *cor, *ind_mean, *ind_max;
+	int32_t *ind_partner;
+} mc_resid_result;
+void mc_residual_ratios(int I, const double *G /* [I][I] */, const double *D /* [I][I] */, double *cor /* [I][I] */);
+void mc_residual_summary(int I, const double *cor /* [I][I] */, mc_resid_result *r /* its three [I] arrays allocated */);
+int mc_residual_correlation(const mc_data *dat, mc_model *mod, mc_resid_result *out);
+void mc_resid_result_free(mc_resid_result *r);
+/* "Residual correlation (K=<K>): mean <%.6f> mean |r| <%.6f> max <%.6f> (<i>, <j>) over <n> pairs", with "no pairs" behind the colon
+ * when no pair has a number; no line end */
+void mc_resid_line(FILE *fp, const mc_resid_result *r);
+
 /* ---- opt-in watchdog (mc_watchdog.c): nothing in the reference corresponds -- it has nothing to wait for ----
  * mc_watchdog_start(s): a detached thread that polls the library's event count (mchip_progress_report) and, when it has stood
  * still for s seconds, prints where every thread stands (library record + /proc/self/task) on stderr and leaves with _exit(3).

@@ -13,6 +13,8 @@
  * --fill fills the missing genotypes from the best fit of every K (one more stdout line per K and a filled copy of the data file; without it nothing changes);
  * --fst describes the clusters of the best fit of every K: expected heterozygosity, net distance and F_ST of every pair, F_ST per locus and among
  * the clusters (one more stdout line per K and two more files; either model; without it nothing changes);
+ * --resid checks the best fit of every K against the data: the correlation over the loci of the residuals "observed allele count minus predicted
+ * count" of every pair of individuals (one more stdout line per K and two more files; admixture model; without it nothing changes);
  * --query <file> keeps the individuals the file marks out of every fit and fits their mixing proportions against the best fit of every K
  * afterwards (one more stdout line per K and one more file; without it nothing changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
@@ -22,7 +24,7 @@
  * over the same workers as whole units for both models; the mixture model's initialisations are not sharded.
  * Where a post-fit analysis plugs in: the serial and the sharded path differ in who fits which unit and share the rest.  Both keep
  * the best fit of a K in a fit_record, hand it to new_maximum() when it improved on the K before (H0 estimate, result files, -A) and
- * end in post_fit(), which puts the record back into a model once and runs --fst, --cv, --se, --query, --fill; an analysis that refits derived
+ * end in post_fit(), which puts the record back into a model once and runs --fst, --resid, --cv, --se, --query, --fill; an analysis that refits derived
  * data sets builds on mc_refit_* (mc_refit.c), adds its line to post_fit()'s text and its refusals to parse_options' refuse().
  */
 #include "mc_cli.h"
@@ -81,7 +83,11 @@ static void usage(FILE *fp, const char *prog)
 		"  --fst         divergence of the clusters of the best fit of every K: one more line 'Divergence (K=..)' per K -- mean, smallest and\n"
 		"                largest pairwise Fst and the Fst among the clusters -- and the files <stem>.<admix|mix>.K=<K>.fst.txt (weight and expected\n"
 		"                heterozygosity of every cluster, net distances, pairwise Fst) and .fst.loci.txt (Fst per locus); either model; not\n"
-		"                with -b, -w, -M or --gpus above 1\n", prog);
+		"                with -b, -w, -M or --gpus above 1\n"
+		"  --resid       residual correlation of the best fit of every K between every pair of individuals (near zero under an adequate fit;\n"
+		"                relatives, duplicates and a K that is too small show as positive blocks): one more line 'Residual correlation\n"
+		"                (K=..)' per K and the files <stem>.admix.K=<K>.resid.txt (the I x I matrix: I*I numbers) and .resid.ind.txt (mean,\n"
+		"                largest and partner per individual); needs -a, not with -b, -w, -M or --gpus above 1\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -205,6 +211,7 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 		case 'A': if (++i >= argc) BAD("-A"); o->afile = argv[i]; break;	/* multiclust.c:1416-1418 */
 		case 'R': o->R_format = 1; break;
 		case 'r':
+			if (!strcmp(argv[i], "--resid")) { o->resid = 1; break; }	/* (in full: -r... is the seed) */
 			/* extension: --randem selects the Rand-EM initialisation the reference carries but cannot reach
 			 * (initialization_procedure stays NOTHING, multiclust.c:935); -m <n> is its number of candidates */
 			if (!strncmp(w, "ra", 2)) { o->em.initialization_procedure = MC_RAND_EM; break; }
@@ -285,6 +292,11 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			o->n_bootstrap ? "--fst cannot be combined with the bootstrap (-b)" :
 			o->n_gpus > 1 ? "--fst cannot be combined with --gpus above 1" :
 			timed ? "--fst cannot be combined with -w or -M" : NULL))) return rc;
+	if (o->resid && (rc = refuse("--resid",
+			!o->em.admixture ? "--resid needs the admixture model (-a)" :
+			o->n_bootstrap ? "--resid cannot be combined with the bootstrap (-b)" :
+			o->n_gpus > 1 ? "--resid cannot be combined with --gpus above 1" :
+			timed ? "--resid cannot be combined with -w or -M" : NULL))) return rc;
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -512,13 +524,13 @@ static int new_maximum(const mc_cli_options *o, const mc_cli_data *d, run_state 
 	return rc;
 }
 
-/* ---- the post-fit stage: --fst, --cv, --se, --query and --fill, in that order, on the best fit of one K ----
+/* ---- the post-fit stage: --fst, --resid, --cv, --se, --query and --fill, in that order, on the best fit of one K ----
  * fit: that fit, with its parameters.  mod: the model that fitted it (its slots are free again; --query needs this one: the
  * hold-out that hides the query individuals is in force on its context), or NULL: a model is created on `device` for the purpose
  * (the workers of a sharded fit are gone by the time the best unit is known).  The fit goes back into the model once: every
  * analysis leaves slot pindex and the host state of the model as it found them (mc_host.h).  Each analysis writes its file
  * (result files on) and adds its stdout line to st->post_lines. */
-static int wants_post_fit(const mc_cli_options *o, int bootstrap) { return (o->fst || o->cv_folds || o->se_replicates || o->query_file || o->fill) && !bootstrap; }
+static int wants_post_fit(const mc_cli_options *o, int bootstrap) { return (o->fst || o->resid || o->cv_folds || o->se_replicates || o->query_file || o->fill) && !bootstrap; }
 
 static int post_fit(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, const fit_record *fit, mc_model *mod, int device)
 {
@@ -543,6 +555,17 @@ static int post_fit(const mc_cli_options *o, const mc_cli_data *d, const mc_data
 			fputc('\n', say);
 			if (o->write_files) rc = mc_write_divergence(o, d, &res);
 			mc_divergence_result_free(&res);
+		}
+	}
+	if (!rc && o->resid) {	/* next: it reads the slot and the installed data set, before anything installs another.  With result files on:
+				 * <stem>.admix.K=<K>.resid.txt, .resid.ind.txt */
+		mc_resid_result res;
+		mchip_progress_note("residual correlation");
+		if (!(rc = mc_residual_correlation(md, mod, &res))) {
+			mc_resid_line(say, &res);
+			fputc('\n', say);
+			if (o->write_files) rc = mc_write_resid(o, &res);
+			mc_resid_result_free(&res);
 		}
 	}
 	if (!rc && o->cv_folds) {
@@ -705,7 +728,7 @@ static int maximize_likelihood_sharded(const mc_cli_options *o, const mc_cli_dat
 {
 	const int n_dev = n_workers(o), n_gpus = o->n_gpus < 1 ? 1 : o->n_gpus, n_units = (K == 1) ? 1 : o->n_init;
 	const int npar = mc_no_parameters(&o->em, md, K);
-	const int want_params = (!bootstrap && (o->write_files || o->fst || o->cv_folds || o->se_replicates || o->fill || (o->n_bootstrap && K == st->null_K))) || o->afile != NULL;
+	const int want_params = (!bootstrap && (o->write_files || o->fst || o->resid || o->cv_folds || o->se_replicates || o->fill || (o->n_bootstrap && K == st->null_K))) || o->afile != NULL;
 	const double max_logL_keep = st->sum.max_logL, aic_keep = st->sum.aic, bic_keep = st->sum.bic;
 	shard_worker *w = calloc((size_t)n_dev, sizeof *w);
 	pthread_t *th = calloc((size_t)n_dev, sizeof *th);
@@ -827,7 +850,7 @@ static int estimate_model(const mc_cli_options *o, const mc_cli_data *d, const m
 		if (rc) return rc;
 		if (o->n_repeat == 1 && o->em.verbosity)
 			print_model_state(o, d, st, K, (int)(((double)clock() - start) / CLOCKS_PER_SEC), 1);
-		if (st->post_lines) {	/* --fst, --cv, --se, --query, --fill (post_fit) */
+		if (st->post_lines) {	/* --fst, --resid, --cv, --se, --query, --fill (post_fit) */
 			fputs(st->post_lines, st->out);
 			free(st->post_lines);
 			st->post_lines = NULL;
