@@ -517,6 +517,31 @@ int mchip_profile_end(mchip_context *ctx, double *total_ms, double *kernel_ms, i
 /* device properties the bench reports (name, CU count, memory) */
 int mchip_device_info(mchip_context *ctx, char *name, int name_len, int *compute_units, double *hbm_bytes);
 
+/*
+ * Which kernels a model on a data set of this shape would launch, and with what geometry: the library's own kernel selection
+ * ("Kernel selection"), for tests and diagnosis.  Needs no context and no device.  The tuning knobs come from the
+ * environment, as they do for a real model; n_cu is the compute-unit count of the device asked about (mchip_device_info).
+ * buf receives one line per fact:
+ *   - the kernel instances, spelled as in the source (k_column_counts<2,false,true>, k_finalize_qp, ...), that one mchip_em_step
+ *     followed by mchip_loglik, mchip_e_step and mchip_loglik_prefetch would launch, or with accel_cycle != 0 one cycle of
+ *     mchip_accel_run: the passes over the genotype matrix and the finalisers, each once, not the small fixed launches around them.
+ *     An E step that runs as one paired launch is listed as k_estep_pair<...> and as the two instances whose bodies that launch runs;
+ *   - key=value lines: n_ichunks, lchunk, n_lchunks, ind_waves, xcd_rows, sparse, col_slabs, ind_slabs, ll_parts, pair, dual,
+ *     shared_eta, byte_flags.
+ * MCHIP_ERR_INVALID for a bad query or a buffer too small (4 KiB always suffice); MCHIP_ERR_UNSUPPORTED for K > MCHIP_MAX_K and
+ * for a cycle where mchip_accel_run itself is unsupported (loci with more alleles than the sparse pass takes).
+ */
+typedef struct mchip_plan_query {
+	int K, I, L, T, ploidy;			/* T = sum of uniquealleles */
+	int min_alleles, max_alleles;		/* smallest and largest uniquealleles[l] */
+	int has_missing;			/* the data set has a missing allele copy */
+	int admixture, eta_constrained, do_projection;	/* as for mchip_set_model */
+	double p_lb;
+	int n_cu;
+	int accel_cycle;
+} mchip_plan_query;
+int mchip_describe_plan(const mchip_plan_query *q, char *buf, int buf_len);
+
 /* ---- where the process stands: the record a watchdog reads when a run makes no progress ----
  * The reference is one thread of plain C that blocks on nothing but its own loops (em_alg.c:78-88, log_likelihood.c:212-221);
  * this library blocks on the HIP runtime (stream synchronisation behind every entry point that returns a value, copies,

@@ -10,6 +10,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
 #include <sys/syscall.h>
 #include <unistd.h>
 
@@ -60,29 +61,29 @@ const mchip_ktable *mchip_get_ktable(int K)
 }
 
 /* ------------------------------------------------------------------ context */
-static void read_knobs(mchip_context *ctx)
+static void read_knobs(mchip_knobs *knob)
 {
 	auto on = [](const char *name) { return getenv(name) != nullptr ? 1 : 0; };
 	auto num = [](const char *name, int dflt) { const char *e = getenv(name); return (e && atoi(e) > 0) ? atoi(e) : dflt; };
-	ctx->knob.no_bial = on("MCHIP_NO_BIAL");
-	ctx->knob.no_counts = on("MCHIP_NO_COUNTS");
-	ctx->knob.force_dense = on("MCHIP_FORCE_DENSE");
-	ctx->knob.force_safe = on("MCHIP_FORCE_SAFE");
-	ctx->knob.no_graph = on("MCHIP_NO_GRAPH");
-	ctx->knob.no_dual = on("MCHIP_NO_DUAL");
-	ctx->knob.no_slab_sum = on("MCHIP_NO_SLAB_SUM");
-	ctx->knob.no_fused_finalize = on("MCHIP_NO_FUSED_FINALIZE");
-	ctx->knob.no_pair = on("MCHIP_NO_PAIR");
-	ctx->knob.no_col_split = on("MCHIP_NO_COL_SPLIT");
-	ctx->knob.part_no_tile = on("MCHIP_PART_NO_TILE");
-	ctx->knob.sim_no_tile = on("MCHIP_SIM_NO_TILE");
+	knob->no_bial = on("MCHIP_NO_BIAL");
+	knob->no_counts = on("MCHIP_NO_COUNTS");
+	knob->force_dense = on("MCHIP_FORCE_DENSE");
+	knob->force_safe = on("MCHIP_FORCE_SAFE");
+	knob->no_graph = on("MCHIP_NO_GRAPH");
+	knob->no_dual = on("MCHIP_NO_DUAL");
+	knob->no_slab_sum = on("MCHIP_NO_SLAB_SUM");
+	knob->no_fused_finalize = on("MCHIP_NO_FUSED_FINALIZE");
+	knob->no_pair = on("MCHIP_NO_PAIR");
+	knob->no_col_split = on("MCHIP_NO_COL_SPLIT");
+	knob->part_no_tile = on("MCHIP_PART_NO_TILE");
+	knob->sim_no_tile = on("MCHIP_SIM_NO_TILE");
 	const int both = num("MCHIP_BLOCKS_PER_CU", 64);
-	ctx->knob.per_cu_col = num("MCHIP_BLOCKS_PER_CU_COL", both);
-	ctx->knob.per_cu_ind = num("MCHIP_BLOCKS_PER_CU_IND", both);
+	knob->per_cu_col = num("MCHIP_BLOCKS_PER_CU_COL", both);
+	knob->per_cu_ind = num("MCHIP_BLOCKS_PER_CU_IND", both);
 	const char *f = getenv("MCHIP_SLAB_FRAC");
-	ctx->knob.slab_frac = (f && atof(f) > 0) ? atof(f) : 0.3;
-	ctx->knob.no_roundup = on("MCHIP_NO_CHUNK_ROUNDUP");
-	ctx->knob.geometry_given = on("MCHIP_BLOCKS_PER_CU") || on("MCHIP_BLOCKS_PER_CU_COL") || on("MCHIP_SLAB_FRAC");
+	knob->slab_frac = (f && atof(f) > 0) ? atof(f) : 0.3;
+	knob->no_roundup = on("MCHIP_NO_CHUNK_ROUNDUP");
+	knob->geometry_given = on("MCHIP_BLOCKS_PER_CU") || on("MCHIP_BLOCKS_PER_CU_COL") || on("MCHIP_SLAB_FRAC");
 }
 
 /* ------------------------------------------------------------------ K-independent kernels */
@@ -966,7 +967,7 @@ __global__ __launch_bounds__(PAIR_SPAN_THREADS) void k_pair_spans(const unsigned
 {
 	__shared__ unsigned long long red[4][PAIR_SPAN_THREADS];
 	unsigned long long lo[2] = { ~0ull, ~0ull }, hi[2] = { 0ull, 0ull };
-	for (unsigned r = threadIdx.x; r < n_blocks / MCHIP_PAIR_RUN; r += PAIR_SPAN_THREADS) {	/* (n_blocks: whole runs, pair_blocks()) */
+	for (unsigned r = threadIdx.x; r < n_blocks / MCHIP_PAIR_RUN; r += PAIR_SPAN_THREADS) {	/* (n_blocks: whole runs, mchip_plan::pair_blocks) */
 		unsigned logical;
 		const int kind = mchip_pair_is_ind(r * MCHIP_PAIR_RUN, runs, &logical) ? 1 : 0;
 #pragma unroll
@@ -997,10 +998,8 @@ __global__ __launch_bounds__(PAIR_SPAN_THREADS) void k_pair_spans(const unsigned
 }
 
 /* room for the next profiled paired launch: its blocks' clock readings and its span */
-static int pair_profile_slot(mchip_context *ctx, const mchip_pass_args &a, unsigned long long **marks)
+static int pair_profile_slot(mchip_context *ctx, size_t n_blocks, unsigned long long **marks)
 {
-	mchip_pair_runs runs;
-	const size_t n_blocks = ctx->kt->pair_blocks(a, &runs);
 	if (n_blocks > ctx->pair_marks_cap) {
 		HIPCHK(hipStreamSynchronize(ctx->stream));	/* (an earlier launch may still be writing the smaller buffer) */
 		dfree(ctx->d_pair_marks);
@@ -1067,25 +1066,182 @@ void free_data(mchip_context *ctx, int keep)
 	ctx->I = ctx->L = ctx->T = 0;
 }
 
-static mchip_pass_args pass_args(mchip_context *ctx, int slot)
+/* what a data set's shape is to the launch geometry and the plan */
+struct mchip_shape { int I, L, T, ploidy, min_M, max_M, count_bits; };
+
+/* bits per packed allele count of the column pass's second genotype layout (gtC), 0 = none */
+static int count_bits_for(int ploidy, const mchip_knobs &kn)
+{
+	if (kn.no_counts) return 0;
+	return ploidy <= 3 ? 2 : (ploidy <= 15 ? 4 : 0);
+}
+
+/* Launch geometry of a model on a data set: a function of the shape, the model, the knobs and the device's CU count alone (it
+ * touches neither the device nor a context: mchip_describe_plan runs it on a machine without a GPU). */
+static mchip_geometry model_geometry(const mchip_shape &sh, int K, int admixture, int do_projection, double p_lb, const mchip_knobs &kn, int n_cu)
+{
+	mchip_geometry g = {};
+	/* launch geometry.  Both passes are FP64-issue-bound and every workgroup does the same amount of work, so
+	 * the grid's last partial "round" of workgroups runs at low occupancy: measured at config 3, 8 workgroups
+	 * per CU cost 6.9 ms per EM step, 64 per CU 5.4 ms (profiles/r01_geometry_sweep.txt).  More chunks mean
+	 * more partial-sum slabs (Apart/Spart are written and re-read once per step), so the chunk count is capped
+	 * where the slab bytes reach ~30 % of the genotype bytes the pass streams (config 2: 0.188 -> 0.179 ms per step against 15 %;
+	 * config 3 reaches its 64 workgroups per CU before either cap).  The column pass stops at 15 % once the grid fills the
+	 * device twice over: its slabs are K*T doubles each and k_finalize_p reads them all (config 5: 28 -> 15 slabs, 1.61 ->
+	 * 1.56 ms per step; scripts/diag/geom.sh).  Chunk sizes are multiples of 8. */
+	const int per_cu_col = kn.per_cu_col, per_cu_ind = kn.per_cu_ind;	/* tuning knobs (default 64) */
+	int target = per_cu_col * n_cu;
+	const int col_tiles = (sh.T + MCHIP_BLOCK - 1) / MCHIP_BLOCK;
+	const int iblocks = (sh.I + 7) / 8, lblocks = (sh.L + 7) / 8;
+	const double slab_frac = kn.slab_frac;	/* tuning knob (default 0.3) */
+	/* column pass: slab bytes per chunk 8*K*T, genotype bytes per chunk ichunk*L*ploidy */
+	int min_ichunk = (int)ceil(8.0 * K * sh.T / (slab_frac * sh.L * sh.ploidy));
+	int want = (target + col_tiles - 1) / col_tiles;
+	int cap = sh.I / (min_ichunk > 0 ? min_ichunk : 1);
+	{
+		const int cap_lo = cap / 2;						/* half the slab budget */
+		const int fill = (2 * 8 * n_cu + col_tiles - 1) / col_tiles;	/* two rounds of 8 resident workgroups per CU */
+		const int soft = cap_lo > (fill < cap ? fill : cap) ? cap_lo : (fill < cap ? fill : cap);
+		if (!kn.geometry_given && want > soft) want = soft;
+	}
+	if (want > cap) want = cap;
+	if (want < 1) want = 1;
+	if (want > iblocks) want = iblocks;
+	if (sh.count_bits && !kn.no_roundup) {	/* the packed-count column pass puts MCHIP_COL_WAVES chunks into a workgroup: whole workgroups where the caps allow */
+		const int up = ((want + MCHIP_COL_WAVES - 1) / MCHIP_COL_WAVES) * MCHIP_COL_WAVES;
+		if (up <= cap && up <= iblocks) want = up;
+	}
+	{
+		const int gran = sh.count_bits ? 128 / sh.count_bits : 8;	/* individuals per packed word */
+		const int per = (sh.I + want - 1) / want;
+		g.ichunk = ((per + gran - 1) / gran) * gran;
+	}
+	g.n_ichunks = (sh.I + g.ichunk - 1) / g.ichunk;
+	/* individual pass: slab bytes per chunk 8*K*I, genotype bytes per chunk lchunk*I*ploidy */
+	/* (the sparse pass gives an individual mchip_ind_split(K) lanes; the dense and mixture kernels one, and do not use n_ll_ind) */
+	const int ind_per_block = mchip_qblock(K) / (admixture ? mchip_ind_split(K) : 1);
+	const int ind_tiles = (sh.I + ind_per_block - 1) / ind_per_block;
+	int min_lchunk = (int)ceil(8.0 * K / (slab_frac * sh.ploidy));
+	target = per_cu_ind * n_cu;
+	want = (target + ind_tiles - 1) / ind_tiles;
+	cap = sh.L / (min_lchunk > 0 ? min_lchunk : 1);
+	if (want > cap) want = cap;
+	if (want < 1) want = 1;
+	if (want > lblocks) want = lblocks;
+	{	/* the sparse individual pass stages two tiles of 8 loci of P rows in LDS: use it while they fit 64 KiB */
+		const size_t kp = (size_t)mchip_kp(K);
+		const size_t lds = (2 * 8 * (size_t)sh.max_M * kp + mchip_qblock(K)) * sizeof(double);
+		g.sparse = (sh.max_M <= MCHIP_SPARSE_MAX_M) && lds <= 65536 && !kn.force_dense;
+	}
+	/* cooperating waves (mchip_internal.h): chunks are still what ONE WAVE takes; a workgroup of the sparse individual-side kernels
+	 * is ind_waves of them, so a whole number of workgroups wants a multiple of that many chunks where the caps allow it */
+	const bool ind_coop = admixture && g.sparse && mchip_ind_split(K) == 1;
+	g.ind_waves = ind_coop ? mchip_ind_waves(K, 8 * sh.max_M) : 1;
+	if (ind_coop) {
+		/* ... and a multiple of eight slab rows where possible: the sparse kernel then keeps a row on one XCD (coop_rows() in
+		 * mchip_kernels_k.hip), and eight XCDs with 52 rows between them would have 7 and 6 each */
+		const int w8 = 8 * g.ind_waves, w1 = g.ind_waves;
+		const int up8 = ((want + w8 - 1) / w8) * w8, up1 = ((want + w1 - 1) / w1) * w1;
+		if (up8 <= cap && up8 <= lblocks) want = up8;
+		else if (up1 <= cap && up1 <= lblocks) want = up1;
+	}
+	g.lchunk = ((lblocks + want - 1) / want) * 8;
+	g.n_lchunks = (sh.L + g.lchunk - 1) / g.lchunk;
+	g.xcd_rows = (ind_coop && ((g.n_lchunks + g.ind_waves - 1) / g.ind_waves) % 8 == 0) ? 1 : 0;
+	{	/* partial log likelihoods any pass can leave: one per workgroup; no individual-side kernel has fewer than 64 individuals
+		 * per workgroup, no column-side one fewer than 64 columns */
+		const int by_col = ((sh.T + 63) / 64) * g.n_ichunks, by_ind = ((sh.I + 63) / 64) * g.n_lchunks;
+		(void)col_tiles; (void)ind_tiles;
+		g.n_llpart = by_col > by_ind ? by_col : by_ind;
+	}
+	/* log-product check interval: with every parameter >= its lower bound, t = sum_k q_k p_k >= p_lb / K, so
+	 * floor(200 / -log10(t_min)) multiplications keep a product that starts above 1e-100 above 1e-300
+	 * (DESIGN.md section 4).  A block of 8 loci (or individuals) multiplies 8*ploidy times. */
+	{
+		const double tmin = p_lb / K;
+		int blocks = 0;
+		if (do_projection && tmin > 0 && tmin < 1) {
+			const double mults = floor(200.0 / -log10(tmin));
+			/* the sparse tetraploid pass checks twice per block (every 4 loci = 16 multiplications) */
+			blocks = (int)(mults / (sh.ploidy == 4 ? 16.0 : 8.0 * sh.ploidy));
+			if (blocks > 1 << 16) blocks = 1 << 16;
+		}
+		g.flush_blocks = blocks;
+		/* Supported lower bounds (--bound): any value >= 0.  The fast kernels share one reciprocal among the four cells of a
+		 * column-pass step (1 / (t0 t1 t2 t3)) and between the two copies of a locus, which needs every t > 0 and
+		 * t^4 >= DBL_MIN: guaranteed when projection is on and p_lb >= 1e-75 (t >= p_lb).  Otherwise -- projection off
+		 * (--projection: an unobserved allele column, e.g. the phantom slot of a locus with missing data or an allele a
+		 * bootstrap replicate lacks, has P = 0 for every k, so t = 0 in its zero-count cells) or a smaller bound -- the
+		 * kernels take one reciprocal per non-empty cell and zero-count cells contribute exactly 0, as in em_alg.c:338-342.
+		 * A non-empty cell with t = 0 is NaN here as it is in the reference (n * 0 / 0). */
+		g.safe_rcp = (!do_projection || !(p_lb >= 1e-75)) ? 1 : 0;
+		if (kn.force_safe) g.safe_rcp = 1;
+		if (g.safe_rcp) g.flush_blocks = 0;
+	}
+	return g;
+}
+
+/* the pass arguments that shape, geometry and knobs give: everything the plan reads, no buffer */
+static mchip_pass_args shape_args(const mchip_shape &sh, const mchip_geometry &g, const mchip_knobs &kn, int K, int qstride, int has_missing)
 {
 	mchip_pass_args a;
 	memset(&a, 0, sizeof a);
-	a.I = ctx->I; a.L = ctx->L; a.T = ctx->T; a.ploidy = ctx->ploidy; a.K = ctx->K;
-	a.gtA = ctx->d_gtA; a.gtS = ctx->d_gtS; a.gtC = ctx->d_gtC; a.count_bits = ctx->count_bits; a.has_missing = ctx->has_missing;
-	a.ua = ctx->d_ua; a.toff = ctx->d_toff; a.col_locus = ctx->d_col_locus; a.col_allele = ctx->d_col_allele;
-	a.P = ctx->d_p[slot]; a.Q = ctx->d_q[slot]; a.qstride = ctx->qstride;
-	a.ichunk = ctx->ichunk; a.n_ichunks = ctx->n_ichunks; a.Apart = ctx->d_Apart; a.llpart = ctx->d_llpart;
-	a.flush_blocks = ctx->flush_blocks;
-	a.safe_rcp = ctx->safe_rcp;
-	a.lchunk = ctx->lchunk; a.n_lchunks = ctx->n_lchunks; a.Spart = ctx->d_Spart;
-	a.asA = ctx->d_asA; a.asS = ctx->d_asS;
-	a.sparse = ctx->sparse; a.tile_cols = 8 * ctx->max_M;
-	a.biallelic = (ctx->min_M == 2 && ctx->max_M == 2 && !ctx->knob.no_bial) ? 1 : 0;
-	a.ind_waves = ctx->ind_waves;
-	a.xcd_rows = ctx->xcd_rows;
-	a.no_col_split = ctx->knob.no_col_split;
+	a.I = sh.I; a.L = sh.L; a.T = sh.T; a.ploidy = sh.ploidy; a.K = K;
+	a.count_bits = sh.count_bits; a.has_missing = has_missing;
+	a.qstride = qstride;
+	a.ichunk = g.ichunk; a.n_ichunks = g.n_ichunks;
+	a.flush_blocks = g.flush_blocks;
+	a.safe_rcp = g.safe_rcp;
+	a.lchunk = g.lchunk; a.n_lchunks = g.n_lchunks;
+	a.sparse = g.sparse; a.tile_cols = 8 * sh.max_M;
+	a.biallelic = (sh.min_M == 2 && sh.max_M == 2 && !kn.no_bial) ? 1 : 0;
+	a.ind_waves = g.ind_waves;
+	a.xcd_rows = g.xcd_rows;
+	a.no_col_split = kn.no_col_split;
 	return a;
+}
+
+static mchip_shape shape_of(const mchip_context *ctx)
+{
+	return mchip_shape{ ctx->I, ctx->L, ctx->T, ctx->ploidy, ctx->min_M, ctx->max_M, ctx->count_bits };
+}
+
+static mchip_pass_args pass_args(mchip_context *ctx, int slot)
+{
+	mchip_pass_args a = shape_args(shape_of(ctx), ctx->geo, ctx->knob, ctx->K, ctx->qstride, ctx->has_missing);
+	a.gtA = ctx->d_gtA; a.gtS = ctx->d_gtS; a.gtC = ctx->d_gtC;
+	a.ua = ctx->d_ua; a.toff = ctx->d_toff; a.col_locus = ctx->d_col_locus; a.col_allele = ctx->d_col_allele;
+	a.P = ctx->d_p[slot]; a.Q = ctx->d_q[slot];
+	a.Apart = ctx->d_Apart; a.llpart = ctx->d_llpart; a.Spart = ctx->d_Spart;
+	a.asA = ctx->d_asA; a.asS = ctx->d_asS;
+	return a;
+}
+
+/* partial log likelihoods k_mix_finalize leaves: one per workgroup */
+static int mix_ll_parts(int I) { return (I + MCHIP_BLOCK - 1) / MCHIP_BLOCK; }
+/* the projection of P keeps its "fixed" flags in registers up to 64 alleles per locus, above that in d_flags */
+static bool needs_byte_flags(int max_M) { return max_M > 64; }
+
+/* the plan of these arguments, less what the knobs switch off */
+static mchip_plan plan_for(const mchip_ktable *kt, const mchip_pass_args &a, const mchip_knobs &kn)
+{
+	mchip_plan p;
+	kt->plan(a, &p);
+	if (kn.no_pair) p.pair = 0;
+	if (kn.no_dual) p.dual = 0;
+	return p;
+}
+
+/* the finalisers behind an E step's passes: both in one launch (k_finalize_qp: an M step with individual mixing proportions whose P
+ * side takes the tiled form), or k_finalize_q and the P side's, the latter behind k_sum_slabs where the column pass left many slabs */
+struct estep_finish { int p_loci; bool slab_sum, fused; };
+static estep_finish finish_for(const mchip_plan &p, int K, int max_M, bool indiv, int do_mstep, const mchip_knobs &kn)
+{
+	estep_finish f;
+	f.p_loci = finalize_p_loci(K, max_M);
+	f.slab_sum = p.col_slabs > 8 && !kn.no_slab_sum;
+	f.fused = do_mstep && indiv && f.p_loci && !f.slab_sum && !kn.no_fused_finalize;
+	return f;
 }
 
 /* P[to] from n_slabs slabs of N-side sums: the tiled form where the data set allows it */
@@ -1131,8 +1287,8 @@ int mchip_create(mchip_context **out, int device)
 	ctx->cv_fold = -1;
 	ctx->device = device;
 	ctx->err[0] = 0;
-	ctx->ind_waves = 1;
-	read_knobs(ctx);
+	ctx->geo.ind_waves = 1;
+	read_knobs(&ctx->knob);
 	if (MCHIP_WAIT(hipSetDevice(device)) != hipSuccess || MCHIP_WAIT(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) {
 		delete ctx;
 		return MCHIP_ERR_HIP;
@@ -1183,6 +1339,96 @@ int mchip_synchronize(mchip_context *ctx)
 	return MCHIP_OK;
 }
 
+/* How an instance is spelled: its kernel's name and, in the order of the kernel's template arguments, the fields of mchip_instance
+ * that are those arguments (p pl, b bits, A accum, S safe, N nomiss, L ll, M mix, D dual, G staged). */
+static const struct { const char *name, *args; } kernel_names[MCHIP_K_KINDS] = {
+	{ "", "" },
+	{ "k_column_pass", "pASL" },
+	{ "k_column_counts", "bMS" },
+	{ "k_column_counts_split", "bS" },
+	{ "k_individual_pass", "p" },
+	{ "k_individual_sparse", "pASND" },
+	{ "k_individual_sparse_w", "pASND" },
+	{ "k_individual_bial", "AN" },
+	{ "k_estep_pair", "bpSN" },
+	{ "k_mix_gather", "pG" },
+	{ "k_mix_column", "p" },
+};
+static std::string instance_name(const mchip_instance &k)
+{
+	std::string out = kernel_names[k.kernel].name;
+	for (const char *c = kernel_names[k.kernel].args; *c; c++) {
+		const bool flag = *c == 'A' ? k.accum : *c == 'S' ? k.safe : *c == 'N' ? k.nomiss : *c == 'L' ? k.ll : *c == 'M' ? k.mix : *c == 'D' ? k.dual : k.staged;
+		out += c == kernel_names[k.kernel].args ? "<" : ",";
+		out += *c == 'p' ? std::to_string(k.pl) : *c == 'b' ? std::to_string(k.bits) : flag ? "true" : "false";
+	}
+	return out + ">";
+}
+
+int mchip_describe_plan(const mchip_plan_query *q, char *buf, int buf_len)
+{
+	if (!q || !buf || buf_len < 1) return MCHIP_ERR_INVALID;
+	if (q->K < 1 || q->I < 1 || q->L < 1 || q->T < 1 || q->ploidy < 1 || q->ploidy > 64 || q->min_alleles > q->max_alleles ||
+	    q->max_alleles < 1 || q->max_alleles > 255 || q->n_cu < 1)
+		return MCHIP_ERR_INVALID;
+	if (q->K > MCHIP_MAX_K) return MCHIP_ERR_UNSUPPORTED;
+	mchip_knobs kn;
+	read_knobs(&kn);
+	const int K = q->K, indiv = q->admixture && !q->eta_constrained;
+	const mchip_shape sh = { q->I, q->L, q->T, q->ploidy, q->min_alleles, q->max_alleles, count_bits_for(q->ploidy, kn) };
+	const mchip_geometry g = model_geometry(sh, K, q->admixture, q->do_projection, q->p_lb, kn, q->n_cu);
+	const mchip_pass_args a = shape_args(sh, g, kn, K, indiv ? K : 0, q->has_missing);
+	const mchip_plan p = plan_for(mchip_get_ktable(K), a, kn);
+	const estep_finish fin = finish_for(p, K, sh.max_M, indiv, 1, kn);
+	std::vector<std::string> lines;
+	auto launch = [&](const std::string &name) {
+		for (const std::string &l : lines) if (l == name) return;
+		lines.push_back(name);
+	};
+	auto fact = [&](const char *key, long v) { lines.push_back(std::string(key) + "=" + std::to_string(v)); };
+	const char *finalize_p = fin.p_loci ? "k_finalize_p_tile" : "k_finalize_p";	/* (launch_finalize_p) */
+	if (!q->admixture) {	/* run_mixture, with and without the M step, whatever the calls */
+		launch(instance_name(p.mix_gather));
+		launch("k_mix_finalize");
+		launch(instance_name(p.mix_col));
+		launch(finalize_p);
+	} else {
+		if (q->accel_cycle && p.col.ll) return MCHIP_ERR_UNSUPPORTED;	/* (mchip_accel_run: the dense pair runs cycle by cycle) */
+		/* run_estep with the M step: the passes, then the finalisers */
+		if (p.pair) launch(instance_name(p.pair_pass));	/* (one launch that runs the bodies of the two below) */
+		launch(instance_name(p.col));
+		launch(instance_name(p.sside));
+		if (fin.fused) launch("k_finalize_qp");
+		else {
+			launch("k_finalize_q");
+			if (fin.slab_sum) launch("k_sum_slabs");
+			launch(finalize_p);
+		}
+		if (q->accel_cycle) {	/* accel_cycle_enqueue: log L of the second EM iterate and of the extrapolated point */
+			if (p.dual) launch(instance_name(p.dual_pass));
+			else { launch(instance_name(p.ll)); launch(instance_name(p.sside)); }
+		} else {
+			launch(instance_name(p.ll));						/* mchip_loglik */
+			if (p.col.ll) launch(instance_name(p.ll));				/* mchip_e_step: run_estep without the M step */
+			launch(instance_name(p.sside));
+			launch("k_finalize_q");
+			launch(instance_name(p.col.ll ? p.ll : p.sside));			/* mchip_loglik_prefetch */
+		}
+	}
+	fact("n_ichunks", g.n_ichunks); fact("lchunk", g.lchunk); fact("n_lchunks", g.n_lchunks);
+	fact("ind_waves", g.ind_waves); fact("xcd_rows", g.xcd_rows); fact("sparse", g.sparse);
+	fact("col_slabs", q->admixture ? p.col_slabs : p.mix_col_slabs);
+	fact("ind_slabs", p.ind_slabs);
+	fact("ll_parts", q->admixture ? p.ll_parts : mix_ll_parts(q->I));
+	fact("pair", q->admixture ? p.pair : 0); fact("dual", q->admixture ? p.dual : 0);
+	fact("shared_eta", !indiv); fact("byte_flags", needs_byte_flags(sh.max_M));
+	std::string out;
+	for (const std::string &l : lines) out += l + "\n";
+	if (out.size() >= (size_t)buf_len) return MCHIP_ERR_INVALID;
+	memcpy(buf, out.c_str(), out.size() + 1);
+	return MCHIP_OK;
+}
+
 int mchip_device_info(mchip_context *ctx, char *name, int name_len, int *compute_units, double *hbm_bytes)
 {
 	MCHIP_ENTRY();
@@ -1203,7 +1449,7 @@ static int set_shape_impl(mchip_context *ctx, int I, int L, int ploidy, const in
 {
 	if (I <= 0 || L <= 0 || ploidy <= 0 || ploidy > 64 || !ua)
 		return fail(ctx, MCHIP_ERR_INVALID, "set_genotypes: bad shape or null pointer%s", nullptr);
-	read_knobs(ctx);
+	read_knobs(&ctx->knob);
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	drop_cv(ctx);	/* folds, the saved full data set and a hold-out in force belong to the data set that goes */
@@ -1288,8 +1534,7 @@ int install_layouts(mchip_context *ctx, int has_missing)
 	if (ctx->has_missing != has_missing) drop_graphs(ctx);	/* parked model buffers: the kernel variant changes */
 	ctx->has_missing = has_missing;
 	ctx->counts_valid = 0;	/* counted when asked for (mchip_data_counts): a bootstrap replicate never asks */
-	ctx->count_bits = ploidy <= 3 ? 2 : (ploidy <= 15 ? 4 : 0);
-	if (ctx->knob.no_counts) ctx->count_bits = 0;
+	ctx->count_bits = count_bits_for(ploidy, ctx->knob);
 	if (ctx->count_bits) {
 		const int G = 128 / ctx->count_bits;
 		const size_t nwords = (size_t)((I + G - 1) / G) * T;
@@ -1525,7 +1770,7 @@ static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_cons
 	/* the element-per-thread kernels over parameters take one work-item per entry of P or Q */
 	if ((size_t)K * ctx->T >= ((size_t)1 << 31) || (size_t)K * ctx->I >= ((size_t)1 << 31))
 		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "K*T or K*I of 2^31 or more is not supported%s", nullptr);
-	read_knobs(ctx);
+	read_knobs(&ctx->knob);
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	{	/* the buffers of this very model are still allocated (same data shape, same arguments): zero the parameters and go */
@@ -1573,110 +1818,14 @@ static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_cons
 	HIPCHK(hipMalloc((void **)&ctx->d_stage, KT * sizeof(double)));
 	if (!admixture) HIPCHK(hipMalloc((void **)&ctx->d_logp, KT * sizeof(double)));
 
-	/* launch geometry.  Both passes are FP64-issue-bound and every workgroup does the same amount of work, so
-	 * the grid's last partial "round" of workgroups runs at low occupancy: measured at config 3, 8 workgroups
-	 * per CU cost 6.9 ms per EM step, 64 per CU 5.4 ms (profiles/r01_geometry_sweep.txt).  More chunks mean
-	 * more partial-sum slabs (Apart/Spart are written and re-read once per step), so the chunk count is capped
-	 * where the slab bytes reach ~30 % of the genotype bytes the pass streams (config 2: 0.188 -> 0.179 ms per step against 15 %;
-	 * config 3 reaches its 64 workgroups per CU before either cap).  The column pass stops at 15 % once the grid fills the
-	 * device twice over: its slabs are K*T doubles each and k_finalize_p reads them all (config 5: 28 -> 15 slabs, 1.61 ->
-	 * 1.56 ms per step; scripts/diag/geom.sh).  Chunk sizes are multiples of 8. */
-	const int per_cu_col = ctx->knob.per_cu_col, per_cu_ind = ctx->knob.per_cu_ind;	/* tuning knobs (default 64) */
-	int target = per_cu_col * ctx->n_cu;
-	const int col_tiles = (ctx->T + MCHIP_BLOCK - 1) / MCHIP_BLOCK;
-	const int iblocks = (ctx->I + 7) / 8, lblocks = (ctx->L + 7) / 8;
-	const double slab_frac = ctx->knob.slab_frac;	/* tuning knob (default 0.3) */
-	/* column pass: slab bytes per chunk 8*K*T, genotype bytes per chunk ichunk*L*ploidy */
-	int min_ichunk = (int)ceil(8.0 * K * ctx->T / (slab_frac * ctx->L * ctx->ploidy));
-	int want = (target + col_tiles - 1) / col_tiles;
-	int cap = ctx->I / (min_ichunk > 0 ? min_ichunk : 1);
-	{
-		const int cap_lo = cap / 2;						/* half the slab budget */
-		const int fill = (2 * 8 * ctx->n_cu + col_tiles - 1) / col_tiles;	/* two rounds of 8 resident workgroups per CU */
-		const int soft = cap_lo > (fill < cap ? fill : cap) ? cap_lo : (fill < cap ? fill : cap);
-		if (!ctx->knob.geometry_given && want > soft) want = soft;
-	}
-	if (want > cap) want = cap;
-	if (want < 1) want = 1;
-	if (want > iblocks) want = iblocks;
-	if (ctx->count_bits && !ctx->knob.no_roundup) {	/* the packed-count column pass puts MCHIP_COL_WAVES chunks into a workgroup: whole workgroups where the caps allow */
-		const int up = ((want + MCHIP_COL_WAVES - 1) / MCHIP_COL_WAVES) * MCHIP_COL_WAVES;
-		if (up <= cap && up <= iblocks) want = up;
-	}
-	{
-		const int gran = ctx->count_bits ? 128 / ctx->count_bits : 8;	/* individuals per packed word */
-		const int per = (ctx->I + want - 1) / want;
-		ctx->ichunk = ((per + gran - 1) / gran) * gran;
-	}
-	ctx->n_ichunks = (ctx->I + ctx->ichunk - 1) / ctx->ichunk;
-	/* individual pass: slab bytes per chunk 8*K*I, genotype bytes per chunk lchunk*I*ploidy */
-	/* (the sparse pass gives an individual mchip_ind_split(K) lanes; the dense and mixture kernels one, and do not use n_ll_ind) */
-	const int ind_per_block = mchip_qblock(K) / (admixture ? mchip_ind_split(K) : 1);
-	const int ind_tiles = (ctx->I + ind_per_block - 1) / ind_per_block;
-	int min_lchunk = (int)ceil(8.0 * K / (slab_frac * ctx->ploidy));
-	target = per_cu_ind * ctx->n_cu;
-	want = (target + ind_tiles - 1) / ind_tiles;
-	cap = ctx->L / (min_lchunk > 0 ? min_lchunk : 1);
-	if (want > cap) want = cap;
-	if (want < 1) want = 1;
-	if (want > lblocks) want = lblocks;
-	{	/* the sparse individual pass stages two tiles of 8 loci of P rows in LDS: use it while they fit 64 KiB */
-		const size_t kp = (size_t)mchip_kp(K);
-		const size_t lds = (2 * 8 * (size_t)ctx->max_M * kp + mchip_qblock(K)) * sizeof(double);
-		ctx->sparse = (ctx->max_M <= MCHIP_SPARSE_MAX_M) && lds <= 65536 && !ctx->knob.force_dense;
-	}
-	/* cooperating waves (mchip_internal.h): chunks are still what ONE WAVE takes; a workgroup of the sparse individual-side kernels
-	 * is ind_waves of them, so a whole number of workgroups wants a multiple of that many chunks where the caps allow it */
-	ctx->ind_waves = (admixture && ctx->sparse && mchip_ind_split(K) == 1) ? mchip_ind_waves(K, 8 * ctx->max_M) : 1;
-	const bool ind_coop = admixture && ctx->sparse && mchip_ind_split(K) == 1;
-	if (ind_coop) {
-		/* ... and a multiple of eight slab rows where possible: the sparse kernel then keeps a row on one XCD (coop_rows() in
-		 * mchip_kernels_k.hip), and eight XCDs with 52 rows between them would have 7 and 6 each */
-		const int w8 = 8 * ctx->ind_waves, w1 = ctx->ind_waves;
-		const int up8 = ((want + w8 - 1) / w8) * w8, up1 = ((want + w1 - 1) / w1) * w1;
-		if (up8 <= cap && up8 <= lblocks) want = up8;
-		else if (up1 <= cap && up1 <= lblocks) want = up1;
-	}
-	ctx->lchunk = ((lblocks + want - 1) / want) * 8;
-	ctx->n_lchunks = (ctx->L + ctx->lchunk - 1) / ctx->lchunk;
-	ctx->xcd_rows = (ind_coop && ((ctx->n_lchunks + ctx->ind_waves - 1) / ctx->ind_waves) % 8 == 0) ? 1 : 0;
-	{	/* partial log likelihoods any pass can leave: one per workgroup; no individual-side kernel has fewer than 64 individuals
-		 * per workgroup, no column-side one fewer than 64 columns */
-		const int by_col = ((ctx->T + 63) / 64) * ctx->n_ichunks, by_ind = ((ctx->I + 63) / 64) * ctx->n_lchunks;
-		(void)col_tiles; (void)ind_tiles;
-		ctx->n_llpart = by_col > by_ind ? by_col : by_ind;
-	}
-	HIPCHK(hipMalloc((void **)&ctx->d_Apart, (size_t)ctx->n_ichunks * KT * sizeof(double)));
-	HIPCHK(hipMalloc((void **)&ctx->d_Spart, (size_t)ctx->n_lchunks * ctx->I * K * sizeof(double)));
-	HIPCHK(hipMalloc((void **)&ctx->d_llpart, (size_t)ctx->n_llpart * sizeof(double)));
-	HIPCHK(hipMalloc((void **)&ctx->d_llpart2, (size_t)ctx->n_llpart * sizeof(double)));
+	ctx->geo = model_geometry(shape_of(ctx), K, admixture, do_projection, p_lb, ctx->knob, ctx->n_cu);
+	HIPCHK(hipMalloc((void **)&ctx->d_Apart, (size_t)ctx->geo.n_ichunks * KT * sizeof(double)));
+	HIPCHK(hipMalloc((void **)&ctx->d_Spart, (size_t)ctx->geo.n_lchunks * ctx->I * K * sizeof(double)));
+	HIPCHK(hipMalloc((void **)&ctx->d_llpart, (size_t)ctx->geo.n_llpart * sizeof(double)));
+	HIPCHK(hipMalloc((void **)&ctx->d_llpart2, (size_t)ctx->geo.n_llpart * sizeof(double)));
 	HIPCHK(hipMalloc((void **)&ctx->d_redpart, (size_t)3 * 1024 * sizeof(double)));
-	if (ctx->max_M > 64) {
+	if (needs_byte_flags(ctx->max_M)) {
 		HIPCHK(hipMalloc((void **)&ctx->d_flags, KT));
-	}
-	/* log-product check interval: with every parameter >= its lower bound, t = sum_k q_k p_k >= p_lb / K, so
-	 * floor(200 / -log10(t_min)) multiplications keep a product that starts above 1e-100 above 1e-300
-	 * (DESIGN.md section 4).  A block of 8 loci (or individuals) multiplies 8*ploidy times. */
-	{
-		const double tmin = p_lb / K;
-		int blocks = 0;
-		if (do_projection && tmin > 0 && tmin < 1) {
-			const double mults = floor(200.0 / -log10(tmin));
-			/* the sparse tetraploid pass checks twice per block (every 4 loci = 16 multiplications) */
-			blocks = (int)(mults / (ctx->ploidy == 4 ? 16.0 : 8.0 * ctx->ploidy));
-			if (blocks > 1 << 16) blocks = 1 << 16;
-		}
-		ctx->flush_blocks = blocks;
-		/* Supported lower bounds (--bound): any value >= 0.  The fast kernels share one reciprocal among the four cells of a
-		 * column-pass step (1 / (t0 t1 t2 t3)) and between the two copies of a locus, which needs every t > 0 and
-		 * t^4 >= DBL_MIN: guaranteed when projection is on and p_lb >= 1e-75 (t >= p_lb).  Otherwise -- projection off
-		 * (--projection: an unobserved allele column, e.g. the phantom slot of a locus with missing data or an allele a
-		 * bootstrap replicate lacks, has P = 0 for every k, so t = 0 in its zero-count cells) or a smaller bound -- the
-		 * kernels take one reciprocal per non-empty cell and zero-count cells contribute exactly 0, as in em_alg.c:338-342.
-		 * A non-empty cell with t = 0 is NaN here as it is in the reference (n * 0 / 0). */
-		ctx->safe_rcp = (!do_projection || !(p_lb >= 1e-75)) ? 1 : 0;
-		if (ctx->knob.force_safe) ctx->safe_rcp = 1;
-		if (ctx->safe_rcp) ctx->flush_blocks = 0;
 	}
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	return MCHIP_OK;
@@ -1815,6 +1964,23 @@ static int finalize_shared_eta(mchip_context *ctx, int to, const int *stop = nul
 	return MCHIP_OK;
 }
 
+/* d_scalars[slot] = the sum of the n partial log likelihoods a pass left in d_llpart */
+static void reduce_ll(mchip_context *ctx, int n, int slot, const int *stop)
+{
+	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, n, ctx->d_scalars + slot, stop);
+}
+
+/* one pass that takes the log likelihood (kt->accum_q or kt->loglik), between the marks of a profiled run; slot >= 0: its partial
+ * sums' sum goes to d_scalars[slot] (else the caller's next kernel adds them up) */
+typedef void (*ll_pass_fn)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);
+static void ll_pass(mchip_context *ctx, int kind, ll_pass_fn launch, const mchip_pass_args &a, const mchip_plan &p, int slot, const int *stop = nullptr)
+{
+	prof_mark(ctx, kind, true);
+	launch(a, p, ctx->stream);
+	prof_mark(ctx, kind, false);
+	if (slot >= 0) reduce_ll(ctx, p.ll_parts, slot, stop);
+}
+
 /* mixture model: E step (mode 0, optionally followed by the M step) or logL_mixture (mode 1) */
 static int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int mode, const int *stop = nullptr, int ll_slot = -1,
 		       bool defer_ll = false)
@@ -1825,14 +1991,14 @@ static int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int m
 	mchip_pass_args a = pass_args(ctx, from);
 	a.P = ctx->d_logp;
 	a.stop = stop;
+	const mchip_plan plan = plan_for(ctx->kt, a, ctx->knob);
 	prof_mark(ctx, mode == 0 ? MCHIP_KERN_ACCUM_Q : MCHIP_KERN_LOGLIK, true);
-	ctx->kt->mix_gather(a, ctx->stream);
+	ctx->kt->mix_gather(a, plan, ctx->stream);
 	prof_mark(ctx, mode == 0 ? MCHIP_KERN_ACCUM_Q : MCHIP_KERN_LOGLIK, false);
-	const int nb = (ctx->I + MCHIP_BLOCK - 1) / MCHIP_BLOCK;
-	ctx->kt->mix_finalize(ctx->I, ctx->n_lchunks, ctx->d_Spart, ctx->d_q[from], ctx->d_sik, ctx->d_llpart, mode, stop, ctx->stream);
+	const int nb = mix_ll_parts(ctx->I);
+	ctx->kt->mix_finalize(ctx->I, ctx->geo.n_lchunks, ctx->d_Spart, ctx->d_q[from], ctx->d_sik, ctx->d_llpart, mode, stop, ctx->stream);
 	ctx->ll_parts = nb;
-	if (!defer_ll)
-		hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, nb, ctx->d_scalars + ll_slot, stop);
+	if (!defer_ll) reduce_ll(ctx, nb, ll_slot, stop);
 	if (do_mstep) {
 		int rc = finalize_shared_eta(ctx, to, stop);		/* em_alg.c:916-962 */
 		if (rc) return rc;
@@ -1841,9 +2007,9 @@ static int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int m
 		b.qstride = ctx->K;
 		b.stop = stop;
 		prof_mark(ctx, MCHIP_KERN_ACCUM_P, true);
-		ctx->kt->mix_column(b, ctx->stream);
+		ctx->kt->mix_column(b, plan, ctx->stream);
 		prof_mark(ctx, MCHIP_KERN_ACCUM_P, false);
-		launch_finalize_p(ctx, ctx->kt->col_slabs(b, 1), ctx->d_Apart, from, to, 0, ctx->p_lb, ctx->do_projection, stop);
+		launch_finalize_p(ctx, plan.mix_col_slabs, ctx->d_Apart, from, to, 0, ctx->p_lb, ctx->do_projection, stop);
 	}
 	HIPCHK(hipGetLastError());
 	if (mode == 0) ctx->have_ll = 1;
@@ -1858,67 +2024,58 @@ static int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const i
 	mchip_pass_args a = pass_args(ctx, from);
 	a.stop = stop;
 	a.skip_ind = skip_ind;
-	const bool s_cached = ctx->sparse && do_mstep && !stop && ctx->s_cache_slot == from;
-	/* both passes of this E step as one launch (k_estep_pair: the same bodies, the same bits).  The choice depends on the model and
-	 * the data set alone: captured, eager and call-by-call steps take it alike */
-	const bool paired = do_mstep && !s_cached && !ctx->knob.no_pair && ctx->kt->pair_available(a);
-	if (paired) {
+	const mchip_plan plan = plan_for(ctx->kt, a, ctx->knob);
+	const int indiv = ctx->qstride != 0, ll_slot = defer_ll ? -1 : 0;
+	const estep_finish fin = finish_for(plan, ctx->K, ctx->max_M, indiv, do_mstep, ctx->knob);
+	/* the individual pass over these very parameters already ran (mchip_loglik_prefetch): its sums are in Spart, its log likelihood
+	 * in d_scalars[2] */
+	const bool s_cached = !plan.col.ll && do_mstep && !stop && ctx->s_cache_slot == from;
+	if (do_mstep && !s_cached && plan.pair) {
+		/* both passes of this E step as one launch (k_estep_pair: the same bodies, the same bits).  The choice depends on the model
+		 * and the data set alone: captured, eager and call-by-call steps take it alike */
 		unsigned long long *marks = nullptr;
 		if (ctx->profiling) {
-			int rc = pair_profile_slot(ctx, a, &marks);
+			int rc = pair_profile_slot(ctx, plan.pair_blocks, &marks);
 			if (rc) return rc;
 		}
-		ctx->kt->estep_pair(a, marks, ctx->stream);
+		ctx->kt->estep_pair(a, plan, marks, ctx->stream);
 		if (marks) {
-			mchip_pair_runs runs;
-			const unsigned n_blocks = ctx->kt->pair_blocks(a, &runs);
-			hipLaunchKernelGGL(k_pair_spans, dim3(1), dim3(PAIR_SPAN_THREADS), 0, ctx->stream, marks, n_blocks, runs,
+			hipLaunchKernelGGL(k_pair_spans, dim3(1), dim3(PAIR_SPAN_THREADS), 0, ctx->stream, marks, plan.pair_blocks, plan.pair_runs,
 					   ctx->pair_spans[ctx->pair_used / PAIR_SPAN_CHUNK] + ctx->pair_used % PAIR_SPAN_CHUNK);
 			ctx->pair_used++;
 		}
-		ctx->ll_parts = ctx->kt->ind_ll_parts(a);
-		if (!defer_ll)
-			hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, ctx->ll_parts, ctx->d_scalars, stop);
-	}
-	if (!paired && (do_mstep || !ctx->sparse)) {
-		prof_mark(ctx, MCHIP_KERN_ACCUM_P, true);
-		if (do_mstep) ctx->kt->accum_p(a, ctx->stream); else ctx->kt->loglik(a, ctx->stream);
-		prof_mark(ctx, MCHIP_KERN_ACCUM_P, false);
-	}
-	if (paired) {
-		/* (done above) */
-	} else if (s_cached) {
-		/* the individual pass over these very parameters already ran (mchip_loglik_prefetch): its sums are in Spart,
-		 * its log likelihood in d_scalars[2] */
-		HIPCHK(hipMemcpyAsync(ctx->d_scalars, ctx->d_scalars + 2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+		ctx->ll_parts = plan.ll_parts;
+		if (!defer_ll) reduce_ll(ctx, plan.ll_parts, 0, stop);
 	} else {
-		prof_mark(ctx, MCHIP_KERN_ACCUM_Q, true);
-		ctx->kt->accum_q(a, ctx->stream);
-		prof_mark(ctx, MCHIP_KERN_ACCUM_Q, false);
-		ctx->ll_parts = ctx->kt->ind_ll_parts(a);
-		if (!defer_ll)
-			hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, ctx->ll_parts, ctx->d_scalars, stop);
+		/* the column pass: N-side sums of an M step; where it is the pass that takes the log likelihood, on every E step */
+		if (do_mstep || plan.col.ll) {
+			prof_mark(ctx, MCHIP_KERN_ACCUM_P, true);
+			if (do_mstep) ctx->kt->accum_p(a, plan, ctx->stream); else ctx->kt->loglik(a, plan, ctx->stream);
+			prof_mark(ctx, MCHIP_KERN_ACCUM_P, false);
+		}
+		if (s_cached) {
+			HIPCHK(hipMemcpyAsync(ctx->d_scalars, ctx->d_scalars + 2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+		} else {
+			ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, ll_slot, stop);
+			ctx->ll_parts = plan.ll_parts;
+		}
 	}
 	ctx->s_cache_slot = -1;		/* Spart is consumed below; slot `to` is about to change */
-	const int indiv = ctx->qstride != 0;
-	const int s_slabs = ctx->kt->ind_slabs(a), n_slabs = ctx->kt->col_slabs(a, 0);	/* what the passes above left (cooperating waves: a quarter) */
-	/* an M step with individual mixing proportions whose P side takes the tiled form: both finalisers in one launch */
-	const int p_loci = finalize_p_loci(ctx->K, ctx->max_M);
-	if (do_mstep && indiv && p_loci && !(n_slabs > 8 && !ctx->knob.no_slab_sum) && !ctx->knob.no_fused_finalize) {
+	ctx->have_ll = 1;
+	if (fin.fused) {
 		mchip_finalize_p_args p;
-		p.L = ctx->L; p.K = ctx->K; p.T = ctx->T; p.loci_per_block = p_loci; p.n_slabs = n_slabs; p.weighted = 1;
+		p.L = ctx->L; p.K = ctx->K; p.T = ctx->T; p.loci_per_block = fin.p_loci; p.n_slabs = plan.col_slabs; p.weighted = 1;
 		p.do_projection = ctx->do_projection; p.toff = ctx->d_toff; p.Apart = ctx->d_Apart; p.Pfrom = ctx->d_p[from];
 		p.Pto = ctx->d_p[to]; p.add_lb = 0.0; p.lb = ctx->p_lb;
-		ctx->kt->finalize_qp(ctx->I, s_slabs, ctx->d_Spart, ctx->d_q[from], ctx->qstride, ctx->d_q[to], ctx->d_sik,
+		ctx->kt->finalize_qp(ctx->I, plan.ind_slabs, ctx->d_Spart, ctx->d_q[from], ctx->qstride, ctx->d_q[to], ctx->d_sik,
 				     ctx->do_projection, ctx->eta_lb, p, stop, ctx->stream);
 		ctx->empty_rows_nan[to] = 1;
 		HIPCHK(hipGetLastError());
-		ctx->have_ll = 1;
 		return MCHIP_OK;
 	}
 	/* k_finalize_q adds the slabs itself, eight threads per individual (no slab-sum launch in front of it: at config 2 that launch
 	 * was 4 of the 137 us of a step, at config 3 two of the cycle's small kernels) */
-	ctx->kt->finalize_q(ctx->I, ctx->K, s_slabs, ctx->d_Spart, ctx->d_q[from], ctx->qstride,
+	ctx->kt->finalize_q(ctx->I, ctx->K, plan.ind_slabs, ctx->d_Spart, ctx->d_q[from], ctx->qstride,
 			    ctx->d_q[to], ctx->d_sik, do_mstep && indiv, 1, ctx->do_projection, ctx->eta_lb, stop, ctx->stream, 0.0);
 	if (do_mstep && indiv) ctx->empty_rows_nan[to] = 1;
 	if (do_mstep) {
@@ -1926,18 +2083,17 @@ static int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const i
 			int rc = finalize_shared_eta(ctx, to, stop);
 			if (rc) return rc;
 		}
-		if (n_slabs > 8 && !ctx->knob.no_slab_sum) {
+		if (fin.slab_sum) {
 			/* many N-side slabs: k_sum_slabs adds them at 5 TB/s (element- and slab-level parallelism, fully coalesced; the
 			 * (l, k) threads of k_finalize_p reach 2.7 TB/s on the same bytes), k_finalize_p then reads one slab */
 			const size_t n = (size_t)ctx->K * ctx->T;
-			hipLaunchKernelGGL(k_sum_slabs, dim3(nblk(n, 32)), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_Apart, n_slabs, n, ctx->d_stage, stop);
+			hipLaunchKernelGGL(k_sum_slabs, dim3(nblk(n, 32)), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_Apart, plan.col_slabs, n, ctx->d_stage, stop);
 			launch_finalize_p(ctx, 1, ctx->d_stage, from, to, 1, 0.0, ctx->do_projection, stop);
 		} else {
-			launch_finalize_p(ctx, n_slabs, ctx->d_Apart, from, to, 1, 0.0, ctx->do_projection, stop);
+			launch_finalize_p(ctx, plan.col_slabs, ctx->d_Apart, from, to, 1, 0.0, ctx->do_projection, stop);
 		}
 	}
 	HIPCHK(hipGetLastError());
-	ctx->have_ll = 1;
 	return MCHIP_OK;
 }
 
@@ -2026,11 +2182,8 @@ int mchip_loglik(mchip_context *ctx, int slot, double *loglik)
 		if (loglik) return fetch_scalars(ctx, 1, 1, loglik);
 		return MCHIP_OK;
 	}
-	mchip_pass_args a = pass_args(ctx, slot);
-	prof_mark(ctx, MCHIP_KERN_LOGLIK, true);
-	ctx->kt->loglik(a, ctx->stream);
-	prof_mark(ctx, MCHIP_KERN_LOGLIK, false);
-	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, ctx->kt->ind_ll_parts(a), ctx->d_scalars + 1);
+	const mchip_pass_args a = pass_args(ctx, slot);
+	ll_pass(ctx, MCHIP_KERN_LOGLIK, ctx->kt->loglik, a, plan_for(ctx->kt, a, ctx->knob), 1);
 	HIPCHK(hipGetLastError());
 	if (loglik) return fetch_scalars(ctx, 1, 1, loglik);
 	return MCHIP_OK;
@@ -2041,13 +2194,11 @@ int mchip_loglik_prefetch(mchip_context *ctx, int slot, double *loglik)
 	MCHIP_ENTRY();
 	int rc = check_slot(ctx, slot);
 	if (rc) return rc;
-	if (!ctx->admixture || !ctx->sparse) return mchip_loglik(ctx, slot, loglik);	/* nothing to share on those paths */
+	const mchip_pass_args a = pass_args(ctx, slot);
+	const mchip_plan plan = plan_for(ctx->kt, a, ctx->knob);
+	if (!ctx->admixture || plan.col.ll) return mchip_loglik(ctx, slot, loglik);	/* nothing to share on those paths */
 	HIPCHK(hipSetDevice(ctx->device));
-	mchip_pass_args a = pass_args(ctx, slot);
-	prof_mark(ctx, MCHIP_KERN_ACCUM_Q, true);
-	ctx->kt->accum_q(a, ctx->stream);		/* S-side sums -> Spart, logL partials -> llpart */
-	prof_mark(ctx, MCHIP_KERN_ACCUM_Q, false);
-	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, ctx->kt->ind_ll_parts(a), ctx->d_scalars + 2);
+	ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, 2);	/* S-side sums -> Spart, logL -> d_scalars[2] */
 	HIPCHK(hipGetLastError());
 	ctx->s_cache_slot = slot;
 	if (loglik) return fetch_scalars(ctx, 2, 1, loglik);
@@ -2065,7 +2216,7 @@ int partition_finalize(mchip_context *ctx, int to, int counts, int n_aslabs)
 	const double add = counts ? 1.0 : 0.0;
 	ctx->empty_rows_nan[to] = counts ? 0 : (ctx->qstride ? 1 : 0);	/* an M step of the hard partition: 0 / 0 for such a row (rnd_init.c:356); with counts
 									 * every count starts at 1 (rnd_init.c:624): 1 / K, as the device holds it */
-	ctx->kt->finalize_q(ctx->I, ctx->K, ctx->n_lchunks, ctx->d_Spart, ctx->d_q[to], ctx->qstride,
+	ctx->kt->finalize_q(ctx->I, ctx->K, ctx->geo.n_lchunks, ctx->d_Spart, ctx->d_q[to], ctx->qstride,
 			    ctx->d_q[to], ctx->d_sik, indiv, 0, project, ctx->eta_lb, nullptr, ctx->stream, add);
 	if (!indiv && (rc = finalize_shared_eta(ctx, to, nullptr, add, !counts))) return rc;
 	hipLaunchKernelGGL(k_finalize_p, dim3(nblk((size_t)ctx->L * ctx->K)), dim3(MCHIP_BLOCK), 0, ctx->stream,
@@ -2101,7 +2252,7 @@ int partition_mstep(mchip_context *ctx, const uint8_t *d_raw, int to, int counts
 	a.part_counts = counts;
 	ctx->kt->part_p(a, ctx->stream);
 	ctx->kt->part_q(a, ctx->stream);
-	return partition_finalize(ctx, to, counts, ctx->n_ichunks);
+	return partition_finalize(ctx, to, counts, ctx->geo.n_ichunks);
 }
 
 int check_partition_call(mchip_context *ctx, const void *arg, int to)
@@ -2437,16 +2588,14 @@ static int accel_cycle_enqueue(mchip_context *ctx, int A, int scheme)
 	dual.P2 = ctx->d_p[C];
 	dual.Q2 = ctx->d_q[C];
 	dual.llpart2 = ctx->d_llpart2;
-	const bool use_dual = ctx->admixture && !ctx->knob.no_dual && ctx->kt->dual_available(dual);
+	const mchip_plan plan = plan_for(ctx->kt, dual, ctx->knob);	/* (of slot C's arguments too: a plan does not depend on the slot) */
+	const bool use_dual = ctx->admixture && plan.dual;
 	if (!ctx->admixture) {
 		if ((rc = run_mixture(ctx, C, C, 0, 1, stop, 1))) return rc;	/* logL_mixture */
 	} else if (!use_dual) {
 		mchip_pass_args a = pass_args(ctx, C);
 		a.stop = stop;
-		prof_mark(ctx, MCHIP_KERN_LOGLIK, true);
-		ctx->kt->loglik(a, ctx->stream);
-		prof_mark(ctx, MCHIP_KERN_LOGLIK, false);
-		hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, ctx->kt->ind_ll_parts(a), ctx->d_scalars + 1, stop);
+		ll_pass(ctx, MCHIP_KERN_LOGLIK, ctx->kt->loglik, a, plan, 1, stop);
 	}
 	/* step size (accel_em.c:130-243) -> d_scalars[24] */
 	{	/* (the secants u = B - A, v = C - B are formed inside the kernels that use them: nothing stores them in a batched cycle) */
@@ -2468,20 +2617,18 @@ static int accel_cycle_enqueue(mchip_context *ctx, int A, int scheme)
 	} else {
 		if (use_dual) {
 			prof_mark(ctx, MCHIP_KERN_DUAL, true);
-			ctx->kt->accum_q_dual(dual, ctx->stream);
+			ctx->kt->accum_q_dual(dual, plan, ctx->stream);
 			prof_mark(ctx, MCHIP_KERN_DUAL, false);
 		} else {
 			mchip_pass_args a = pass_args(ctx, B);
 			a.stop = stop;
-			prof_mark(ctx, MCHIP_KERN_ACCUM_Q, true);
-			ctx->kt->accum_q(a, ctx->stream);
-			prof_mark(ctx, MCHIP_KERN_ACCUM_Q, false);
+			ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, -1);	/* (k_reduce_accept adds its partial sums up) */
 		}
 	}
 	/* the two log likelihoods' sums and accept iff ll > emll, one launch; the outcome goes back to slot A */
 	if (ctx->admixture)
 		hipLaunchKernelGGL(k_reduce_accept, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, use_dual ? ctx->d_llpart2 : (const double *)nullptr, ctx->d_llpart,
-				   ctx->kt->ind_ll_parts(dual), ctx->d_scalars, cyc, stop);
+				   plan.ll_parts, ctx->d_scalars, cyc, stop);
 	else
 		hipLaunchKernelGGL(k_accept, dim3(1), dim3(64), 0, ctx->stream, ctx->d_scalars, cyc, stop);
 	hipLaunchKernelGGL(k_select_copy, dim3(nblk(nq + KT)), dim3(256), 0, ctx->stream, ctx->d_q[A], ctx->d_q[B], ctx->d_q[C], nq,
@@ -2496,7 +2643,7 @@ int mchip_accel_run(mchip_context *ctx, int slot, int scheme, int n_cycles, mchi
 	int rc = check_slot(ctx, slot);
 	if (rc) return rc;
 	if (!state || n_cycles < 1 || scheme < 1 || scheme > 4) return fail(ctx, MCHIP_ERR_INVALID, "accel_run: bad arguments%s", nullptr);
-	if ((ctx->admixture && !ctx->sparse) || ctx->nsec < 1)
+	if ((ctx->admixture && !ctx->geo.sparse) || ctx->nsec < 1)
 		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "accel_run: needs a secant pair; loci with more than 32 alleles run cycle by cycle%s", nullptr);
 	if (ctx->qstride) ctx->empty_rows_nan[0] = ctx->empty_rows_nan[1] = ctx->empty_rows_nan[2] = 1;	/* every slot is written by the cycle's M steps */
 	HIPCHK(hipSetDevice(ctx->device));

@@ -25,6 +25,21 @@ struct saved_set {
 	std::vector<int> empty;		/* its empty_rows */
 };
 
+/* testing / tuning knobs of the environment (README) */
+struct mchip_knobs {
+	int no_bial, no_counts, force_dense, force_safe, no_graph, no_dual, no_slab_sum, no_col_split, part_no_tile, sim_no_tile;
+	int no_fused_finalize, no_pair;
+	int per_cu_col, per_cu_ind, geometry_given, no_roundup;
+	double slab_frac;
+};
+
+/* launch geometry of a model on a data set (mchip.hip: model_geometry) */
+struct mchip_geometry {
+	int ichunk, n_ichunks, lchunk, n_lchunks, n_llpart, flush_blocks, safe_rcp, sparse;
+	int ind_waves;			/* waves per workgroup of the cooperating individual-side kernels (mchip_internal.h) */
+	int xcd_rows;			/* their slab rows come in whole groups of eight: one row, one XCD */
+};
+
 struct mchip_context {
 	int device;
 	hipStream_t stream;
@@ -89,17 +104,9 @@ struct mchip_context {
 	double *d_stage;		/* K*T staging for the [K][T] <-> [T][K] transposes */
 	double *d_logp;			/* mixture model: log P table [T][K] */
 	/* workspaces */
-	int ichunk, n_ichunks, lchunk, n_lchunks, n_llpart, flush_blocks, safe_rcp, sparse;
-	int ind_waves;			/* waves per workgroup of the cooperating individual-side kernels (mchip_internal.h) */
-	int xcd_rows;			/* their slab rows come in whole groups of eight: one row, one XCD */
-	/* testing / tuning knobs of the environment (README), read when a context is created and again with every data set and every
-	 * model -- never on a launch path */
-	struct {
-		int no_bial, no_counts, force_dense, force_safe, no_graph, no_dual, no_slab_sum, no_col_split, part_no_tile, sim_no_tile;
-		int no_fused_finalize, no_pair;
-		int per_cu_col, per_cu_ind, geometry_given, no_roundup;
-		double slab_frac;
-	} knob;
+	mchip_geometry geo;
+	/* read when a context is created and again with every data set and every model -- never on a launch path */
+	mchip_knobs knob;
 	double *d_Apart, *d_Spart, *d_llpart, *d_scalars;	/* d_scalars: [0]=logL, [1..3]=dots, [4..]=eta sums */
 	double *d_llpart2;		/* partial log likelihoods of the second parameter set of a dual individual pass */
 	double *d_redpart;		/* block partials of the dot products / column sums */

@@ -777,24 +777,24 @@ extern "C" {
 static int rand_partition_tiled(mchip_context *ctx, const uint32_t *window, int to)
 {
 	const int K = ctx->K, KP = (K + 1) & ~1, pl = ctx->ploidy;
-	if (pl > 8 || (size_t)ctx->lchunk * pl > 65535 || ctx->knob.part_no_tile) return -1;
+	if (pl > 8 || (size_t)ctx->geo.lchunk * pl > 65535 || ctx->knob.part_no_tile) return -1;
 	/* N-side counters of a tile: tile * max_M * KP / 2 words, about 16 KiB, a multiple of 8 loci */
 	int tile = (int)((16384 / ((size_t)ctx->max_M * KP * 2)) & ~(size_t)7);
 	if (tile < 8) tile = 8;
-	if (tile > ctx->lchunk) tile = ctx->lchunk;
+	if (tile > ctx->geo.lchunk) tile = ctx->geo.lchunk;
 	const size_t lds = ((size_t)RNG_LAG * 256 + (size_t)(KP / 2) * 256 + (size_t)tile * ctx->max_M * (KP / 2)) * sizeof(uint32_t);
 	if (lds > 64 * 1024) return -1;
 	int rc;
 	const rng_window base = rng_window_from(window);
-	if ((rc = lattice_tables(ctx, 1, (uint64_t)ctx->L * pl, (unsigned)ctx->I, (uint64_t)ctx->lchunk * pl, (unsigned)ctx->n_lchunks))) return rc;
+	if ((rc = lattice_tables(ctx, 1, (uint64_t)ctx->L * pl, (unsigned)ctx->I, (uint64_t)ctx->geo.lchunk * pl, (unsigned)ctx->geo.n_lchunks))) return rc;
 	const size_t slab_words = (size_t)ctx->T * (KP / 2), n_slabs = (size_t)(ctx->I + 255) / 256;
 	HIPCHK(grow_dev(ctx, &ctx->d_part_slabs, &ctx->part_slab_bytes, n_slabs * slab_words * sizeof(uint32_t)));
 	uint32_t magic = 0, shift = 0;
 	if (K > 1) mod_k_magic(K, &magic, &shift);
 	const uint8_t *gtS = ctx->init_geno_set ? ctx->d_initS : ctx->d_gtS;	/* bootstrap fits: the observed haplotypes (rnd_init.c:471) */
 	with_ploidy(pl, [&](auto PL) {
-		hipLaunchKernelGGL(k_partition_tile<PL()>, dim3((unsigned)ctx->n_lchunks, nblk((size_t)ctx->I)), dim3(256), lds, ctx->stream, base,
-				   ctx->lat[1].d_i, ctx->lat[1].d_r, ctx->I, ctx->L, K, magic, shift, ctx->lchunk, tile, ctx->d_toff, gtS, ctx->d_part_slabs,
+		hipLaunchKernelGGL(k_partition_tile<PL()>, dim3((unsigned)ctx->geo.n_lchunks, nblk((size_t)ctx->I)), dim3(256), lds, ctx->stream, base,
+				   ctx->lat[1].d_i, ctx->lat[1].d_r, ctx->I, ctx->L, K, magic, shift, ctx->geo.lchunk, tile, ctx->d_toff, gtS, ctx->d_part_slabs,
 				   slab_words, ctx->d_Spart);
 	});
 	HIPCHK(hipGetLastError());

@@ -176,11 +176,62 @@ struct mchip_finalize_p_args {
 	double add_lb, lb;
 };
 
-/* per-K kernel table (one translation unit per K keeps each hipcc job small and `make -j` parallel) */
+/* Kernel selection.  A pass is one template instance of one kernel; mchip_plan names the instance of every pass for given pass
+ * arguments and says what those instances leave behind.  plan() of the K's translation unit (mchip_kernels_k.hip) is the only place
+ * that decides any of it: the launchers switch on the plan, the callers read slab and partial counts from it, and
+ * mchip_describe_plan prints it.  A template argument an instance's kernel does not have stays 0 / false. */
+enum mchip_kernel {
+	MCHIP_K_NONE = 0,
+	MCHIP_K_COLUMN_PASS,		/* k_column_pass<pl, accum, safe, ll>: dense column pass */
+	MCHIP_K_COLUMN_COUNTS,		/* k_column_counts<bits, mix, safe>: column pass on packed counts, cooperating waves */
+	MCHIP_K_COLUMN_COUNTS_SPLIT,	/* k_column_counts_split<bits, safe>: ... with the lanes of a column sharing its k range */
+	MCHIP_K_INDIVIDUAL_PASS,	/* k_individual_pass<pl>: dense individual pass */
+	MCHIP_K_INDIVIDUAL_SPARSE,	/* k_individual_sparse<pl, accum, safe, nomiss, dual> */
+	MCHIP_K_INDIVIDUAL_SPARSE_W,	/* k_individual_sparse_w<pl, accum, safe, nomiss, dual>: cooperating waves */
+	MCHIP_K_INDIVIDUAL_BIAL,	/* k_individual_bial<accum, nomiss> */
+	MCHIP_K_ESTEP_PAIR,		/* k_estep_pair<bits, pl, safe, nomiss> */
+	MCHIP_K_MIX_GATHER,		/* k_mix_gather<pl, staged> */
+	MCHIP_K_MIX_COLUMN,		/* k_mix_column<pl> */
+	MCHIP_K_KINDS
+};
+struct mchip_instance {
+	int kernel;		/* mchip_kernel */
+	int pl;			/* ploidy specialisation: 2, 4, or 0 = any */
+	int bits;		/* bits per packed allele count: 2 or 4 */
+	bool accum;		/* leaves sums (S side / N side), not the log likelihood alone */
+	bool safe;		/* one reciprocal per non-empty cell (SAFE) */
+	bool nomiss;		/* the data set has no missing copy (NOMISS) */
+	bool ll;		/* column pass: takes the log likelihood too */
+	bool mix;		/* packed-count column pass of the mixture model */
+	bool dual;		/* takes the log likelihood of a second parameter set */
+	bool staged;		/* mixture gather: P rows staged in LDS */
+};
+struct mchip_plan {
+	mchip_instance col;		/* column pass of an E step (accum_p) */
+	mchip_instance sside;		/* individual pass for the S-side sums (accum_q) */
+	mchip_instance ll;		/* the pass that takes the log likelihood alone (loglik) */
+	mchip_instance mix_gather, mix_col;	/* mixture model: individual pass, column pass */
+	/* what those leave: N-side slabs of col / of mix_col, S-side slabs of sside (= of ll's partial sums), partial log likelihoods
+	 * of sside and ll alike */
+	int col_slabs, mix_col_slabs, ind_slabs, ll_parts;
+	/* the individual pass of (a.Q, a.P) that also takes log L of (a.Q2, a.P2) into a.llpart2 exists (accum_q_dual): both halves
+	 * would run `dual_pass` without its DUAL, so its results are theirs bit for bit */
+	int dual;
+	mchip_instance dual_pass;
+	/* col and sside of one E step exist as one launch (estep_pair): the same bodies, the same bits; its grid */
+	int pair;
+	mchip_instance pair_pass;
+	unsigned pair_blocks;
+	mchip_pair_runs pair_runs;
+};
+
+/* per-K kernel table (one translation unit per K keeps each hipcc job small and `make -j` parallel).  plan() chooses; every
+ * launcher of a pass takes the plan made from the same arguments and launches what it names. */
 struct mchip_ktable {
-	void (*accum_p)(const mchip_pass_args &a, hipStream_t s);	/* column pass: Apart + logL */
-	void (*loglik)(const mchip_pass_args &a, hipStream_t s);	/* column pass: logL only */
-	void (*accum_q)(const mchip_pass_args &a, hipStream_t s);	/* individual pass: Spart */
+	void (*plan)(const mchip_pass_args &a, mchip_plan *p);
+	void (*accum_p)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);	/* column pass: Apart (+ logL: dense pair) */
+	void (*loglik)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);	/* logL only */
+	void (*accum_q)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);	/* individual pass: Spart (+ logL: sparse) */
 	void (*part_p)(const mchip_pass_args &a, hipStream_t s);	/* hard partition, column pass */
 	void (*part_q)(const mchip_pass_args &a, hipStream_t s);	/* hard partition, individual pass */
 	/* finalize: Q[to] from Spart (normalise + project), stores expected counts */
@@ -189,26 +240,16 @@ struct mchip_ktable {
 			   double add);
 	void (*project_q)(int nrows, int K, double *Q, double lb, const int *stop, hipStream_t s);
 	/* mixture model */
-	void (*mix_gather)(const mchip_pass_args &a, hipStream_t s);	/* a.P = log P table; Spart = per-chunk sums */
+	void (*mix_gather)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);	/* a.P = log P table; Spart = per-chunk sums */
 	void (*mix_finalize)(int I, int n_lchunks, const double *Vpart, const double *eta, double *vik, double *llpart, int mode,
 			     const int *stop, hipStream_t s);
-	void (*mix_column)(const mchip_pass_args &a, hipStream_t s);	/* a.Q = vik; Apart = sum_i vik n */
-	/* individual pass of (a.Q, a.P) that also takes log L of (a.Q2, a.P2) into a.llpart2, where dual_available() says so */
-	int (*dual_available)(const mchip_pass_args &a);
-	void (*accum_q_dual)(const mchip_pass_args &a, hipStream_t s);
-	/* what the launchers above will leave for these arguments: N-side slabs of accum_p (mix = 0) / mix_column (mix = 1); S-side
-	 * slabs of accum_q / accum_q_dual (= of loglik's partial sums), and partial log likelihoods of accum_q / loglik */
-	int (*col_slabs)(const mchip_pass_args &a, int mix);
-	int (*ind_slabs)(const mchip_pass_args &a);
-	int (*ind_ll_parts)(const mchip_pass_args &a);
+	void (*mix_column)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);	/* a.Q = vik; Apart = sum_i vik n */
+	void (*accum_q_dual)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);	/* where p.dual */
 	/* both finalisers of an EM step in one launch (k_finalize_qp): individual mixing proportions, tiled P side */
 	void (*finalize_qp)(int I, int n_slabs_q, const double *Spart, const double *Qfrom, int qstride_from, double *Qto, double *sik,
 			    int do_projection_q, double lb_q, const mchip_finalize_p_args &p, const int *stop, hipStream_t s);
-	/* accum_p and accum_q of one E step as one launch (k_estep_pair), where pair_available() says so: the same bodies, the same
-	 * bits.  marks (profiled runs; else NULL): two clock readings per block of the launch, pair_blocks() blocks */
-	int (*pair_available)(const mchip_pass_args &a);
-	unsigned (*pair_blocks)(const mchip_pass_args &a, mchip_pair_runs *runs);
-	void (*estep_pair)(const mchip_pass_args &a, unsigned long long *marks, hipStream_t s);
+	/* where p.pair.  marks (profiled runs; else NULL): two clock readings per block of the launch, p.pair_blocks blocks */
+	void (*estep_pair)(const mchip_pass_args &a, const mchip_plan &p, unsigned long long *marks, hipStream_t s);
 };
 
 const mchip_ktable *mchip_get_ktable(int K);

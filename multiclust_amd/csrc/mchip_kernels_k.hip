@@ -1864,176 +1864,256 @@ inline size_t coop_lds_bytes(const mchip_pass_args &a, int sets)
 	return (tiles > hand_over ? tiles : hand_over) * sizeof(double);
 }
 
-/* a.sparse: the column pass only accumulates the N-side sums; S-side sums and logL come from the sparse
- * individual pass.  Otherwise (loci with more alleles than the LDS tile is sized for) the dense pair is used:
- * the column pass also produces logL and the individual pass loops over every allele of every locus. */
-void launch_accum_p(const mchip_pass_args &a, hipStream_t s)
-{
-	if constexpr (CSPLIT > 1) {
-		if (a.sparse && a.count_bits && !a.no_col_split) {
-			const dim3 grid((a.T + MCHIP_BLOCK / CSPLIT - 1) / (MCHIP_BLOCK / CSPLIT), a.n_ichunks);
-			if (a.count_bits == 2 && a.safe_rcp) hipLaunchKernelGGL((k_column_counts_split<2, true>), grid, dim3(MCHIP_BLOCK), 0, s, a);
-			else if (a.count_bits == 2) hipLaunchKernelGGL((k_column_counts_split<2, false>), grid, dim3(MCHIP_BLOCK), 0, s, a);
-			else if (a.safe_rcp) hipLaunchKernelGGL((k_column_counts_split<4, true>), grid, dim3(MCHIP_BLOCK), 0, s, a);
-			else hipLaunchKernelGGL((k_column_counts_split<4, false>), grid, dim3(MCHIP_BLOCK), 0, s, a);
-			return;
-		}
-	}
-	if (a.sparse && a.count_bits == 2 && a.safe_rcp) { hipLaunchKernelGGL((k_column_counts<2, false, true>), counts_grid(a), dim3(MCHIP_BLOCK), 0, s, a); return; }
-	if (a.sparse && a.count_bits == 4 && a.safe_rcp) { hipLaunchKernelGGL((k_column_counts<4, false, true>), counts_grid(a), dim3(MCHIP_BLOCK), 0, s, a); return; }
-	if (a.sparse && a.count_bits == 2) { hipLaunchKernelGGL((k_column_counts<2, false>), counts_grid(a), dim3(MCHIP_BLOCK), 0, s, a); return; }
-	if (a.sparse && a.count_bits == 4) { hipLaunchKernelGGL((k_column_counts<4, false>), counts_grid(a), dim3(MCHIP_BLOCK), 0, s, a); return; }
-	if (a.sparse) {
-		if (a.ploidy == 2) hipLaunchKernelGGL((k_column_pass<2, true, false, false>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-		else hipLaunchKernelGGL((k_column_pass<0, true, false, false>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-		return;
-	}
-	if (a.ploidy == 2 && a.flush_blocks >= 1) hipLaunchKernelGGL((k_column_pass<2, true, false, true>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-	else if (a.ploidy == 2) hipLaunchKernelGGL((k_column_pass<2, true, true, true>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-	else hipLaunchKernelGGL((k_column_pass<0, true, true, true>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-}
 #ifdef MCHIP_EXP_SCATTER
 inline size_t sparse_lds_bytes(const mchip_pass_args &a) { return (3 * (size_t)a.tile_cols * KP + QBLOCK) * sizeof(double); }
 #else
 inline size_t sparse_lds_bytes(const mchip_pass_args &a) { return (2 * (size_t)a.tile_cols * KP + QBLOCK) * sizeof(double); }
 #endif
-template <bool ACCUM> void launch_sparse(const mchip_pass_args &a, hipStream_t s)
+
+/* ---------------------------------------------------------------- the plan (mchip_internal.h): every choice of an instance */
+/* the sparse individual pass of these arguments: S-side sums and logL (accum) or logL alone */
+mchip_instance sparse_instance(const mchip_pass_args &a, bool accum)
 {
-	const size_t lds = sparse_lds_bytes(a);
-	const bool nomiss = !a.has_missing;	/* idle lanes of the last block recompute individual I-1 and are dropped at the end */
+	mchip_instance k = {};
 	const bool safe = a.flush_blocks < 1;
+	k.accum = accum;
 	/* measured (profiles/r02_biallelic_variant.txt): the stand-alone log-likelihood pass gains 6-21 % from K = 6 up (it is
 	 * LDS-bound in the general kernel), the S-side pass only from K = 10 (it is FP64-bound, and the dense-over-two-alleles
 	 * form costs more instructions per locus: +8-19 % below that) */
-	constexpr bool bial_pays = SPLIT == 1 && (ACCUM ? (K >= 10) : (K >= 6));	/* (its grid and partials are one lane per individual) */
-	if constexpr (SPLIT == 1) {
-		const dim3 grid = coop_grid(a), rows = coop_rows(a), block(64 * a.ind_waves);
-		const size_t cl = coop_lds_bytes(a, 1);
-		if (bial_pays && a.biallelic && a.ploidy == 2 && !safe) {
-			if (nomiss) hipLaunchKernelGGL((k_individual_bial<ACCUM, true>), grid, block, 0, s, a);
-			else hipLaunchKernelGGL((k_individual_bial<ACCUM, false>), grid, block, 0, s, a);
-			return;
-		}
-#define MCHIP_SPARSE_W(PLV) \
-		do { \
-			if (nomiss && !safe) hipLaunchKernelGGL((k_individual_sparse_w<PLV, ACCUM, false, true>), rows, block, cl, s, a); \
-			else if (!safe) hipLaunchKernelGGL((k_individual_sparse_w<PLV, ACCUM, false, false>), rows, block, cl, s, a); \
-			else hipLaunchKernelGGL((k_individual_sparse_w<PLV, ACCUM, true, false>), rows, block, cl, s, a); \
-		} while (0)
-		if (a.ploidy == 2) MCHIP_SPARSE_W(2);
-		else if (a.ploidy == 4) MCHIP_SPARSE_W(4);
-		else hipLaunchKernelGGL((k_individual_sparse_w<0, ACCUM, true, false>), rows, block, cl, s, a);
-#undef MCHIP_SPARSE_W
+	const bool bial_pays = SPLIT == 1 && (accum ? (K >= 10) : (K >= 6));	/* (its grid and partials are one lane per individual) */
+	if (bial_pays && a.biallelic && a.ploidy == 2 && !safe) {
+		k.kernel = MCHIP_K_INDIVIDUAL_BIAL;
+		k.nomiss = !a.has_missing;
+		return k;
+	}
+	k.kernel = SPLIT == 1 ? MCHIP_K_INDIVIDUAL_SPARSE_W : MCHIP_K_INDIVIDUAL_SPARSE;
+	k.pl = (a.ploidy == 2 || a.ploidy == 4) ? a.ploidy : 0;
+	k.safe = safe || k.pl == 0;
+	k.nomiss = !a.has_missing && !k.safe;	/* idle lanes of the last block recompute individual I-1 and are dropped at the end */
+	return k;
+}
+void plan(const mchip_pass_args &a, mchip_plan *p)
+{
+	*p = mchip_plan();
+	const int pl2 = a.ploidy == 2 ? 2 : 0;		/* the dense kernels are specialised for diploids only */
+	const bool dense_safe = pl2 == 0 || a.flush_blocks < 1;
+	/* a.sparse: the column pass only accumulates the N-side sums; S-side sums and logL come from the sparse
+	 * individual pass.  Otherwise (loci with more alleles than the LDS tile is sized for) the dense pair is used:
+	 * the column pass also produces logL and the individual pass loops over every allele of every locus. */
+	p->col.accum = true;
+	if (a.sparse && a.count_bits) {
+		const bool split = CSPLIT > 1 && !a.no_col_split;
+		p->col.kernel = split ? MCHIP_K_COLUMN_COUNTS_SPLIT : MCHIP_K_COLUMN_COUNTS;
+		p->col.bits = a.count_bits;
+		p->col.safe = a.safe_rcp != 0;
+		p->col_slabs = split ? a.n_ichunks : mchip_col_slabs(a);
 	} else {
-#define MCHIP_SPARSE(PLV) \
-		do { \
-			if (nomiss && !safe) hipLaunchKernelGGL((k_individual_sparse<PLV, ACCUM, false, true>), sparse_grid(a), dim3(QBLOCK), lds, s, a); \
-			else if (!safe) hipLaunchKernelGGL((k_individual_sparse<PLV, ACCUM, false, false>), sparse_grid(a), dim3(QBLOCK), lds, s, a); \
-			else hipLaunchKernelGGL((k_individual_sparse<PLV, ACCUM, true, false>), sparse_grid(a), dim3(QBLOCK), lds, s, a); \
-		} while (0)
-		if (a.ploidy == 2) MCHIP_SPARSE(2);
-		else if (a.ploidy == 4) MCHIP_SPARSE(4);
-		else hipLaunchKernelGGL((k_individual_sparse<0, ACCUM, true, false>), sparse_grid(a), dim3(QBLOCK), lds, s, a);
-#undef MCHIP_SPARSE
+		p->col.kernel = MCHIP_K_COLUMN_PASS;
+		p->col.pl = pl2;
+		p->col.ll = !a.sparse;
+		p->col.safe = !a.sparse && dense_safe;
+		p->col_slabs = a.n_ichunks;
+	}
+	if (a.sparse) {
+		p->sside = sparse_instance(a, true);
+		p->ll = sparse_instance(a, false);
+		p->ind_slabs = SPLIT == 1 ? mchip_ind_slabs(a) : a.n_lchunks;
+		p->ll_parts = SPLIT == 1 ? ((a.I + 63) / 64) * mchip_ind_slabs(a) : ((a.I + QBLOCK / SPLIT - 1) / (QBLOCK / SPLIT)) * a.n_lchunks;
+	} else {
+		p->sside.kernel = MCHIP_K_INDIVIDUAL_PASS;
+		p->sside.accum = true;
+		p->sside.pl = pl2;
+		p->ll.kernel = MCHIP_K_COLUMN_PASS;
+		p->ll.pl = pl2;
+		p->ll.ll = true;
+		p->ll.safe = dense_safe;
+		p->ind_slabs = a.n_lchunks;
+		p->ll_parts = ((a.T + MCHIP_BLOCK - 1) / MCHIP_BLOCK) * a.n_ichunks;	/* dense pair: the column pass takes the log likelihood */
+	}
+	/* mixture model */
+	p->mix_gather.kernel = MCHIP_K_MIX_GATHER;
+	p->mix_gather.pl = pl2;
+	p->mix_gather.staged = a.sparse != 0;
+	p->mix_col.accum = true;
+	if (a.count_bits) {
+		p->mix_col.kernel = MCHIP_K_COLUMN_COUNTS;
+		p->mix_col.bits = a.count_bits;
+		p->mix_col.mix = true;
+		p->mix_col_slabs = mchip_col_slabs(a);
+	} else {
+		p->mix_col.kernel = MCHIP_K_MIX_COLUMN;
+		p->mix_col.pl = pl2;
+		p->mix_col_slabs = a.n_ichunks;
+	}
+	/* the dual pass exists where both of its halves would run the sparse kernel with shared reciprocals (so that its results are
+	 * theirs bit for bit) and the second set's registers still fit */
+	const bool diploid_w = p->sside.kernel == MCHIP_K_INDIVIDUAL_SPARSE_W && p->sside.pl == 2;
+	if (K <= 12 && diploid_w && !p->sside.safe && p->ll.kernel == MCHIP_K_INDIVIDUAL_SPARSE_W && coop_lds_bytes(a, 2) <= 64 * 1024) {
+		p->dual = 1;
+		p->dual_pass = p->sside;
+		p->dual_pass.dual = true;
+	}
+	/* the paired E step exists where col is k_column_counts<2, false, SAFE> and sside k_individual_sparse_w<2, true, SAFE, NOMISS>
+	 * with four waves and the same SAFE (so that its results are theirs bit for bit), at the K where both bodies fit a 256-thread
+	 * workgroup's registers */
+	if (K <= 12 && SPLIT == 1 && CSPLIT == 1 && p->col.kernel == MCHIP_K_COLUMN_COUNTS && p->col.bits == 2 && diploid_w &&
+	    a.ind_waves * 64 == MCHIP_BLOCK && p->col.safe == p->sside.safe) {
+		const dim3 cg = counts_grid(a);
+		const unsigned n_col = cg.x * cg.y, n_ind = coop_rows(a).x;
+		mchip_pair_runs r;
+		r.col_runs = (n_col + MCHIP_PAIR_RUN - 1) / MCHIP_PAIR_RUN;
+		r.ind_runs = (n_ind + MCHIP_PAIR_RUN - 1) / MCHIP_PAIR_RUN;
+		/* (mchip_pair_is_ind's 32-bit products) */
+		if (r.col_runs && r.ind_runs && (unsigned long long)(r.col_runs + r.ind_runs) * r.ind_runs < (1ull << 32)) {
+			p->pair = 1;
+			p->pair_pass = p->sside;
+			p->pair_pass.kernel = MCHIP_K_ESTEP_PAIR;
+			p->pair_pass.bits = 2;
+			p->pair_runs = r;
+			p->pair_blocks = (r.col_runs + r.ind_runs) * MCHIP_PAIR_RUN;
+		}
 	}
 }
-/* the dual pass exists where both of its halves would run the sparse kernel with shared reciprocals (so that its results are
- * theirs bit for bit) and the second set's registers still fit */
-int dual_available(const mchip_pass_args &a)
+
+/* ---------------------------------------------------------------- launchers of the passes: what the plan names, nothing else.
+ * The case labels list the instances that exist; the `if constexpr` guards keep those from being compiled at a K where no plan
+ * names them. */
+constexpr int tkey(int n, bool x, bool y = false) { return n * 4 + (x ? 2 : 0) + (y ? 1 : 0); }
+
+void launch_column(const mchip_pass_args &a, const mchip_instance &k, hipStream_t s)
 {
-	if (K > 12 || !a.sparse || a.flush_blocks < 1 || a.ploidy != 2) return 0;
-	if (a.biallelic && K >= 6) return 0;	/* launch_sparse takes k_individual_bial for one or both passes */
-	return coop_lds_bytes(a, 2) <= 64 * 1024;
+	const dim3 block(MCHIP_BLOCK);
+	auto go = [&](auto kernel, dim3 grid, dim3 blk, size_t lds) { hipLaunchKernelGGL(kernel, grid, blk, lds, s, a); };
+	switch (k.kernel) {
+	case MCHIP_K_COLUMN_COUNTS_SPLIT:
+		if constexpr (CSPLIT > 1) {
+			const dim3 grid((a.T + MCHIP_BLOCK / CSPLIT - 1) / (MCHIP_BLOCK / CSPLIT), a.n_ichunks);
+			switch (tkey(k.bits, k.safe)) {
+			case tkey(2, true): go(k_column_counts_split<2, true>, grid, block, 0); break;
+			case tkey(2, false): go(k_column_counts_split<2, false>, grid, block, 0); break;
+			case tkey(4, true): go(k_column_counts_split<4, true>, grid, block, 0); break;
+			case tkey(4, false): go(k_column_counts_split<4, false>, grid, block, 0); break;
+			}
+		}
+		break;
+	case MCHIP_K_COLUMN_COUNTS:
+		switch (tkey(k.bits, k.mix, k.safe)) {
+		case tkey(2, false, true): go(k_column_counts<2, false, true>, counts_grid(a), block, 0); break;
+		case tkey(4, false, true): go(k_column_counts<4, false, true>, counts_grid(a), block, 0); break;
+		case tkey(2, false, false): go(k_column_counts<2, false>, counts_grid(a), block, 0); break;
+		case tkey(4, false, false): go(k_column_counts<4, false>, counts_grid(a), block, 0); break;
+		case tkey(2, true, false): go(k_column_counts<2, true>, counts_grid(a), block, 0); break;
+		case tkey(4, true, false): go(k_column_counts<4, true>, counts_grid(a), block, 0); break;
+		}
+		break;
+	case MCHIP_K_COLUMN_PASS:	/* <pl, accum, safe, ll> */
+		switch (tkey(k.pl + (k.accum ? 1 : 0), k.safe, k.ll)) {
+		case tkey(2 + 1, false, false): go(k_column_pass<2, true, false, false>, column_grid(a), block, 0); break;
+		case tkey(0 + 1, false, false): go(k_column_pass<0, true, false, false>, column_grid(a), block, 0); break;
+		case tkey(2 + 1, false, true): go(k_column_pass<2, true, false, true>, column_grid(a), block, 0); break;
+		case tkey(2 + 1, true, true): go(k_column_pass<2, true, true, true>, column_grid(a), block, 0); break;
+		case tkey(0 + 1, true, true): go(k_column_pass<0, true, true, true>, column_grid(a), block, 0); break;
+		case tkey(2, false, true): go(k_column_pass<2, false, false, true>, column_grid(a), block, 0); break;
+		case tkey(2, true, true): go(k_column_pass<2, false, true, true>, column_grid(a), block, 0); break;
+		case tkey(0, true, true): go(k_column_pass<0, false, true, true>, column_grid(a), block, 0); break;
+		}
+		break;
+	case MCHIP_K_MIX_COLUMN:
+		if (k.pl == 2) hipLaunchKernelGGL((k_mix_column<2>), column_grid(a), block, 0, s, a);
+		else hipLaunchKernelGGL((k_mix_column<0>), column_grid(a), block, 0, s, a);
+		break;
+	}
 }
-void launch_accum_q_dual(const mchip_pass_args &a, hipStream_t s)
+/* (the (SAFE, NOMISS) pairs of the sparse kernels: shared reciprocals without and with missing data, one reciprocal per cell) */
+template <bool ACCUM> void launch_individual(const mchip_pass_args &a, const mchip_instance &k, hipStream_t s)
+{
+	auto go = [&](auto kernel, dim3 grid, dim3 blk, size_t lds) { hipLaunchKernelGGL(kernel, grid, blk, lds, s, a); };
+	switch (k.kernel) {
+	case MCHIP_K_INDIVIDUAL_PASS:
+		if (k.pl == 2) hipLaunchKernelGGL((k_individual_pass<2>), indiv_grid(a), dim3(QBLOCK), 0, s, a);
+		else hipLaunchKernelGGL((k_individual_pass<0>), indiv_grid(a), dim3(QBLOCK), 0, s, a);
+		break;
+	case MCHIP_K_INDIVIDUAL_BIAL:
+		if constexpr (SPLIT == 1) {
+			const dim3 grid = coop_grid(a), block(64 * a.ind_waves);
+			if (k.nomiss) hipLaunchKernelGGL((k_individual_bial<ACCUM, true>), grid, block, 0, s, a);
+			else hipLaunchKernelGGL((k_individual_bial<ACCUM, false>), grid, block, 0, s, a);
+		}
+		break;
+	case MCHIP_K_INDIVIDUAL_SPARSE_W:
+		if constexpr (SPLIT == 1) {
+			const dim3 rows = coop_rows(a), block(64 * a.ind_waves);
+			const size_t cl = coop_lds_bytes(a, 1);
+			switch (tkey(k.pl, k.safe, k.nomiss)) {
+			case tkey(2, false, true): go(k_individual_sparse_w<2, ACCUM, false, true>, rows, block, cl); break;
+			case tkey(2, false, false): go(k_individual_sparse_w<2, ACCUM, false, false>, rows, block, cl); break;
+			case tkey(2, true, false): go(k_individual_sparse_w<2, ACCUM, true, false>, rows, block, cl); break;
+			case tkey(4, false, true): go(k_individual_sparse_w<4, ACCUM, false, true>, rows, block, cl); break;
+			case tkey(4, false, false): go(k_individual_sparse_w<4, ACCUM, false, false>, rows, block, cl); break;
+			case tkey(4, true, false): go(k_individual_sparse_w<4, ACCUM, true, false>, rows, block, cl); break;
+			case tkey(0, true, false): go(k_individual_sparse_w<0, ACCUM, true, false>, rows, block, cl); break;
+			}
+		}
+		break;
+	case MCHIP_K_INDIVIDUAL_SPARSE:
+		if constexpr (SPLIT != 1) {
+			const dim3 grid = sparse_grid(a), block(QBLOCK);
+			const size_t lds = sparse_lds_bytes(a);
+			switch (tkey(k.pl, k.safe, k.nomiss)) {
+			case tkey(2, false, true): go(k_individual_sparse<2, ACCUM, false, true>, grid, block, lds); break;
+			case tkey(2, false, false): go(k_individual_sparse<2, ACCUM, false, false>, grid, block, lds); break;
+			case tkey(2, true, false): go(k_individual_sparse<2, ACCUM, true, false>, grid, block, lds); break;
+			case tkey(4, false, true): go(k_individual_sparse<4, ACCUM, false, true>, grid, block, lds); break;
+			case tkey(4, false, false): go(k_individual_sparse<4, ACCUM, false, false>, grid, block, lds); break;
+			case tkey(4, true, false): go(k_individual_sparse<4, ACCUM, true, false>, grid, block, lds); break;
+			case tkey(0, true, false): go(k_individual_sparse<0, ACCUM, true, false>, grid, block, lds); break;
+			}
+		}
+		break;
+	}
+}
+void launch_accum_p(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s) { launch_column(a, p.col, s); }
+void launch_mix_column(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s) { launch_column(a, p.mix_col, s); }
+void launch_accum_q(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s) { launch_individual<true>(a, p.sside, s); }
+void launch_loglik(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s)
+{
+	if (p.ll.kernel == MCHIP_K_COLUMN_PASS) launch_column(a, p.ll, s);
+	else launch_individual<false>(a, p.ll, s);
+}
+void launch_accum_q_dual(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s)
 {
 	if constexpr (K <= 12) {
 		const size_t lds = coop_lds_bytes(a, 2);
-		if (!a.has_missing) hipLaunchKernelGGL((k_individual_sparse_w<2, true, false, true, true>), coop_rows(a), dim3(64 * a.ind_waves), lds, s, a);
+		if (p.dual_pass.nomiss) hipLaunchKernelGGL((k_individual_sparse_w<2, true, false, true, true>), coop_rows(a), dim3(64 * a.ind_waves), lds, s, a);
 		else hipLaunchKernelGGL((k_individual_sparse_w<2, true, false, false, true>), coop_rows(a), dim3(64 * a.ind_waves), lds, s, a);
 	}
 }
-/* the paired E step exists where launch_accum_p would run k_column_counts<2, false, SAFE> and launch_sparse<true> would run
- * k_individual_sparse_w<2, true, SAFE, NOMISS> with four waves (so that its results are theirs bit for bit), at the K where both
- * bodies fit a 256-thread workgroup's registers */
-unsigned pair_blocks(const mchip_pass_args &a, mchip_pair_runs *runs)
-{
-	const dim3 cg = counts_grid(a);
-	const unsigned n_col = cg.x * cg.y, n_ind = coop_rows(a).x;
-	runs->col_runs = (n_col + MCHIP_PAIR_RUN - 1) / MCHIP_PAIR_RUN;
-	runs->ind_runs = (n_ind + MCHIP_PAIR_RUN - 1) / MCHIP_PAIR_RUN;
-	return (runs->col_runs + runs->ind_runs) * MCHIP_PAIR_RUN;
-}
-int pair_available(const mchip_pass_args &a)
-{
-	if (K > 12 || SPLIT != 1 || CSPLIT != 1) return 0;
-	if (!a.sparse || a.count_bits != 2 || a.ploidy != 2 || a.ind_waves * 64 != MCHIP_BLOCK) return 0;
-	if ((a.safe_rcp != 0) != (a.flush_blocks < 1)) return 0;	/* (one SAFE for both bodies; mchip_set_model keeps them together) */
-	if (a.biallelic && K >= 10 && a.flush_blocks >= 1) return 0;	/* launch_sparse<true> takes k_individual_bial */
-	mchip_pair_runs r;
-	pair_blocks(a, &r);
-	if (r.col_runs == 0 || r.ind_runs == 0) return 0;
-	return (unsigned long long)(r.col_runs + r.ind_runs) * r.ind_runs < (1ull << 32);	/* mchip_pair_is_ind's 32-bit products */
-}
-void launch_estep_pair(const mchip_pass_args &a, unsigned long long *marks, hipStream_t s)
+void launch_estep_pair(const mchip_pass_args &a, const mchip_plan &p, unsigned long long *marks, hipStream_t s)
 {
 	if constexpr (K <= 12 && SPLIT == 1 && CSPLIT == 1) {
-		mchip_pair_runs r;
-		const dim3 grid(pair_blocks(a, &r)), block(MCHIP_BLOCK);
+		const mchip_pair_runs r = p.pair_runs;
+		const dim3 grid(p.pair_blocks), block(MCHIP_BLOCK);
 		const size_t ind_lds = coop_lds_bytes(a, 1), col_lds = (size_t)K * 64 * sizeof(double);
 		const size_t lds = ind_lds > col_lds ? ind_lds : col_lds;
-		if (a.flush_blocks < 1) hipLaunchKernelGGL((k_estep_pair<2, 2, true, false>), grid, block, lds, s, a, r, marks);
-		else if (!a.has_missing) hipLaunchKernelGGL((k_estep_pair<2, 2, false, true>), grid, block, lds, s, a, r, marks);
+		if (p.pair_pass.safe) hipLaunchKernelGGL((k_estep_pair<2, 2, true, false>), grid, block, lds, s, a, r, marks);
+		else if (p.pair_pass.nomiss) hipLaunchKernelGGL((k_estep_pair<2, 2, false, true>), grid, block, lds, s, a, r, marks);
 		else hipLaunchKernelGGL((k_estep_pair<2, 2, false, false>), grid, block, lds, s, a, r, marks);
 	}
 }
-/* what the launchers leave behind (mchip_ktable) */
-int col_slabs(const mchip_pass_args &a, int mix)
+void launch_mix_gather(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s)
 {
-	if (mix) return a.count_bits ? mchip_col_slabs(a) : a.n_ichunks;
-	return (a.sparse && a.count_bits && (CSPLIT == 1 || a.no_col_split)) ? mchip_col_slabs(a) : a.n_ichunks;
-}
-int ind_slabs(const mchip_pass_args &a) { return (a.sparse && SPLIT == 1) ? mchip_ind_slabs(a) : a.n_lchunks; }
-int ind_ll_parts(const mchip_pass_args &a)
-{
-	if (a.sparse && SPLIT == 1) return ((a.I + 63) / 64) * mchip_ind_slabs(a);
-	if (a.sparse) return ((a.I + QBLOCK / SPLIT - 1) / (QBLOCK / SPLIT)) * a.n_lchunks;
-	return ((a.T + MCHIP_BLOCK - 1) / MCHIP_BLOCK) * a.n_ichunks;	/* dense pair: the column pass takes the log likelihood */
-}
-void launch_loglik(const mchip_pass_args &a, hipStream_t s)
-{
-	if (a.sparse) { launch_sparse<false>(a, s); return; }
-	if (a.ploidy == 2 && a.flush_blocks >= 1) hipLaunchKernelGGL((k_column_pass<2, false, false, true>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-	else if (a.ploidy == 2) hipLaunchKernelGGL((k_column_pass<2, false, true, true>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-	else hipLaunchKernelGGL((k_column_pass<0, false, true, true>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-}
-void launch_accum_q(const mchip_pass_args &a, hipStream_t s)
-{
-	if (a.sparse) { launch_sparse<true>(a, s); return; }
-	if (a.ploidy == 2) hipLaunchKernelGGL((k_individual_pass<2>), indiv_grid(a), dim3(QBLOCK), 0, s, a);
-	else hipLaunchKernelGGL((k_individual_pass<0>), indiv_grid(a), dim3(QBLOCK), 0, s, a);
-}
-void launch_mix_gather(const mchip_pass_args &a, hipStream_t s)
-{
+	const mchip_instance &k = p.mix_gather;
 	const size_t lds = 2 * (size_t)a.tile_cols * KP * sizeof(double);
-	if (a.sparse) {
-		if (a.ploidy == 2) hipLaunchKernelGGL((k_mix_gather<2, true>), indiv_grid(a), dim3(QBLOCK), lds, s, a);
-		else hipLaunchKernelGGL((k_mix_gather<0, true>), indiv_grid(a), dim3(QBLOCK), lds, s, a);
-	} else {
-		if (a.ploidy == 2) hipLaunchKernelGGL((k_mix_gather<2, false>), indiv_grid(a), dim3(QBLOCK), 0, s, a);
-		else hipLaunchKernelGGL((k_mix_gather<0, false>), indiv_grid(a), dim3(QBLOCK), 0, s, a);
+	switch (tkey(k.pl, k.staged)) {
+	case tkey(2, true): hipLaunchKernelGGL((k_mix_gather<2, true>), indiv_grid(a), dim3(QBLOCK), lds, s, a); break;
+	case tkey(0, true): hipLaunchKernelGGL((k_mix_gather<0, true>), indiv_grid(a), dim3(QBLOCK), lds, s, a); break;
+	case tkey(2, false): hipLaunchKernelGGL((k_mix_gather<2, false>), indiv_grid(a), dim3(QBLOCK), 0, s, a); break;
+	case tkey(0, false): hipLaunchKernelGGL((k_mix_gather<0, false>), indiv_grid(a), dim3(QBLOCK), 0, s, a); break;
 	}
 }
 void launch_mix_finalize(int I, int n_lchunks, const double *Vpart, const double *eta, double *vik, double *llpart, int mode, const int *stop, hipStream_t s)
 {
 	hipLaunchKernelGGL(k_mix_finalize, dim3((I + MCHIP_BLOCK - 1) / MCHIP_BLOCK), dim3(MCHIP_BLOCK), 0, s, I, n_lchunks, Vpart, eta, vik, llpart, mode, stop);
-}
-void launch_mix_column(const mchip_pass_args &a, hipStream_t s)
-{
-	if (a.count_bits == 2) { hipLaunchKernelGGL((k_column_counts<2, true>), counts_grid(a), dim3(MCHIP_BLOCK), 0, s, a); return; }
-	if (a.count_bits == 4) { hipLaunchKernelGGL((k_column_counts<4, true>), counts_grid(a), dim3(MCHIP_BLOCK), 0, s, a); return; }
-	if (a.ploidy == 2) hipLaunchKernelGGL((k_mix_column<2>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
-	else hipLaunchKernelGGL((k_mix_column<0>), column_grid(a), dim3(MCHIP_BLOCK), 0, s, a);
 }
 void launch_part_p(const mchip_pass_args &a, hipStream_t s)
 {
@@ -2074,9 +2154,8 @@ void launch_project_q(int nrows, int, double *Q, double lb, const int *stop, hip
 const mchip_ktable *MCHIP_CAT(mchip_ktable_get_, MCHIP_K)()
 {
 	static mchip_ktable t = {
-		launch_accum_p, launch_loglik, launch_accum_q, launch_part_p, launch_part_q, launch_finalize_q, launch_project_q,
-		launch_mix_gather, launch_mix_finalize, launch_mix_column, dual_available, launch_accum_q_dual,
-		col_slabs, ind_slabs, ind_ll_parts, launch_finalize_qp, pair_available, pair_blocks, launch_estep_pair,
+		plan, launch_accum_p, launch_loglik, launch_accum_q, launch_part_p, launch_part_q, launch_finalize_q, launch_project_q,
+		launch_mix_gather, launch_mix_finalize, launch_mix_column, launch_accum_q_dual, launch_finalize_qp, launch_estep_pair,
 	};
 	return &t;
 }

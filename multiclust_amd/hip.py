@@ -21,6 +21,14 @@ class RunState(C.Structure):
                 ("iter_stop", C.c_int), ("fatal", C.c_int)]
 
 
+class PlanQuery(C.Structure):
+    """mchip_plan_query (include/multiclust_hip.h)"""
+    _fields_ = [("K", C.c_int), ("I", C.c_int), ("L", C.c_int), ("T", C.c_int), ("ploidy", C.c_int),
+                ("min_alleles", C.c_int), ("max_alleles", C.c_int), ("has_missing", C.c_int),
+                ("admixture", C.c_int), ("eta_constrained", C.c_int), ("do_projection", C.c_int),
+                ("p_lb", C.c_double), ("n_cu", C.c_int), ("accel_cycle", C.c_int)]
+
+
 def lib_path():
     # MCHIP_LIB_PATH: an experimental build of the library (scripts/diag/*_exp.sh); the product path is the in-tree one
     return os.environ.get("MCHIP_LIB_PATH") or os.path.join(_HERE, "lib", "libmulticlust_hip.so")
@@ -103,6 +111,7 @@ def load():
         "mchip_impute_missing": ([vp, i32, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp], i32),
         "mchip_divergence": ([vp, i32, vp, vp, vp, vp, vp, dp, dp, ip], i32),
         "mchip_residual_products": ([vp, i32, vp, vp], i32),
+        "mchip_describe_plan": ([C.POINTER(PlanQuery), C.c_char_p, i32], i32),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("MCHIP_ALLOW_PARTIAL_ABI") == "1" and not hasattr(lib, name):
@@ -127,8 +136,16 @@ ABI_SYMBOLS = [
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
     "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
-    "mchip_residual_products",
+    "mchip_residual_products", "mchip_describe_plan",
 ]
+
+
+def describe_plan(**query):
+    """mchip_describe_plan: (status, kernel names, {key: value}) of the library's kernel selection; needs no device"""
+    buf = C.create_string_buffer(4096)
+    rc = load().mchip_describe_plan(C.byref(PlanQuery(**query)), buf, len(buf))
+    lines = buf.value.decode().split() if rc == 0 else []
+    return rc, {x for x in lines if "=" not in x}, {x.split("=")[0]: int(x.split("=")[1]) for x in lines if "=" in x}
 
 
 class Context:

@@ -1,11 +1,12 @@
 """Every K instance of every EM kernel variant against the oracle.
 
-Each K from 1 to 64 is its own translation unit (Makefile: -DMCHIP_K=K), and inside it the launchers of mchip_kernels_k.hip pick
+Each K from 1 to 64 is its own translation unit (Makefile: -DMCHIP_K=K), and inside it plan() of mchip_kernels_k.hip picks
 one of about thirty template instances by ploidy, allele counts, missing data, the reciprocal-per-cell condition, the LDS budget,
 the testing knobs and the launch geometry.  One such instance (K = 52, tetraploid, reciprocal per cell) once came out of hipcc
 miscompiled.  This module visits every (K, instance) cell the dispatch can reach:
 
   * DISPATCH RULE: a Python statement of which kernels a case reaches (`reach`), each condition citing the C it restates;
+    tests/test_kernel_plan_cpu.py holds it against the library's own account (mchip_describe_plan), without a GPU;
   * CASES: a fixed case list, per K and per variant family, on small data sets around the tile edges (I = 64 n +- 1, L not a
     multiple of 8);
   * test_the_case_list_covers_every_reachable_cell (CPU): every (K, kernel) cell the rule can reach over a grid of
@@ -38,7 +39,7 @@ FP_TILE = 1024              # mchip_finalize.h
 N_CU = 256
 # the knobs read_knobs() takes (mchip.hip); every test starts from none of them
 KNOBS = ("MCHIP_NO_BIAL", "MCHIP_NO_COUNTS", "MCHIP_FORCE_DENSE", "MCHIP_FORCE_SAFE", "MCHIP_NO_GRAPH", "MCHIP_NO_DUAL",
-         "MCHIP_NO_SLAB_SUM", "MCHIP_NO_FUSED_FINALIZE", "MCHIP_NO_COL_SPLIT", "MCHIP_PART_NO_TILE", "MCHIP_SIM_NO_TILE",
+         "MCHIP_NO_SLAB_SUM", "MCHIP_NO_FUSED_FINALIZE", "MCHIP_NO_PAIR", "MCHIP_NO_COL_SPLIT", "MCHIP_PART_NO_TILE", "MCHIP_SIM_NO_TILE",
          "MCHIP_BLOCKS_PER_CU", "MCHIP_BLOCKS_PER_CU_COL", "MCHIP_BLOCKS_PER_CU_IND", "MCHIP_SLAB_FRAC", "MCHIP_NO_CHUNK_ROUNDUP")
 
 
@@ -84,7 +85,7 @@ def ind_waves_for(K, tile_cols):     # mchip_ind_waves (mchip_internal.h)
     return 1
 
 
-def lds_sparse(K, max_M):    # ctx->sparse (mchip.hip): two staged tiles of 8 loci fit 64 KiB
+def lds_sparse(K, max_M):    # model_geometry's sparse (mchip.hip): two staged tiles of 8 loci fit 64 KiB
     return max_M <= SPARSE_MAX_M and (2 * 8 * max_M * kp(K) + qblock(K)) * 8 <= 65536
 
 
@@ -92,7 +93,7 @@ def sparse_edge(K):          # the largest max_M that still takes the sparse pas
     return max(m for m in range(1, SPARSE_MAX_M + 1) if lds_sparse(K, m))
 
 
-def count_bits(ploidy, knobs):       # install_layouts (mchip.hip)
+def count_bits(ploidy, knobs):       # count_bits_for (mchip.hip)
     if "MCHIP_NO_COUNTS" in knobs:
         return 0
     return 2 if ploidy <= 3 else (4 if ploidy <= 15 else 0)
@@ -106,8 +107,8 @@ def finalize_p_loci(K, max_M):       # finalize_p_loci (mchip.hip)
 
 
 def flush_blocks(K, ploidy, projection, p_lb):
-    """(safe_rcp, flush_blocks) of set_model_impl (mchip.hip).  The column passes on packed counts take the
-    reciprocal per cell where safe_rcp; the individual-side passes and the dense pair wherever flush_blocks < 1 (launch_sparse:
+    """(safe_rcp, flush_blocks) of model_geometry (mchip.hip).  The column passes on packed counts take the
+    reciprocal per cell where safe_rcp; the individual-side passes and the dense pair wherever flush_blocks < 1 (sparse_instance:
     `safe = a.flush_blocks < 1`), which a lower bound such as 1e-40 gives without safe_rcp."""
     safe = (not projection) or not (p_lb >= 1e-75)
     tmin = p_lb / K
@@ -119,7 +120,7 @@ def flush_blocks(K, ploidy, projection, p_lb):
 
 
 def geometry(K, I, L, T, ploidy, max_M, admixture, cbits, knobs, n_cu=N_CU):
-    """set_model_impl's launch geometry (mchip.hip): chunks of either pass, waves of the cooperating sparse pass"""
+    """model_geometry (mchip.hip): chunks of either pass, waves of the cooperating sparse pass"""
     def num(name, dflt):
         v = int(knobs.get(name, "0"))
         return v if v > 0 else dflt
@@ -162,18 +163,33 @@ def geometry(K, I, L, T, ploidy, max_M, admixture, cbits, knobs, n_cu=N_CU):
     return dict(n_ichunks=n_ichunks, lchunk=lchunk, n_lchunks=n_lchunks, sparse=sparse, coop=coop, waves=waves, xcd_rows=xcd_rows)
 
 
-def bial_pays(K, accum):     # launch_sparse (mchip_kernels_k.hip): SPLIT == 1 && (ACCUM ? K >= 10 : K >= 6)
+def bial_pays(K, accum):     # sparse_instance (mchip_kernels_k.hip): SPLIT == 1 && (accum ? K >= 10 : K >= 6)
     return ind_split(K) == 1 and (K >= 10 if accum else K >= 6)
 
 
-def dual_available(K, sparse, ind_safe, ploidy, biallelic, waves, max_M):     # dual_available (mchip_kernels_k.hip)
+def dual_available(K, sparse, ind_safe, ploidy, biallelic, waves, max_M):     # plan()'s dual (mchip_kernels_k.hip)
     if K > 12 or not sparse or ind_safe or ploidy != 2:
         return False
-    if biallelic and K >= 6:
+    if biallelic and K >= 6:                                                   # either half would run k_individual_bial
         return False
     tc, p = 8 * max_M, kp(K)
     stride = cdiv(tc * p, 128) * 128 if (p == K and K % 2 == 0 and ind_split(K) == 1) else tc * p
     return max(waves * 2 * 2 * stride, (K + 2) * 64) * 8 <= 64 * 1024
+
+
+def pair_available(K, sparse, cbits, ploidy, waves, col_safe, ind_safe, biallelic, col_blocks, ind_blocks):
+    """plan()'s pair (mchip_kernels_k.hip): col is k_column_counts<2,false,SAFE>, sside k_individual_sparse_w<2,true,SAFE,NOMISS>
+    with four waves and the same SAFE; col_blocks / ind_blocks = workgroups of the two (counts_grid, coop_rows)"""
+    if K > 12 or ind_split(K) != 1 or col_split(K) != 1:
+        return False
+    if not sparse or cbits != 2 or ploidy != 2 or waves * 64 != 256:
+        return False
+    if col_safe != ind_safe:
+        return False
+    if biallelic and K >= 10 and not ind_safe:                                 # sside would be k_individual_bial
+        return False
+    col_runs, ind_runs = cdiv(col_blocks, 8), cdiv(ind_blocks, 8)              # MCHIP_PAIR_RUN
+    return col_runs > 0 and ind_runs > 0 and (col_runs + ind_runs) * ind_runs < 1 << 32
 
 
 def B(x):
@@ -181,7 +197,7 @@ def B(x):
 
 
 def sparse_instances(K, ploidy, accum, nomiss, safe, biallelic):
-    """launch_sparse<ACCUM> (mchip_kernels_k.hip)"""
+    """sparse_instance (mchip_kernels_k.hip)"""
     if ind_split(K) == 1:
         if bial_pays(K, accum) and biallelic and ploidy == 2 and not safe:
             return "k_individual_bial<%s,%s>" % (B(accum), B(nomiss))
@@ -195,11 +211,13 @@ def sparse_instances(K, ploidy, accum, nomiss, safe, biallelic):
 
 def reach(case):
     """The kernels (and geometry facts) one case reaches: an EM step from slot 0 into slot 1 (mchip_em_step), then mchip_loglik,
-    mchip_e_step and mchip_loglik_prefetch of slot 1; for `accel` cases one batched SQUAREM cycle (mchip_accel_run)."""
+    mchip_e_step and mchip_loglik_prefetch of slot 1; for `accel` cases one batched SQUAREM cycle (mchip_accel_run) instead.
+    Nothing where that call is unsupported (a cycle on the dense pair)."""
     K, I, L, pl, knobs = case["K"], case["I"], case["L"], case["ploidy"], case["knobs"]
     ua, missing = case["ua"], case["missing"]
     min_M, max_M, T = int(ua.min()), int(ua.max()), int(ua.sum())
     admixture, constrained = case["model"] != "mix", case["model"] == "admix_c"
+    accel = bool(case.get("accel"))
     cbits = count_bits(pl, knobs)
     g = geometry(K, I, L, T, pl, max_M, admixture, cbits, knobs)
     sparse = g["sparse"]
@@ -207,60 +225,94 @@ def reach(case):
     if "MCHIP_FORCE_SAFE" in knobs:
         safe, flush = True, 0
     ind_safe = flush < 1
-    biallelic = min_M == 2 and max_M == 2 and "MCHIP_NO_BIAL" not in knobs      # pass_args (mchip.hip)
+    biallelic = min_M == 2 and max_M == 2 and "MCHIP_NO_BIAL" not in knobs      # shape_args (mchip.hip)
     nomiss = not missing
     out = set()
+    p_loci = finalize_p_loci(K, max_M)
+    if max_M > 64:
+        out.add("byte_flag_projection")          # k_finalize_p / k_project_p with d_flags (mchip.hip: needs_byte_flags)
     if not admixture:
-        # run_mixture (mchip.hip): k_logp, launch_mix_gather, k_mix_finalize, shared eta, launch_mix_column, finalize_p
+        # run_mixture (mchip.hip): k_logp, mix_gather, k_mix_finalize, shared eta, mix_column, finalize_p; plan()'s mix_gather, mix_col
         out.add("k_mix_gather<%d,%s>" % (2 if pl == 2 else 0, B(sparse)))
         out |= {"k_mix_finalize", "finalize_shared_eta"}
         out.add("k_column_counts<%d,true,false>" % cbits if cbits else "k_mix_column<%d>" % (2 if pl == 2 else 0))
-        out.add("k_finalize_p_tile" if finalize_p_loci(K, max_M) else "k_finalize_p")
+        out.add("k_finalize_p_tile" if p_loci else "k_finalize_p")
+        if (cdiv(g["n_ichunks"], COL_WAVES) if cbits else g["n_ichunks"]) > 8:  # plan()'s mix_col_slabs
+            out.add("col_slabs>8")
+        if g["n_lchunks"] > 8:
+            out.add("ind_slabs>8")
         return out
+    if accel and not sparse:
+        return set()                             # mchip_accel_run: MCHIP_ERR_UNSUPPORTED
     split_ok = col_split(K) > 1 and "MCHIP_NO_COL_SPLIT" not in knobs
-    # launch_accum_p (mchip_kernels_k.hip)
+    # plan()'s col (mchip_kernels_k.hip)
     if sparse and cbits and split_ok:
-        out.add("k_column_counts_split<%d,%s>" % (cbits, B(safe)))
+        col = "k_column_counts_split<%d,%s>" % (cbits, B(safe))
     elif sparse and cbits:
-        out.add("k_column_counts<%d,false,%s>" % (cbits, B(safe)))
+        col = "k_column_counts<%d,false,%s>" % (cbits, B(safe))
     elif sparse:
-        out.add("k_column_pass<%d,true,false,false>" % (2 if pl == 2 else 0))
+        col = "k_column_pass<%d,true,false,false>" % (2 if pl == 2 else 0)
     elif pl == 2:
-        out.add("k_column_pass<2,true,%s,true>" % B(flush < 1))
+        col = "k_column_pass<2,true,%s,true>" % B(flush < 1)
     else:
-        out.add("k_column_pass<0,true,true,true>")
-    if sparse:              # launch_accum_q / launch_loglik / mchip_loglik_prefetch
-        out.add(sparse_instances(K, pl, True, nomiss, ind_safe, biallelic))
-        out.add(sparse_instances(K, pl, False, nomiss, ind_safe, biallelic))
+        col = "k_column_pass<0,true,true,true>"
+    if sparse:              # plan()'s sside and ll
+        sside = sparse_instances(K, pl, True, nomiss, ind_safe, biallelic)
+        ll = sparse_instances(K, pl, False, nomiss, ind_safe, biallelic)
     else:
-        out.add("k_individual_pass<%d>" % (2 if pl == 2 else 0))
-        out.add("k_column_pass<2,false,%s,true>" % B(flush < 1) if pl == 2 else "k_column_pass<0,false,true,true>")
-    # run_estep's finalisers (mchip.hip) and col_slabs / ind_slabs (mchip_kernels_k.hip)
+        sside = "k_individual_pass<%d>" % (2 if pl == 2 else 0)
+        ll = "k_column_pass<2,false,%s,true>" % B(flush < 1) if pl == 2 else "k_column_pass<0,false,true,true>"
+    # plan()'s col_slabs, ind_slabs, pair and dual
     n_slabs = cdiv(g["n_ichunks"], COL_WAVES) if (sparse and cbits and not split_ok) else g["n_ichunks"]
     s_slabs = cdiv(g["n_lchunks"], g["waves"]) if (sparse and ind_split(K) == 1) else g["n_lchunks"]
-    p_loci = finalize_p_loci(K, max_M)
+    pair = "MCHIP_NO_PAIR" not in knobs and pair_available(K, sparse, cbits, pl, g["waves"], safe, ind_safe, biallelic,
+                                                           cdiv(T, 64) * n_slabs, cdiv(I, 64) * s_slabs)
+    dual = "MCHIP_NO_DUAL" not in knobs and dual_available(K, sparse, ind_safe, pl, biallelic, g["waves"], max_M)
+    # run_estep (mchip.hip) with the M step: the two passes, where the pair exists as one launch that runs the bodies of both
+    # (mchip_describe_plan lists all three), then the finalisers (finish_for)
+    out |= {col, sside}
+    if pair:
+        out.add("k_estep_pair<2,2,%s,%s>" % (B(ind_safe), B(nomiss and not ind_safe)))
     slab_sum = n_slabs > 8 and "MCHIP_NO_SLAB_SUM" not in knobs
     if not constrained and p_loci and not slab_sum and "MCHIP_NO_FUSED_FINALIZE" not in knobs:
         out.add("k_finalize_qp")
     else:
         out.add("k_finalize_q")
-        if constrained:
-            out.add("finalize_shared_eta")
         if slab_sum:
             out.add("k_sum_slabs")
         out.add("k_finalize_p_tile" if p_loci else "k_finalize_p")
-    if max_M > 64:
-        out.add("byte_flag_projection")          # k_finalize_p / k_project_p with d_flags (mchip.hip)
+    if constrained:
+        out.add("finalize_shared_eta")
+    if accel:               # accel_cycle_enqueue (mchip.hip): log L of the second iterate and of the extrapolated point
+        out |= {"k_individual_sparse_w<2,true,false,%s,true>" % B(nomiss)} if dual else {ll, sside}
+    else:                   # mchip_loglik; mchip_e_step (run_estep without the M step: k_finalize_q); mchip_loglik_prefetch
+        out |= {ll, sside, "k_finalize_q"}
     if n_slabs > 8:
         out.add("col_slabs>8")
     if s_slabs > 8:
         out.add("ind_slabs>8")
     if g["xcd_rows"]:
         out.add("xcd_rows")
-    if case.get("accel") and admixture and "MCHIP_NO_DUAL" not in knobs and \
-            dual_available(K, sparse, ind_safe, pl, biallelic, g["waves"], max_M):     # accel_cycle_enqueue (mchip.hip)
-        out.add("k_individual_sparse_w<2,true,false,%s,true>" % B(nomiss))
     return out
+
+
+# pseudo-cell of reach -> the same statement about the key=value lines of mchip_describe_plan
+PSEUDO = {
+    "col_slabs>8": lambda f: f["col_slabs"] > 8,
+    "ind_slabs>8": lambda f: f["ind_slabs"] > 8,
+    "xcd_rows": lambda f: f["xcd_rows"],
+    "byte_flag_projection": lambda f: f["byte_flags"],
+    "finalize_shared_eta": lambda f: f["shared_eta"],
+}
+
+
+def plan_query(c, n_cu=N_CU):
+    """the case as mchip_describe_plan takes it (multiclust_amd.hip.describe_plan)"""
+    ua = c["ua"]
+    return dict(K=c["K"], I=c["I"], L=c["L"], T=int(ua.sum()), ploidy=c["ploidy"], min_alleles=int(ua.min()),
+                max_alleles=int(ua.max()), has_missing=int(bool(c["missing"])), admixture=int(c["model"] != "mix"),
+                eta_constrained=int(c["model"] == "admix_c"), do_projection=c["projection"], p_lb=c["lb"], n_cu=n_cu,
+                accel_cycle=int(bool(c.get("accel"))))
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CASES
@@ -417,10 +469,9 @@ def case_id(c):
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU test
-def grid_reach(K):
-    """every (kernel, geometry fact) the rule gives at this K over a grid of configurations"""
+def grid_configs(K):
+    """the grid of configurations (cases as `reach` takes them) of grid_reach"""
     rs = np.random.default_rng(K)
-    cells = set()
     specs = [(2, 2), (2, 4), (2, sparse_edge(K)), (2, sparse_edge(K) + 1), (2, 100)]
     bounds = [(1, 1e-8), (1, 1e-20), (1, 1e-40), (0, 1e-8)]
     knobsets = [{}, {"MCHIP_NO_COUNTS": "1"}, {"MCHIP_FORCE_DENSE": "1"}, {"MCHIP_NO_COL_SPLIT": "1"}]
@@ -438,14 +489,21 @@ def grid_reach(K):
                                     continue
                                 c = dict(K=K, I=I, L=L, ploidy=pl, knobs=dict(kn, **geo), ua=ua, missing=missing, model=model,
                                          projection=proj, lb=min(bound, 0.5 / (I * pl)))
-                                cells |= reach(c)
+                                yield c
                                 if model == "admix" and not kn and not geo:
-                                    cells |= reach(dict(c, accel=True))
+                                    yield dict(c, accel=True)
+
+
+def grid_reach(K):
+    """every (kernel, geometry fact) the rule gives at this K over a grid of configurations"""
+    cells = set()
+    for c in grid_configs(K):
+        cells |= reach(c)
     return cells
 
 
 def test_sparse_edge_table():
-    """the LDS edge (ctx->sparse) as derived from mchip_kp: the largest max_M of the sparse pass, K by K"""
+    """the LDS edge (model_geometry's sparse) as derived from mchip_kp: the largest max_M of the sparse pass, K by K"""
     want = {1: 32, 14: 32, 15: 28, 18: 28, 19: 25, 20: 25, 21: 22, 22: 22, 23: 21, 24: 21, 25: 19, 26: 19, 27: 18, 28: 18,
             29: 14, 36: 14, 37: 12, 40: 12, 41: 11, 44: 11, 45: 10, 48: 10, 49: 8, 56: 8, 57: 6, 64: 6}
     assert {K: sparse_edge(K) for K in want} == want
@@ -469,6 +527,10 @@ def test_the_case_list_covers_every_reachable_cell():
         assert ("k_individual_bial<true,true>" in h) == (10 <= K <= 27) and ("k_individual_bial<false,false>" in h) == (6 <= K <= 27), K
         assert "k_individual_pass<2>" in h and "k_individual_pass<0>" in h and "k_column_pass<2,true,true,true>" in h, K
         assert ("k_individual_sparse_w<2,true,false,true,true>" in h) == (K <= 12), K
+        # the pair (plan(): K <= 12; two to four alleles stage 32 columns of at most 12 doubles, four waves' tiles fill the 48 KiB
+        # of mchip_ind_waves exactly at K = 11 and 12), with shared reciprocals without and with missing data, and without them
+        for inst in ("false,true", "false,false", "true,false"):
+            assert ("k_estep_pair<2,2,%s>" % inst in h) == (K <= 12), (K, inst)
     ids = [case_id(c) for c in CASES + DUAL]
     assert len(ids) == len(set(ids))
     assert {c["K"] for c in CASES} == set(range(1, MAX_K + 1))
@@ -525,6 +587,13 @@ def test_kernel_matrix_em_step_vs_oracle(contexts, monkeypatch, c):
     ctx = contexts(c["knobs"])
     ctx.set_genotypes(ua, geno)
     ctx.set_model(K, admixture=admixture, eta_constrained=con, do_projection=c["projection"], lower_bound=lb)
+    n_cu = ctx.device_info()[1]
+    if n_cu == N_CU:        # what the library launches on this device is what the rule (and so the coverage proof) says
+        cd["missing"] = bool((geno == 0xFF).any())
+        rc, kernels, facts = mc.hip.describe_plan(**plan_query(cd, n_cu))
+        want = reach(cd)
+        assert rc == 0 and kernels == want - set(PSEUDO), (rc, sorted(kernels ^ (want - set(PSEUDO))))
+        assert all((cell in want) == bool(says(facts)) for cell, says in PSEUDO.items()), (facts, sorted(want))
     ctx.set_q(0, q0)
     ctx.set_p(0, p0)
     ll = ctx.em_step(0, 1)
@@ -560,7 +629,7 @@ def test_kernel_matrix_em_step_vs_oracle(contexts, monkeypatch, c):
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", DUAL, ids=case_id)
 def test_kernel_matrix_dual_cycle_vs_oracle(contexts, monkeypatch, c):
-    """One batched SQUAREM-3 cycle (mchip_accel_run; the dual individual pass where dual_available) against the oracle's
+    """One batched SQUAREM-3 cycle (mchip_accel_run; the dual individual pass where the plan has one) against the oracle's
     accelerated_em_step from the same point, and bit for bit against the same cycle with the dual pass off (MCHIP_NO_DUAL=1)."""
     ua, geno = build_data(c)
     K, I, L, pl = c["K"], c["I"], c["L"], c["ploidy"]

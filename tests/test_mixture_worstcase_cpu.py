@@ -357,7 +357,7 @@ def test_case_list_reaches_every_mixture_kernel():
             cbits = count_bits(c["ploidy"], c["knobs"])
             g = geometry(K, c["I"], c["L"], int(ua.sum()), c["ploidy"], int(ua.max()), False, cbits, c["knobs"])
             chunks = max(chunks, g["n_lchunks"])
-            slabs = max(slabs, -(-g["n_ichunks"] // 4) if cbits else g["n_ichunks"])      # col_slabs(a, 1) of mchip_kernels_k.hip
+            slabs = max(slabs, -(-g["n_ichunks"] // 4) if cbits else g["n_ichunks"])      # plan()'s mix_col_slabs (mchip_kernels_k.hip)
         want = {"k_mix_gather<2,true>", "k_mix_gather<0,true>", "k_mix_gather<2,false>", "k_mix_gather<0,false>",
                 "k_column_counts<2,true,false>", "k_column_counts<4,true,false>", "k_mix_column<2>", "k_mix_column<0>",
                 "k_finalize_p_tile", "k_finalize_p", "k_mix_finalize", "finalize_shared_eta"}

@@ -4,7 +4,7 @@ The rest of the suite draws Q and P from Dirichlet(1): every t = sum_k q_k p_k a
 numerical contracts of DESIGN.md section 4.2 are never near their limits:
 
   * the running-product log likelihood is looked at every `flush_blocks` units of 16 multiplications, an interval the host
-    sizes (set_model_impl, mchip.hip) so that a product that starts above 1e-100 stays above 1e-300;
+    sizes (model_geometry, mchip.hip) so that a product that starts above 1e-100 stays above 1e-300;
   * shared reciprocals (rcp4, rcp_group, the pair and the tetraploid four of the individual side, k_individual_bial's
     rcp_full(t0 t1)) are allowed down to a bound of 1e-75.
 
@@ -57,14 +57,14 @@ K_SHARED = (8, 28, 64)
 FAMILIES = ("dip", "bial", "tet", "dense", "shared")
 BOUNDS = ("edge1", "edge2", "edge3", "1e-75", "1e-8")
 # whole-axis chunks: a chunk restarts the product, and at small K the default geometry cuts 130 loci into chunks of two looks
-# (set_model_impl: min_lchunk = ceil(8 K / (slab_frac ploidy)) > L leaves one chunk; likewise min_ichunk > I)
+# (model_geometry: min_lchunk = ceil(8 K / (slab_frac ploidy)) > L leaves one chunk; likewise min_ichunk > I)
 WHOLE_AXIS = {"MCHIP_SLAB_FRAC": "0.001"}
 WORST_ROW_EVERY, WORST_COL_EVERY, VERTEX_EVERY = 5, 4, 5       # worst rows 0, 5, ...; vertex rows 2, 7, ...
 
 
 # ------------------------------------------------------------------------------------------------------------ the host's sizing
 def host_flush_blocks(K, p_lb, ploidy=2, projection=True):
-    """set_model_impl (mchip.hip), the block behind "log-product check interval":
+    """model_geometry (mchip.hip), the block behind "log-product check interval":
         tmin = p_lb / K;  mults = floor(200.0 / -log10(tmin));  blocks = (int)(mults / (ploidy == 4 ? 16.0 : 8.0 * ploidy));
         safe_rcp = !do_projection || !(p_lb >= 1e-75);  if (safe_rcp) flush_blocks = 0
     Returns (safe_rcp, flush_blocks)."""
@@ -78,7 +78,7 @@ def host_flush_blocks(K, p_lb, ploidy=2, projection=True):
 
 
 def edge_bound(K, b, unit=16):
-    """the smallest p_lb (to 0.1 %) for which set_model_impl yields flush_blocks == b on diploid and tetraploid data, where a
+    """the smallest p_lb (to 0.1 %) for which model_geometry yields flush_blocks == b on diploid and tetraploid data, where a
     unit is 16 multiplications: K 10^(-200 / (unit b)) 1.001"""
     lb = K * 10.0 ** (-200.0 / (unit * b)) * 1.001
     for ploidy in (2, 4):
