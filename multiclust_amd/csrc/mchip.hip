@@ -463,16 +463,8 @@ __global__ __launch_bounds__(256) void k_count_cells(const uint8_t *__restrict__
 			copies += cnt;
 		}
 	}
-	red[0][threadIdx.x] = cells;
-	red[1][threadIdx.x] = copies;
-	__syncthreads();
-	for (int w = 128; w > 0; w >>= 1) {
-		if ((int)threadIdx.x < w) {
-			red[0][threadIdx.x] += red[0][threadIdx.x + w];
-			red[1][threadIdx.x] += red[1][threadIdx.x + w];
-		}
-		__syncthreads();
-	}
+	const unsigned mine[2] = {cells, copies};
+	block_tree_sum<256>(red[0], 256, mine);
 	if (threadIdx.x == 0) {
 		atomicAdd(&out[0], (unsigned long long)red[0][0]);
 		atomicAdd(&out[1], (unsigned long long)red[1][0]);
@@ -518,13 +510,7 @@ __device__ __forceinline__ double ordered_sum(double acc, const double *__restri
 __device__ __forceinline__ double block_ordered_sum(const double *__restrict__ in, int n, double *red)
 {
 	const double s = (int)threadIdx.x < n ? ordered_sum(0.0, in, threadIdx.x, MCHIP_BLOCK, (n - (int)threadIdx.x + MCHIP_BLOCK - 1) / MCHIP_BLOCK) : 0.0;
-	red[threadIdx.x] = s;
-	__syncthreads();
-	for (int w = MCHIP_BLOCK / 2; w > 0; w >>= 1) {
-		if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-		__syncthreads();
-	}
-	const double v = red[0];
+	const double v = block_tree_sum<MCHIP_BLOCK>(red, s);
 	__syncthreads();
 	return v;
 }
@@ -534,6 +520,13 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_sum(const double *__rest
 	if (stop && *stop) return;
 	const double v = block_ordered_sum(in, n, red);
 	if (threadIdx.x == 0) *out = v;
+}
+/* out[r] = the sum of row r of in [gridDim.x][n]: block r is k_reduce_sum on its row */
+__global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_rows(const double *__restrict__ in, int n, double *__restrict__ out)
+{
+	__shared__ double red[MCHIP_BLOCK];
+	const double v = block_ordered_sum(in + (size_t)blockIdx.x * n, n, red);
+	if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 /* the end of a batched accelerated cycle in one single-block launch: emll (when in1 is given: the dual pass's second log
  * likelihood) -> sc[1], the extrapolated point's log likelihood -> sc[2] (k_reduce_sum's sums), accept iff ll > emll */
@@ -686,12 +679,7 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_column_sums(const double *__res
 	const int k = blockIdx.x;
 	double s = 0.0;
 	for (int i = threadIdx.x; i < I; i += MCHIP_BLOCK) s += sik[(size_t)i * K + k];
-	red[threadIdx.x] = s;
-	__syncthreads();
-	for (int w = MCHIP_BLOCK / 2; w > 0; w >>= 1) {
-		if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-		__syncthreads();
-	}
+	block_tree_sum<MCHIP_BLOCK>(red, s);
 	if (threadIdx.x == 0) out[k] = red[0];
 }
 __global__ void k_normalize_row(const double *__restrict__ sums, int K, double *eta, const int *stop = nullptr, double add = 0.0)
@@ -720,18 +708,11 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_stop_check(mchip_run_state *s, 
 {
 	__shared__ double red[MCHIP_BLOCK];
 	if (s->stopped) return;		/* uniform */
-	if (part) {
-		const double acc = (int)threadIdx.x < n ? ordered_sum(0.0, part, threadIdx.x, MCHIP_BLOCK, (n - (int)threadIdx.x + MCHIP_BLOCK - 1) / MCHIP_BLOCK) : 0.0;
-		red[threadIdx.x] = acc;
-		__syncthreads();
-		for (int w = MCHIP_BLOCK / 2; w > 0; w >>= 1) {
-			if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-			__syncthreads();
-		}
-		if (threadIdx.x == 0) *ll = red[0];
-	}
+	double loglik = 0.0;
+	if (part) loglik = block_ordered_sum(part, n, red);
 	if (threadIdx.x) return;
-	const double loglik = part ? red[0] : *ll;
+	if (part) *ll = loglik;
+	else loglik = *ll;
 	s->n_iter++;
 	if (loglik != loglik) {
 		s->fatal = 1;
@@ -787,16 +768,8 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_dots(const double *__restrict__
 			s0 += uu * u2[x]; s1 += uu * v[x];
 		}
 	}
-	red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
-	__syncthreads();
-	for (int w = MCHIP_BLOCK / 2; w > 0; w >>= 1) {
-		if ((int)threadIdx.x < w) {
-			red[0][threadIdx.x] += red[0][threadIdx.x + w];
-			red[1][threadIdx.x] += red[1][threadIdx.x + w];
-			red[2][threadIdx.x] += red[2][threadIdx.x + w];
-		}
-		__syncthreads();
-	}
+	const double mine[3] = {s0, s1, s2};
+	block_tree_sum<MCHIP_BLOCK>(red[0], MCHIP_BLOCK, mine);
 	if (threadIdx.x == 0) {
 		part[blockIdx.x] = red[0][0];
 		part[gridDim.x + blockIdx.x] = red[1][0];
@@ -818,16 +791,8 @@ __device__ __forceinline__ void dots_slots_body(const double *__restrict__ x0, c
 		const double d = vv - uu;
 		s0 += uu * uu; s1 += uu * d; s2 += d * d;
 	}
-	red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
-	__syncthreads();
-	for (int w = MCHIP_BLOCK / 2; w > 0; w >>= 1) {
-		if ((int)threadIdx.x < w) {
-			red[0][threadIdx.x] += red[0][threadIdx.x + w];
-			red[1][threadIdx.x] += red[1][threadIdx.x + w];
-			red[2][threadIdx.x] += red[2][threadIdx.x + w];
-		}
-		__syncthreads();
-	}
+	const double mine[3] = {s0, s1, s2};
+	block_tree_sum<MCHIP_BLOCK>(red[0], MCHIP_BLOCK, mine);
 	if (threadIdx.x == 0) {
 		part[bid] = red[0][0];
 		part[gdim + bid] = red[1][0];
@@ -1730,7 +1695,7 @@ int mchip_data_counts(mchip_context *ctx, uint64_t *nonempty_cells, uint64_t *al
 		unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(ctx->d_scalars + 60), h_cnt[2] = {0, 0};
 		HIPCHK(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), ctx->stream));
 		const size_t n = (size_t)((ctx->I + 7) / 8) * ctx->T;
-		hipLaunchKernelGGL(k_count_cells, dim3(nblk_capped(n) > 65536u ? 65536u : nblk_capped(n)), dim3(256), 0, ctx->stream, ctx->d_gtA,
+		hipLaunchKernelGGL(k_count_cells, dim3(nblk_capped(n, 256, 65536)), dim3(256), 0, ctx->stream, ctx->d_gtA,
 				   ctx->I, ctx->L, ctx->ploidy, ctx->T, ctx->d_col_locus, ctx->d_col_allele, d_cnt);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, ctx->stream));
@@ -2268,6 +2233,10 @@ int check_partition_call(mchip_context *ctx, const void *arg, int to)
 void launch_reduce_sum(mchip_context *ctx, const double *in, int n, double *out)
 {
 	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, in, n, out, (const int *)nullptr);
+}
+void launch_reduce_rows(mchip_context *ctx, const double *in, int n_rows, int n, double *out)
+{
+	hipLaunchKernelGGL(k_reduce_rows, dim3((unsigned)n_rows), dim3(MCHIP_BLOCK), 0, ctx->stream, in, n, out);
 }
 
 extern "C" {

@@ -7,6 +7,7 @@
 #define MCHIP_CONTEXT_H
 
 #include "mchip_internal.h"
+#include "mchip_feature_geometry.h"
 #include "mchip_progress.h"
 
 #include <functional>
@@ -194,10 +195,10 @@ template <typename F> static void with_ploidy(int pl, F &&f)
 }
 
 static inline unsigned nblk(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
-/* for the byte-per-thread layout kernels (grid-stride loops): at most 2^30 work-items per launch */
-static inline unsigned nblk_capped(size_t n, unsigned b = 256)
+/* for the kernels with a grid-stride loop: at most cap_blocks blocks; 0 = the layout kernels' 2^30 work-items per launch */
+static inline unsigned nblk_capped(size_t n, unsigned b = 256, size_t cap_blocks = 0)
 {
-	const size_t blocks = (n + b - 1) / b, cap = ((size_t)1 << 30) / b;
+	const size_t blocks = (n + b - 1) / b, cap = cap_blocks ? cap_blocks : ((size_t)1 << 30) / b;
 	return (unsigned)(blocks < cap ? blocks : cap);
 }
 
@@ -243,6 +244,27 @@ int partition_mstep(mchip_context *ctx, const uint8_t *d_raw, int to, int counts
 int partition_finalize(mchip_context *ctx, int to, int counts, int n_aslabs);
 /* out[0] = in[0] + ... + in[n - 1] in k_reduce_sum's fixed order, one workgroup */
 void launch_reduce_sum(mchip_context *ctx, const double *in, int n, double *out);
+/* out[r] = in[r][0] + ... + in[r][n - 1] for the n_rows rows of in, each as launch_reduce_sum adds it, in one launch */
+void launch_reduce_rows(mchip_context *ctx, const double *in, int n_rows, int n, double *out);
+
+/* what an entry point that reads a fitted slot asks first: a data set, a model, a slot; admixture_message (NULL: either model
+ * will do) refuses the mixture model in the unit's own words */
+static inline int require_fit(mchip_context *ctx, int slot, const char *admixture_message)
+{
+	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
+	const int rc = check_slot(ctx, slot);
+	if (rc) return rc;
+	if (admixture_message && !ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "%s", admixture_message);
+	return MCHIP_OK;
+}
+/* a kernel launched with dynamic LDS sized against a budget below 64 KiB: its static LDS still fits beside it */
+template <typename Kern> static int check_lds(mchip_context *ctx, Kern kernel, size_t dynamic_bytes, const char *message)
+{
+	hipFuncAttributes attr;
+	HIPCHK(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel)));
+	if (attr.sharedSizeBytes + dynamic_bytes > 64 * 1024) return fail(ctx, MCHIP_ERR_STATE, "%s", message);
+	return MCHIP_OK;
+}
 
 /* mchip_generators.hip */
 /* rand() % m for the n_draws draws that follow `window`, one byte each, to d_out: whole chunks of RNG_CHUNK bytes are written */

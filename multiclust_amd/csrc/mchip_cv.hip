@@ -6,21 +6,19 @@
  *   k_cv_mask    a thread per genotype: copies its `ploidy` bytes of the saved full data set into the stream buffer, or 0xFF when
  *                the genotype's fold is the one held out; marks the individuals that keep an observed copy.
  *   k_cv_score   the held-out score, runtime K (it runs F times per K against hundreds of EM passes: one instance, not 64).
- *                Lane = individual, as the S-side pass.  The workgroup's q rows sit in LDS, K doubles per lane, the rows an odd
- *                number of doubles apart: lane i reads dwords 2 (KS i + k) and the next one, and with KS odd the 32 lanes of a
- *                ds_read_b64 lane group fall on 32 different bank pairs of the 64.  The P rows of the current block of 8 loci are
- *                staged per workgroup as they lie in the slot's [T][K] form (columns toff[l0] .. toff[l0 + 8], K contiguous
- *                doubles each, rows KS apart), when they fit beside the q rows; a data set with so many alleles per locus that
- *                they do not reads its rows from memory.  A lane reads the eight fold bytes of its block at once and then only
+ *                Lane = individual, as the S-side pass.  The workgroup's q rows sit in LDS, K doubles per lane, lds_pitch(K)
+ *                apart (mchip_device_util.h).  The P rows of the current block of 8 loci are staged per workgroup as they lie in
+ *                the slot's [T][K] form (columns toff[l0] .. toff[l0 + 8]) when they fit beside the q rows; a data set with so
+ *                many alleles per locus that they do not reads its rows from memory (lane_pass_geometry_of,
+ *                mchip_feature_geometry.h).  A lane reads the eight fold bytes of its block at once and then only
  *                the genotype bytes of the loci that are in the fold; the K-FMA dot product and the logarithm run for the
  *                observed copies of those loci alone, about 1 / F of the cells.
  *                Measured at 10 000 x 100 000, K = 8, F = 5: 8.5 ms (profiles/cv_passes.txt).  Two other forms were tried and were
  *                slower: the workgroup staging tiles of fold and genotype rows in LDS with aligned word loads (12.0 ms), and the
  *                same with every lane walking the in-fold loci of its own row, so that the lanes of a wave are busy at different
  *                loci (12.3 ms; 10.5 ms with eight staging loads in flight per thread).  What binds is not established.
- *                Sums: a lane adds its terms in locus order; the workgroup's lanes are added by a fixed tree in LDS; one partial
- *                per workgroup, k_reduce_sum (mchip.hip) adds the partials.  No floating-point atomics: the same state gives the
- *                same bits.  The two counts are integers and go through atomics.
+ *                Sums: a lane adds its terms in locus order; the workgroup's lanes by block_tree_sum; one partial per workgroup,
+ *                k_reduce_sum (mchip.hip) adds the partials.  The two counts are integers: block_add_counts.
  */
 #include "mchip_context.h"
 
@@ -54,39 +52,9 @@ __device__ __forceinline__ uint64_t cv_load8(const uint8_t *__restrict__ base, s
 	return sh ? (lo >> sh) | (w[1] << (64u - sh)) : lo;
 }
 
-constexpr int CV_LBLOCK = 8;			/* loci per staged block */
-constexpr size_t CV_LDS_BUDGET = 64 * 1024 - 64;	/* dynamic LDS per workgroup (the kernel has 16 static bytes beside it) */
-
-/* geometry of the score pass: lanes per workgroup, whether the P rows of a block are staged, locus chunks */
-struct cv_geometry {
-	int threads, stage, lchunk, n_lchunks, n_itiles;
-	size_t lds;
-};
-static inline int cv_ks(int K) { return K | 1; }
-static cv_geometry cv_score_geometry(int I, int L, int K, int max_M, int n_cu)
-{
-	cv_geometry g;
-	const size_t ks = (size_t)cv_ks(K), red = 256 * sizeof(double);
-	const size_t ptile = (size_t)CV_LBLOCK * (size_t)max_M * ks * sizeof(double);
-	/* the most lanes whose q rows leave room for the P tile; when no workgroup size does, the most lanes that fit alone */
-	g.threads = 0;
-	for (int t = 256; t >= 64 && !g.threads; t >>= 1)
-		if ((size_t)t * ks * sizeof(double) + red + ptile <= CV_LDS_BUDGET) g.threads = t;
-	g.stage = g.threads ? 1 : 0;
-	for (int t = 256; t >= 64 && !g.threads; t >>= 1)
-		if ((size_t)t * ks * sizeof(double) + red <= CV_LDS_BUDGET) g.threads = t;	/* (64 lanes at K = 64: 35 KB) */
-	g.lds = (size_t)g.threads * ks * sizeof(double) + red + (g.stage ? ptile : 0);
-	g.n_itiles = (I + g.threads - 1) / g.threads;
-	/* enough workgroups to fill the device a few times over; chunks are whole blocks of 8 loci */
-	const int lblocks = (L + CV_LBLOCK - 1) / CV_LBLOCK;
-	int want = (16 * (n_cu > 0 ? n_cu : 256) + g.n_itiles - 1) / g.n_itiles;
-	if (want > lblocks) want = lblocks;
-	if (want > 65535) want = 65535;
-	if (want < 1) want = 1;
-	g.lchunk = ((lblocks + want - 1) / want) * CV_LBLOCK;
-	g.n_lchunks = (L + g.lchunk - 1) / g.lchunk;
-	return g;
-}
+constexpr int CV_LBLOCK = LANE_PASS_LBLOCK;	/* loci per staged block */
+constexpr size_t CV_LDS_BUDGET = 64 * 1024 - 64;	/* dynamic LDS per workgroup (the kernel has 16 static bytes beside it: its counts) */
+constexpr size_t CV_RED_BYTES = 256 * sizeof(double);	/* the tree's space */
 
 /* sum of log max(t, floor) over the observed copies of the fold, one partial per workgroup in part[] (n_itiles * n_lchunks of
  * them); counts[0] += copies, counts[1] += floored copies (zeroed by the caller).  P is a slot's [T][K], Q its [I][K]
@@ -103,13 +71,7 @@ __global__ __launch_bounds__(256) void k_cv_score(int I, int L, int pl, int K, i
 	const int nthr = blockDim.x, tid = threadIdx.x;
 	const int i0 = blockIdx.x * nthr, i = i0 + tid;
 	const int lbeg = blockIdx.y * lchunk, lend = min(L, lbeg + lchunk);
-	/* q rows of the workgroup's individuals: consecutive threads read consecutive doubles of Q */
-	if (qstride) {
-		const int rows = min(nthr, I - i0);
-		for (int x = tid; x < rows * K; x += nthr) qs[(x / K) * KS + x % K] = Q[(size_t)i0 * K + x];
-	} else {
-		for (int x = tid; x < nthr * K; x += nthr) qs[(x / K) * KS + x % K] = Q[x % K];
-	}
+	stage_q_rows(qs, KS, Q, qstride, i0, I, K, tid, nthr);
 	const double *q = qs + (size_t)tid * KS;
 	const bool live = i < I;
 	const size_t row = (size_t)i * L;
@@ -119,8 +81,7 @@ __global__ __launch_bounds__(256) void k_cv_score(int I, int L, int pl, int K, i
 	for (int l0 = lbeg; l0 < lend; l0 += CV_LBLOCK) {
 		const int c0 = toff[l0];	/* (toff is padded: offsets behind the last locus are T) */
 		if (stage) {
-			const int ncols = toff[min(L, l0 + CV_LBLOCK)] - c0;
-			for (int x = tid; x < ncols * K; x += nthr) ps[(x / K) * KS + x % K] = P[(size_t)c0 * K + x];
+			stage_rows(ps, KS, P + (size_t)c0 * K, toff[min(L, l0 + CV_LBLOCK)] - c0, K, tid, nthr);
 			__syncthreads();
 		}
 		if (live) {
@@ -153,25 +114,10 @@ __global__ __launch_bounds__(256) void k_cv_score(int I, int L, int pl, int K, i
 		}
 		if (stage) __syncthreads();	/* the tile is overwritten by the next block */
 	}
-	/* the workgroup's lanes in a fixed tree (lanes of a wave first, then the waves) */
-	red[tid] = sum;
-	__syncthreads();
-	for (int w = nthr >> 1; w > 0; w >>= 1) {
-		if (tid < w) red[tid] += red[tid + w];
-		__syncthreads();
-	}
+	block_tree_sum(red, sum);
 	if (tid == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
-	/* counts: integers, order does not matter */
-	__shared__ unsigned long long cnt[2];
-	if (tid == 0) cnt[0] = cnt[1] = 0;
-	__syncthreads();
-	if (n_in) atomicAdd(&cnt[0], n_in);
-	if (n_fl) atomicAdd(&cnt[1], n_fl);
-	__syncthreads();
-	if (tid == 0) {
-		if (cnt[0]) atomicAdd(&counts[0], cnt[0]);
-		if (cnt[1]) atomicAdd(&counts[1], cnt[1]);
-	}
+	const unsigned long long mine[2] = {n_in, n_fl};
+	block_add_counts(mine, counts);
 }
 
 /* folds, the saved full data set and a hold-out in force belong to the data set that goes */
@@ -267,9 +213,8 @@ int mchip_cv_hold_out(mchip_context *ctx, int fold)
 		rc = install_saved(ctx, ctx->cv_full);
 	else
 		rc = install_derived(ctx, [&](uint8_t *d_out, uint8_t *d_seen) {
-			const size_t n = (size_t)ctx->I * ctx->L, blocks = (n + 255) / 256, cap = (size_t)1 << 20;
-			hipLaunchKernelGGL(k_cv_mask, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, ctx->stream, ctx->cv_full.d_raw,
-					   ctx->d_cv_fold, fold, ctx->I, ctx->L, ctx->ploidy, d_out, d_seen);
+			hipLaunchKernelGGL(k_cv_mask, dim3(nblk_capped((size_t)ctx->I * ctx->L, 256, (size_t)1 << 20)), dim3(256), 0, ctx->stream,
+					   ctx->cv_full.d_raw, ctx->d_cv_fold, fold, ctx->I, ctx->L, ctx->ploidy, d_out, d_seen);
 		});
 	if (rc) return rc;
 	ctx->s_cache_slot = -1;
@@ -282,13 +227,12 @@ int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor, double *
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
 	int rc = cv_check_data(ctx, 1);
-	if (rc) return rc;
-	if ((rc = check_slot(ctx, slot))) return rc;
-	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "cv: the held-out score is the admixture model's%s", nullptr);
+	if (rc || (rc = require_fit(ctx, slot, "cv: the held-out score is the admixture model's"))) return rc;
 	if (ctx->cv_fold < 0 || !ctx->cv_full.d_raw) return fail(ctx, MCHIP_ERR_STATE, "cv: no fold is held out%s", nullptr);
 	if (!(floor > 0.0 && floor <= 1.0)) return fail(ctx, MCHIP_ERR_INVALID, "cv: floor must be in (0, 1]%s", nullptr);
 	HIPCHK(hipSetDevice(ctx->device));
-	const cv_geometry g = cv_score_geometry(ctx->I, ctx->L, ctx->K, ctx->max_M, ctx->n_cu);
+	const lane_pass_geometry g = lane_pass_geometry_of(ctx->I, ctx->L, ctx->K, ctx->max_M, ctx->n_cu, CV_RED_BYTES, 64, CV_LDS_BUDGET);
+	if ((rc = check_lds(ctx, k_cv_score, g.lds, "cv: the kernel's static LDS has outgrown CV_LDS_BUDGET"))) return rc;
 	const size_t parts = (size_t)g.n_itiles * g.n_lchunks;
 	if (ctx->cv_part_cap < parts) {
 		dfree(ctx->d_cv_part);
@@ -298,7 +242,7 @@ int mchip_cv_heldout_loglik(mchip_context *ctx, int slot, double floor, double *
 	}
 	HIPCHK(hipMemsetAsync(ctx->d_cv_out, 0, 4 * sizeof(unsigned long long), ctx->stream));
 	hipLaunchKernelGGL(k_cv_score, dim3((unsigned)g.n_itiles, (unsigned)g.n_lchunks), dim3((unsigned)g.threads), g.lds, ctx->stream, ctx->I,
-			   ctx->L, ctx->ploidy, ctx->K, cv_ks(ctx->K), g.stage, g.lchunk, ctx->cv_full.d_raw, ctx->d_cv_fold, ctx->cv_fold, ctx->d_toff,
+			   ctx->L, ctx->ploidy, ctx->K, lds_pitch(ctx->K), g.stage, g.lchunk, ctx->cv_full.d_raw, ctx->d_cv_fold, ctx->cv_fold, ctx->d_toff,
 			   ctx->d_p[slot], ctx->d_q[slot], ctx->qstride, floor, ctx->d_cv_part, ctx->d_cv_out + 1);
 	HIPCHK(hipGetLastError());
 	launch_reduce_sum(ctx, ctx->d_cv_part, (int)parts, reinterpret_cast<double *>(ctx->d_cv_out));

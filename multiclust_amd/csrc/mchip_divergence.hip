@@ -6,17 +6,15 @@
  *   k_div_pairs   runtime K, one instance.  The K (K + 1) / 2 entries of the a <= b list are (a, a) -> h_a = sum_c p_a (1 - p_a) and
  *                 (a, b) -> s_ab = sum_c (p_a - p_b)^2 over the T columns.  A workgroup owns one chunk of DIV_CHUNK columns -- a
  *                 constant: the chunk, hence the order of every addition, does not depend on the device's compute units -- and
- *                 reads its part of the [T][K] slot once, DIV_STAGE columns at a time into LDS, rows K | 1 doubles apart.  Thread t
+ *                 reads its part of the [T][K] slot once, DIV_STAGE columns at a time into LDS, rows lds_pitch(K) apart.  Thread t
  *                 owns entries t, t + 256, ... (at most DIV_EPT = 9 at K = 64) in registers and walks the staged columns in column
- *                 order; one partial per entry and chunk, stored [entry][chunk].
- *   k_div_reduce  one workgroup per entry: the chunk partials in k_reduce_sum's order (thread t adds partials t, t + 256, ... in
- *                 that order, then the fixed tree over the 256 threads).
+ *                 order; one partial per entry and chunk, stored [entry][chunk]; launch_reduce_rows (mchip.hip) adds each entry's.
  *   k_div_loci    runtime K, lane = locus; the weights sit in LDS (every lane reads the same word: a broadcast).  The M_l K doubles
  *                 of a locus are contiguous from toff[l] K.  Per column: pbar = sum_k w_k p_k as an fma chain in k order, HT +=
  *                 pbar (1 - pbar), then the K values of the column once more (they are in the cache) for V += w_k (p_k - pbar)^2:
  *                 nothing is kept per allele, so 254 alleles run in the registers of 2.  V_l and HT_l go to [L] arrays; a
- *                 workgroup's 256 loci are added by a fixed tree in LDS (lane order = locus order), one partial of each per
- *                 workgroup, k_reduce_sum (mchip.hip) adds the partials.
+ *                 workgroup's 256 loci are added by block_tree_sum (lane order = locus order), one partial of each per
+ *                 workgroup, stored [2][workgroups]; launch_reduce_rows adds the two rows.
  *   No floating-point atomics anywhere: the same state gives the same bits, on any device and under any geometry knob.
  *   Timed once and not tuned (profiles/divergence.txt, scripts/divergence_bench.py): it runs once per K of a run.
  */
@@ -28,8 +26,6 @@ constexpr int DIV_CHUNK = 1024;		/* columns per workgroup of the pair kernel (te
 constexpr int DIV_STAGE = 64;		/* of which this many are in LDS at a time: 64 (64 | 1) doubles = 33 KB at K = 64 */
 constexpr int DIV_THREADS = 256;
 constexpr int DIV_EPT = (MCHIP_MAX_K * (MCHIP_MAX_K + 1) / 2 + DIV_THREADS - 1) / DIV_THREADS;	/* entries per thread: 9 */
-
-static inline int div_ks(int K) { return K | 1; }
 
 /* P: a slot's [T][K].  part[e * n_chunks + chunk]: the chunk's partial of entry e of the a <= b list (row a: b = a .. K - 1). */
 __global__ __launch_bounds__(DIV_THREADS) void k_div_pairs(int T, int K, int KS, int n_pairs, const double *__restrict__ P,
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(DIV_THREADS) void k_div_pairs(int T, int K, int KS,
 	for (int c0 = cbeg; c0 < cend; c0 += DIV_STAGE) {
 		const int ncols = min(DIV_STAGE, cend - c0);
 		__syncthreads();	/* everybody is done with the columns staged before */
-		for (int x = tid; x < ncols * K; x += DIV_THREADS) div_lds[(x / K) * KS + x % K] = P[(size_t)c0 * K + x];
+		stage_rows(div_lds, KS, P + (size_t)c0 * K, ncols, K, tid, DIV_THREADS);
 		__syncthreads();
 #pragma unroll
 		for (int j = 0; j < DIV_EPT; j++) {
@@ -83,31 +79,13 @@ __global__ __launch_bounds__(DIV_THREADS) void k_div_pairs(int T, int K, int KS,
 	}
 }
 
-/* out[e] = part[e][0] + ... + part[e][n - 1]: block e is k_reduce_sum (mchip.hip) on its row -- thread t adds t, t + 256, ... in
- * that order, then the same tree */
-__global__ __launch_bounds__(DIV_THREADS) void k_div_reduce(const double *__restrict__ part, int n, double *__restrict__ out)
-{
-	__shared__ double red[DIV_THREADS];
-	const int tid = threadIdx.x;
-	const double *in = part + (size_t)blockIdx.x * n;
-	double s = 0.0;
-	for (int x = tid; x < n; x += DIV_THREADS) s += in[x];
-	red[tid] = s;
-	__syncthreads();
-	for (int w = DIV_THREADS >> 1; w > 0; w >>= 1) {
-		if (tid < w) red[tid] += red[tid + w];
-		__syncthreads();
-	}
-	if (tid == 0) out[blockIdx.x] = red[0];
-}
-
 /* w: the K weights.  lv / lht [L]: V_l and HT_l (0 for a locus without a column).  part_v / part_ht: one partial per workgroup. */
 __global__ __launch_bounds__(DIV_THREADS) void k_div_loci(int L, int K, const int32_t *__restrict__ toff, const double *__restrict__ P,
 							  const double *__restrict__ w, double *__restrict__ lv, double *__restrict__ lht,
 							  double *__restrict__ part_v, double *__restrict__ part_ht)
 {
 	__shared__ double ws[MCHIP_MAX_K];
-	__shared__ double red_v[DIV_THREADS], red_ht[DIV_THREADS];
+	__shared__ double red[2][DIV_THREADS];
 	const int tid = threadIdx.x, l = blockIdx.x * DIV_THREADS + tid;
 	if (tid < K) ws[tid] = w[tid];
 	__syncthreads();
@@ -127,19 +105,11 @@ __global__ __launch_bounds__(DIV_THREADS) void k_div_loci(int L, int K, const in
 		lv[l] = V;
 		lht[l] = HT;
 	}
-	red_v[tid] = V;
-	red_ht[tid] = HT;
-	__syncthreads();
-	for (int x = DIV_THREADS >> 1; x > 0; x >>= 1) {
-		if (tid < x) {
-			red_v[tid] += red_v[tid + x];
-			red_ht[tid] += red_ht[tid + x];
-		}
-		__syncthreads();
-	}
+	const double mine[2] = {V, HT};
+	block_tree_sum<DIV_THREADS>(red[0], DIV_THREADS, mine);
 	if (tid == 0) {
-		part_v[blockIdx.x] = red_v[0];
-		part_ht[blockIdx.x] = red_ht[0];
+		part_v[blockIdx.x] = red[0][0];
+		part_ht[blockIdx.x] = red[1][0];
 	}
 }
 
@@ -148,8 +118,7 @@ extern "C" int mchip_divergence(mchip_context *ctx, int slot, const double *weig
 {
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
-	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
-	int rc = check_slot(ctx, slot);
+	const int rc = require_fit(ctx, slot, nullptr);	/* (both models) */
 	if (rc) return rc;
 	if (!weights || !het || !sqdiff || !sum_v || !sum_ht || !n_loci) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
 	const int L = ctx->L, T = ctx->T, K = ctx->K;
@@ -162,7 +131,7 @@ extern "C" int mchip_divergence(mchip_context *ctx, int slot, const double *weig
 	if (!(wsum > 0.0)) return fail(ctx, MCHIP_ERR_INVALID, "divergence: every weight is zero%s", nullptr);
 	HIPCHK(hipSetDevice(ctx->device));
 	const int n_pairs = K * (K + 1) / 2, n_chunks = (T + DIV_CHUNK - 1) / DIV_CHUNK, n_lblocks = (L + DIV_THREADS - 1) / DIV_THREADS;
-	const size_t lds = (size_t)DIV_STAGE * div_ks(K) * sizeof(double);
+	const size_t lds = (size_t)DIV_STAGE * lds_pitch(K) * sizeof(double);
 	scoped_dev<double> d_w, d_part, d_pair, d_lv, d_lht, d_lpart, d_sums;
 	HIPCHK(d_w.alloc((size_t)K));
 	HIPCHK(d_part.alloc((size_t)n_pairs * n_chunks));
@@ -172,17 +141,15 @@ extern "C" int mchip_divergence(mchip_context *ctx, int slot, const double *weig
 	HIPCHK(d_lpart.alloc(2 * (size_t)n_lblocks));
 	HIPCHK(d_sums.alloc(2));
 	HIPCHK(hipMemcpyAsync(d_w.p, weights, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	hipLaunchKernelGGL(k_div_pairs, dim3((unsigned)n_chunks), dim3(DIV_THREADS), lds, ctx->stream, T, K, div_ks(K), n_pairs, ctx->d_p[slot],
+	hipLaunchKernelGGL(k_div_pairs, dim3((unsigned)n_chunks), dim3(DIV_THREADS), lds, ctx->stream, T, K, lds_pitch(K), n_pairs, ctx->d_p[slot],
 			   d_part.p);
 	HIPCHK(hipGetLastError());
-	hipLaunchKernelGGL(k_div_reduce, dim3((unsigned)n_pairs), dim3(DIV_THREADS), 0, ctx->stream, d_part.p, n_chunks, d_pair.p);
+	launch_reduce_rows(ctx, d_part.p, n_pairs, n_chunks, d_pair.p);
 	HIPCHK(hipGetLastError());
 	hipLaunchKernelGGL(k_div_loci, dim3((unsigned)n_lblocks), dim3(DIV_THREADS), 0, ctx->stream, L, K, ctx->d_toff, ctx->d_p[slot], d_w.p,
 			   d_lv.p, d_lht.p, d_lpart.p, d_lpart.p + n_lblocks);
 	HIPCHK(hipGetLastError());
-	launch_reduce_sum(ctx, d_lpart.p, n_lblocks, d_sums.p);
-	HIPCHK(hipGetLastError());
-	launch_reduce_sum(ctx, d_lpart.p + n_lblocks, n_lblocks, d_sums.p + 1);
+	launch_reduce_rows(ctx, d_lpart.p, 2, n_lblocks, d_sums.p);
 	HIPCHK(hipGetLastError());
 	std::vector<double> h_pair((size_t)n_pairs);
 	double h_sums[2];

@@ -6,56 +6,25 @@
  *              lane's 8 loci of a block are the 8 * ploidy contiguous bytes of its gtS group, read as `ploidy` aligned 64-bit
  *              words; consecutive lanes read consecutive groups.  A word without a 0xFF byte costs one compare, and a block in
  *              which no lane of the workgroup has a missing copy is left after one vote (it stages nothing).  The q rows sit in
- *              LDS, K | 1 doubles apart (k_cv_score's reasoning: 32 lanes, 32 bank pairs); the P rows of the block of 8 loci are
- *              staged per workgroup as they lie in the slot's [T][K] form when they fit beside the q rows, and read from memory
- *              when a data set has so many alleles per locus that they do not.
+ *              LDS, lds_pitch(K) apart (mchip_device_util.h); the P rows of the block of 8 loci are staged per workgroup when they
+ *              fit beside the q rows and read from memory when they do not (lane_pass_geometry_of, mchip_feature_geometry.h).
  *              A genotype with r missing copies: t_m = sum_k q_k p_klm by an fma chain in k order over the first n_real[l]
  *              slots; copy j = 1 .. r goes to the first m with the largest t_m / (c_m + 1), c_m the copies given to m so far
  *              (the t_m are computed again for every copy: nothing is kept per candidate, so any number of alleles runs in the
  *              same registers).  The picks are kept in ascending order in a per-lane array of `ploidy` bytes of private
  *              memory and stored into the missing positions of the upload-form scratch in copy order; the observed bytes of the
  *              scratch are never written.  c = prod_j j t_mj / ((c_mj + 1) sum_m t_m).
- *              sum_conf: a lane adds its c in locus order; the workgroup's lanes are added by a fixed tree in LDS; one partial per
- *              workgroup, k_reduce_sum (mchip.hip) adds the partials.  No floating-point atomics: the same state gives the same
- *              bits.  The three counts are integers and go through atomics.
+ *              sum_conf: a lane adds its c in locus order; the workgroup's lanes by block_tree_sum; one partial per workgroup,
+ *              k_reduce_sum (mchip.hip) adds the partials.  The three counts are integers: block_add_counts.
  *              Not yet timed on a device and not tuned (profiles/impute.txt, scripts/impute_bench.py).
  */
 #include "mchip_context.h"
 
-constexpr int IMP_LBLOCK = 8;				/* loci per gtS group and per staged block */
+constexpr int IMP_LBLOCK = LANE_PASS_LBLOCK;		/* loci per gtS group and per staged block */
 constexpr size_t IMP_LDS_BUDGET = 64 * 1024 - 512;	/* dynamic LDS per workgroup (the kernel has 288 static bytes beside it: its
 							 * counts and the scratch of the workgroup vote; checked at the launch) */
+constexpr size_t IMP_RED_BYTES = 256 * sizeof(double);	/* the tree's space */
 constexpr int IMP_MAX_PL = 64;				/* set_shape's limit on the ploidy */
-
-/* geometry of the pass: lanes per workgroup, whether the P rows of a block are staged, locus chunks (whole blocks of 8) */
-struct imp_geometry {
-	int threads, stage, lchunk, n_lchunks, n_itiles;
-	size_t lds;
-};
-static inline int imp_ks(int K) { return K | 1; }
-static imp_geometry impute_geometry(int I, int L, int K, int max_M, int n_cu)
-{
-	imp_geometry g;
-	const size_t ks = (size_t)imp_ks(K), red = 256 * sizeof(double);
-	const size_t ptile = (size_t)IMP_LBLOCK * (size_t)max_M * ks * sizeof(double);
-	/* the most lanes whose q rows leave room for the P tile; when no workgroup size does, the most lanes that fit alone */
-	g.threads = 0;
-	for (int t = 256; t >= 64 && !g.threads; t >>= 1)
-		if ((size_t)t * ks * sizeof(double) + red + ptile <= IMP_LDS_BUDGET) g.threads = t;
-	g.stage = g.threads ? 1 : 0;
-	for (int t = 256; t >= 64 && !g.threads; t >>= 1)
-		if ((size_t)t * ks * sizeof(double) + red <= IMP_LDS_BUDGET) g.threads = t;	/* (64 lanes at K = 64: 35 KB) */
-	g.lds = (size_t)g.threads * ks * sizeof(double) + red + (g.stage ? ptile : 0);
-	g.n_itiles = (I + g.threads - 1) / g.threads;
-	const int lblocks = (L + IMP_LBLOCK - 1) / IMP_LBLOCK;
-	int want = (16 * (n_cu > 0 ? n_cu : 256) + g.n_itiles - 1) / g.n_itiles;
-	if (want > lblocks) want = lblocks;
-	if (want > 65535) want = 65535;
-	if (want < 1) want = 1;
-	g.lchunk = ((lblocks + want - 1) / want) * IMP_LBLOCK;
-	g.n_lchunks = (L + g.lchunk - 1) / g.lchunk;
-	return g;
-}
 
 /* non-zero iff a byte of v is 0xFF */
 __device__ __forceinline__ uint64_t imp_has_missing(uint64_t v)
@@ -88,12 +57,7 @@ __global__ __launch_bounds__(256) void k_impute(int I, int L, int pl, int K, int
 	const int nthr = blockDim.x, tid = threadIdx.x;
 	const int i0 = blockIdx.x * nthr, i = i0 + tid;
 	const int lbeg = blockIdx.y * lchunk, lend = min(L, lbeg + lchunk);
-	if (qstride) {
-		const int rows = min(nthr, I - i0);
-		for (int x = tid; x < rows * K; x += nthr) qs[(x / K) * KS + x % K] = Q[(size_t)i0 * K + x];
-	} else {
-		for (int x = tid; x < nthr * K; x += nthr) qs[(x / K) * KS + x % K] = Q[x % K];
-	}
+	stage_q_rows(qs, KS, Q, qstride, i0, I, K, tid, nthr);
 	const double *q = qs + (size_t)tid * KS;
 	const bool live = i < I;
 	const size_t grp = (size_t)IMP_LBLOCK * pl;
@@ -112,8 +76,7 @@ __global__ __launch_bounds__(256) void k_impute(int I, int L, int pl, int K, int
 		if (!__syncthreads_or(any != 0)) continue;	/* also: everybody is done with the tile of the block before */
 		const int c0 = toff[l0];	/* (toff is padded: offsets behind the last locus are T) */
 		if (stage) {
-			const int ncols = toff[min(L, l0 + IMP_LBLOCK)] - c0;
-			for (int x = tid; x < ncols * K; x += nthr) ps[(x / K) * KS + x % K] = P[(size_t)c0 * K + x];
+			stage_rows(ps, KS, P + (size_t)c0 * K, toff[min(L, l0 + IMP_LBLOCK)] - c0, K, tid, nthr);
 			__syncthreads();
 		}
 		if (!any) continue;
@@ -174,25 +137,10 @@ __global__ __launch_bounds__(256) void k_impute(int I, int L, int pl, int K, int
 			n_geno++;
 		}
 	}
-	/* the workgroup's lanes in a fixed tree */
-	red[tid] = sum;
-	__syncthreads();
-	for (int w = nthr >> 1; w > 0; w >>= 1) {
-		if (tid < w) red[tid] += red[tid + w];
-		__syncthreads();
-	}
+	block_tree_sum(red, sum);
 	if (tid == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
-	/* counts: integers, order does not matter */
-	__shared__ unsigned long long cnt[3];
-	if (tid == 0) cnt[0] = cnt[1] = cnt[2] = 0;
-	__syncthreads();
-	if (n_fill) atomicAdd(&cnt[0], n_fill);
-	if (n_left) atomicAdd(&cnt[1], n_left);
-	if (n_geno) atomicAdd(&cnt[2], n_geno);
-	__syncthreads();
-	if (tid == 0)
-		for (int x = 0; x < 3; x++)
-			if (cnt[x]) atomicAdd(&counts[x], cnt[x]);
+	const unsigned long long mine[3] = {n_fill, n_left, n_geno};
+	block_add_counts(mine, counts);
 }
 
 extern "C" int mchip_impute_missing(mchip_context *ctx, int slot, const int32_t *n_real, uint8_t *geno_out, double *conf_out,
@@ -200,21 +148,17 @@ extern "C" int mchip_impute_missing(mchip_context *ctx, int slot, const int32_t 
 {
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
-	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
-	int rc = check_slot(ctx, slot);
+	int rc = require_fit(ctx, slot, "impute: the predictive distribution used is the admixture model's");
 	if (rc) return rc;
-	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "impute: the predictive distribution used is the admixture model's%s", nullptr);
 	if (!n_real || !geno_out) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
 	const int I = ctx->I, L = ctx->L, pl = ctx->ploidy, K = ctx->K;
 	for (int l = 0; l < L; l++)
 		if (n_real[l] < 0 || n_real[l] > ctx->h_ua[(size_t)l])
 			return fail(ctx, MCHIP_ERR_INVALID, "impute: n_real[l] outside [0, uniquealleles[l]]%s", nullptr);
 	HIPCHK(hipSetDevice(ctx->device));
-	const imp_geometry g = impute_geometry(I, L, K, ctx->max_M, ctx->n_cu);
+	const lane_pass_geometry g = lane_pass_geometry_of(I, L, K, ctx->max_M, ctx->n_cu, IMP_RED_BYTES, 64, IMP_LDS_BUDGET);
 	const size_t parts = (size_t)g.n_itiles * g.n_lchunks, n_geno = (size_t)I * L;
-	hipFuncAttributes attr;
-	HIPCHK(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(k_impute)));
-	if (attr.sharedSizeBytes + g.lds > 64 * 1024) return fail(ctx, MCHIP_ERR_STATE, "impute: the kernel's static LDS has outgrown IMP_LDS_BUDGET%s", nullptr);
+	if ((rc = check_lds(ctx, k_impute, g.lds, "impute: the kernel's static LDS has outgrown IMP_LDS_BUDGET"))) return rc;
 	/* the installed data set in upload form: the kernel stores the filled bytes into it */
 	saved_set scratch;
 	if ((rc = save_installed(ctx, scratch))) return rc;
@@ -235,7 +179,7 @@ extern "C" int mchip_impute_missing(mchip_context *ctx, int slot, const int32_t 
 	HIPCHK(hipMemcpyAsync(d_nreal.p, n_real, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(hipMemsetAsync(d_out.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
 	hipLaunchKernelGGL(k_impute, dim3((unsigned)g.n_itiles, (unsigned)g.n_lchunks), dim3((unsigned)g.threads), g.lds, ctx->stream, I, L, pl, K,
-			   imp_ks(K), g.stage, g.lchunk, ctx->d_gtS, ctx->d_toff, d_nreal.p, ctx->d_p[slot], ctx->d_q[slot], ctx->qstride,
+			   lds_pitch(K), g.stage, g.lchunk, ctx->d_gtS, ctx->d_toff, d_nreal.p, ctx->d_p[slot], ctx->d_q[slot], ctx->qstride,
 			   scratch.d_raw, d_conf.p, d_part.p, d_out.p + 1);
 	HIPCHK(hipGetLastError());
 	launch_reduce_sum(ctx, d_part.p, (int)parts, reinterpret_cast<double *>(d_out.p));

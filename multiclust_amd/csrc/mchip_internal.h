@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <vector>
 #include "multiclust_hip.h"
+#include "mchip_device_util.h"
 
 #define MCHIP_BLOCK 256
 #define MCHIP_SPARSE_MAX_M 32	/* sparse individual pass is used when no locus has more alleles than this */

@@ -149,18 +149,6 @@ template <> struct geno_group<0> {	/* any ploidy: byte loads */
 	int stride_pl;
 };
 
-template <int NT> __device__ __forceinline__ double block_sum(double v, double *red)
-{
-	const int tid = threadIdx.x;
-	red[tid] = v;
-	__syncthreads();
-	for (int s = NT / 2; s > 0; s >>= 1) {
-		if (tid < s) red[tid] += red[tid + s];
-		__syncthreads();
-	}
-	return red[0];
-}
-
 /* ---------------------------------------------------------------- column pass */
 /* SAFE = false: the log-product is checked once per `flush_blocks` blocks of 8 individuals (host guarantees that
  * 8*ploidy*flush_blocks multiplications cannot underflow a product that starts above 1e-100);
@@ -252,7 +240,7 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_column_pass(mchip_pass_args a)
 	}
 	if (LL) {
 		ll += log(prod);
-		const double tot = block_sum<MCHIP_BLOCK>(ll, red);
+		const double tot = block_tree_sum<MCHIP_BLOCK>(red, ll);
 		if (threadIdx.x == 0) a.llpart[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
 	}
 }
@@ -898,12 +886,12 @@ __global__ __launch_bounds__(QBLOCK, sparse_min_waves(PL, ACCUM)) void k_individ
 			if (SPLIT == 1 || k0 + k < K) out[k] = acc[k];
 	}
 	/* every lane of an individual carries the same log-product: part 0 speaks for it */
-	const double tot = block_sum<QBLOCK>((active && part == 0) ? ll : 0.0, red);
+	const double tot = block_tree_sum<QBLOCK>(red, (active && part == 0) ? ll : 0.0);
 	if (threadIdx.x == 0) a.llpart[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
 	if (DUAL) {
 		const double ll2 = (double)ex2 * 0.693147180559945309417 + log(prod2);
 		__syncthreads();	/* red[] is read by thread 0 above */
-		const double tot2 = block_sum<QBLOCK>(active ? ll2 : 0.0, red);
+		const double tot2 = block_tree_sum<QBLOCK>(red, active ? ll2 : 0.0);
 		if (threadIdx.x == 0) a.llpart2[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot2;
 	}
 }
@@ -1567,7 +1555,7 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_mix_finalize(int I, int n_lchun
 			}
 		}
 	}
-	const double tot = block_sum<MCHIP_BLOCK>(ll, red);
+	const double tot = block_tree_sum<MCHIP_BLOCK>(red, ll);
 	if (threadIdx.x == 0) llpart[blockIdx.x] = tot;
 }
 

@@ -171,10 +171,8 @@ extern "C" int mchip_fit_q_rows(mchip_context *ctx, int slot, const int32_t *row
 {
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
-	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
-	int rc = check_slot(ctx, slot);
+	const int rc = require_fit(ctx, slot, "fit_q_rows: the mixture model has no mixing proportions per individual");
 	if (rc) return rc;
-	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixture model has no mixing proportions per individual%s", nullptr);
 	if (!ctx->qstride) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "fit_q_rows: the mixing proportions are shared by all individuals%s", nullptr);
 	if (!rows || !q_rows || !loglik_rows || !iter_rows || !converged_rows) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
 	if (n_rows < 1 || n_rows > ctx->I) return fail(ctx, MCHIP_ERR_INVALID, "fit_q_rows: n_rows must be in [1, I]%s", nullptr);
@@ -203,11 +201,8 @@ extern "C" int mchip_fit_q_rows(mchip_context *ctx, int slot, const int32_t *row
 	HIPCHK(hipMemcpyAsync(d_rows.p, rows, nr * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
 	/* the full data set: the saved one while a fold is held out of the installed one */
 	const bool saved = ctx->cv_fold >= 0 && ctx->cv_full.d_raw;
-	{
-		const size_t n = nr * L * pl, blocks = (n + 255) / 256, cap = (size_t)1 << 20;
-		hipLaunchKernelGGL(k_query_gather, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, ctx->stream,
-				   saved ? ctx->cv_full.d_raw : ctx->d_gtA, saved ? 1 : 0, d_rows.p, n_rows, L, pl, d_geno.p);
-	}
+	hipLaunchKernelGGL(k_query_gather, dim3(nblk_capped(nr * L * pl, 256, (size_t)1 << 20)), dim3(256), 0, ctx->stream,
+			   saved ? ctx->cv_full.d_raw : ctx->d_gtA, saved ? 1 : 0, d_rows.p, n_rows, L, pl, d_geno.p);
 	HIPCHK(hipGetLastError());
 	const double *Q0 = from_slot ? ctx->d_q[slot] : nullptr;
 #define FQR_LAUNCH(KB)                                                                                                                   \

@@ -49,10 +49,8 @@ static int install_selection(mchip_context *ctx, const int32_t *src, int L2)
 	return install_derived(ctx, [&](uint8_t *d_out, uint8_t *d_seen) {
 		const unsigned chunks = (unsigned)((L2 + RS_CHUNK - 1) / RS_CHUNK);
 		/* enough workgroups to fill the device many times over, each staging its indices for several individuals */
-		unsigned rows = (unsigned)ctx->I;
 		const unsigned want = (65536u + chunks - 1) / chunks;
-		if (rows > want) rows = want;
-		if (rows > 65535u) rows = 65535u;
+		const unsigned rows = nblk_capped((size_t)ctx->I, 1, want < 65535u ? want : 65535u);
 		hipLaunchKernelGGL(k_resample_gather, dim3(chunks, rows), dim3(256), 0, ctx->stream, ctx->rs_base.d_raw, d_src.p, ctx->I,
 				   ctx->rs_base.L, L2, ctx->ploidy, d_out, d_seen);
 	});

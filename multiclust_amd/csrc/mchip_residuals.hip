@@ -9,8 +9,8 @@
  *
  *   k_resid_tile   runtime K, one instance.  Lane = individual, as k_impute: a workgroup takes one block of 8 loci (the part of it
  *                  that lies in the chunk) and a tile of individuals; a lane reads its gtS group as aligned 64-bit words.  The q
- *                  rows sit in LDS K | 1 doubles apart, the P rows of the block are staged as they lie in the slot's [T][K] form
- *                  when they fit beside the q rows and read from memory when they do not (impute_geometry's reasoning).  Per
+ *                  rows sit in LDS lds_pitch(K) apart (mchip_device_util.h), the P rows of the block are staged when they fit
+ *                  beside the q rows and read from memory when they do not (lane_pass_geometry_of, mchip_feature_geometry.h).  Per
  *                  locus: a = observed copies; per column t = sum_k q_k p_k by an fma chain in k order, r = fma(-a, t, n) (0 where
  *                  a = 0), s = fma(r, r, s) in m order.  Written as doubles, individual-contiguous: R [chunk column][Ipad], S and
  *                  O [chunk locus][Ipad]; Ipad = I rounded up to RES_TILE, the lanes behind I write zeros, so the product kernel
@@ -42,7 +42,7 @@
 #include <vector>
 
 constexpr int RES_CHUNK = 512;		/* columns, and loci, per chunk at most (tests/test_gpu_resid.py restates it); > 255 = the most columns of a locus */
-constexpr int RES_LBLOCK = 8;		/* loci per gtS group */
+constexpr int RES_LBLOCK = LANE_PASS_LBLOCK;	/* loci per gtS group */
 constexpr int RES_TILE = 64;		/* individuals per side of a workgroup's tile of G; I is padded to it */
 constexpr int RES_DEPTH = 16;		/* rows of the operand panels in LDS at a time */
 constexpr int RES_PITCH = RES_TILE + 16;	/* doubles between two staged rows: the two rows a half wave reads (k and k + 1, 16 doubles each)
@@ -50,29 +50,6 @@ constexpr int RES_PITCH = RES_TILE + 16;	/* doubles between two staged rows: the
 constexpr size_t RES_LDS_BUDGET = 64 * 1024 - 512;	/* dynamic LDS of k_resid_tile (checked with its static LDS at the launch) */
 
 typedef double res_d4 __attribute__((ext_vector_type(4)));
-
-static inline int res_ks(int K) { return K | 1; }
-
-/* geometry of k_resid_tile: lanes per workgroup (a divisor of 256, at least RES_TILE), whether the P rows of a block are staged */
-struct res_geometry {
-	int threads, stage;
-	size_t lds;
-};
-static res_geometry resid_geometry(int K, int max_M)
-{
-	res_geometry g;
-	const size_t ks = (size_t)res_ks(K);
-	const size_t ptile = (size_t)RES_LBLOCK * (size_t)max_M * ks * sizeof(double);
-	/* the most lanes whose q rows leave room for the P tile; when no workgroup size does, the most lanes that fit alone */
-	g.threads = 0;
-	for (int t = 256; t >= RES_TILE && !g.threads; t >>= 1)
-		if ((size_t)t * ks * sizeof(double) + ptile <= RES_LDS_BUDGET) g.threads = t;
-	g.stage = g.threads ? 1 : 0;
-	for (int t = 256; t >= RES_TILE && !g.threads; t >>= 1)
-		if ((size_t)t * ks * sizeof(double) <= RES_LDS_BUDGET) g.threads = t;	/* (64 lanes at K = 64: 33 KB) */
-	g.lds = (size_t)g.threads * ks * sizeof(double) + (g.stage ? ptile : 0);
-	return g;
-}
 
 /* byte x of a gtS group held as aligned 64-bit words */
 __device__ __forceinline__ unsigned res_byte(const uint64_t *__restrict__ gw, int x)
@@ -96,16 +73,8 @@ __global__ __launch_bounds__(256) void k_resid_tile(int I, int Ipad, int L, int 
 	const int l0 = (lbeg / RES_LBLOCK + (int)blockIdx.y) * RES_LBLOCK;
 	const int jbeg = max(l0, lbeg), jend = min(l0 + RES_LBLOCK, lend);	/* (jbeg < jend: the grid covers the chunk's blocks only) */
 	const int cbeg = toff[lbeg], c0 = toff[jbeg];
-	if (qstride) {
-		const int rows = max(0, min(nthr, I - i0));
-		for (int x = tid; x < rows * K; x += nthr) qs[(x / K) * KS + x % K] = Q[(size_t)i0 * K + x];
-	} else {
-		for (int x = tid; x < nthr * K; x += nthr) qs[(x / K) * KS + x % K] = Q[x % K];
-	}
-	if (stage) {
-		const int ncols = toff[jend] - c0;
-		for (int x = tid; x < ncols * K; x += nthr) ps[(x / K) * KS + x % K] = P[(size_t)c0 * K + x];
-	}
+	stage_q_rows(qs, KS, Q, qstride, i0, I, K, tid, nthr);
+	if (stage) stage_rows(ps, KS, P + (size_t)c0 * K, toff[jend] - c0, K, tid, nthr);
 	__syncthreads();
 	if (i >= Ipad) return;
 	const bool live = i < I;
@@ -217,19 +186,16 @@ extern "C" int mchip_residual_products(mchip_context *ctx, int slot, double *gra
 {
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
-	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
-	int rc = check_slot(ctx, slot);
+	int rc = require_fit(ctx, slot, "residuals: the prediction used is the admixture model's");
 	if (rc) return rc;
-	if (!ctx->admixture) return fail(ctx, MCHIP_ERR_UNSUPPORTED, "residuals: the prediction used is the admixture model's%s", nullptr);
 	if (!gram) return fail(ctx, MCHIP_ERR_INVALID, "null pointer%s", nullptr);
 	const int I = ctx->I, L = ctx->L, pl = ctx->ploidy, K = ctx->K;
 	const int Ipad = (I + RES_TILE - 1) / RES_TILE * RES_TILE, nt = Ipad / RES_TILE;
 	const size_t n2 = (size_t)Ipad * Ipad;
 	HIPCHK(hipSetDevice(ctx->device));
-	const res_geometry g = resid_geometry(K, ctx->max_M);
-	hipFuncAttributes attr;
-	HIPCHK(hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(k_resid_tile)));
-	if (attr.sharedSizeBytes + g.lds > 64 * 1024) return fail(ctx, MCHIP_ERR_STATE, "residuals: the kernel's static LDS has outgrown RES_LDS_BUDGET%s", nullptr);
+	/* lanes per workgroup: a divisor of 256, at least RES_TILE; no reduction space; the blocks of a chunk are the grid's, not the geometry's */
+	const lane_pass_geometry g = lane_pass_geometry_of(Ipad, L, K, ctx->max_M, ctx->n_cu, 0, RES_TILE, RES_LDS_BUDGET);
+	if ((rc = check_lds(ctx, k_resid_tile, g.lds, "residuals: the kernel's static LDS has outgrown RES_LDS_BUDGET"))) return rc;
 	/* the chunks: whole loci, greedily, at most RES_CHUNK columns and RES_CHUNK loci each */
 	std::vector<int> cut(1, 0), width;	/* chunk ch: loci cut[ch] .. cut[ch + 1] - 1, width[ch] columns */
 	int cols = 0;
@@ -253,12 +219,11 @@ extern "C" int mchip_residual_products(mchip_context *ctx, int slot, double *gra
 	}
 	HIPCHK(hipMemsetAsync(d_G.p, 0, n2 * sizeof(double), ctx->stream));
 	if (d_by_product) HIPCHK(hipMemsetAsync(d_D.p, 0, n2 * sizeof(double), ctx->stream));
-	const unsigned n_itiles = (unsigned)((Ipad + g.threads - 1) / g.threads);
 	for (size_t ch = 0; ch + 1 < cut.size(); ch++) {
 		const int lbeg = cut[ch], lend = cut[ch + 1];
 		const int ncols = width[ch];
 		const unsigned nblocks = (unsigned)((lend - 1) / RES_LBLOCK - lbeg / RES_LBLOCK + 1);
-		hipLaunchKernelGGL(k_resid_tile, dim3(n_itiles, nblocks), dim3((unsigned)g.threads), g.lds, ctx->stream, I, Ipad, L, pl, K, res_ks(K),
+		hipLaunchKernelGGL(k_resid_tile, dim3((unsigned)g.n_itiles, nblocks), dim3((unsigned)g.threads), g.lds, ctx->stream, I, Ipad, L, pl, K, lds_pitch(K),
 				   g.stage, lbeg, lend, ctx->d_gtS, ctx->d_toff, ctx->d_p[slot], ctx->d_q[slot], ctx->qstride, d_R.p, d_S.p, d_O.p);
 		HIPCHK(hipGetLastError());
 		if (ncols) {

@@ -8,8 +8,10 @@ import numpy as np
 import pytest
 
 import cv_util as cu
+import impute_util as iu
 import oracle_bind as ob
 import rand_window as rw
+from feature_geometry import EDGES
 from multiclust_amd import hip, host
 from synth import make_dataset, random_params
 
@@ -237,6 +239,29 @@ def test_heldout_score(I, L, pl, contexts):
                     if f == 0:       # floor = 1: q rows sum to one and every p is below one, so every term is floored: log 1
                         assert ctx.cv_heldout_loglik(0, 1.0) == (0.0, got[1], got[1]), label
         ctx.cv_hold_out(-1)
+
+
+@pytest.mark.parametrize("K,alleles", sorted(EDGES))
+def test_heldout_score_on_either_side_of_every_edge(K, alleles, contexts):
+    """k_cv_score takes its lanes and its staging from the geometry k_impute has (lane_pass_geometry_of; tests/feature_geometry.py):
+    the (K, alleles) pairs on either side of every edge of it, with a second, partial tile of individuals at every workgroup size
+    (I = 257) and a partial block of 8 loci (L = 9)"""
+    ctx = contexts[0]
+    I, L, pl, F = 257, 9, 2, 5
+    ua, _, geno = iu.impute_dataset(I, L, pl, alleles, 0.05, seed=K + alleles, specials=False)
+    assert int(ua.max()) == alleles + 1
+    ctx.set_genotypes(ua, geno)
+    folds = forced_folds(windows()["first"], geno, F)
+    ctx.cv_set_folds(folds, F)
+    q0, p0 = random_params(I, ua, K, seed=K)
+    for f in range(F):
+        ctx.cv_hold_out(f)
+        ctx.set_model(K, admixture=1)
+        ctx.set_q(0, q0)
+        ctx.set_p(0, p0)
+        got = check_score(ctx, ua, geno, folds, f, q0, p0, K, 1.0 / (I * pl + 1), "edge K%d alleles%d f%d" % (K, alleles, f))
+        assert got[1] > 0
+    ctx.cv_hold_out(-1)
 
 
 def test_floor_one_scores_exactly_zero(contexts):

@@ -1,12 +1,13 @@
 """-m gpu: mchip_impute_missing (multiclust_amd/csrc/mchip_impute.hip) against the numpy form of its rule (tests/impute_util.py).
 
-The edges of the kernel as built (impute_geometry): a workgroup has 256, 128 or 64 lanes -- the most whose q rows (K | 1 doubles
-each) fit into 64 KiB - 512 of LDS beside 2 KiB of reduction space and the staged P rows of a block of 8 loci (8 max_M (K | 1)
-doubles) -- and when not even 64 lanes leave room for the P rows, they are read from memory.  With max_M = 3 (two alleles and the
-phantom slot) K = 27 | 28 is the edge between 256 and 128 lanes and K = 51 | 52 the one between 128 and 64; with max_M = 5 they are
-K = 25 | 26 and 45 | 46; at K = 64 the rows are staged up to max_M = 7 and read from memory from max_M = 8 on (35 alleles
-included).  EDGES has a case on either side of each, and geometry() below restates the arithmetic so that a case that no longer
-sits where it is meant to fails.  A workgroup walks several blocks of 8 loci (and reuses its staged rows) only when there are more
+The edges of the kernel as built (lane_pass_geometry_of): a workgroup has 256, 128 or 64 lanes -- the most whose q rows (K | 1
+doubles each) fit into 64 KiB - 512 of LDS beside 2 KiB of reduction space and the staged P rows of a block of 8 loci (8 max_M
+(K | 1) doubles) -- and when not even 64 lanes leave room for the P rows, they are read from memory.  With max_M = 3 (two alleles
+and the phantom slot) K = 27 | 28 is the edge between 256 and 128 lanes and K = 51 | 52 the one between 128 and 64; with max_M = 5
+they are K = 25 | 26 and 45 | 46; at K = 64 the rows are staged up to max_M = 7 and read from memory from max_M = 8 on (35 alleles
+included).  EDGES has a case on either side of each, and geometry() (tests/feature_geometry.py, held against the C++ by
+test_feature_geometry_cpu.py) restates the arithmetic so that a case that no longer sits where it is meant to fails.
+A workgroup walks several blocks of 8 loci (and reuses its staged rows) only when there are more
 blocks than 16 x compute units / individual tiles: the LONG case.  A block of 8 loci is partial at L = 1, 7, 9 and 130."""
 import ctypes as C
 import math
@@ -16,6 +17,7 @@ import pytest
 
 import cv_util as cu
 import impute_util as iu
+from feature_geometry import EDGES, geometry
 from multiclust_amd import hip
 from synth import random_params
 
@@ -38,19 +40,6 @@ def contexts():
     yield ctxs
     for c in ctxs:
         c.close()
-
-
-def geometry(K, max_M):
-    """(lanes per workgroup, P rows staged) as impute_geometry chooses them"""
-    ks, budget = K | 1, 64 * 1024 - 512
-    tile = 8 * max_M * ks * 8
-    for t in (256, 128, 64):
-        if t * ks * 8 + 2048 + tile <= budget:
-            return t, 1
-    for t in (256, 128, 64):
-        if t * ks * 8 + 2048 <= budget:
-            return t, 0
-    raise AssertionError
 
 
 def install(ctx, ua, geno, K, q, p, shared=False, projection=1):
@@ -105,9 +94,6 @@ def check(ctx, ua, n_real, geno, q, p, K, slot=0):
 SWEEP = []
 for n, (I, L) in enumerate((I, L) for I in (1, 63, 65, 257) for L in (1, 7, 9, 130)):
     SWEEP.append((I, L, 1 + (n + n // 4) % 4, KS[n % 6], (2, 4)[(n // 2) % 2], (0.05, 0.5)[n % 2], n % 3 == 1))
-# either side of every edge of the geometry: (K, alleles) -> (lanes, staged); max_M = alleles + 1
-EDGES = {(27, 2): (256, 1), (28, 2): (128, 1), (51, 2): (128, 1), (52, 2): (64, 1), (25, 4): (256, 1), (26, 4): (128, 1),
-         (45, 4): (128, 1), (46, 4): (64, 1), (64, 6): (64, 1), (64, 7): (64, 0), (64, 35): (64, 0)}
 
 
 @pytest.mark.parametrize("I,L,pl,K,alleles,missing,shared", SWEEP)
