@@ -78,6 +78,28 @@ int mchip_set_genotypes(mchip_context *ctx, int I, int L, int ploidy,
  */
 int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes,
 			    int32_t *uniquealleles_out);
+/*
+ * Linkage disequilibrium between neighbouring variants of packed records (an extension): the band of squared correlations that
+ * --prune thins a fileset by.  bed, I, L and record_bytes as for mchip_set_genotypes_bed: the whole fileset behind its header.
+ * Definition.  At a variant individual j carries code c_j in {0, 1, 2, 3} as above; its dosage is x_j = 0, none, 1, 2 for the codes
+ * 0, 1 (missing), 2, 3.  For two variants a < b, over the individuals missing at neither (x at a, y at b; padding bits carry no
+ * individual): n their number, Sx = sum x, Sy = sum y, Sxx = sum x^2, Syy = sum y^2, Sxy = sum x y.  In exact signed 64-bit
+ * integers C = n Sxy - Sx Sy, Vx = n Sxx - Sx^2, Vy = n Syy - Sy^2, and then
+ *     r2 = ((double)C * (double)C) / ((double)Vx * (double)Vy)
+ * -- two products and one division, nothing that could be contracted -- or NaN exactly when Vx = 0 or Vy = 0 (a monomorphic
+ * variant, an all-missing one, n < 2).  This is the Pearson r^2 of the dosages over pairwise-complete individuals, the quantity
+ * PLINK's --indep-pairwise thresholds; it does not depend on which allele is counted.  Every sum is an integer: the result is the
+ * same bits on every device, under every launch geometry and every knob of the environment.
+ * Contract.  For l in [l0, l0 + n_first) and d in 1 ... window, r2[(l - l0) * window + d - 1] = r2(l, l + d), NaN where l + d >= L.
+ * Only the records l0 ... min(L, l0 + n_first + window) - 1 cross to the device.  The context supplies the device, the stream and
+ * mchip_last_error and nothing else: no data set need be installed, and nothing of an installed data set, model, slot, fold or
+ * saved set changes.  Checked before anything runs: I, L >= 1, record_bytes >= ceil(I/4), 0 <= l0, 0 <= n_first, l0 + n_first <= L,
+ * 1 <= window <= MCHIP_LD_MAX_WINDOW, non-null pointers; a failed check returns MCHIP_ERR_INVALID and leaves the array untouched.
+ * MCHIP_ERR_ALLOC when the records, the six sums of every pair (24 bytes) and the band do not fit on the device.
+ */
+#define MCHIP_LD_MAX_WINDOW 4096
+int mchip_bed_ld_band(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int l0, int n_first, int window,
+		      double *r2);
 /* Counted on the device when a data set is installed: cells (i, l, m) with ILM[i][l][m] > 0 -- the cells the reference's E step
  * visits (em_alg.c:338-342) and the unit the flop count of the path is stated in -- and non-missing allele copies. */
 int mchip_data_counts(mchip_context *ctx, uint64_t *nonempty_cells, uint64_t *allele_copies);

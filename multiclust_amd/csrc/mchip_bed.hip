@@ -10,6 +10,20 @@
  *                 of gtA [ceil(I/8)][L][8][2] and of gtS [ceil(L/8)][I][8][2] as whole 16-byte groups, 1 KB contiguous per wave on
  *                 either side, and marks the individuals that have an observed call.
  * The upload form [I][L][2] never exists.
+ *
+ * mchip_bed_ld_band reads the same records for another purpose and installs nothing: the band of r^2 between every variant and
+ * its `window` successors (the definition is in the header), L * window * I / 32 word pairs.
+ *   k_ld_band     one workgroup per LD_TILE first variants x LD_DCHUNK offsets x a run of individuals (ld_band_geometry_of,
+ *                 mchip_feature_geometry.h).  Per stage of LD_STAGE 64-bit words (32 individuals each) it forms three bit planes of
+ *                 its LD_TILE first and LD_TILE + LD_DCHUNK - 1 second records in LDS (15 KB): valid, dosage 1, dosage 2.  A lane
+ *                 owns one first variant and LD_DCHUNK / 4 offsets and counts with __popcll into 6 integer registers per pair; the
+ *                 64 lanes of a wave read 64 consecutive words of a plane (no bank conflict).  At the end the six sums of a pair
+ *                 go to memory with integer atomics: runs of individuals combine in any order, the sums are the same.
+ *   k_ld_r2       one lane per pair: the six sums -> C, Vx, Vy in 64-bit integers -> r2, NaN where a variance is 0 or the second
+ *                 variant does not exist.
+ *   Compile report (hipcc of ROCm 7.2, gfx950, -O3, -Rpass-analysis=kernel-resource-usage):  k_ld_band 81 VGPRs, scratch 0, 15360
+ *   bytes of static LDS, 5 waves / SIMD (the loop over a stage's words is kept rolled: unrolled it takes 135 VGPRs and 3 waves);
+ *   k_ld_r2 25 VGPRs, scratch 0, 8 waves / SIMD.  Timed once and not tuned (profiles/ld.txt, scripts/ld_bench.py).
  */
 #include "mchip_context.h"
 
@@ -161,4 +175,149 @@ extern "C" int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const u
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	set_empty_rows_unseen(ctx, seen);
 	return install_layouts(ctx, (bad & 2) ? 1 : 0);
+}
+
+/* ---- linkage disequilibrium between neighbouring variants: mchip_bed_ld_band (include/multiclust_hip.h has the definition) ---- */
+constexpr int LD_YROWS = LD_TILE + LD_DCHUNK - 1;	/* second variants a workgroup meets */
+constexpr int LD_PER_LANE = LD_DCHUNK / 4;		/* offsets of a lane: wave q of the four takes offsets q * LD_PER_LANE ... */
+
+/* the three bit planes of word wg (individuals 32 wg ... 32 wg + 31, bit 2 j for the j-th of them) of the record at rec:
+ * valid = not missing, b0 = dosage 1 (code 2), b1 = dosage 2 (code 3); bits behind individual I - 1 are 0 in all three */
+__device__ __forceinline__ void ld_planes(const uint8_t *__restrict__ bed, size_t rb, int I, size_t rec, int wg, uint64_t &valid, uint64_t &b0,
+					  uint64_t &b1)
+{
+	const size_t off = 8 * (size_t)wg;
+	const int n = I - 32 * wg;	/* samples in this word: bits behind them are padding, or the next record */
+	valid = b0 = b1 = 0;
+	if (n <= 0 || off >= rb) return;
+	uint64_t v = bed_word(bed, rec * rb + off);
+	if (off + 4 < rb) v |= (uint64_t)bed_word(bed, rec * rb + off + 4) << 32;
+	const uint64_t low = 0x5555555555555555ull;
+	const uint64_t m = n >= 32 ? low : (((1ull << (2 * n)) - 1ull) & low);
+	const uint64_t lo = v & m, hi = (v >> 1) & m;
+	valid = m & ~(lo & ~hi);	/* code 1 is the missing call */
+	b0 = hi & ~lo;
+	b1 = hi & lo;
+}
+
+/* sums[(a * window + d - 1) * 6 + 0..5] += n, Sx, Sy, Sxx, Syy, Sxy of the pair (a, a + d) over this workgroup's run of
+ * individuals; rows count from the first uploaded record.  blockIdx.x = tile of first variants + n_tiles * chunk of offsets,
+ * blockIdx.y = run of individuals.  Lane = first variant ax of the tile, wave q = offsets q * LD_PER_LANE + 1 ... of the chunk: the
+ * 64 lanes of a wave read 64 consecutive words of a plane.  With c1 / c2 the carriers of dosage 1 / 2 among the individuals typed
+ * at both variants, Sx = c1x + 2 c2x and Sxx = c1x + 4 c2x; b0 and b1 are 0 where the call is missing, so the products of Sxy need
+ * no mask. */
+__global__ __launch_bounds__(256) void k_ld_band(const uint8_t *__restrict__ bed, size_t rb, int I, int n_up, int n_first, int window,
+						 ld_band_geometry g, uint32_t *__restrict__ sums)
+{
+	__shared__ uint64_t xs[3][LD_STAGE][LD_TILE];
+	__shared__ uint64_t ys[3][LD_STAGE][LD_YROWS + 1];
+	const int tile = blockIdx.x % g.n_tiles, dch = blockIdx.x / g.n_tiles;
+	const int a0 = tile * LD_TILE, y0 = a0 + dch * LD_DCHUNK + 1;
+	if (y0 >= n_up) return;		/* (the whole workgroup) no pair of this tile and chunk lies inside the records */
+	const int nwords = (I + 31) / 32;
+	const int w_begin = (int)blockIdx.y * g.stages_per_split * LD_STAGE;
+	const int w_end = min(nwords, w_begin + g.stages_per_split * LD_STAGE);
+	const int ax = threadIdx.x & 63, q = threadIdx.x >> 6;
+	uint32_t acc[LD_PER_LANE][6];
+#pragma unroll
+	for (int j = 0; j < LD_PER_LANE; j++)
+#pragma unroll
+		for (int s = 0; s < 6; s++) acc[j][s] = 0;
+	for (int ws = w_begin; ws < w_end; ws += LD_STAGE) {
+		__syncthreads();	/* the stage before has been read */
+		for (int x = threadIdx.x; x < (LD_TILE + LD_YROWS) * LD_STAGE; x += 256) {
+			const int row = x / LD_STAGE, w = x % LD_STAGE;
+			const bool first = row < LD_TILE;
+			const int r = first ? a0 + row : y0 + row - LD_TILE;
+			uint64_t v = 0, b0 = 0, b1 = 0;
+			if (r < n_up && ws + w < w_end) ld_planes(bed, rb, I, (size_t)r, ws + w, v, b0, b1);
+			if (first) { xs[0][w][row] = v; xs[1][w][row] = b0; xs[2][w][row] = b1; }
+			else { ys[0][w][row - LD_TILE] = v; ys[1][w][row - LD_TILE] = b0; ys[2][w][row - LD_TILE] = b1; }
+		}
+		__syncthreads();
+#pragma unroll 1
+		for (int w = 0; w < LD_STAGE; w++) {	/* (words behind w_end are staged as zeros) */
+			const uint64_t vx = xs[0][w][ax], b0x = xs[1][w][ax], b1x = xs[2][w][ax];
+#pragma unroll
+			for (int j = 0; j < LD_PER_LANE; j++) {
+				const int yr = ax + q * LD_PER_LANE + j;	/* < LD_YROWS */
+				const uint64_t vy = ys[0][w][yr], b0y = ys[1][w][yr], b1y = ys[2][w][yr];
+				acc[j][0] += (uint32_t)__popcll(vx & vy);
+				acc[j][1] += (uint32_t)__popcll(b0x & vy);
+				acc[j][2] += (uint32_t)__popcll(b1x & vy);
+				acc[j][3] += (uint32_t)__popcll(b0y & vx);
+				acc[j][4] += (uint32_t)__popcll(b1y & vx);
+				acc[j][5] += (uint32_t)__popcll(b0x & b0y) + 2u * (uint32_t)(__popcll(b0x & b1y) + __popcll(b1x & b0y)) +
+					     4u * (uint32_t)__popcll(b1x & b1y);
+			}
+		}
+	}
+	const int a = a0 + ax;
+	if (a >= n_first) return;
+#pragma unroll
+	for (int j = 0; j < LD_PER_LANE; j++) {
+		const int d = dch * LD_DCHUNK + q * LD_PER_LANE + j + 1;
+		if (d > window || a + d >= n_up) continue;
+		uint32_t *s = sums + ((size_t)a * (size_t)window + (size_t)(d - 1)) * 6;
+		atomicAdd(s + 0, acc[j][0]);
+		atomicAdd(s + 1, acc[j][1] + 2u * acc[j][2]);
+		atomicAdd(s + 2, acc[j][3] + 2u * acc[j][4]);
+		atomicAdd(s + 3, acc[j][1] + 4u * acc[j][2]);
+		atomicAdd(s + 4, acc[j][3] + 4u * acc[j][4]);
+		atomicAdd(s + 5, acc[j][5]);
+	}
+}
+
+/* r2 of every pair from its six sums, in exact 64-bit integers up to the two products and the division of the definition; NaN where
+ * either variance is 0 and where the second variant lies behind the last record */
+__global__ __launch_bounds__(256) void k_ld_r2(const uint32_t *__restrict__ sums, size_t n_pairs, int window, int n_up, double *__restrict__ r2)
+{
+	for (size_t x = (size_t)blockIdx.x * 256 + threadIdx.x; x < n_pairs; x += (size_t)gridDim.x * 256) {
+		const size_t a = x / (size_t)window, d = x % (size_t)window + 1;
+		double out = __longlong_as_double(0x7FF8000000000000ll);
+		if (a + d < (size_t)n_up) {
+			const uint32_t *s = sums + x * 6;
+			const int64_t n = s[0], Sx = s[1], Sy = s[2], Sxx = s[3], Syy = s[4], Sxy = s[5];
+			const int64_t C = n * Sxy - Sx * Sy, Vx = n * Sxx - Sx * Sx, Vy = n * Syy - Sy * Sy;
+			if (Vx != 0 && Vy != 0) out = ((double)C * (double)C) / ((double)Vx * (double)Vy);
+		}
+		r2[x] = out;
+	}
+}
+
+extern "C" int mchip_bed_ld_band(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int l0, int n_first, int window,
+				 double *r2)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (I <= 0 || L <= 0 || !bed || !r2 || record_bytes < ((size_t)I + 3) / 4)
+		return fail(ctx, MCHIP_ERR_INVALID, "bed_ld_band: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
+	if (l0 < 0 || n_first < 0 || (long long)l0 + n_first > L || window < 1 || window > MCHIP_LD_MAX_WINDOW)
+		return fail(ctx, MCHIP_ERR_INVALID, "bed_ld_band: first variants outside the records, or a window outside 1 ... 4096%s", nullptr);
+	if (!n_first) return MCHIP_OK;
+	const long long reach = (long long)n_first + window;
+	const int n_up = (int)((long long)(L - l0) < reach ? (long long)(L - l0) : reach);	/* records that cross: rows count from l0 */
+	const ld_band_geometry g = ld_band_geometry_of(I, n_first, window, (long long)ctx->knob.per_cu_ind * (ctx->n_cu > 0 ? ctx->n_cu : 256));
+	if ((long long)g.n_tiles * g.n_dchunks >= (1ll << 24))
+		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "bed_ld_band: too many first variants times offsets for one launch; call it in slabs%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t up_bytes = (size_t)n_up * record_bytes, n_pairs = (size_t)n_first * (size_t)window;
+	scoped_dev<uint8_t> d_bed;
+	scoped_dev<uint32_t> d_sums;
+	scoped_dev<double> d_r2;
+	if (d_bed.alloc(up_bytes + BED_PAD) != hipSuccess || d_sums.alloc(n_pairs * 6) != hipSuccess || d_r2.alloc(n_pairs) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(ctx, MCHIP_ERR_ALLOC, "bed_ld_band: the records, the sums or the band do not fit on the device%s", nullptr);
+	}
+	HIPCHK(hipMemcpyAsync(d_bed.p, bed + (size_t)l0 * record_bytes, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_bed.p + up_bytes, 0, BED_PAD, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_sums.p, 0, n_pairs * 6 * sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_ld_band, dim3((unsigned)(g.n_tiles * g.n_dchunks), (unsigned)g.n_split), dim3(256), 0, ctx->stream, d_bed.p, record_bytes,
+			   I, n_up, n_first, window, g, d_sums.p);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(k_ld_r2, dim3(nblk_capped(n_pairs)), dim3(256), 0, ctx->stream, d_sums.p, n_pairs, window, n_up, d_r2.p);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(r2, d_r2.p, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	return MCHIP_OK;
 }

@@ -46,4 +46,33 @@ static inline lane_pass_geometry lane_pass_geometry_of(int I, int L, int K, int 
 	return g;
 }
 
+/* ---- the LD band of packed records (k_ld_band, mchip_bed.hip; tests/ld_util.py restates the constants) ----
+ * A workgroup owns LD_TILE first variants x LD_DCHUNK offsets and a run of whole stages of LD_STAGE 64-bit words (32 individuals
+ * each).  The individuals are cut into n_split runs only while that takes the launch towards target_blocks workgroups: the sums
+ * are integers, so the cut shows in no bit of the result. */
+constexpr int LD_TILE = 64;	/* first variants per workgroup */
+constexpr int LD_DCHUNK = 32;	/* offsets per workgroup: a lane owns one first variant and LD_DCHUNK / 4 offsets */
+constexpr int LD_STAGE = 4;	/* 64-bit words of every staged record's planes in LDS at a time: 128 individuals */
+
+struct ld_band_geometry {
+	int n_tiles, n_dchunks;		/* workgroups along the first variants and along the offsets */
+	int n_split, stages_per_split;	/* workgroups along the individuals, and the stages each of them walks */
+};
+
+static inline ld_band_geometry ld_band_geometry_of(int I, int n_first, int window, long long target_blocks)
+{
+	ld_band_geometry g;
+	g.n_tiles = (n_first + LD_TILE - 1) / LD_TILE;
+	g.n_dchunks = (window + LD_DCHUNK - 1) / LD_DCHUNK;
+	const long long base = (long long)g.n_tiles * g.n_dchunks;
+	const int n_stages = ((I + 31) / 32 + LD_STAGE - 1) / LD_STAGE;
+	long long want = base > 0 ? (target_blocks + base - 1) / base : 1;
+	if (want > n_stages) want = n_stages;
+	if (want > 65535) want = 65535;
+	if (want < 1) want = 1;
+	g.stages_per_split = (int)((n_stages + want - 1) / want);
+	g.n_split = (n_stages + g.stages_per_split - 1) / g.stages_per_split;
+	return g;
+}
+
 #endif

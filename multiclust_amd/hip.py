@@ -57,6 +57,7 @@ def load():
         "mchip_synchronize": ([vp], i32),
         "mchip_set_genotypes": ([vp, i32, i32, i32, vp, vp], i32),
         "mchip_set_genotypes_bed": ([vp, i32, i32, vp, C.c_size_t, vp], i32),
+        "mchip_bed_ld_band": ([vp, i32, i32, vp, C.c_size_t, i32, i32, i32, vp], i32),
         "mchip_set_model": ([vp, i32, i32, i32, i32, C.c_double, C.c_double, i32], i32),
         "mchip_set_p": ([vp, i32, vp], i32),
         "mchip_get_p": ([vp, i32, vp], i32),
@@ -136,7 +137,7 @@ ABI_SYMBOLS = [
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
     "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
-    "mchip_residual_products", "mchip_describe_plan",
+    "mchip_residual_products", "mchip_describe_plan", "mchip_bed_ld_band",
 ]
 
 
@@ -198,6 +199,19 @@ class Context:
         self.I, self.L, self.ploidy, self.T = I, L, 2, int(ua.sum())
         self._ua, self._rs_ua = ua.copy(), None
         return ua
+
+    def bed_ld_band(self, I, bed, l0=0, n_first=None, window=50, record_bytes=None, L=None):
+        """mchip_bed_ld_band: r2[n_first][window] of the variants l0 ... l0 + n_first - 1 of the packed records [L][record_bytes]
+        with their `window` successors (include/multiclust_hip.h has the definition); NaN behind the last variant and where a
+        variance is 0.  Installs nothing and changes nothing of the context."""
+        bed = np.ascontiguousarray(bed, dtype=np.uint8)
+        assert bed.ndim == 2
+        L = bed.shape[0] if L is None else L
+        rb = bed.shape[1] if record_bytes is None else record_bytes
+        n_first = L - l0 if n_first is None else n_first
+        out = np.empty((max(n_first, 0), max(window, 0)), dtype=np.float64)
+        self._chk(self.lib.mchip_bed_ld_band(self.h, I, L, bed.ctypes.data, rb, l0, n_first, window, out.ctypes.data))
+        return out
 
     def data_counts(self):
         """(cells with n_ic > 0, non-missing allele copies) of the data set held, counted on the device"""

@@ -116,8 +116,16 @@ class CliOptions(C.Structure):
                 ("max_repeat_seconds", C.c_uint), ("write_files", C.c_int), ("compact", C.c_int), ("parallel", C.c_int),
                 ("device", C.c_int), ("n_gpus", C.c_int), ("n_streams", C.c_int), ("pfile", C.c_char_p), ("qfile", C.c_char_p),
                 ("afile", C.c_char_p), ("bed_prefix", C.c_char_p)]
-    # (the C struct ends with cv_folds / cv_floor, se_replicates / se_block, query_file, fill, fst and resid, the command line's --cv, --se,
-    # --query, --fill, --fst and --resid: only mc_main.c reads them, the readers and writers this mirror is handed to stop at bed_prefix)
+    # (the C struct goes on: CliOptionsAll)
+
+
+class CliOptionsAll(CliOptions):
+    """the whole of mc_cli_options: what the readers and writers are handed, since mc_read_bed reads the last fields"""
+    _fields_ = [  # the command line's --cv, --se, --query, --fill, --fst and --resid: only mc_main.c reads them
+                ("cv_folds", C.c_int), ("cv_floor", C.c_double), ("se_replicates", C.c_int), ("se_block", C.c_int),
+                ("query_file", C.c_char_p), ("fill", C.c_int), ("fst", C.c_int), ("resid", C.c_int),
+                # --prune / --prune-window
+                ("prune", C.c_int), ("prune_window_given", C.c_int), ("prune_t", C.c_double), ("prune_window", C.c_int)]
 
 
 class CliData(C.Structure):
@@ -128,6 +136,13 @@ class CliData(C.Structure):
                 ("names", C.POINTER(C.c_char_p)), ("locale", C.POINTER(C.c_int)), ("pops", C.POINTER(C.c_char_p)),
                 ("numpops", C.c_int), ("i_p", C.POINTER(C.c_int)), ("T", C.c_int), ("toff", C.POINTER(C.c_int32)),
                 ("bed", C.POINTER(C.c_uint8)), ("bed_record_bytes", C.c_size_t), ("lazy", C.c_void_p)]
+    # (the C struct goes on: CliDataAll)
+
+
+class CliDataAll(CliData):
+    """the whole of mc_cli_data: what the readers fill (they clear all of it) and the writers read"""
+    _fields_ = [("L_file", C.c_int), ("bim_text", C.c_void_p), ("chrom", C.POINTER(C.c_char_p)),
+                ("variant_id", C.POINTER(C.c_char_p)), ("variant_of", C.POINTER(C.c_int))]
 
 
 def _cli_data_fields(d, geno):
@@ -149,12 +164,12 @@ def read_structure(path, ploidy=2, missing=-9, r_format=0):
     """mc_read_structure (host/mc_reader.c; reference read_file.c:38-300, 443-663) on a STRUCTURE file: (status, None) on
     failure, else (0, dict of the fields the EM path and the writers read)."""
     lib = load()
-    lib.mc_read_structure.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
-    lib.mc_free_data.argtypes = [C.POINTER(CliData)]
-    o = CliOptions()
+    lib.mc_read_structure.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll)]
+    lib.mc_free_data.argtypes = [C.POINTER(CliDataAll)]
+    o = CliOptionsAll()
     o.filename = path.encode()
     o.ploidy, o.missing_value, o.R_format = ploidy, missing, r_format
-    d = CliData()
+    d = CliDataAll()
     rc = lib.mc_read_structure(C.byref(o), C.byref(d))
     if rc:
         return rc, None
@@ -180,26 +195,38 @@ def bed_decode(I, bed):
     return ua, geno
 
 
-def read_bed(prefix, decode=True):
+def read_bed(prefix, decode=True, prune=None, prune_window=50, device=0):
     """mc_read_bed (host/mc_bed.c) on the PLINK 1 fileset prefix.bed/.bim/.fam: (status, None) on failure, else (0, dict) with
     the fields of read_structure.  The reader keeps the data set packed -- `bed` [L][record_bytes], geno_is_null says that it
-    built no genotype; `geno` (and L_alleles) come from mc_bed_decode on those records, unless decode is False."""
+    built no genotype; `geno` (and L_alleles) come from mc_bed_decode on those records, unless decode is False.  chrom and
+    variant_id are the first two fields of the L_file lines of the .bim.  prune = t: the variants thinned by linkage disequilibrium
+    on `device` as --prune t --prune-window prune_window does (host/mc_ld.c): everything is the pruned data set's, variant_of its
+    loci's places in the fileset (None without pruning)."""
     lib = load()
-    lib.mc_read_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
-    lib.mc_free_data.argtypes = [C.POINTER(CliData)]
-    o = CliOptions()
+    lib.mc_read_bed.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll)]
+    lib.mc_free_data.argtypes = [C.POINTER(CliDataAll)]
+    o = CliOptionsAll()
     o.bed_prefix = prefix.encode()
     o.ploidy = 2
-    d = CliData()
+    d = CliDataAll()
     rc = lib.mc_read_bed(C.byref(o), C.byref(d))
     if rc:
         return rc, None
+    if prune is not None:
+        lib.mc_ld_prune_data.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll)]
+        o.device, o.prune, o.prune_t, o.prune_window = device, 1, prune, prune_window
+        rc = lib.mc_ld_prune_data(C.byref(o), C.byref(d))
+        if rc:
+            lib.mc_free_data(C.byref(d))
+            return rc, None
     bed = np.ctypeslib.as_array(d.bed, shape=(d.L, d.bed_record_bytes)).copy()
     geno = ua_dec = None
     if decode:
         ua_dec, geno = bed_decode(d.I, bed)
     out = _cli_data_fields(d, geno)
-    out.update(geno_is_null=not bool(d.geno), bed=bed)
+    out.update(geno_is_null=not bool(d.geno), bed=bed, L_file=d.L_file, chrom=[d.chrom[v].decode() for v in range(d.L_file)],
+               variant_id=[d.variant_id[v].decode() for v in range(d.L_file)],
+               variant_of=[d.variant_of[l] for l in range(d.L)] if d.variant_of else None)
     if decode:
         out.update(geno=geno, ua_decoded=ua_dec)
     lib.mc_free_data(C.byref(d))
@@ -211,10 +238,10 @@ def write_filled_structure(path, out_path, filled, ploidy=2, missing=-9, r_forma
     with every missing allele token whose copy is not 0xFF in filled [I][L][ploidy] replaced by that allele's label; returns the
     status (0 = written)."""
     lib = load()
-    o = CliOptions()
+    o = CliOptionsAll()
     o.filename = path.encode()
     o.ploidy, o.missing_value, o.R_format = ploidy, missing, r_format
-    d = CliData()
+    d = CliDataAll()
     rc = lib.mc_read_structure(C.byref(o), C.byref(d))
     if rc:
         return rc
@@ -229,10 +256,10 @@ def write_filled_bed(prefix, out_prefix, filled):
     """mc_write_filled_bed (host/mc_impute.c): the PLINK fileset `prefix` copied to out_prefix.bed/.bim/.fam with every missing
     record whose two copies are not 0xFF in filled [I][L][2] replaced by the genotype they spell; returns the status."""
     lib = load()
-    o = CliOptions()
+    o = CliOptionsAll()
     o.bed_prefix = prefix.encode()
     o.ploidy = 2
-    d = CliData()
+    d = CliDataAll()
     rc = lib.mc_read_bed(C.byref(o), C.byref(d))
     if rc:
         return rc
@@ -429,11 +456,11 @@ def load():
     lib.mc_residual_ratios.restype = None
     lib.mc_residual_summary.argtypes = [C.c_int, C.c_void_p, C.POINTER(McResidResult)]
     lib.mc_residual_summary.restype = None
-    lib.mc_read_structure.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
-    lib.mc_read_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData)]
-    lib.mc_free_data.argtypes = [C.POINTER(CliData)]
-    lib.mc_write_filled_structure.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData), C.c_void_p, C.c_char_p]
-    lib.mc_write_filled_bed.argtypes = [C.POINTER(CliOptions), C.POINTER(CliData), C.c_void_p, C.c_char_p]
+    lib.mc_read_structure.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll)]
+    lib.mc_read_bed.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll)]
+    lib.mc_free_data.argtypes = [C.POINTER(CliDataAll)]
+    lib.mc_write_filled_structure.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll), C.c_void_p, C.c_char_p]
+    lib.mc_write_filled_bed.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll), C.c_void_p, C.c_char_p]
     lib.mc_aic.restype = C.c_double
     lib.mc_aic.argtypes = [C.c_double, C.c_int]
     lib.mc_bic.restype = C.c_double

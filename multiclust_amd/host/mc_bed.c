@@ -217,6 +217,67 @@ static int read_fam(const char *path, mc_cli_data *dat)
 	return 0;
 }
 
+/* summarize_alleles (read_file.c:443-600) from the flags of the L records held: uniquealleles, L_alleles, toff, T, M and
+ * missing_data made anew (the caller has freed what was there) */
+int mc_bed_summarize(mc_cli_data *dat)
+{
+	const int I = dat->I, L = dat->L;
+	const size_t rb = dat->bed_record_bytes;
+	dat->M = dat->T = dat->missing_data = 0;
+	dat->uniquealleles = calloc((size_t)L, sizeof *dat->uniquealleles);
+	dat->L_alleles = calloc((size_t)L, sizeof *dat->L_alleles);
+	dat->toff = calloc((size_t)L + 1, sizeof *dat->toff);
+	if (!dat->uniquealleles || !dat->L_alleles || !dat->toff) return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL);
+	for (int l = 0; l < L; l++) {
+		const int fl = record_flags(dat->bed + (size_t)l * rb, I);
+		const int nu = !!(fl & BED_A1) + !!(fl & BED_A2);
+		int *al = malloc(sizeof(int) * (size_t)(nu ? nu : 1));
+		if (!al) return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL);
+		int x = 0;
+		if (fl & BED_A1) al[x++] = 1;	/* the allele codes of the equivalent STRUCTURE file */
+		if (fl & BED_A2) al[x++] = 2;
+		dat->L_alleles[l] = al;
+		dat->uniquealleles[l] = flags_ua(fl);
+		if ((fl & BED_MISSING) && nu) dat->missing_data = 1;
+		if (dat->uniquealleles[l] > dat->M) dat->M = dat->uniquealleles[l];
+		dat->toff[l + 1] = dat->toff[l] + dat->uniquealleles[l];
+	}
+	dat->T = dat->toff[L];
+	return 0;
+}
+
+/* .bim: one line per variant, chromosome, variant id, ...: the two tokens are terminated in place (dat->bim_text, n bytes) and
+ * pointed to by dat->chrom and dat->variant_id */
+static int bim_fields(mc_cli_data *dat, size_t n, size_t nloci)
+{
+	dat->chrom = calloc(nloci, sizeof *dat->chrom);
+	dat->variant_id = calloc(nloci, sizeof *dat->variant_id);
+	if (!dat->chrom || !dat->variant_id) return MC_EXIT_MEMORY_ALLOCATION;
+	size_t l = 0;
+	for (char *p = dat->bim_text, *eof = p + n; p < eof;) {
+		char *q = memchr(p, '\n', (size_t)(eof - p));
+		if (!q) q = eof;
+		char *s = p;
+		while (s < q && is_blank(*s)) s++;
+		if (s < q) {
+			char *c = s;
+			while (s < q && !is_blank(*s)) s++;
+			char *c_end = s;
+			while (s < q && is_blank(*s)) s++;
+			char *id = s;
+			while (s < q && !is_blank(*s)) s++;
+			*c_end = 0;
+			*s = 0;		/* (the line's end, or the blank behind the id; the text has one more byte behind its last.  A line
+					 * without a second field has the empty id) */
+			dat->chrom[l] = c;
+			dat->variant_id[l] = id;
+			l++;
+		}
+		p = q + 1;
+	}
+	return 0;
+}
+
 int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat)
 {
 	int rc = MC_EXIT_MEMORY_ALLOCATION;
@@ -233,10 +294,11 @@ int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat)
 	if ((rc = read_fam(famf, dat))) goto DONE;
 	if ((rc = slurp(bimf, &buf, &n))) goto DONE;
 	const size_t nloci = count_lines(buf, n);
-	free(buf);
-	buf = NULL;
 	if (!nloci || nloci > 0x7FFFFFFF / 4) { rc = FAIL(MC_EXIT_FILE_FORMAT_ERROR, "no variants (or too many) in '%s'", bimf); goto DONE; }
-	const int I = dat->I, L = dat->L = (int)nloci;
+	dat->bim_text = buf;
+	buf = NULL;
+	if ((rc = bim_fields(dat, n, nloci))) { rc = FAIL(rc, "out of memory reading '%s'", bimf); goto DONE; }
+	const int I = dat->I, L = dat->L = dat->L_file = (int)nloci;
 	const size_t rb = ((size_t)I + 3) / 4;
 
 	mchip_progress_note("mc_read_bed: .bed");
@@ -255,9 +317,6 @@ int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat)
 	dat->bed_record_bytes = rb;
 
 	mchip_progress_note("mc_read_bed: allele lists");
-	dat->uniquealleles = calloc((size_t)L, sizeof *dat->uniquealleles);
-	dat->L_alleles = calloc((size_t)L, sizeof *dat->L_alleles);
-	dat->toff = calloc((size_t)L + 1, sizeof *dat->toff);
 	bed_lazy *z = calloc(1, sizeof *z);
 	if (z) {
 		z->base.get = lazy_get;
@@ -265,22 +324,8 @@ int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat)
 		pthread_mutex_init(&z->lock, NULL);
 		dat->lazy = &z->base;
 	}
-	if (!dat->uniquealleles || !dat->L_alleles || !dat->toff || !z) { rc = FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); goto DONE; }
-	for (int l = 0; l < L; l++) {	/* summarize_alleles (read_file.c:443-600) from the flags of the record */
-		const int fl = record_flags(dat->bed + (size_t)l * rb, I);
-		const int nu = !!(fl & BED_A1) + !!(fl & BED_A2);
-		int *al = malloc(sizeof(int) * (size_t)(nu ? nu : 1));
-		if (!al) { rc = FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); goto DONE; }
-		int x = 0;
-		if (fl & BED_A1) al[x++] = 1;	/* the allele codes of the equivalent STRUCTURE file */
-		if (fl & BED_A2) al[x++] = 2;
-		dat->L_alleles[l] = al;
-		dat->uniquealleles[l] = flags_ua(fl);
-		if ((fl & BED_MISSING) && nu) dat->missing_data = 1;
-		if (dat->uniquealleles[l] > dat->M) dat->M = dat->uniquealleles[l];
-		dat->toff[l + 1] = dat->toff[l] + dat->uniquealleles[l];
-	}
-	dat->T = dat->toff[L];
+	if (!z) { rc = FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); goto DONE; }
+	if ((rc = mc_bed_summarize(dat))) goto DONE;
 	if (getenv("MC_READER_TIMING"))		/* as mc_read_structure reports its phases */
 		fprintf(stderr, "INFO [mc_bed.c]: %-18s %.3f s\n", "fileset read", now_s() - t_start);
 	rc = 0;

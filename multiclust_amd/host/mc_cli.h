@@ -55,6 +55,9 @@ typedef struct mc_cli_options {
 	int fill;			/* --fill (extension): the missing genotypes filled from the best fit of every K (mc_impute.c) */
 	int fst;			/* --fst (extension): divergence of the clusters of the best fit of every K (mc_diverge.c) */
 	int resid;			/* --resid (extension): residual correlation between the individuals under the best fit of every K (mc_resid.c) */
+	int prune, prune_window_given;	/* --prune <t> / --prune-window <W> seen (extension, mc_ld.c; both need --bed) */
+	double prune_t;			/* --prune <t>: a variant in r2 > t with a kept variant of its chromosome at most W before it is removed; 0 < t <= 1 */
+	int prune_window;		/* --prune-window <W>: in variants, 1 ... MCHIP_LD_MAX_WINDOW; default 50 */
 } mc_cli_options;
 
 typedef struct mc_cli_data {
@@ -76,6 +79,11 @@ typedef struct mc_cli_data {
 	uint8_t *bed;			/* [L][bed_record_bytes]: the .bed file behind its three header bytes */
 	size_t bed_record_bytes;	/* ceil(I/4) */
 	struct mc_lazy_geno *lazy;
+	/* the fileset's variants, L_file of them (mc_read_bed): chromosome and id of each, the first two fields of its .bim line (tokens of
+	 * bim_text).  --prune leaves L of them: locus l is variant variant_of[l] of the fileset (ascending); NULL = every variant is a locus */
+	int L_file;
+	char *bim_text, **chrom, **variant_id;
+	int *variant_of;
 } mc_cli_data;
 
 /* read_file + summarize_alleles + sufficient_statistics (read_file.c:38-300,443-663), default (allele-code) mode */
@@ -89,8 +97,12 @@ void mc_free_data(mc_cli_data *dat);
  * first appearance, and uniquealleles, L_alleles, M, T, toff and missing_data are the reader's (a locus without an observed
  * call has no allele column and does not set missing_data).  ploidy = 2; geno stays NULL, the records are kept packed (bed,
  * bed_record_bytes) and models upload them as they are.  Returns 0 or the reference's exit status for the failure: a file that
- * cannot be opened 5; magic bytes, sample-major mode, file size against the line counts of .bim and .fam 7. */
+ * cannot be opened 5; magic bytes, sample-major mode, file size against the line counts of .bim and .fam 7.
+ * L_file = L; chrom and variant_id are the first two fields of every .bim line, variant_of stays NULL (mc_ld_prune_data sets it). */
 int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat);
+/* the part of mc_read_bed that follows the records: uniquealleles, L_alleles, M, T, toff and missing_data of the L records held in
+ * dat->bed, allocated anew (the pointers are overwritten).  Returns 0 or MC_EXIT_MEMORY_ALLOCATION. */
+int mc_bed_summarize(mc_cli_data *dat);
 /* The CPU form of the device's unpacking: L records of record_bytes bytes (sample j of a record in byte j/4, bits 2(j%4) and
  * 2(j%4)+1: 0 homozygous A1, 1 missing, 2 heterozygous, 3 homozygous A2; padding bits ignored) -> uniquealleles[L] and
  * geno[I][L][2] of the equivalent STRUCTURE file.  Either output may be NULL. */
@@ -136,7 +148,8 @@ int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows,
  * mc_write_filled_structure: opt->filename byte for byte -- header, "-1" line, both layouts, label columns, white space, line ends --
  * except that each token the reader took for a missing allele copy and that was filled is the decimal label L_alleles[l][m].
  * mc_write_filled_bed: <out_prefix>.bed with each missing record that was filled replaced by homozygous A1 / heterozygous /
- * homozygous A2 (magic bytes and padding bits kept), .bim and .fam of opt->bed_prefix copied byte for byte.
+ * homozygous A2 (magic bytes and padding bits kept), .bim and .fam of opt->bed_prefix copied byte for byte (of a data set
+ * pruned by --prune the .bim lines of the variants kept).
  * mc_write_filled: the one the input calls for, to <stem>.admix.K=<K>.filled.stru or <stem>.admix.K=<K>.filled.bed / .bim / .fam.
  * Return 0 or an exit status of the enum above. */
 int mc_write_filled_structure(const mc_cli_options *opt, const mc_cli_data *dat, const uint8_t *filled, const char *out_path);
@@ -153,5 +166,26 @@ int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const
  * <stem>.admix.K=<K>.resid.ind.txt -- per individual its index, mean and largest correlation and the partner of that; the formats are
  * in the header comment of mc_resid.c.  Returns 0 or an exit status of the enum above. */
 int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r);
+
+/* --prune (an extension, mc_ld.c; r2 is defined in include/multiclust_hip.h, the rule in the header comment of mc_ld.c).
+ * mc_ld_band_fn: r2[n_first][window] of the variants l0 ... l0 + n_first - 1 with their successors, as mchip_bed_ld_band fills it;
+ * returns 0 or a status.
+ * mc_ld_prune_greedy: keep[l] = 1 / 0 for the L variants under the forward greedy rule with window W and threshold t (a pair counts
+ * when its r2 > t: NaN never does); the band is asked for in slabs of at most `slab` first variants, in ascending order; chrom[l]
+ * (NULL: one chromosome) are compared as strings, pairs on different chromosomes do not count.  Returns 0, MCHIP_ERR_INVALID,
+ * MCHIP_ERR_ALLOC or the band's status.
+ * mc_ld_compact: the kept records of bed [L][record_bytes] moved to its front in order; variant_of[n] (may be NULL) = the index the
+ * n-th kept record had.  Returns their number.
+ * mc_ld_prune_data: a data set as mc_read_bed yields it, pruned by opt->prune_t and opt->prune_window with the band of device
+ * opt->device: the data set mc_read_bed yields on the fileset of the variants kept -- bed compacted, L their number, uniquealleles,
+ * L_alleles, M, T, toff and missing_data theirs (mc_bed_summarize) -- with variant_of set; L_file, chrom and variant_id stay the
+ * fileset's.  Under MC_READER_TIMING it reports its seconds as the readers do.  Returns 0 or a status.
+ * mc_write_prune_lists: <stem>.prune.in and <stem>.prune.out -- the ids of the variants kept and removed, one per line in file order. */
+#define MC_LD_SLAB 65536
+typedef int (*mc_ld_band_fn)(void *arg, int l0, int n_first, int window, double *r2);
+int mc_ld_prune_greedy(int L, int W, double t, int slab, mc_ld_band_fn band, void *arg, const char *const *chrom, uint8_t *keep);
+int mc_ld_compact(int L, size_t record_bytes, const uint8_t *keep, uint8_t *bed, int *variant_of);
+int mc_ld_prune_data(const mc_cli_options *opt, mc_cli_data *dat);
+int mc_write_prune_lists(const mc_cli_options *opt, const mc_cli_data *dat);
 
 #endif

@@ -174,6 +174,32 @@ static int copy_file(const char *from, const char *to)
 	return rc;
 }
 
+/* the .bim of a pruned data set: of the lines that hold anything but white space, the variant_of[0 .. L - 1]-th, byte for byte */
+static int copy_kept_lines(const char *from, const char *to, const int *variant_of, int L)
+{
+	char *buf;
+	size_t n;
+	int rc = slurp(from, &buf, &n);
+	if (rc) return rc;
+	FILE *fp = open_out(to);
+	if (!fp) { free(buf); return MC_EXIT_FILE_OPEN_ERROR; }
+	int v = 0, l = 0;
+	for (const char *p = buf, *eof = buf + n; p < eof && l < L;) {
+		const char *q = memchr(p, '\n', (size_t)(eof - p));
+		q = q ? q + 1 : eof;
+		int content = 0;
+		for (const char *c = p; c < q; c++) if (*c != ' ' && *c != '\t' && *c != '\r' && *c != '\n') { content = 1; break; }
+		if (content) {
+			if (variant_of[l] == v) { l++; if (fwrite(p, 1, (size_t)(q - p), fp) != (size_t)(q - p)) rc = MC_EXIT_FILE_OPEN_ERROR; }
+			v++;
+		}
+		p = q;
+	}
+	if (fclose(fp)) rc = rc ? rc : MC_EXIT_FILE_OPEN_ERROR;
+	free(buf);
+	return rc;
+}
+
 static char *path_of(const char *prefix, const char *ext)
 {
 	char *p = malloc(strlen(prefix) + strlen(ext) + 1);
@@ -215,7 +241,8 @@ int mc_write_filled_bed(const mc_cli_options *opt, const mc_cli_data *dat, const
 	}
 	if (fclose(fp)) rc = rc ? rc : MC_EXIT_FILE_OPEN_ERROR;
 	fp = NULL;
-	for (int x = 0; x < 2 && !rc; x++) rc = copy_file(src[x], dst[x]);
+	/* (the variants --prune removed have no record above and no line here) */
+	for (int x = 0; x < 2 && !rc; x++) rc = (x == 0 && dat->variant_of) ? copy_kept_lines(src[x], dst[x], dat->variant_of, L) : copy_file(src[x], dst[x]);
 DONE:
 	if (fp) fclose(fp);
 	if (rc) fprintf(stderr, "ERROR [mc_impute.c::mc_write_filled_bed]: could not write the fileset '%s' (%d)\n", out_prefix, rc);

@@ -15,6 +15,8 @@
  * the clusters (one more stdout line per K and two more files; either model; without it nothing changes);
  * --resid checks the best fit of every K against the data: the correlation over the loci of the residuals "observed allele count minus predicted
  * count" of every pair of individuals (one more stdout line per K and two more files; admixture model; without it nothing changes);
+ * --prune <t> thins the variants of a fileset (--bed) by linkage disequilibrium on the device before anything is fitted (mc_ld.c; one more stdout
+ * line and two more files; the run is the run on the fileset of the variants kept; without it nothing changes);
  * --query <file> keeps the individuals the file marks out of every fit and fits their mixing proportions against the best fit of every K
  * afterwards (one more stdout line per K and one more file; without it nothing changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
@@ -87,7 +89,12 @@ static void usage(FILE *fp, const char *prog)
 		"  --resid       residual correlation of the best fit of every K between every pair of individuals (near zero under an adequate fit;\n"
 		"                relatives, duplicates and a K that is too small show as positive blocks): one more line 'Residual correlation\n"
 		"                (K=..)' per K and the files <stem>.admix.K=<K>.resid.txt (the I x I matrix: I*I numbers) and .resid.ind.txt (mean,\n"
-		"                largest and partner per individual); needs -a, not with -b, -w, -M or --gpus above 1\n", prog);
+		"                largest and partner per individual); needs -a, not with -b, -w, -M or --gpus above 1\n"
+		"  --prune <t>   thin the variants of --bed by linkage disequilibrium before anything is fitted: in file order, a variant whose\n"
+		"                squared dosage correlation with a variant already kept, on its chromosome and at most W variants before it,\n"
+		"                exceeds t (0 < t <= 1) is removed (forward greedy, as SNPRelate's snpgdsLDpruning; not PLINK's --indep-pairwise);\n"
+		"                one more line 'LD pruning: ...' and the ids kept and removed in <stem>.prune.in / .prune.out; the run is the run\n"
+		"                on the fileset of the kept variants; needs --bed        --prune-window <W>  W in variants, 1..4096 (50)\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -123,17 +130,19 @@ static void defaults(mc_cli_options *o)
 	o->n_gpus = 1;
 	o->n_streams = 1;
 	o->se_block = 1;
+	o->prune_window = 50;
 }
 
 #define BAD(msg) do { fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '%s'); try -h\n", msg, i < argc ? argv[i] : ""); return MC_EXIT_INVALID_CMD_ARGUMENT; } while (0)
 
-/* "option X cannot be combined with ...": why = NULL when it can */
-static int refuse(const char *option, const char *why)
+/* "option X cannot be combined with ...": why = NULL when it can; the status is a bad argument's, or the one given */
+static int refuse_as(const char *option, const char *why, int status)
 {
 	if (!why) return 0;
 	fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '%s'); try -h\n", why, option);
-	return MC_EXIT_INVALID_CMD_ARGUMENT;
+	return status;
 }
+static int refuse(const char *option, const char *why) { return refuse_as(option, why, MC_EXIT_INVALID_CMD_ARGUMENT); }
 
 static int parse_options(mc_cli_options *o, int argc, const char **argv)
 {
@@ -194,6 +203,8 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 		case 'n': if (arg_int(argc, argv, ++i, &v)) BAD("-n"); o->n_init = (int)v; if (!v) o->n_repeat = 0; break;
 		case 'o': if (++i >= argc) BAD("-o"); o->outfile_name = argv[i]; break;
 		case 'p':
+			if (!strcmp(argv[i], "--prune")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--prune"); o->prune = 1; o->prune_t = d; break; }	/* (in full: --pr... is --projection) */
+			if (!strcmp(argv[i], "--prune-window")) { if (arg_int(argc, argv, ++i, &v)) BAD("--prune-window"); o->prune_window_given = 1; o->prune_window = (int)(v < -1 ? -1 : v > 1000000 ? 1000000 : v); break; }
 			if (!strncmp(w, "pr", 2)) o->em.do_projection = 0;
 			else if (!strncmp(w, "pl", 2)) ;	/* --plus: data-writer option */
 			else { if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-p"); o->ploidy = (int)v; }
@@ -297,6 +308,12 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			o->n_bootstrap ? "--resid cannot be combined with the bootstrap (-b)" :
 			o->n_gpus > 1 ? "--resid cannot be combined with --gpus above 1" :
 			timed ? "--resid cannot be combined with -w or -M" : NULL))) return rc;
+	if ((o->prune || o->prune_window_given) && (rc = refuse_as(o->prune ? "--prune" : "--prune-window",
+			!o->bed_prefix ? "--prune and --prune-window need a PLINK fileset (--bed)" :
+			!o->prune ? "--prune-window needs --prune" :
+			!(o->prune_t > 0 && o->prune_t <= 1) ? "the r2 threshold of --prune must lie in (0, 1]" :
+			o->prune_window < 1 || o->prune_window > MCHIP_LD_MAX_WINDOW ? "--prune-window must lie in 1 ... 4096 variants" : NULL,
+			MC_EXIT_INVALID_USER_SETUP))) return rc;
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -988,6 +1005,12 @@ int main(int argc, const char **argv)
 	if ((rc = parse_options(&o, argc, argv))) return rc;	/* -h included: the reference's -h leaves with status 1 */
 	mchip_progress_note(o.bed_prefix ? "mc_read_bed" : "mc_read_structure");
 	if ((rc = o.bed_prefix ? mc_read_bed(&o, &d) : mc_read_structure(&o, &d))) return rc;
+	if (o.prune) {	/* the data set is the pruned one from here on; the lists say which variants it holds */
+		mchip_progress_note("mc_ld_prune_data");
+		if ((rc = mc_ld_prune_data(&o, &d))) return rc;
+		printf("LD pruning: kept %d of %d variants (r2 > %g within %d)\n", d.L, d.L_file, o.prune_t, o.prune_window);
+		if (o.write_files && (rc = mc_write_prune_lists(&o, &d))) return rc;
+	}
 	mchip_progress_note("estimate_model");
 	if (o.em.verbosity >= MC_TALKATIVE)
 		fprintf(stderr, "INFO: Finished reading data: %d %d-ploid individuals at %d loci.\n", d.I, d.ploidy, d.L);

@@ -370,6 +370,7 @@ void mc_free_data(mc_cli_data *dat)
 	if (dat->pops) for (int n = 0; n < dat->numpops; n++) free(dat->pops[n]);
 	free(dat->pops);
 	free(dat->bed);
+	free(dat->bim_text); free(dat->chrom); free(dat->variant_id); free(dat->variant_of);
 	if (dat->lazy) dat->lazy->release(dat->lazy);
 	memset(dat, 0, sizeof *dat);
 }
