@@ -529,34 +529,34 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_rows(const double *__res
 	if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 /* the end of a batched accelerated cycle in one single-block launch: emll (when in1 is given: the dual pass's second log
- * likelihood) -> sc[1], the extrapolated point's log likelihood -> sc[2] (k_reduce_sum's sums), accept iff ll > emll */
-__global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_accept(const double *__restrict__ in1, const double *__restrict__ in2, int n, double *sc,
-		int *cyc, const int *stop)
+ * likelihood) -> sc->emll, the extrapolated point's log likelihood -> sc->ll_point (k_reduce_sum's sums), accept iff ll > emll */
+__global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_accept(const double *__restrict__ in1, const double *__restrict__ in2, int n, mchip_scalars *sc,
+		mchip_cycle_flags *cyc, const int *stop)
 {
 	__shared__ double red[MCHIP_BLOCK];
 	if (stop && *stop) return;
 	if (in1) {
 		const double v = block_ordered_sum(in1, n, red);
-		if (threadIdx.x == 0) sc[1] = v;
+		if (threadIdx.x == 0) sc->emll = v;
 	}
 	const double v2 = block_ordered_sum(in2, n, red);
 	if (threadIdx.x == 0) {
-		sc[2] = v2;
-		cyc[1] = (!cyc[0] && sc[2] > sc[1]) ? 1 : 0;
+		sc->ll_point = v2;
+		cyc->accepted = (!cyc->no_update && sc->ll_point > sc->emll) ? 1 : 0;
 	}
 }
 
-/* the 2 * nout sums of a dot-product pass in one launch (block x < nout: eta part x -> sc[16 + x]; the others: p part -> sc[20 + .]):
- * each block is k_reduce_sum on its array, same order, same tree */
+/* the 2 * nout sums of a dot-product pass in one launch (block x < nout: eta part x -> sc->dots[DOT_ETA + x]; the others: p part ->
+ * sc->dots[DOT_P + .]): each block is k_reduce_sum on its array, same order, same tree */
 __global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_dots(const double *__restrict__ part_q, int gq, const double *__restrict__ part_p, int gp,
-		int nout, double *sc, const int *stop)
+		int nout, mchip_scalars *sc, const int *stop)
 {
 	__shared__ double red[MCHIP_BLOCK];
 	if (stop && *stop) return;
 	const int x = blockIdx.x;
 	const double *in = x < nout ? part_q + (size_t)x * gq : part_p + (size_t)(x - nout) * gp;
 	const int n = x < nout ? gq : gp;
-	double *out = x < nout ? sc + 16 + x : sc + 20 + (x - nout);
+	double *out = x < nout ? sc->dots + DOT_ETA + x : sc->dots + DOT_P + (x - nout);
 	const double v = block_ordered_sum(in, n, red);
 	if (threadIdx.x == 0) *out = v;
 }
@@ -852,25 +852,26 @@ __global__ void k_add(const double *__restrict__ a, const double *__restrict__ b
 	if (idx < n) out[idx] = a[idx] + b[idx];
 }
 
-/* step_size() of accel_em.c:130-243 on the device (batched accelerated runs): sc[16..18] / sc[20..22] are the eta / p
- * parts of utu, u(v-u), (v-u)^2 (eta terms first, accel_em.c:143-184); the step goes to sc[24]; cyc[0] = 1 when the
+/* step_size() of accel_em.c:130-243 on the device (batched accelerated runs): sc->dots from DOT_ETA / DOT_P on are the eta / p
+ * parts of utu, u(v-u), (v-u)^2 (eta terms first, accel_em.c:143-184); the step goes to sc->step; cyc->no_update = 1 when the
  * reference would leave the cycle without an update (NaN / infinite step, S3's sqrt(utu) < 1e-8 guard) */
-__device__ __forceinline__ void step_size_body(double *sc, int scheme, int *cyc)
+__device__ __forceinline__ void step_size_body(mchip_scalars *sc, int scheme, mchip_cycle_flags *cyc)
 {
-	const double utu = sc[16] + sc[20], utvu = sc[17] + sc[21], vutvu = sc[18] + sc[22];
+	const double *eta = sc->dots + DOT_ETA, *p = sc->dots + DOT_P;
+	const double utu = eta[0] + p[0], utvu = eta[1] + p[1], vutvu = eta[2] + p[2];
 	double s;
 	if (scheme == 1) s = utu / utvu;
 	else if (scheme == 2) s = utvu / vutvu;
 	else if (scheme == 3) s = (sqrt(utu) < 1e-8) ? (double)NAN : -sqrt(utu / vutvu);
 	else s = -utu / utvu;				/* QN with one secant */
 	if (scheme < 4 && s > -1) s = -1;		/* SQUAREM clamp (accel_em.c:236-237); false for NaN */
-	sc[24] = s;
-	cyc[0] = (s != s || s - s != 0.0) ? 1 : 0;	/* isnan || isinf */
+	sc->step = s;
+	cyc->no_update = (s != s || s - s != 0.0) ? 1 : 0;	/* isnan || isinf */
 }
 /* the six sums of the step-size dot products (k_reduce_dots's blocks, one after the other: same order, same tree, same bits) and
  * step_size (accel_em.c:130-243) in one single-block launch */
 __global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_dots_step(const double *__restrict__ part_q, int gq, const double *__restrict__ part_p,
-		int gp, double *sc, int scheme, int *cyc, const int *stop)
+		int gp, mchip_scalars *sc, int scheme, mchip_cycle_flags *cyc, const int *stop)
 {
 	__shared__ double red[MCHIP_BLOCK];
 	if (stop && *stop) return;
@@ -878,26 +879,26 @@ __global__ __launch_bounds__(MCHIP_BLOCK) void k_reduce_dots_step(const double *
 		const double *in = x < 3 ? part_q + (size_t)x * gq : part_p + (size_t)(x - 3) * gp;
 		const int n = x < 3 ? gq : gp;
 		const double v = block_ordered_sum(in, n, red);
-		if (threadIdx.x == 0) sc[(x < 3 ? 16 : 20) + (x % 3)] = v;
+		if (threadIdx.x == 0) sc->dots[(x < 3 ? DOT_ETA : DOT_P) + (x % 3)] = v;
 	}
 	if (threadIdx.x == 0) step_size_body(sc, scheme, cyc);
 }
-__global__ void k_accept(const double *sc, int *cyc, const int *stop)
+__global__ void k_accept(const mchip_scalars *sc, mchip_cycle_flags *cyc, const int *stop)
 {
 	if (threadIdx.x || blockIdx.x || (stop && *stop)) return;
-	cyc[1] = (!cyc[0] && sc[2] > sc[1]) ? 1 : 0;
+	cyc->accepted = (!cyc->no_update && sc->ll_point > sc->emll) ? 1 : 0;
 }
 
 /* the cycle's outcome goes back to the slot every cycle starts from: the extrapolated point if accepted, else the second
  * EM iterate (pindex = tindex / findex, accel_em.c:89-101), so that the slot roles are the same in every cycle */
 __global__ void k_select_copy(double *qdst, const double *__restrict__ q_if_accepted, const double *__restrict__ q_otherwise, size_t nq,
 			      double *pdst, const double *__restrict__ p_if_accepted, const double *__restrict__ p_otherwise, size_t np,
-			      const int *cyc, const int *stop)
+			      const mchip_cycle_flags *cyc, const int *stop)
 {
 	size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (idx >= nq + np || (stop && *stop)) return;
-	if (idx < nq) qdst[idx] = cyc[1] ? q_if_accepted[idx] : q_otherwise[idx];
-	else { idx -= nq; pdst[idx] = cyc[1] ? p_if_accepted[idx] : p_otherwise[idx]; }
+	if (idx < nq) qdst[idx] = cyc->accepted ? q_if_accepted[idx] : q_otherwise[idx];
+	else { idx -= nq; pdst[idx] = cyc->accepted ? p_if_accepted[idx] : p_otherwise[idx]; }
 }
 
 /* ------------------------------------------------------------------ helpers */
@@ -1260,10 +1261,10 @@ int mchip_create(mchip_context **out, int device)
 	}
 	hipDeviceProp_t prop;
 	ctx->n_cu = (MCHIP_WAIT(hipGetDeviceProperties(&prop, device)) == hipSuccess) ? prop.multiProcessorCount : 256;
-	if (MCHIP_WAIT(hipHostMalloc((void **)&ctx->h_pinned, 64 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
-	    MCHIP_WAIT(hipMalloc((void **)&ctx->d_scalars, 64 * sizeof(double))) != hipSuccess ||
+	if (MCHIP_WAIT(hipHostMalloc((void **)&ctx->h_pinned, sizeof(mchip_scalars), hipHostMallocDefault)) != hipSuccess ||
+	    MCHIP_WAIT(hipMalloc((void **)&ctx->d_scalars, sizeof(mchip_scalars))) != hipSuccess ||
 	    MCHIP_WAIT(hipMalloc((void **)&ctx->d_run, sizeof(mchip_run_state))) != hipSuccess ||
-	    MCHIP_WAIT(hipMalloc((void **)&ctx->d_cyc, 4 * sizeof(int))) != hipSuccess ||
+	    MCHIP_WAIT(hipMalloc((void **)&ctx->d_cyc, sizeof(mchip_cycle_flags))) != hipSuccess ||
 	    MCHIP_WAIT(hipEventCreate(&ctx->ev_begin)) != hipSuccess || MCHIP_WAIT(hipEventCreate(&ctx->ev_end)) != hipSuccess) {
 		delete ctx;
 		return MCHIP_ERR_ALLOC;
@@ -1692,8 +1693,8 @@ int mchip_data_counts(mchip_context *ctx, uint64_t *nonempty_cells, uint64_t *al
 	if (!ctx->T) return fail(ctx, MCHIP_ERR_STATE, "no genotypes set%s", nullptr);
 	if (!ctx->counts_valid) {	/* integer sums: order does not matter */
 		HIPCHK(hipSetDevice(ctx->device));
-		unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(ctx->d_scalars + 60), h_cnt[2] = {0, 0};
-		HIPCHK(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), ctx->stream));
+		unsigned long long *d_cnt = ctx->d_scalars->cells, h_cnt[2] = {0, 0};
+		HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, ctx->stream));
 		const size_t n = (size_t)((ctx->I + 7) / 8) * ctx->T;
 		hipLaunchKernelGGL(k_count_cells, dim3(nblk_capped(n, 256, 65536)), dim3(256), 0, ctx->stream, ctx->d_gtA,
 				   ctx->I, ctx->L, ctx->ploidy, ctx->T, ctx->d_col_locus, ctx->d_col_allele, d_cnt);
@@ -1788,7 +1789,7 @@ static int set_model_impl(mchip_context *ctx, int K, int admixture, int eta_cons
 	HIPCHK(hipMalloc((void **)&ctx->d_Spart, (size_t)ctx->geo.n_lchunks * ctx->I * K * sizeof(double)));
 	HIPCHK(hipMalloc((void **)&ctx->d_llpart, (size_t)ctx->geo.n_llpart * sizeof(double)));
 	HIPCHK(hipMalloc((void **)&ctx->d_llpart2, (size_t)ctx->geo.n_llpart * sizeof(double)));
-	HIPCHK(hipMalloc((void **)&ctx->d_redpart, (size_t)3 * 1024 * sizeof(double)));
+	HIPCHK(hipMalloc((void **)&ctx->d_redpart, DOT_PARTIALS * sizeof(double)));
 	if (needs_byte_flags(ctx->max_M)) {
 		HIPCHK(hipMalloc((void **)&ctx->d_flags, KT));
 	}
@@ -1911,9 +1912,10 @@ int mchip_empty_individuals(const mchip_context *ctx, int *first)
 	return (int)ctx->empty_rows.size();
 }
 
-static int fetch_scalars(mchip_context *ctx, int first, int count, double *out)
+/* out[0 .. count) = the `count` doubles of d_scalars that begin at `field` */
+static int fetch_scalars(mchip_context *ctx, const double *field, int count, double *out)
 {
-	HIPCHK(hipMemcpyAsync(ctx->h_pinned, ctx->d_scalars + first, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(ctx->h_pinned, field, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	for (int x = 0; x < count; x++) out[x] = ctx->h_pinned[x];
 	return MCHIP_OK;
@@ -1922,35 +1924,42 @@ static int fetch_scalars(mchip_context *ctx, int first, int count, double *out)
 /* shared eta: eta[to] = normalise(sum_i S_ik), project (em_alg.c:604-648) */
 static int finalize_shared_eta(mchip_context *ctx, int to, const int *stop = nullptr, double add = 0.0, int project = 1)
 {
-	hipLaunchKernelGGL(k_column_sums, dim3(ctx->K), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_sik, ctx->I, ctx->K, ctx->d_scalars + 8, stop);
-	hipLaunchKernelGGL(k_normalize_row, dim3(1), dim3(64), 0, ctx->stream, ctx->d_scalars + 8, ctx->K, ctx->d_q[to], stop, add);
+	double *sums = ctx->d_scalars->eta_sums;	/* one per block of k_column_sums: K <= MCHIP_MAX_K of them */
+	hipLaunchKernelGGL(k_column_sums, dim3(ctx->K), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_sik, ctx->I, ctx->K, sums, stop);
+	hipLaunchKernelGGL(k_normalize_row, dim3(1), dim3(64), 0, ctx->stream, sums, ctx->K, ctx->d_q[to], stop, add);
 	if (ctx->do_projection && project) ctx->kt->project_q(1, ctx->K, ctx->d_q[to], ctx->eta_lb, stop, ctx->stream);
 	HIPCHK(hipGetLastError());
 	return MCHIP_OK;
 }
 
-/* d_scalars[slot] = the sum of the n partial log likelihoods a pass left in d_llpart */
-static void reduce_ll(mchip_context *ctx, int n, int slot, const int *stop)
+/* *ll (a field of d_scalars) = the sum of the n partial log likelihoods a pass left in d_llpart */
+static void reduce_ll(mchip_context *ctx, int n, double *ll, const int *stop)
 {
-	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, n, ctx->d_scalars + slot, stop);
+	hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_llpart, n, ll, stop);
+}
+/* the stop rule of the batched loops on the E step that has just run; it adds that step's partial log likelihoods up itself */
+static void stop_check(mchip_context *ctx)
+{
+	hipLaunchKernelGGL(k_stop_check, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_run, &ctx->d_scalars->logL, ctx->d_llpart, ctx->ll_parts);
 }
 
-/* one pass that takes the log likelihood (kt->accum_q or kt->loglik), between the marks of a profiled run; slot >= 0: its partial
- * sums' sum goes to d_scalars[slot] (else the caller's next kernel adds them up) */
+/* one pass that takes the log likelihood (kt->accum_q or kt->loglik), between the marks of a profiled run; ll given: its partial
+ * sums' sum goes to that field of d_scalars (else the caller's next kernel adds them up) */
 typedef void (*ll_pass_fn)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);
-static void ll_pass(mchip_context *ctx, int kind, ll_pass_fn launch, const mchip_pass_args &a, const mchip_plan &p, int slot, const int *stop = nullptr)
+static void ll_pass(mchip_context *ctx, int kind, ll_pass_fn launch, const mchip_pass_args &a, const mchip_plan &p, double *ll, const int *stop = nullptr)
 {
 	prof_mark(ctx, kind, true);
 	launch(a, p, ctx->stream);
 	prof_mark(ctx, kind, false);
-	if (slot >= 0) reduce_ll(ctx, p.ll_parts, slot, stop);
+	if (ll) reduce_ll(ctx, p.ll_parts, ll, stop);
 }
 
-/* mixture model: E step (mode 0, optionally followed by the M step) or logL_mixture (mode 1) */
-static int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int mode, const int *stop = nullptr, int ll_slot = -1,
+/* mixture model: E step (mode 0, optionally followed by the M step) or logL_mixture (mode 1); ll: the field of d_scalars that
+ * receives the log likelihood, by default logL for an E step and emll for logL_mixture */
+static int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int mode, const int *stop = nullptr, double *ll = nullptr,
 		       bool defer_ll = false)
 {
-	if (ll_slot < 0) ll_slot = mode ? 1 : 0;	/* d_scalars entry that receives the log likelihood */
+	if (!ll) ll = mode ? &ctx->d_scalars->emll : &ctx->d_scalars->logL;
 	const size_t KT = (size_t)ctx->K * ctx->T;
 	hipLaunchKernelGGL(k_logp, dim3(nblk(KT)), dim3(256), 0, ctx->stream, ctx->d_p[from], ctx->d_logp, KT, mode == 0, stop);
 	mchip_pass_args a = pass_args(ctx, from);
@@ -1963,7 +1972,7 @@ static int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int m
 	const int nb = mix_ll_parts(ctx->I);
 	ctx->kt->mix_finalize(ctx->I, ctx->geo.n_lchunks, ctx->d_Spart, ctx->d_q[from], ctx->d_sik, ctx->d_llpart, mode, stop, ctx->stream);
 	ctx->ll_parts = nb;
-	if (!defer_ll) reduce_ll(ctx, nb, ll_slot, stop);
+	if (!defer_ll) reduce_ll(ctx, nb, ll, stop);
 	if (do_mstep) {
 		int rc = finalize_shared_eta(ctx, to, stop);		/* em_alg.c:916-962 */
 		if (rc) return rc;
@@ -1985,15 +1994,16 @@ static int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int m
 static int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const int *stop = nullptr, const int *skip_ind = nullptr,
 		     bool defer_ll = false)
 {
-	if (!ctx->admixture) return run_mixture(ctx, from, to, do_mstep, 0, stop, -1, defer_ll);
+	if (!ctx->admixture) return run_mixture(ctx, from, to, do_mstep, 0, stop, nullptr, defer_ll);
 	mchip_pass_args a = pass_args(ctx, from);
 	a.stop = stop;
 	a.skip_ind = skip_ind;
 	const mchip_plan plan = plan_for(ctx->kt, a, ctx->knob);
-	const int indiv = ctx->qstride != 0, ll_slot = defer_ll ? -1 : 0;
+	const int indiv = ctx->qstride != 0;
+	double *ll = defer_ll ? nullptr : &ctx->d_scalars->logL;
 	const estep_finish fin = finish_for(plan, ctx->K, ctx->max_M, indiv, do_mstep, ctx->knob);
 	/* the individual pass over these very parameters already ran (mchip_loglik_prefetch): its sums are in Spart, its log likelihood
-	 * in d_scalars[2] */
+	 * in d_scalars->ll_point */
 	const bool s_cached = !plan.col.ll && do_mstep && !stop && ctx->s_cache_slot == from;
 	if (do_mstep && !s_cached && plan.pair) {
 		/* both passes of this E step as one launch (k_estep_pair: the same bodies, the same bits).  The choice depends on the model
@@ -2010,7 +2020,7 @@ static int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const i
 			ctx->pair_used++;
 		}
 		ctx->ll_parts = plan.ll_parts;
-		if (!defer_ll) reduce_ll(ctx, plan.ll_parts, 0, stop);
+		if (ll) reduce_ll(ctx, plan.ll_parts, ll, stop);
 	} else {
 		/* the column pass: N-side sums of an M step; where it is the pass that takes the log likelihood, on every E step */
 		if (do_mstep || plan.col.ll) {
@@ -2019,9 +2029,9 @@ static int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const i
 			prof_mark(ctx, MCHIP_KERN_ACCUM_P, false);
 		}
 		if (s_cached) {
-			HIPCHK(hipMemcpyAsync(ctx->d_scalars, ctx->d_scalars + 2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+			HIPCHK(hipMemcpyAsync(&ctx->d_scalars->logL, &ctx->d_scalars->ll_point, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
 		} else {
-			ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, ll_slot, stop);
+			ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, ll, stop);
 			ctx->ll_parts = plan.ll_parts;
 		}
 	}
@@ -2062,6 +2072,21 @@ static int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const i
 	return MCHIP_OK;
 }
 
+/* A launch-bound sequence as a hipGraph: unless *exec holds one, what enqueue() puts on the stream is captured into it.  Returns
+ * whether there is a graph to launch; if not (capture unavailable, or enqueue failed) the caller enqueues eagerly, and no error of
+ * the attempt is left behind for its HIPCHK(hipGetLastError()). */
+static bool captured(mchip_context *ctx, hipGraphExec_t *exec, const std::function<int()> &enqueue)
+{
+	hipGraph_t graph = nullptr;
+	if (*exec || MCHIP_WAIT(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal)) != hipSuccess) return *exec != nullptr;
+	const int rc = enqueue();
+	const hipError_t e = MCHIP_WAIT(hipStreamEndCapture(ctx->stream, &graph));
+	if (rc || e != hipSuccess || !graph || MCHIP_WAIT(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0)) != hipSuccess) *exec = nullptr;
+	if (graph) (void)MCHIP_WAIT(hipGraphDestroy(graph));
+	(void)hipGetLastError();
+	return *exec != nullptr;
+}
+
 int mchip_em_run(mchip_context *ctx, int slot, int n_steps, mchip_run_state *state)
 {
 	MCHIP_ENTRY();
@@ -2075,27 +2100,11 @@ int mchip_em_run(mchip_context *ctx, int slot, int n_steps, mchip_run_state *sta
 	/* The step is a launch-bound chain of 6-7 kernels on small data sets: capture it once into a hipGraph and replay it
 	 * (eager launches cost ~8 us of host time each here, graph nodes ~1.5 us of device time).  Event marks cannot be
 	 * captured, so profiled runs stay eager. */
-	bool use_graph = !ctx->profiling && n_steps >= 4 && !ctx->knob.no_graph;
-	if (use_graph && !ctx->step_graph[slot]) {
-		hipGraph_t graph = nullptr;
-		if (MCHIP_WAIT(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal)) == hipSuccess) {
-			rc = run_estep(ctx, slot, slot, 1, stop, nullptr, true);
-			hipLaunchKernelGGL(k_stop_check, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_run, ctx->d_scalars, ctx->d_llpart, ctx->ll_parts);
-			const hipError_t e = MCHIP_WAIT(hipStreamEndCapture(ctx->stream, &graph));
-			if (rc || e != hipSuccess || !graph || MCHIP_WAIT(hipGraphInstantiate(&ctx->step_graph[slot], graph, nullptr, nullptr, 0)) != hipSuccess)
-				ctx->step_graph[slot] = nullptr;
-			if (graph) (void)MCHIP_WAIT(hipGraphDestroy(graph));
-			(void)hipGetLastError();
-		}
-		if (!ctx->step_graph[slot]) use_graph = false;	/* capture unavailable: eager path below */
-	}
+	const auto step = [&] { const int r = run_estep(ctx, slot, slot, 1, stop, nullptr, true); if (!r) stop_check(ctx); return r; };
+	const bool use_graph = !ctx->profiling && n_steps >= 4 && !ctx->knob.no_graph && captured(ctx, &ctx->step_graph[slot], step);
 	for (int s = 0; s < n_steps; s++) {
-		if (use_graph) {
-			HIPCHK(hipGraphLaunch(ctx->step_graph[slot], ctx->stream));
-			continue;
-		}
-		if ((rc = run_estep(ctx, slot, slot, 1, stop, nullptr, true))) return rc;
-		hipLaunchKernelGGL(k_stop_check, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_run, ctx->d_scalars, ctx->d_llpart, ctx->ll_parts);
+		if (use_graph) HIPCHK(hipGraphLaunch(ctx->step_graph[slot], ctx->stream));
+		else if ((rc = step())) return rc;
 	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(state, ctx->d_run, sizeof *state, hipMemcpyDeviceToHost, ctx->stream));
@@ -2112,7 +2121,7 @@ int mchip_em_step(mchip_context *ctx, int from, int to, double *loglik)
 	HIPCHK(hipSetDevice(ctx->device));
 	if ((rc = run_estep(ctx, from, to, 1))) return rc;
 	if (ctx->qstride) ctx->empty_rows_nan[to] = 1;
-	if (loglik) return fetch_scalars(ctx, 0, 1, loglik);
+	if (loglik) return fetch_scalars(ctx, &ctx->d_scalars->logL, 1, loglik);
 	return MCHIP_OK;
 }
 
@@ -2122,7 +2131,7 @@ int mchip_last_loglik(mchip_context *ctx, double *loglik)
 	if (!ctx || !loglik) return MCHIP_ERR_INVALID;
 	if (!ctx->have_ll) return fail(ctx, MCHIP_ERR_STATE, "no log likelihood computed yet%s", nullptr);
 	HIPCHK(hipSetDevice(ctx->device));
-	return fetch_scalars(ctx, 0, 1, loglik);
+	return fetch_scalars(ctx, &ctx->d_scalars->logL, 1, loglik);
 }
 
 int mchip_e_step(mchip_context *ctx, int slot, double *loglik)
@@ -2132,7 +2141,7 @@ int mchip_e_step(mchip_context *ctx, int slot, double *loglik)
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(ctx->device));
 	if ((rc = run_estep(ctx, slot, slot, 0))) return rc;
-	if (loglik) return fetch_scalars(ctx, 0, 1, loglik);
+	if (loglik) return fetch_scalars(ctx, &ctx->d_scalars->logL, 1, loglik);
 	return MCHIP_OK;
 }
 
@@ -2144,13 +2153,13 @@ int mchip_loglik(mchip_context *ctx, int slot, double *loglik)
 	HIPCHK(hipSetDevice(ctx->device));
 	if (!ctx->admixture) {
 		if ((rc = run_mixture(ctx, slot, slot, 0, 1))) return rc;
-		if (loglik) return fetch_scalars(ctx, 1, 1, loglik);
+		if (loglik) return fetch_scalars(ctx, &ctx->d_scalars->emll, 1, loglik);
 		return MCHIP_OK;
 	}
 	const mchip_pass_args a = pass_args(ctx, slot);
-	ll_pass(ctx, MCHIP_KERN_LOGLIK, ctx->kt->loglik, a, plan_for(ctx->kt, a, ctx->knob), 1);
+	ll_pass(ctx, MCHIP_KERN_LOGLIK, ctx->kt->loglik, a, plan_for(ctx->kt, a, ctx->knob), &ctx->d_scalars->emll);
 	HIPCHK(hipGetLastError());
-	if (loglik) return fetch_scalars(ctx, 1, 1, loglik);
+	if (loglik) return fetch_scalars(ctx, &ctx->d_scalars->emll, 1, loglik);
 	return MCHIP_OK;
 }
 
@@ -2163,10 +2172,10 @@ int mchip_loglik_prefetch(mchip_context *ctx, int slot, double *loglik)
 	const mchip_plan plan = plan_for(ctx->kt, a, ctx->knob);
 	if (!ctx->admixture || plan.col.ll) return mchip_loglik(ctx, slot, loglik);	/* nothing to share on those paths */
 	HIPCHK(hipSetDevice(ctx->device));
-	ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, 2);	/* S-side sums -> Spart, logL -> d_scalars[2] */
+	ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, &ctx->d_scalars->ll_point);	/* S-side sums -> Spart */
 	HIPCHK(hipGetLastError());
 	ctx->s_cache_slot = slot;
-	if (loglik) return fetch_scalars(ctx, 2, 1, loglik);
+	if (loglik) return fetch_scalars(ctx, &ctx->d_scalars->ll_point, 1, loglik);
 	return MCHIP_OK;
 }
 
@@ -2461,14 +2470,13 @@ int mchip_secant(mchip_context *ctx, int which, int j, int to, int from)
 	return MCHIP_OK;
 }
 
-/* the dot products' eta parts land in d_scalars[16 + x], the p parts in d_scalars[20 + x] */
+/* the dot products' eta parts land in d_scalars->dots[DOT_ETA + x], the p parts in d_scalars->dots[DOT_P + x] */
 static void dots_enqueue(mchip_context *ctx, const double *uq, const double *vq, const double *u2q,
 			 const double *up, const double *vp, const double *u2p, int mode, int nout, const int *stop = nullptr)
 {
 	const size_t KT = (size_t)ctx->K * ctx->T;
-	const int gq = (int)((ctx->nq + 4095) / 4096) > 512 ? 512 : (int)((ctx->nq + 4095) / 4096);
-	const int gp = (int)((KT + 4095) / 4096) > 512 ? 512 : (int)((KT + 4095) / 4096);
-	double *part_q = ctx->d_redpart, *part_p = ctx->d_redpart + 3 * 512;
+	const int gq = dot_blocks((size_t)ctx->nq), gp = dot_blocks(KT);
+	double *part_q = dot_part_eta(ctx->d_redpart), *part_p = dot_part_p(ctx->d_redpart);
 	hipLaunchKernelGGL(k_dots, dim3(gq), dim3(MCHIP_BLOCK), 0, ctx->stream, uq, vq, u2q, (size_t)ctx->nq, mode, part_q, stop);
 	hipLaunchKernelGGL(k_dots, dim3(gp), dim3(MCHIP_BLOCK), 0, ctx->stream, up, vp, u2p, KT, mode, part_p, stop);
 	hipLaunchKernelGGL(k_reduce_dots, dim3(2 * nout), dim3(MCHIP_BLOCK), 0, ctx->stream, part_q, gq, part_p, gp, nout, ctx->d_scalars, stop);
@@ -2480,9 +2488,9 @@ static int dots_common(mchip_context *ctx, const double *uq, const double *vq, c
 	dots_enqueue(ctx, uq, vq, u2q, up, vp, u2p, mode, nout);
 	HIPCHK(hipGetLastError());
 	double tmp[8];
-	int rc = fetch_scalars(ctx, 16, 8, tmp);
+	int rc = fetch_scalars(ctx, ctx->d_scalars->dots, 8, tmp);
 	if (rc) return rc;
-	for (int x = 0; x < nout; x++) out[x] = tmp[x] + tmp[4 + x];	/* eta terms first, then p (accel_em.c:143-184) */
+	for (int x = 0; x < nout; x++) out[x] = tmp[DOT_ETA + x] + tmp[DOT_P + x];	/* eta terms first, then p (accel_em.c:143-184) */
 	return MCHIP_OK;
 }
 
@@ -2542,15 +2550,16 @@ static int accel_cycle_enqueue(mchip_context *ctx, int A, int scheme)
 {
 	const int B = (A + 1) % 3, C = (A + 2) % 3;
 	const int *stop = &ctx->d_run->stopped;
-	int *cyc = ctx->d_cyc;
+	mchip_cycle_flags *cyc = ctx->d_cyc;
+	mchip_scalars *sc = ctx->d_scalars;
 	const size_t KT = (size_t)ctx->K * ctx->T, nq = (size_t)ctx->nq;
 	int rc;
 	/* em_2_steps (em_alg.c:1072-1211): E(A) M(->B) stop, u = B - A; E(B) M(->C) stop, v = C - B */
-	if ((rc = run_estep(ctx, A, B, 1, stop, cyc + 1, true))) return rc;
-	hipLaunchKernelGGL(k_stop_check, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_run, ctx->d_scalars, ctx->d_llpart, ctx->ll_parts);
+	if ((rc = run_estep(ctx, A, B, 1, stop, &cyc->accepted, true))) return rc;
+	stop_check(ctx);
 	if ((rc = run_estep(ctx, B, C, 1, stop, nullptr, true))) return rc;
-	hipLaunchKernelGGL(k_stop_check, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_run, ctx->d_scalars, ctx->d_llpart, ctx->ll_parts);
-	/* emll = log_likelihood(findex = C) -> d_scalars[1] (accel_em.c:53).  Admixture model: where the dual individual pass
+	stop_check(ctx);
+	/* emll = log_likelihood(findex = C) -> sc->emll (accel_em.c:53).  Admixture model: where the dual individual pass
 	 * exists, emll is taken below, by the pass that visits the extrapolated point (same kernel arithmetic, same bits) */
 	mchip_pass_args dual = pass_args(ctx, B);
 	dual.stop = stop;
@@ -2560,29 +2569,27 @@ static int accel_cycle_enqueue(mchip_context *ctx, int A, int scheme)
 	const mchip_plan plan = plan_for(ctx->kt, dual, ctx->knob);	/* (of slot C's arguments too: a plan does not depend on the slot) */
 	const bool use_dual = ctx->admixture && plan.dual;
 	if (!ctx->admixture) {
-		if ((rc = run_mixture(ctx, C, C, 0, 1, stop, 1))) return rc;	/* logL_mixture */
+		if ((rc = run_mixture(ctx, C, C, 0, 1, stop, &sc->emll))) return rc;	/* logL_mixture */
 	} else if (!use_dual) {
 		mchip_pass_args a = pass_args(ctx, C);
 		a.stop = stop;
-		ll_pass(ctx, MCHIP_KERN_LOGLIK, ctx->kt->loglik, a, plan, 1, stop);
+		ll_pass(ctx, MCHIP_KERN_LOGLIK, ctx->kt->loglik, a, plan, &sc->emll, stop);
 	}
-	/* step size (accel_em.c:130-243) -> d_scalars[24] */
 	{	/* (the secants u = B - A, v = C - B are formed inside the kernels that use them: nothing stores them in a batched cycle) */
-		const int gq = (int)((ctx->nq + 4095) / 4096) > 512 ? 512 : (int)((ctx->nq + 4095) / 4096);
-		const int gp = (int)((KT + 4095) / 4096) > 512 ? 512 : (int)((KT + 4095) / 4096);
-		double *part_q = ctx->d_redpart, *part_p = ctx->d_redpart + 3 * 512;
+		const int gq = dot_blocks(nq), gp = dot_blocks(KT);
+		double *part_q = dot_part_eta(ctx->d_redpart), *part_p = dot_part_p(ctx->d_redpart);
 		hipLaunchKernelGGL(k_dots_slots, dim3(gq + gp), dim3(MCHIP_BLOCK), 0, ctx->stream, ctx->d_q[A], ctx->d_q[B], ctx->d_q[C], nq, part_q, (unsigned)gq,
 				   ctx->d_p[A], ctx->d_p[B], ctx->d_p[C], KT, part_p, stop);
-		/* step size (accel_em.c:130-243) -> d_scalars[24], by the launch that adds up the partial dot products */
-		hipLaunchKernelGGL(k_reduce_dots_step, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, part_q, gq, part_p, gp, ctx->d_scalars, scheme, cyc, stop);
+		/* step size (accel_em.c:130-243) -> sc->step, by the launch that adds up the partial dot products */
+		hipLaunchKernelGGL(k_reduce_dots_step, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, part_q, gq, part_p, gp, sc, scheme, cyc, stop);
 	}
 	/* accelerated_update (accel_em.c:422-551): B = A - 2 s u + s^2 (v - u) (or A + u + s v), projected; its log likelihood,
-	 * taken by the pass that also leaves the S-side sums -> d_scalars[2] */
+	 * taken by the pass that also leaves the S-side sums -> sc->ll_point */
 	hipLaunchKernelGGL(k_accel_update_slots, dim3(nblk(nq + KT)), dim3(256), 0, ctx->stream, ctx->d_q[A], ctx->d_q[B], ctx->d_q[C], ctx->d_q[B], nq,
-			   ctx->d_p[A], ctx->d_p[B], ctx->d_p[C], ctx->d_p[B], KT, scheme == 4, ctx->d_scalars + 24, stop);
+			   ctx->d_p[A], ctx->d_p[B], ctx->d_p[C], ctx->d_p[B], KT, scheme == 4, &sc->step, stop);
 	if ((rc = project_slot(ctx, B, stop))) return rc;
 	if (!ctx->admixture) {
-		if ((rc = run_mixture(ctx, B, B, 0, 1, stop, 2))) return rc;	/* nothing of this pass serves the next E step */
+		if ((rc = run_mixture(ctx, B, B, 0, 1, stop, &sc->ll_point))) return rc;	/* nothing of this pass serves the next E step */
 	} else {
 		if (use_dual) {
 			prof_mark(ctx, MCHIP_KERN_DUAL, true);
@@ -2591,15 +2598,15 @@ static int accel_cycle_enqueue(mchip_context *ctx, int A, int scheme)
 		} else {
 			mchip_pass_args a = pass_args(ctx, B);
 			a.stop = stop;
-			ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, -1);	/* (k_reduce_accept adds its partial sums up) */
+			ll_pass(ctx, MCHIP_KERN_ACCUM_Q, ctx->kt->accum_q, a, plan, nullptr);	/* (k_reduce_accept adds its partial sums up) */
 		}
 	}
 	/* the two log likelihoods' sums and accept iff ll > emll, one launch; the outcome goes back to slot A */
 	if (ctx->admixture)
 		hipLaunchKernelGGL(k_reduce_accept, dim3(1), dim3(MCHIP_BLOCK), 0, ctx->stream, use_dual ? ctx->d_llpart2 : (const double *)nullptr, ctx->d_llpart,
-				   plan.ll_parts, ctx->d_scalars, cyc, stop);
+				   plan.ll_parts, sc, cyc, stop);
 	else
-		hipLaunchKernelGGL(k_accept, dim3(1), dim3(64), 0, ctx->stream, ctx->d_scalars, cyc, stop);
+		hipLaunchKernelGGL(k_accept, dim3(1), dim3(64), 0, ctx->stream, sc, cyc, stop);
 	hipLaunchKernelGGL(k_select_copy, dim3(nblk(nq + KT)), dim3(256), 0, ctx->stream, ctx->d_q[A], ctx->d_q[B], ctx->d_q[C], nq,
 			   ctx->d_p[A], ctx->d_p[B], ctx->d_p[C], KT, cyc, stop);
 	HIPCHK(hipGetLastError());
@@ -2619,33 +2626,22 @@ int mchip_accel_run(mchip_context *ctx, int slot, int scheme, int n_cycles, mchi
 	HIPCHK(hipMemcpyAsync(ctx->d_run, state, sizeof *state, hipMemcpyHostToDevice, ctx->stream));
 	/* does Spart hold the S-side sums of this very slot (mchip_loglik_prefetch, or the accepted cycle that ended the
 	 * previous call)?  The first E step of the batch is told through the device flag the later cycles set themselves */
-	const int cyc0[4] = { 0, (ctx->admixture && ctx->s_cache_slot == slot) ? 1 : 0, 0, 0 };
-	HIPCHK(hipMemcpyAsync(ctx->d_cyc, cyc0, sizeof cyc0, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));	/* cyc0 is a stack array */
+	mchip_cycle_flags flags = { 0, (ctx->admixture && ctx->s_cache_slot == slot) ? 1 : 0 };
+	HIPCHK(hipMemcpyAsync(ctx->d_cyc, &flags, sizeof flags, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));	/* flags is on the stack */
 	ctx->s_cache_slot = -1;
-	bool use_graph = !ctx->profiling && !ctx->knob.no_graph;
-	hipGraphExec_t &exec = ctx->cycle_graph[slot][scheme];
-	if (use_graph && !exec) {
-		hipGraph_t graph = nullptr;
-		if (MCHIP_WAIT(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal)) == hipSuccess) {
-			rc = accel_cycle_enqueue(ctx, slot, scheme);
-			const hipError_t e = MCHIP_WAIT(hipStreamEndCapture(ctx->stream, &graph));
-			if (rc || e != hipSuccess || !graph || MCHIP_WAIT(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)) != hipSuccess) exec = nullptr;
-			if (graph) (void)MCHIP_WAIT(hipGraphDestroy(graph));
-			(void)hipGetLastError();
-		}
-		if (!exec) use_graph = false;
-	}
+	const auto cycle = [&] { return accel_cycle_enqueue(ctx, slot, scheme); };
+	hipGraphExec_t *exec = &ctx->cycle_graph[slot][scheme];
+	const bool use_graph = !ctx->profiling && !ctx->knob.no_graph && captured(ctx, exec, cycle);
 	for (int c = 0; c < n_cycles; c++) {
-		if (use_graph) HIPCHK(hipGraphLaunch(exec, ctx->stream));
-		else if ((rc = accel_cycle_enqueue(ctx, slot, scheme))) return rc;
+		if (use_graph) HIPCHK(hipGraphLaunch(*exec, ctx->stream));
+		else if ((rc = cycle())) return rc;
 	}
-	int cyc_out[4] = { 0, 0, 0, 0 };
 	HIPCHK(hipMemcpyAsync(state, ctx->d_run, sizeof *state, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipMemcpyAsync(cyc_out, ctx->d_cyc, sizeof cyc_out, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipMemcpyAsync(&flags, ctx->d_cyc, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	/* a batch that ran to its end on an accepted cycle leaves that cycle's sums for whoever continues from this slot */
-	ctx->s_cache_slot = (ctx->admixture && !state->stopped && cyc_out[1]) ? slot : -1;
+	ctx->s_cache_slot = (ctx->admixture && !state->stopped && flags.accepted) ? slot : -1;
 	ctx->have_ll = 1;
 	return MCHIP_OK;
 }

@@ -10,6 +10,7 @@
 #include "mchip_feature_geometry.h"
 #include "mchip_progress.h"
 
+#include <cstddef>
 #include <functional>
 #include <type_traits>
 #include <stdio.h>
@@ -40,6 +41,41 @@ struct mchip_geometry {
 	int ind_waves;			/* waves per workgroup of the cooperating individual-side kernels (mchip_internal.h) */
 	int xcd_rows;			/* their slab rows come in whole groups of eight: one row, one XCD */
 };
+
+/* The small results of the device code, one allocation per context (d_scalars): every field has one use and shares storage with
+ * no other, so which launch runs before which decides nothing here.  Kernels are handed the record or &rec->field. */
+struct mchip_scalars {
+	double logL;			/* log likelihood of the last E step (k_stop_check, mchip_last_loglik) */
+	double emll;			/* of the second EM iterate of a cycle; of mchip_loglik */
+	double ll_point;		/* of the extrapolated point of a cycle; of mchip_loglik_prefetch (with s_cache_slot) */
+	double step;			/* step size of a batched cycle (step_size_body -> k_accel_update_slots) */
+	/* up to three dot products: their eta parts from [DOT_ETA] on, their p parts from [DOT_P] on; one array, because dots_common
+	 * fetches the eight doubles in one copy */
+	double dots[8];
+	double eta_sums[MCHIP_MAX_K];	/* column sums of S_ik under shared mixing proportions: k_column_sums runs K blocks */
+	unsigned long long cells[2];	/* mchip_data_counts: cells with n_ic > 0, non-missing allele copies */
+	int bad_input;			/* the layout kernels' "bad input" word (bad_flag) */
+};
+static_assert(std::is_standard_layout<mchip_scalars>::value && std::is_trivially_copyable<mchip_scalars>::value, "copied with hipMemcpy");
+static_assert(sizeof(mchip_scalars::eta_sums) == MCHIP_MAX_K * sizeof(double), "k_column_sums writes one sum per cluster");
+static_assert(offsetof(mchip_scalars, cells) % alignof(unsigned long long) == 0 && offsetof(mchip_scalars, bad_input) % alignof(int) == 0,
+	      "the kernels update the counts as 64-bit words and the bad-input word as a 32-bit one");
+
+enum { DOT_ETA = 0, DOT_P = 4 };
+
+/* what a batched accelerated cycle decides on the device (d_cyc) */
+struct mchip_cycle_flags {
+	int no_update;			/* the reference would leave this cycle without an update (step_size_body) */
+	int accepted;			/* the extrapolated point was accepted: Spart holds its S-side sums for the next cycle's first E step */
+};
+
+/* The block partials of the dot products in d_redpart: up to three sums of at most DOT_MAX_BLOCKS partials for the eta part,
+ * then as many for the p part.  A block of k_dots / k_dots_slots covers 4096 elements, or more once the cap is reached. */
+constexpr int DOT_MAX_BLOCKS = 512, DOT_MAX_SUMS = 3;
+constexpr size_t DOT_PARTIALS = (size_t)2 * DOT_MAX_SUMS * DOT_MAX_BLOCKS;
+static inline int dot_blocks(size_t n) { const size_t g = (n + 4095) / 4096; return g > DOT_MAX_BLOCKS ? DOT_MAX_BLOCKS : (int)g; }
+static inline double *dot_part_eta(double *redpart) { return redpart; }
+static inline double *dot_part_p(double *redpart) { return redpart + (size_t)DOT_MAX_SUMS * DOT_MAX_BLOCKS; }
 
 struct mchip_context {
 	int device;
@@ -108,18 +144,19 @@ struct mchip_context {
 	mchip_geometry geo;
 	/* read when a context is created and again with every data set and every model -- never on a launch path */
 	mchip_knobs knob;
-	double *d_Apart, *d_Spart, *d_llpart, *d_scalars;	/* d_scalars: [0]=logL, [1..3]=dots, [4..]=eta sums */
+	double *d_Apart, *d_Spart, *d_llpart;
+	mchip_scalars *d_scalars;
 	double *d_llpart2;		/* partial log likelihoods of the second parameter set of a dual individual pass */
-	double *d_redpart;		/* block partials of the dot products / column sums */
+	double *d_redpart;		/* block partials of the dot products: DOT_PARTIALS doubles (dot_part_eta, dot_part_p) */
 	uint8_t *d_flags;		/* michelot "fixed" flags for loci with more than 64 alleles */
-	double *h_pinned;		/* 64 doubles */
+	double *h_pinned;		/* sizeof(mchip_scalars) bytes: room for any fetch of its doubles (fetch_scalars) */
 	mchip_run_state *d_run;		/* batched-run state (mchip_em_run) */
 	hipGraphExec_t step_graph[3];	/* one captured {EM step + stop check} per slot; rebuilt when the model changes */
 	hipGraphExec_t cycle_graph[3][5];	/* one captured accelerated cycle per (start slot, scheme) */
-	int *d_cyc;			/* batched accelerated runs: [0] no update this cycle, [1] extrapolation accepted */
+	mchip_cycle_flags *d_cyc;	/* batched accelerated runs */
 	int have_ll;
 	int ll_parts;			/* partial log likelihoods the last E step left in d_llpart */
-	int s_cache_slot;		/* slot whose S-side sums + logL are held in Spart / d_scalars[2] (mchip_loglik_prefetch), or -1 */
+	int s_cache_slot;		/* slot whose S-side sums + logL are held in Spart / d_scalars->ll_point (mchip_loglik_prefetch), or -1 */
 	/* profiling */
 	int profiling;
 	hipEvent_t ev_begin, ev_end;
@@ -202,9 +239,9 @@ static inline unsigned nblk_capped(size_t n, unsigned b = 256, size_t cap_blocks
 	return (unsigned)(blocks < cap ? blocks : cap);
 }
 
-/* the "bad input" word of the layout kernels: the last double of d_scalars (slots 0..47 are in use), so that an
- * initialisation allocates and frees nothing (hipFree waits for the whole device, i.e. for every other stream's fits) */
-static int *bad_flag(mchip_context *ctx) { return reinterpret_cast<int *>(ctx->d_scalars + 63); }
+/* the "bad input" word of the layout kernels lives in the context's scalars, so that an initialisation allocates and frees
+ * nothing (hipFree waits for the whole device, i.e. for every other stream's fits) */
+static int *bad_flag(mchip_context *ctx) { return &ctx->d_scalars->bad_input; }
 
 /* ---- what the feature units call; defined in mchip.hip unless noted, never exported from the library ---- */
 #pragma GCC visibility push(hidden)

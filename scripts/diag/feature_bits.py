@@ -1,6 +1,7 @@
 """Bit-level fingerprint (SHA-256) of every output of the data-set features and of the K-independent reductions, at the smallest
 shapes at which each of their staging and summation helpers (multiclust_amd/csrc/mchip_device_util.h) can go wrong: run it under
-two builds of the library (MCHIP_LIB_PATH), each in a fresh process, and diff the two outputs.  Beside scripts/diag/bits.py, which
+two builds of the library (MCHIP_LIB_PATH), each in a fresh process, and diff the two outputs.  With them, the values that pass through the context's record of device scalars (mchip_scalars): EM steps, dot products,
+a batched EM run and batched accelerated cycles under schemes 1 to 4, for both models.  Beside scripts/diag/bits.py, which
 fingerprints the EM path at larger shapes."""
 import ctypes as C
 import hashlib
@@ -42,6 +43,24 @@ def slots(ctx):
     return [a for s in range(3) for a in (ctx.get_q(s), ctx.get_p(s))]
 
 
+def accel_runs(ctx, label, q0, p0):
+    """batched accelerated cycles (mchip_accel_run) under every scheme, each from two EM steps of (q0, p0): the run state the device
+    decided (stop rule, step size, accept test) and the three slots"""
+    for scheme in (1, 2, 3, 4):
+        ctx.set_q(0, q0)
+        ctx.set_p(0, p0)
+        ctx.em_step(0, 1, sync=False)
+        ctx.em_step(1, 0, sync=False)
+        st = hip.RunState(logL=-np.inf, abs_error=1e-3, max_iter=25, n_iter=0)
+        rc = ctx.lib.mchip_accel_run(ctx.h, 0, scheme, 3, C.byref(st))
+        if rc:      # refused (no sparse layout for this data set): the same under either build
+            print(label, "accel_run scheme %d status %d" % (scheme, rc), flush=True)
+            continue
+        run =(st.logL, st.bad_loglik, st.n_iter, st.stopped, st.converged, st.iter_stop, st.fatal)
+        print(label, "accel_run scheme %d n_iter=%d stopped=%d fatal=%d" % (scheme, st.n_iter, st.stopped, st.fatal), sha(*run), sha(*slots(ctx)),
+              flush=True)
+
+
 def features(ctx, label, ua, n_real, geno, K, shared):
     I, L, pl = geno.shape
     q0, p0 = random_params(I, ua, K, seed=3 + K)
@@ -73,6 +92,14 @@ def features(ctx, label, ua, n_real, geno, K, shared):
     rc = ctx.lib.mchip_em_run(ctx.h, 0, 40, C.byref(st))
     assert rc == 0 and st.stopped and not st.fatal, (label, rc, st.stopped, st.fatal)
     print(label, "em_run n_iter=%d converged=%d" % (st.n_iter, st.converged), sha(st.logL, *slots(ctx)), flush=True)
+    accel_runs(ctx, label, q0.mean(axis=0) if shared else q0, p0)
+
+
+def mixture_accel(ctx, label, ua, geno, K):
+    q0, p0 = random_params(geno.shape[0], ua, K, seed=3 + K)
+    ctx.set_genotypes(ua, geno)
+    ctx.set_model(K, admixture=0)
+    accel_runs(ctx, label, q0.mean(axis=0), p0)
 
 
 def main():
@@ -86,6 +113,7 @@ def main():
                         for shared in (False, True):
                             label = "K%d a%d I%d L%d pl%d miss%g %s:" % (K, alleles, I, L, pl, missing, "shared" if shared else "indiv")
                             features(ctx, label, ua, n_real, geno, K, shared)
+                        mixture_accel(ctx, "K%d a%d I%d L%d pl%d miss%g mixture:" % (K, alleles, I, L, pl, missing), ua, geno, K)
     # divergence with T on either side of the columns staged at a time (64) and of a workgroup's chunk (1024), both models
     for L in (31, 32, 33, 511, 512, 513):
         for K in (1, 8, 27, 64):
