@@ -100,6 +100,35 @@ int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const uint8_t *bed
 #define MCHIP_LD_MAX_WINDOW 4096
 int mchip_bed_ld_band(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int l0, int n_first, int window,
 		      double *r2);
+/*
+ * KING-robust kinship between the individuals of packed records (an extension): the matrix --king-cutoff removes relatives by.
+ * bed, I, L and record_bytes as for mchip_set_genotypes_bed: the whole fileset behind its header.
+ * Definition.  Codes as above: 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2; padding bits carry no
+ * individual.  For individuals i and j, over the L variants:
+ *     n_ij  = variants typed (not missing) in both,
+ *     hh_ij = variants at which both are heterozygous,
+ *     op_ij = variants at which one is homozygous A1 and the other homozygous A2 (IBS0),
+ *     h_ij  = variants at which i is heterozygous and j is typed (not symmetric: h_ji is the other one).
+ * In exact signed 64-bit integers m = min(h_ij, h_ji) and num = 2 hh_ij - 4 op_ij - h_ij - h_ji + 2 m, and then
+ *     phi_ij = (double)num / (double)(4 m)
+ * -- one division -- or NaN exactly when m = 0.  This is eq. 11 of Manichaikul et al. (2010) brought to one fraction,
+ * (hh - 2 op) / (2 m) + 1/2 - (h_ij + h_ji) / (4 m): the estimator of SNPRelate's snpgdsIBDKING(type = "KING-robust").  It needs no
+ * allele frequencies and is robust to population structure.  Nothing is claimed about the bits of PLINK 2's --make-king.  The
+ * diagonal is no special case: the formula at j = i gives 0.5, or NaN for an individual without a heterozygous call.  Every count
+ * is an integer: the result is the same bits on every device, under every launch geometry and every knob of the environment,
+ * whichever slab of rows a row is computed in, and phi_ij and phi_ji are the same bits.
+ * Contract.  For i in [i0, i0 + n_rows) and every j in [0, I): phi[(i - i0) * I + j] = phi_ij and, when counts is not NULL,
+ * counts[((i - i0) * I + j) * 4 + 0..3] = n_ij, hh_ij, op_ij, h_ij.  The context supplies the device, the stream and
+ * mchip_last_error and nothing else: no data set need be installed, and nothing of an installed data set, model, slot, fold or
+ * saved set changes.  Checked before anything runs: I, L >= 1, record_bytes >= ceil(I/4), 0 <= i0, 0 <= n_rows, i0 + n_rows <= I,
+ * non-null bed and phi; a failed check returns MCHIP_ERR_INVALID and leaves the arrays untouched.  MCHIP_ERR_ALLOC when the
+ * records, the three bit planes of every individual (3 L / 8 bytes each) and the slab's counts and kinships (28 bytes a pair) do
+ * not fit on the device.  MCHIP_ERR_UNSUPPORTED, the arrays untouched as well, for a shape beyond one launch: more than 2^31 - 65
+ * individuals, 2^31 or more tiles of 64 x 64 pairs in the slab (ask for fewer rows), or 2^31 or more blocks of 256 individuals x 64
+ * variants in the fileset.
+ */
+int mchip_bed_king(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int i0, int n_rows, double *phi,
+		   uint32_t *counts);
 /* Counted on the device when a data set is installed: cells (i, l, m) with ILM[i][l][m] > 0 -- the cells the reference's E step
  * visits (em_alg.c:338-342) and the unit the flop count of the path is stated in -- and non-missing allele copies. */
 int mchip_data_counts(mchip_context *ctx, uint64_t *nonempty_cells, uint64_t *allele_copies);

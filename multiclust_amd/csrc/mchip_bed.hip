@@ -24,6 +24,22 @@
  *   Compile report (hipcc of ROCm 7.2, gfx950, -O3, -Rpass-analysis=kernel-resource-usage):  k_ld_band 81 VGPRs, scratch 0, 15360
  *   bytes of static LDS, 5 waves / SIMD (the loop over a stage's words is kept rolled: unrolled it takes 135 VGPRs and 3 waves);
  *   k_ld_r2 25 VGPRs, scratch 0, 8 waves / SIMD.  Timed once and not tuned (profiles/ld.txt, scripts/ld_bench.py).
+ *
+ * mchip_bed_king reads the records for a third purpose and installs nothing either: the KING-robust kinship of a slab of individuals
+ * with all individuals (the definition is in the header), n_rows * I * ceil(L / 64) word pairs.
+ *   k_king_planes the records turned round: per individual three bit planes over the variants (valid, heterozygous, homozygous A2),
+ *                 64 variants to a 64-bit word, [plane][word][Ipad] with the individuals contiguous.  One workgroup per word x 256
+ *                 individuals, the record bytes staged as k_bed_expand stages them; a wave-wide __ballot over 64 variants' codes of
+ *                 one individual is one plane word.
+ *   k_king_pairs  one workgroup per KING_TILE x KING_TILE individuals x a run of words (king_geometry_of, mchip_feature_geometry.h).
+ *                 Per stage of KING_STAGE words it holds four planes (hom A1 = valid & ~het & ~hom A2 formed on the way in) of its
+ *                 row and column individuals in LDS (16 KB); a lane owns 4 x 4 pairs and counts with five __popcll per pair and
+ *                 word into 80 integer registers -- n, hh, op, h_ij, and h_ji from the same pass.  At the end the five counts of a
+ *                 pair go to memory with integer atomics: runs of variants combine in any order, the counts are the same.
+ *   k_king_phi    one lane per pair: the counts -> m, num in 64-bit integers -> phi, NaN where m = 0.
+ *   Compile report (same compiler and flags):  k_king_planes 33 VGPRs, scratch 0, 4352 bytes of static LDS, 8 waves / SIMD;
+ *   k_king_pairs 153 VGPRs, scratch 0, 16384 bytes of static LDS, 3 waves / SIMD; k_king_phi 24 VGPRs, scratch 0, 8 waves / SIMD.
+ *   Timed once and not tuned (profiles/king.txt, scripts/king_bench.py).
  */
 #include "mchip_context.h"
 
@@ -318,6 +334,180 @@ extern "C" int mchip_bed_ld_band(mchip_context *ctx, int I, int L, const uint8_t
 	hipLaunchKernelGGL(k_ld_r2, dim3(nblk_capped(n_pairs)), dim3(256), 0, ctx->stream, d_sums.p, n_pairs, window, n_up, d_r2.p);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(r2, d_r2.p, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	return MCHIP_OK;
+}
+
+/* ---- KING-robust kinship between the individuals: mchip_bed_king (include/multiclust_hip.h has the definition) ---- */
+constexpr int KING_PER = KING_TILE / 16;	/* row individuals and column individuals of a lane: KING_PER x KING_PER pairs */
+
+/* the records turned round: planes[(p * n_words + w) * Ipad + i] = plane p (0 valid, 1 heterozygous, 2 homozygous A2) of individual i
+ * over the variants 64 w ... 64 w + 63, bit v for variant 64 w + v; bits behind variant L - 1 and the rows I ... Ipad - 1 are 0.  One
+ * workgroup per word x BT_I individuals: the 64 bytes of each of its 64 records staged as in k_bed_expand (a lane then reads its
+ * record's byte, BT_ROW dwords apart: 64 different banks); lane = variant, a wave walks its 64 individuals and a ballot over the
+ * lanes' codes of one individual is that individual's word; lane k keeps the k-th, so the stores run along the individuals. */
+__global__ __launch_bounds__(256) void k_king_planes(const uint8_t *__restrict__ bed, size_t rb, int I, int L, int n_words, int Ipad,
+						     uint64_t *__restrict__ planes)
+{
+	__shared__ uint32_t tile[BT_L * BT_ROW];
+	const int w = blockIdx.x % n_words, l0 = w * BT_L, i0 = (blockIdx.x / n_words) * BT_I;
+	const size_t b0 = (size_t)(i0 / 4);	/* first staged byte of every record */
+	for (int x = threadIdx.x; x < BT_L * 16; x += 256) {
+		const int ll = x / 16, d = x % 16, l = l0 + ll;
+		const size_t off = b0 + 4 * (size_t)d;
+		tile[ll * BT_ROW + d] = (l < L && off < rb) ? bed_word(bed, (size_t)l * rb + off) : 0u;
+	}
+	__syncthreads();
+	const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+	const int lane = threadIdx.x & 63, first = (threadIdx.x >> 6) * 64;
+	const bool l_in = l0 + lane < L;
+	uint64_t v = 0, h = 0, b = 0;
+	for (int k = 0; k < 64; k++) {
+		const int r = first + k;
+		const uint32_t c = ((uint32_t)tb[lane * (BT_ROW * 4) + r / 4] >> (2 * (r & 3))) & 3u;
+		const bool in = l_in && i0 + r < I;	/* padding bits and staged zeros carry no call */
+		const uint64_t bv = __ballot(in && c != 1u), bh = __ballot(in && c == 2u), bb = __ballot(in && c == 3u);
+		if (lane == k) { v = bv; h = bh; b = bb; }
+	}
+	const int i = i0 + first + lane;
+	if (i >= Ipad) return;
+	const size_t plane = (size_t)n_words * (size_t)Ipad, at = (size_t)w * (size_t)Ipad + (size_t)i;
+	planes[at] = v;
+	planes[plane + at] = h;
+	planes[2 * plane + at] = b;
+}
+
+/* sums[((i - i0) * I + j) * 4 + 0..3] += n, hh, op, h_ij and hji[(i - i0) * I + j] += h_ji of the pair (i, j) over this workgroup's
+ * run of words.  blockIdx.x = tile of rows + n_rtiles * tile of columns, blockIdx.y = run of words.  Per stage the four planes
+ * (valid, het, hom A1 = valid & ~het & ~hom A2, hom A2) of the tile's row and column individuals go to LDS (16 KB).  Lane (tx, ty)
+ * of 16 x 16 owns the rows 4 ty ... 4 ty + 3 and the columns tx, tx + 16, tx + 32, tx + 48 of the tile: the 16 lanes tx of a wave
+ * read 16 consecutive words of a plane, the four ty the same ones (broadcast). */
+__global__ __launch_bounds__(256) void k_king_pairs(const uint64_t *__restrict__ planes, int n_words, int Ipad, int I, int i0, int n_rows,
+						    king_geometry g, uint32_t *__restrict__ sums, uint32_t *__restrict__ hji)
+{
+	__shared__ uint64_t rs[4][KING_STAGE][KING_TILE];
+	__shared__ uint64_t cs[4][KING_STAGE][KING_TILE];
+	const int rt = blockIdx.x % g.n_rtiles, ct = blockIdx.x / g.n_rtiles;
+	const int r0 = i0 + rt * KING_TILE, c0 = ct * KING_TILE;
+	const int w_begin = (int)blockIdx.y * g.stages_per_split * KING_STAGE;
+	const int w_end = min(n_words, w_begin + g.stages_per_split * KING_STAGE);
+	const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+	const size_t plane = (size_t)n_words * (size_t)Ipad;
+	uint32_t acc[KING_PER][KING_PER][5];
+#pragma unroll
+	for (int r = 0; r < KING_PER; r++)
+#pragma unroll
+		for (int c = 0; c < KING_PER; c++)
+#pragma unroll
+			for (int s = 0; s < 5; s++) acc[r][c][s] = 0;
+	for (int ws = w_begin; ws < w_end; ws += KING_STAGE) {
+		__syncthreads();	/* the stage before has been read */
+		for (int x = threadIdx.x; x < 2 * KING_STAGE * KING_TILE; x += 256) {
+			const int side = x / (KING_STAGE * KING_TILE), w = (x / KING_TILE) % KING_STAGE, k = x % KING_TILE;
+			const int idx = (side ? c0 : r0) + k;
+			uint64_t v = 0, h = 0, b = 0;
+			if (idx < Ipad && ws + w < w_end) {	/* (a slab's last row tile may reach behind the padded individuals) */
+				const size_t at = (size_t)(ws + w) * (size_t)Ipad + (size_t)idx;
+				v = planes[at]; h = planes[plane + at]; b = planes[2 * plane + at];
+			}
+			uint64_t (*dst)[KING_STAGE][KING_TILE] = side ? cs : rs;
+			dst[0][w][k] = v; dst[1][w][k] = h; dst[2][w][k] = v & ~h & ~b; dst[3][w][k] = b;
+		}
+		__syncthreads();
+#pragma unroll 1
+		for (int w = 0; w < KING_STAGE; w++) {	/* (words behind w_end are staged as zeros) */
+			uint64_t cv[KING_PER], ch[KING_PER], ca[KING_PER], cb[KING_PER];
+#pragma unroll
+			for (int c = 0; c < KING_PER; c++) {
+				const int k = tx + 16 * c;
+				cv[c] = cs[0][w][k]; ch[c] = cs[1][w][k]; ca[c] = cs[2][w][k]; cb[c] = cs[3][w][k];
+			}
+#pragma unroll
+			for (int r = 0; r < KING_PER; r++) {
+				const int k = ty * KING_PER + r;
+				const uint64_t rv = rs[0][w][k], rh = rs[1][w][k], ra = rs[2][w][k], rb2 = rs[3][w][k];
+#pragma unroll
+				for (int c = 0; c < KING_PER; c++) {
+					acc[r][c][0] += (uint32_t)__popcll(rv & cv[c]);
+					acc[r][c][1] += (uint32_t)__popcll(rh & ch[c]);
+					acc[r][c][2] += (uint32_t)__popcll((ra & cb[c]) | (rb2 & ca[c]));
+					acc[r][c][3] += (uint32_t)__popcll(rh & cv[c]);
+					acc[r][c][4] += (uint32_t)__popcll(ch[c] & rv);
+				}
+			}
+		}
+	}
+#pragma unroll
+	for (int r = 0; r < KING_PER; r++) {
+		const int i = r0 + ty * KING_PER + r;
+		if (i >= i0 + n_rows) continue;
+#pragma unroll
+		for (int c = 0; c < KING_PER; c++) {
+			const int j = c0 + tx + 16 * c;
+			if (j >= I) continue;
+			const size_t p = (size_t)(i - i0) * (size_t)I + (size_t)j;
+			atomicAdd(sums + 4 * p + 0, acc[r][c][0]);
+			atomicAdd(sums + 4 * p + 1, acc[r][c][1]);
+			atomicAdd(sums + 4 * p + 2, acc[r][c][2]);
+			atomicAdd(sums + 4 * p + 3, acc[r][c][3]);
+			atomicAdd(hji + p, acc[r][c][4]);
+		}
+	}
+}
+
+/* phi of every pair from its counts, in exact 64-bit integers up to the one division of the definition; NaN where m = 0 */
+__global__ __launch_bounds__(256) void k_king_phi(const uint32_t *__restrict__ sums, const uint32_t *__restrict__ hji, size_t n_pairs,
+						  double *__restrict__ phi)
+{
+	for (size_t x = (size_t)blockIdx.x * 256 + threadIdx.x; x < n_pairs; x += (size_t)gridDim.x * 256) {
+		const int64_t hh = sums[4 * x + 1], op = sums[4 * x + 2], hij = sums[4 * x + 3], hj = hji[x];
+		const int64_t m = hij < hj ? hij : hj;
+		const int64_t num = 2 * hh - 4 * op - hij - hj + 2 * m;
+		phi[x] = m ? (double)num / (double)(4 * m) : __longlong_as_double(0x7FF8000000000000ll);
+	}
+}
+
+extern "C" int mchip_bed_king(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int i0, int n_rows, double *phi,
+			      uint32_t *counts)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (I <= 0 || L <= 0 || !bed || !phi || record_bytes < ((size_t)I + 3) / 4)
+		return fail(ctx, MCHIP_ERR_INVALID, "bed_king: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
+	if (i0 < 0 || n_rows < 0 || (long long)i0 + n_rows > I)
+		return fail(ctx, MCHIP_ERR_INVALID, "bed_king: rows outside the individuals%s", nullptr);
+	if (!n_rows) return MCHIP_OK;
+	if (I > 0x7FFFFFFF - KING_TILE)
+		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "bed_king: too many individuals%s", nullptr);
+	const int n_words = (int)(((long long)L + 63) / 64), Ipad = (I + KING_TILE - 1) / KING_TILE * KING_TILE;
+	const king_geometry g = king_geometry_of(I, n_rows, L, (long long)ctx->knob.per_cu_ind * (ctx->n_cu > 0 ? ctx->n_cu : 256));
+	const size_t t_blocks = (size_t)n_words * (size_t)((I + BT_I - 1) / BT_I);
+	if ((long long)g.n_rtiles * g.n_ctiles >= (1ll << 31) || t_blocks >= ((size_t)1 << 31))
+		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "bed_king: too many individuals or variants for one launch; call it in slabs of rows%s", nullptr);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t bed_bytes = (size_t)L * record_bytes, n_planes = 3 * (size_t)n_words * (size_t)Ipad, n_pairs = (size_t)n_rows * (size_t)I;
+	scoped_dev<uint8_t> d_bed;
+	scoped_dev<uint64_t> d_planes;
+	scoped_dev<uint32_t> d_sums, d_hji;
+	scoped_dev<double> d_phi;
+	if (d_bed.alloc(bed_bytes + BED_PAD) != hipSuccess || d_planes.alloc(n_planes) != hipSuccess || d_sums.alloc(n_pairs * 4) != hipSuccess ||
+	    d_hji.alloc(n_pairs) != hipSuccess || d_phi.alloc(n_pairs) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(ctx, MCHIP_ERR_ALLOC, "bed_king: the records, the planes or the slab's counts and kinships do not fit on the device%s", nullptr);
+	}
+	HIPCHK(hipMemcpyAsync(d_bed.p, bed, bed_bytes, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_bed.p + bed_bytes, 0, BED_PAD, ctx->stream));
+	HIPCHK(hipMemsetAsync(d_sums.p, 0, n_pairs * 4 * sizeof(uint32_t), ctx->stream));
+	HIPCHK(hipMemsetAsync(d_hji.p, 0, n_pairs * sizeof(uint32_t), ctx->stream));
+	hipLaunchKernelGGL(k_king_planes, dim3((unsigned)t_blocks), dim3(256), 0, ctx->stream, d_bed.p, record_bytes, I, L, n_words, Ipad, d_planes.p);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(k_king_pairs, dim3((unsigned)(g.n_rtiles * g.n_ctiles), (unsigned)g.n_split), dim3(256), 0, ctx->stream, d_planes.p, n_words,
+			   Ipad, I, i0, n_rows, g, d_sums.p, d_hji.p);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(k_king_phi, dim3(nblk_capped(n_pairs)), dim3(256), 0, ctx->stream, d_sums.p, d_hji.p, n_pairs, d_phi.p);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(phi, d_phi.p, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+	if (counts) HIPCHK(hipMemcpyAsync(counts, d_sums.p, sizeof(uint32_t) * 4 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	return MCHIP_OK;
 }

@@ -75,4 +75,33 @@ static inline ld_band_geometry ld_band_geometry_of(int I, int n_first, int windo
 	return g;
 }
 
+/* ---- KING-robust kinship between individuals of packed records (k_king_pairs, mchip_bed.hip; tests/king_util.py restates the
+ * constants) ----
+ * A workgroup owns KING_TILE row individuals x KING_TILE column individuals and a run of whole stages of KING_STAGE 64-bit words (64
+ * variants each) of their bit planes.  The variants are cut into n_split runs only while that takes the launch towards
+ * target_blocks workgroups: the counts are integers, so the cut shows in no bit of the result. */
+constexpr int KING_TILE = 64;	/* row and column individuals per workgroup: a lane owns KING_TILE / 16 of each */
+constexpr int KING_STAGE = 4;	/* 64-bit words of every staged individual's planes in LDS at a time: 256 variants */
+
+struct king_geometry {
+	int n_rtiles, n_ctiles;		/* workgroups along the rows of the slab and along all the individuals */
+	int n_split, stages_per_split;	/* workgroups along the variants, and the stages each of them walks */
+};
+
+static inline king_geometry king_geometry_of(int I, int n_rows, int L, long long target_blocks)
+{
+	king_geometry g;
+	g.n_rtiles = (n_rows + KING_TILE - 1) / KING_TILE;
+	g.n_ctiles = (I + KING_TILE - 1) / KING_TILE;
+	const long long base = (long long)g.n_rtiles * g.n_ctiles;
+	const int n_stages = (int)((((long long)L + 63) / 64 + KING_STAGE - 1) / KING_STAGE);
+	long long want = base > 0 ? (target_blocks + base - 1) / base : 1;
+	if (want > n_stages) want = n_stages;
+	if (want > 65535) want = 65535;
+	if (want < 1) want = 1;
+	g.stages_per_split = (int)((n_stages + want - 1) / want);
+	g.n_split = (n_stages + g.stages_per_split - 1) / g.stages_per_split;
+	return g;
+}
+
 #endif

@@ -58,6 +58,7 @@ def load():
         "mchip_set_genotypes": ([vp, i32, i32, i32, vp, vp], i32),
         "mchip_set_genotypes_bed": ([vp, i32, i32, vp, C.c_size_t, vp], i32),
         "mchip_bed_ld_band": ([vp, i32, i32, vp, C.c_size_t, i32, i32, i32, vp], i32),
+        "mchip_bed_king": ([vp, i32, i32, vp, C.c_size_t, i32, i32, vp, vp], i32),
         "mchip_set_model": ([vp, i32, i32, i32, i32, C.c_double, C.c_double, i32], i32),
         "mchip_set_p": ([vp, i32, vp], i32),
         "mchip_get_p": ([vp, i32, vp], i32),
@@ -137,7 +138,7 @@ ABI_SYMBOLS = [
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
     "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
-    "mchip_residual_products", "mchip_describe_plan", "mchip_bed_ld_band",
+    "mchip_residual_products", "mchip_describe_plan", "mchip_bed_ld_band", "mchip_bed_king",
 ]
 
 
@@ -212,6 +213,22 @@ class Context:
         out = np.empty((max(n_first, 0), max(window, 0)), dtype=np.float64)
         self._chk(self.lib.mchip_bed_ld_band(self.h, I, L, bed.ctypes.data, rb, l0, n_first, window, out.ctypes.data))
         return out
+
+    def bed_king(self, I, bed, i0=0, n_rows=None, counts=True, record_bytes=None, L=None):
+        """mchip_bed_king: (phi [n_rows][I], counts [n_rows][I][4] or None) of the individuals i0 ... i0 + n_rows - 1 against all I
+        of the packed records [L][record_bytes]: the KING-robust kinship and the counts n, hh, op, h_ij it is formed from
+        (include/multiclust_hip.h has the definition); NaN where min(h_ij, h_ji) = 0: either of the two has no heterozygous call at a
+        variant where the other is typed.  Installs nothing and changes nothing of the context."""
+        bed = np.ascontiguousarray(bed, dtype=np.uint8)
+        assert bed.ndim == 2
+        L = bed.shape[0] if L is None else L
+        rb = bed.shape[1] if record_bytes is None else record_bytes
+        n_rows = I - i0 if n_rows is None else n_rows
+        phi = np.empty((max(n_rows, 0), max(I, 0)), dtype=np.float64)
+        cnt = np.empty((max(n_rows, 0), max(I, 0), 4), dtype=np.uint32) if counts else None
+        self._chk(self.lib.mchip_bed_king(self.h, I, L, bed.ctypes.data, rb, i0, n_rows, phi.ctypes.data,
+                                          cnt.ctypes.data if counts else None))
+        return phi, cnt
 
     def data_counts(self):
         """(cells with n_ic > 0, non-missing allele copies) of the data set held, counted on the device"""

@@ -125,7 +125,14 @@ class CliOptionsAll(CliOptions):
                 ("cv_folds", C.c_int), ("cv_floor", C.c_double), ("se_replicates", C.c_int), ("se_block", C.c_int),
                 ("query_file", C.c_char_p), ("fill", C.c_int), ("fst", C.c_int), ("resid", C.c_int),
                 # --prune / --prune-window
-                ("prune", C.c_int), ("prune_window_given", C.c_int), ("prune_t", C.c_double), ("prune_window", C.c_int)]
+                ("prune", C.c_int), ("prune_window_given", C.c_int), ("prune_t", C.c_double), ("prune_window", C.c_int),
+                # --king-cutoff
+                ("king", C.c_int), ("king_t", C.c_double)]
+
+
+class McKingPair(C.Structure):
+    """mc_king_pair (multiclust_amd/host/mc_cli.h)"""
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("n", C.c_uint32), ("hh", C.c_uint32), ("op", C.c_uint32), ("phi", C.c_double)]
 
 
 class CliData(C.Structure):
@@ -142,7 +149,9 @@ class CliData(C.Structure):
 class CliDataAll(CliData):
     """the whole of mc_cli_data: what the readers fill (they clear all of it) and the writers read"""
     _fields_ = [("L_file", C.c_int), ("bim_text", C.c_void_p), ("chrom", C.POINTER(C.c_char_p)),
-                ("variant_id", C.POINTER(C.c_char_p)), ("variant_of", C.POINTER(C.c_int))]
+                ("variant_id", C.POINTER(C.c_char_p)), ("variant_of", C.POINTER(C.c_int)),
+                ("I_file", C.c_int), ("individual_of", C.POINTER(C.c_int)), ("fam_fid", C.POINTER(C.c_char_p)),
+                ("fam_iid", C.POINTER(C.c_char_p)), ("king_pairs", C.POINTER(McKingPair)), ("n_king_pairs", C.c_size_t)]
 
 
 def _cli_data_fields(d, geno):
@@ -195,13 +204,15 @@ def bed_decode(I, bed):
     return ua, geno
 
 
-def read_bed(prefix, decode=True, prune=None, prune_window=50, device=0):
+def read_bed(prefix, decode=True, prune=None, prune_window=50, device=0, king_cutoff=None):
     """mc_read_bed (host/mc_bed.c) on the PLINK 1 fileset prefix.bed/.bim/.fam: (status, None) on failure, else (0, dict) with
     the fields of read_structure.  The reader keeps the data set packed -- `bed` [L][record_bytes], geno_is_null says that it
     built no genotype; `geno` (and L_alleles) come from mc_bed_decode on those records, unless decode is False.  chrom and
     variant_id are the first two fields of the L_file lines of the .bim.  prune = t: the variants thinned by linkage disequilibrium
     on `device` as --prune t --prune-window prune_window does (host/mc_ld.c): everything is the pruned data set's, variant_of its
-    loci's places in the fileset (None without pruning)."""
+    loci's places in the fileset (None without pruning).  king_cutoff = t: after that, close relatives removed on `device` as
+    --king-cutoff t does (host/mc_king.c): everything is the kept individuals', individual_of their places in the fileset (None
+    without it), I_file, fam_fid, fam_iid the fileset's, king_pairs the related pairs as (i, j, n, hh, op, phi)."""
     lib = load()
     lib.mc_read_bed.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll)]
     lib.mc_free_data.argtypes = [C.POINTER(CliDataAll)]
@@ -219,6 +230,13 @@ def read_bed(prefix, decode=True, prune=None, prune_window=50, device=0):
         if rc:
             lib.mc_free_data(C.byref(d))
             return rc, None
+    if king_cutoff is not None:
+        lib.mc_king_data.argtypes = [C.POINTER(CliOptionsAll), C.POINTER(CliDataAll)]
+        o.device, o.king, o.king_t = device, 1, king_cutoff
+        rc = lib.mc_king_data(C.byref(o), C.byref(d))
+        if rc:
+            lib.mc_free_data(C.byref(d))
+            return rc, None
     bed = np.ctypeslib.as_array(d.bed, shape=(d.L, d.bed_record_bytes)).copy()
     geno = ua_dec = None
     if decode:
@@ -226,7 +244,12 @@ def read_bed(prefix, decode=True, prune=None, prune_window=50, device=0):
     out = _cli_data_fields(d, geno)
     out.update(geno_is_null=not bool(d.geno), bed=bed, L_file=d.L_file, chrom=[d.chrom[v].decode() for v in range(d.L_file)],
                variant_id=[d.variant_id[v].decode() for v in range(d.L_file)],
-               variant_of=[d.variant_of[l] for l in range(d.L)] if d.variant_of else None)
+               variant_of=[d.variant_of[l] for l in range(d.L)] if d.variant_of else None,
+               individual_of=[d.individual_of[i] for i in range(d.I)] if d.individual_of else None)
+    if d.individual_of:
+        out.update(I_file=d.I_file, fam_fid=[d.fam_fid[i].decode() for i in range(d.I_file)],
+                   fam_iid=[d.fam_iid[i].decode() for i in range(d.I_file)],
+                   king_pairs=[(k.i, k.j, k.n, k.hh, k.op, k.phi) for k in (d.king_pairs[x] for x in range(d.n_king_pairs))])
     if decode:
         out.update(geno=geno, ua_decoded=ua_dec)
     lib.mc_free_data(C.byref(d))
@@ -338,6 +361,40 @@ def residual_summary(cor):
                       ind_max=ix.ctypes.data_as(C.POINTER(C.c_double)), ind_partner=ip.ctypes.data_as(C.POINTER(C.c_int32)))
     load().mc_residual_summary(I, cor.ctypes.data, C.byref(r))
     return _resid_dict(r)
+
+
+def king_select(bits, I):
+    """mc_king_select (host/mc_king.c): keep [I] bool under the greedy rule on the relatedness graph bits [I][I] (bool, symmetric)"""
+    lib = load()
+    rel = np.asarray(bits, dtype=bool)
+    assert rel.shape == (I, I)
+    rw = (I + 63) // 64
+    packed = np.zeros((I, rw * 64), dtype=np.uint8)
+    packed[:, :I] = rel
+    words = np.packbits(packed, axis=1, bitorder="little").view(np.uint64).reshape(I, rw).copy()
+    keep = np.empty(I, dtype=np.uint8)
+    lib.mc_king_select.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    rc = lib.mc_king_select(I, words.ctypes.data, keep.ctypes.data)
+    if rc:
+        raise hip.HipError("mc_king_select failed (%d)" % rc)
+    return keep.astype(bool)
+
+
+def king_compact(I, bed, keep):
+    """mc_king_compact (host/mc_king.c): (records [L][ceil(I'/4)] of the kept individuals, individual_of [I'])"""
+    lib = load()
+    bed = np.ascontiguousarray(bed, dtype=np.uint8)
+    L, rb = bed.shape
+    buf = np.zeros(L * rb + 8, dtype=np.uint8)
+    buf[:L * rb] = bed.ravel()
+    k = np.ascontiguousarray(keep, dtype=np.uint8)
+    assert k.shape == (I,)
+    of = np.empty(I, dtype=np.int32)
+    lib.mc_king_compact.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    n = lib.mc_king_compact(I, L, rb, k.ctypes.data, buf.ctypes.data, of.ctypes.data)
+    if n < 0:
+        raise hip.HipError("mc_king_compact failed")
+    return buf[:L * ((n + 3) // 4)].reshape(L, (n + 3) // 4).copy(), of[:n].copy()
 
 
 def query_read(path, I):

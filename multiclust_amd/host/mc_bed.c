@@ -112,6 +112,16 @@ static void lazy_release(mc_lazy_geno *self)
 	free(z);
 }
 
+mc_lazy_geno *mc_bed_lazy_new(void)
+{
+	bed_lazy *z = calloc(1, sizeof *z);
+	if (!z) return NULL;
+	z->base.get = lazy_get;
+	z->base.release = lazy_release;
+	pthread_mutex_init(&z->lock, NULL);
+	return &z->base;
+}
+
 static double now_s(void)
 {
 	struct timespec t;
@@ -317,14 +327,7 @@ int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat)
 	dat->bed_record_bytes = rb;
 
 	mchip_progress_note("mc_read_bed: allele lists");
-	bed_lazy *z = calloc(1, sizeof *z);
-	if (z) {
-		z->base.get = lazy_get;
-		z->base.release = lazy_release;
-		pthread_mutex_init(&z->lock, NULL);
-		dat->lazy = &z->base;
-	}
-	if (!z) { rc = FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); goto DONE; }
+	if (!(dat->lazy = mc_bed_lazy_new())) { rc = FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); goto DONE; }
 	if ((rc = mc_bed_summarize(dat))) goto DONE;
 	if (getenv("MC_READER_TIMING"))		/* as mc_read_structure reports its phases */
 		fprintf(stderr, "INFO [mc_bed.c]: %-18s %.3f s\n", "fileset read", now_s() - t_start);

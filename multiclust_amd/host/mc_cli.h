@@ -58,7 +58,16 @@ typedef struct mc_cli_options {
 	int prune, prune_window_given;	/* --prune <t> / --prune-window <W> seen (extension, mc_ld.c; both need --bed) */
 	double prune_t;			/* --prune <t>: a variant in r2 > t with a kept variant of its chromosome at most W before it is removed; 0 < t <= 1 */
 	int prune_window;		/* --prune-window <W>: in variants, 1 ... MCHIP_LD_MAX_WINDOW; default 50 */
+	int king;			/* --king-cutoff <t> seen (extension, mc_king.c; needs --bed) */
+	double king_t;			/* --king-cutoff <t>: individuals are removed until no two kept ones have KING-robust kinship > t; 0 < t < 0.5 */
 } mc_cli_options;
+
+/* one related pair of --king-cutoff: individuals i < j of the fileset, their counts n_ij, hh_ij, op_ij and kinship (mchip_bed_king) */
+typedef struct mc_king_pair {
+	int i, j;
+	uint32_t n, hh, op;
+	double phi;
+} mc_king_pair;
 
 typedef struct mc_cli_data {
 	int I, L, ploidy, M;		/* M = max alleles at a locus */
@@ -84,6 +93,15 @@ typedef struct mc_cli_data {
 	int L_file;
 	char *bim_text, **chrom, **variant_id;
 	int *variant_of;
+	/* the fileset's individuals, I_file of them.  --king-cutoff leaves I of them: individual i is individual individual_of[i] of the
+	 * fileset (ascending), names, locale, pops, numpops and i_p are the kept ones', and fam_fid / fam_iid [I_file] hold every .fam line's
+	 * two ids; king_pairs [n_king_pairs] are the related pairs found, in (i, j) order.  individual_of = NULL: every individual of the
+	 * fileset is in the data set and none of these is set */
+	int I_file;
+	int *individual_of;
+	char **fam_fid, **fam_iid;
+	mc_king_pair *king_pairs;
+	size_t n_king_pairs;
 } mc_cli_data;
 
 /* read_file + summarize_alleles + sufficient_statistics (read_file.c:38-300,443-663), default (allele-code) mode */
@@ -149,7 +167,7 @@ int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows,
  * except that each token the reader took for a missing allele copy and that was filled is the decimal label L_alleles[l][m].
  * mc_write_filled_bed: <out_prefix>.bed with each missing record that was filled replaced by homozygous A1 / heterozygous /
  * homozygous A2 (magic bytes and padding bits kept), .bim and .fam of opt->bed_prefix copied byte for byte (of a data set
- * pruned by --prune the .bim lines of the variants kept).
+ * pruned by --prune the .bim lines of the variants kept, of one thinned by --king-cutoff the .fam lines of the individuals kept).
  * mc_write_filled: the one the input calls for, to <stem>.admix.K=<K>.filled.stru or <stem>.admix.K=<K>.filled.bed / .bim / .fam.
  * Return 0 or an exit status of the enum above. */
 int mc_write_filled_structure(const mc_cli_options *opt, const mc_cli_data *dat, const uint8_t *filled, const char *out_path);
@@ -187,5 +205,35 @@ int mc_ld_prune_greedy(int L, int W, double t, int slab, mc_ld_band_fn band, voi
 int mc_ld_compact(int L, size_t record_bytes, const uint8_t *keep, uint8_t *bed, int *variant_of);
 int mc_ld_prune_data(const mc_cli_options *opt, mc_cli_data *dat);
 int mc_write_prune_lists(const mc_cli_options *opt, const mc_cli_data *dat);
+
+/* --king-cutoff (an extension, mc_king.c; the kinship is defined in include/multiclust_hip.h, the rule in the header comment of
+ * mc_king.c).
+ * mc_king_band_fn: phi[n_rows][I] and counts[n_rows][I][4] of the rows i0 ... i0 + n_rows - 1 against all individuals, as
+ * mchip_bed_king fills them; returns 0 or a status.
+ * mc_king_edges: the relatedness graph of I individuals at threshold t as an I x I bit matrix, ceil(I/64) words a row, bit j % 64
+ * of word j / 64 of row i set where i != j and phi_ij > t (NaN never is), and the pairs i < j among them in (i, j) order; the
+ * kinships are asked for in slabs of at most `slab` rows, in ascending order.  The caller frees both arrays.  Returns 0,
+ * MCHIP_ERR_INVALID, MCHIP_ERR_ALLOC or the band's status.
+ * mc_king_select: keep[i] = 1 / 0 under the greedy rule on such a matrix; at least one individual is kept.
+ * mc_king_compact: every record of bed [L][record_bytes] repacked to the kept individuals' codes in order, ceil(I'/4) bytes a
+ * record, padding bits 0, records back to back from the front, and the 8 bytes behind the last one 0 (bed has the reader's 8 spare
+ * bytes behind its records); individual_of[n] (may be NULL) = the index the n-th kept individual had.  Returns I', or -1 when out of
+ * memory.
+ * mc_king_data: a data set as mc_read_bed (and mc_ld_prune_data) yields it, thinned at opt->king_t with the kinships of device
+ * opt->device: the data set mc_read_bed yields on the fileset of the individuals kept -- I, names, locale, pops, numpops, i_p (locales
+ * in order of first appearance among the kept), bed, bed_record_bytes, lazy, and uniquealleles, L_alleles, M, T, toff and missing_data
+ * (mc_bed_summarize) theirs -- with I_file, individual_of, fam_fid, fam_iid and king_pairs set.  Under MC_READER_TIMING it reports
+ * its seconds as the readers do.  Returns 0 or a status.
+ * mc_write_king_lists: <stem>.king.cutoff.in and <stem>.king.cutoff.out -- "FID\tIID" of the individuals kept and removed, one per
+ * line in file order -- and <stem>.king.kin0, the related pairs (the format is at the function). */
+#define MC_KING_SLAB 1024
+typedef int (*mc_king_band_fn)(void *arg, int i0, int n_rows, double *phi, uint32_t *counts);
+int mc_king_edges(int I, double t, int slab, mc_king_band_fn band, void *arg, uint64_t **bits_out, mc_king_pair **pairs_out, size_t *n_pairs_out);
+int mc_king_select(int I, const uint64_t *bits, uint8_t *keep);
+int mc_king_compact(int I, int L, size_t record_bytes, const uint8_t *keep, uint8_t *bed, int *individual_of);
+int mc_king_data(const mc_cli_options *opt, mc_cli_data *dat);
+int mc_write_king_lists(const mc_cli_options *opt, const mc_cli_data *dat);
+/* a new decoder of the packed records for dat->lazy (mc_bed.c): nothing decoded yet; NULL when out of memory */
+struct mc_lazy_geno *mc_bed_lazy_new(void);
 
 #endif

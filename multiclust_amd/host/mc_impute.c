@@ -241,8 +241,10 @@ int mc_write_filled_bed(const mc_cli_options *opt, const mc_cli_data *dat, const
 	}
 	if (fclose(fp)) rc = rc ? rc : MC_EXIT_FILE_OPEN_ERROR;
 	fp = NULL;
-	/* (the variants --prune removed have no record above and no line here) */
-	for (int x = 0; x < 2 && !rc; x++) rc = (x == 0 && dat->variant_of) ? copy_kept_lines(src[x], dst[x], dat->variant_of, L) : copy_file(src[x], dst[x]);
+	/* (the variants --prune removed have no record above and no line here; the individuals --king-cutoff removed none there) */
+	for (int x = 0; x < 2 && !rc; x++)
+		rc = (x == 0 && dat->variant_of) ? copy_kept_lines(src[x], dst[x], dat->variant_of, L) :
+		     (x == 1 && dat->individual_of) ? copy_kept_lines(src[x], dst[x], dat->individual_of, I) : copy_file(src[x], dst[x]);
 DONE:
 	if (fp) fclose(fp);
 	if (rc) fprintf(stderr, "ERROR [mc_impute.c::mc_write_filled_bed]: could not write the fileset '%s' (%d)\n", out_prefix, rc);

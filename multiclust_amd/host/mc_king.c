@@ -1,0 +1,281 @@
+/*
+ * mc_king.c -- --king-cutoff (an extension): close relatives removed from a PLINK fileset before anything is fitted.  The admixture
+ * model takes a family in the panel for a cluster of its own (--resid shows it afterwards, as a block of positive residual
+ * correlation); every guide to such a fit asks for this step beside LD pruning, and without it the user leaves for another program
+ * and comes back with a second fileset.
+ *
+ * The kinship phi_ij of two individuals is defined in include/multiclust_hip.h (mchip_bed_king): KING-robust (Manichaikul et al.
+ * 2010, eq. 11) from four integer counts per pair over the variants of the data set -- all of them: keeping to the autosomes is the
+ * user's --extract -- the same bits wherever it is computed.  Two individuals are related when phi_ij > t; NaN compares false.
+ *
+ * The rule is greedy and this project's own: while some pair of remaining individuals is related, the remaining individual with
+ * the most remaining related partners is removed; of several with as many, the one with the highest index, so that the individual
+ * earlier in the .fam file stays.  It is in the spirit of PLINK 2's --king-cutoff and NOT its algorithm, and what it keeps is not a
+ * maximum independent set of the relatedness graph: no two kept individuals are related, nothing more is claimed.
+ *
+ * The kinships come in slabs of at most `slab` rows against all individuals; the host keeps one slab (24 bytes a pair) and the
+ * relatedness graph as an I x I bit matrix, I * I / 8 bytes: its only memory quadratic in I.
+ *
+ * Everything in this file is libc but what mc_king_data calls: the device (mchip_create, mchip_bed_king, mchip_destroy) and the
+ * reader (mc_bed_summarize, mc_bed_lazy_new, mc_bed.c).  tests/king_host_driver.c stubs those and runs the rest as a program of its
+ * own.
+ */
+#include "mc_cli.h"
+
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+static size_t row_words(int I) { return ((size_t)I + 63) / 64; }
+
+int mc_king_edges(int I, double t, int slab, mc_king_band_fn band, void *arg, uint64_t **bits_out, mc_king_pair **pairs_out, size_t *n_pairs_out)
+{
+	if (I < 1 || slab < 1 || !band || !bits_out || !pairs_out || !n_pairs_out) return MCHIP_ERR_INVALID;
+	const int ns = slab < I ? slab : I;
+	const size_t rw = row_words(I);
+	double *phi = malloc(sizeof(double) * (size_t)ns * (size_t)I);
+	uint32_t *counts = malloc(sizeof(uint32_t) * 4 * (size_t)ns * (size_t)I);
+	uint64_t *bits = calloc((size_t)I * rw, sizeof *bits);
+	mc_king_pair *pairs = NULL;
+	size_t n_pairs = 0, cap = 0;
+	int rc = (phi && counts && bits) ? 0 : MCHIP_ERR_ALLOC;
+	for (int i0 = 0; i0 < I && !rc; i0 += ns) {
+		const int n = I - i0 < ns ? I - i0 : ns;
+		if ((rc = band(arg, i0, n, phi, counts))) break;
+		for (int a = 0; a < n && !rc; a++) {
+			const int i = i0 + a;
+			const double *row = phi + (size_t)a * (size_t)I;
+			for (int j = 0; j < I; j++) {
+				if (j == i || !(row[j] > t)) continue;
+				bits[(size_t)i * rw + (size_t)j / 64] |= 1ull << (j % 64);
+				if (j < i) continue;
+				if (n_pairs == cap) {
+					const size_t cap2 = cap ? 2 * cap : 64;
+					mc_king_pair *p2 = realloc(pairs, sizeof *pairs * cap2);
+					if (!p2) { rc = MCHIP_ERR_ALLOC; break; }
+					pairs = p2;
+					cap = cap2;
+				}
+				const uint32_t *c = counts + 4 * ((size_t)a * (size_t)I + (size_t)j);
+				pairs[n_pairs++] = (mc_king_pair){ i, j, c[0], c[1], c[2], row[j] };
+			}
+		}
+	}
+	free(phi); free(counts);
+	if (rc) { free(bits); free(pairs); return rc; }
+	*bits_out = bits;
+	*pairs_out = pairs;
+	*n_pairs_out = n_pairs;
+	return 0;
+}
+
+int mc_king_select(int I, const uint64_t *bits, uint8_t *keep)
+{
+	if (I < 1 || !bits || !keep) return MCHIP_ERR_INVALID;
+	const size_t rw = row_words(I);
+	int *deg = malloc(sizeof(int) * (size_t)I);
+	if (!deg) return MCHIP_ERR_ALLOC;
+	for (int i = 0; i < I; i++) {
+		deg[i] = 0;
+		for (size_t w = 0; w < rw; w++) deg[i] += __builtin_popcountll(bits[(size_t)i * rw + w]);
+	}
+	memset(keep, 1, (size_t)I);
+	for (;;) {
+		int worst = -1;
+		for (int i = 0; i < I; i++)
+			if (keep[i] && deg[i] > 0 && (worst < 0 || deg[i] >= deg[worst])) worst = i;	/* >=: of equals the highest index */
+		if (worst < 0) break;
+		keep[worst] = 0;
+		for (size_t w = 0; w < rw; w++)
+			for (uint64_t m = bits[(size_t)worst * rw + w]; m; m &= m - 1) {
+				const int j = (int)(64 * w) + __builtin_ctzll(m);
+				if (keep[j]) deg[j]--;
+			}
+	}
+	free(deg);
+	return 0;
+}
+
+int mc_king_compact(int I, int L, size_t record_bytes, const uint8_t *keep, uint8_t *bed, int *individual_of)
+{
+	int n = 0;
+	for (int i = 0; i < I; i++)
+		if (keep[i]) { if (individual_of) individual_of[n] = i; n++; }
+	const size_t rb2 = ((size_t)n + 3) / 4;
+	uint8_t *rec = calloc(rb2 ? rb2 : 1, 1);
+	if (!rec) return -1;
+	for (int l = 0; l < L; l++) {
+		const uint8_t *src = bed + (size_t)l * record_bytes;
+		memset(rec, 0, rb2);
+		for (int i = 0, x = 0; i < I; i++) {
+			if (!keep[i]) continue;
+			rec[x / 4] |= (uint8_t)(((src[i / 4] >> (2 * (i % 4))) & 3) << (2 * (x % 4)));
+			x++;
+		}
+		memcpy(bed + (size_t)l * rb2, rec, rb2);	/* (at or before the record just read: nothing unread is written over) */
+	}
+	memset(bed + (size_t)L * rb2, 0, 8);	/* the reader's spare bytes behind the last record */
+	free(rec);
+	return n;
+}
+
+static double now_s(void)
+{
+	struct timespec t;
+	clock_gettime(CLOCK_MONOTONIC, &t);
+	return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+}
+
+typedef struct device_band {
+	mchip_context *ctx;
+	const mc_cli_data *dat;
+} device_band;
+
+static int band_on_device(void *arg, int i0, int n_rows, double *phi, uint32_t *counts)
+{
+	const device_band *b = arg;
+	return mchip_bed_king(b->ctx, b->dat->I, b->dat->L, b->dat->bed, b->dat->bed_record_bytes, i0, n_rows, phi, counts);
+}
+
+static char *dup_string(const char *s)
+{
+	char *r = malloc(strlen(s) + 1);
+	if (r) strcpy(r, s);
+	return r;
+}
+
+/* everything of the data set that is per individual, made anew for the n kept ones (map[x] = the x-th kept one's place in the file):
+ * what read_fam (mc_bed.c) yields on their lines.  The file's own ids move to fam_iid / fam_fid. */
+static int rebuild_individuals(mc_cli_data *dat, int n, const int *map)
+{
+	const int I = dat->I;
+	char **fid = calloc((size_t)I, sizeof *fid), **names = calloc((size_t)n, sizeof *names), **pops = calloc((size_t)n, sizeof *pops);
+	int *locale = calloc((size_t)n, sizeof *locale), *i_p = NULL, *new_of = malloc(sizeof(int) * (size_t)(dat->numpops ? dat->numpops : 1));
+	int numpops = 0, ok = fid && names && pops && locale && new_of;
+	for (int i = 0; ok && i < I; i++) ok = (fid[i] = dup_string(dat->pops[dat->locale[i]])) != NULL;
+	for (int p = 0; ok && p < dat->numpops; p++) new_of[p] = -1;
+	for (int x = 0; ok && x < n; x++) {
+		const int old = dat->locale[map[x]];
+		if (new_of[old] < 0) {
+			if (!(pops[numpops] = dup_string(dat->pops[old]))) { ok = 0; break; }
+			new_of[old] = numpops++;
+		}
+		locale[x] = new_of[old];
+		ok = (names[x] = dup_string(dat->names[map[x]])) != NULL;
+	}
+	if (ok) ok = (i_p = calloc((size_t)(numpops ? numpops : 1), sizeof *i_p)) != NULL;
+	free(new_of);
+	if (!ok) {
+		for (int i = 0; fid && i < I; i++) free(fid[i]);
+		for (int x = 0; x < n; x++) { if (names) free(names[x]); if (pops) free(pops[x]); }
+		free(fid); free(names); free(pops); free(locale);
+		return MC_EXIT_MEMORY_ALLOCATION;
+	}
+	for (int x = 0; x < n; x++) i_p[locale[x]]++;
+	for (int p = 0; p < dat->numpops; p++) free(dat->pops[p]);
+	free(dat->pops); free(dat->locale); free(dat->i_p);
+	dat->fam_iid = dat->names;
+	dat->fam_fid = fid;
+	dat->I_file = I;
+	dat->names = names; dat->pops = pops; dat->locale = locale; dat->i_p = i_p;
+	dat->numpops = numpops;
+	dat->I = n;
+	return 0;
+}
+
+int mc_king_data(const mc_cli_options *opt, mc_cli_data *dat)
+{
+	const int I = dat->I, L = dat->L;
+	device_band b = { NULL, dat };
+	uint8_t *keep = malloc((size_t)I);
+	int *map = malloc(sizeof(int) * (size_t)I);
+	uint64_t *bits = NULL;
+	mc_king_pair *pairs = NULL;
+	size_t n_pairs = 0;
+	int rc = MC_EXIT_MEMORY_ALLOCATION;
+	const double t_start = now_s();
+	if (!keep || !map) goto DONE;
+	if (!dat->bed || dat->individual_of) { rc = MC_EXIT_INTERNAL_ERROR; goto DONE; }	/* a fileset, and not thinned before */
+	if ((rc = mchip_create(&b.ctx, opt->device))) {
+		fprintf(stderr, "ERROR [mc_king.c::mc_king_data]: cannot open device %d for --king-cutoff (status %d)\n", opt->device, rc);
+		goto DONE;
+	}
+	if ((rc = mc_king_edges(I, opt->king_t, MC_KING_SLAB, band_on_device, &b, &bits, &pairs, &n_pairs))) {
+		fprintf(stderr, "ERROR [mc_king.c::mc_king_data]: the kinship matrix failed (status %d): %s\n", rc, mchip_last_error(b.ctx));
+		goto DONE;
+	}
+	if ((rc = mc_king_select(I, bits, keep))) goto DONE;
+	/* the data set is the kept individuals' from here on: their codes in every record, their ids, and the reader's summary of those */
+	const int n = mc_king_compact(I, L, dat->bed_record_bytes, keep, dat->bed, map);
+	if (n < 1) { rc = MC_EXIT_MEMORY_ALLOCATION; goto DONE; }
+	dat->bed_record_bytes = ((size_t)n + 3) / 4;
+	if ((rc = rebuild_individuals(dat, n, map))) goto DONE;
+	dat->individual_of = map;
+	map = NULL;
+	dat->king_pairs = pairs;
+	dat->n_king_pairs = n_pairs;
+	pairs = NULL;
+	if (dat->lazy) {	/* (nothing has been decoded yet; a decoded genotype would be the file's) */
+		dat->lazy->release(dat->lazy);
+		if (!(dat->lazy = mc_bed_lazy_new())) { rc = MC_EXIT_MEMORY_ALLOCATION; goto DONE; }
+	}
+	free(dat->uniquealleles); free(dat->toff);
+	if (dat->L_alleles) for (int l = 0; l < L; l++) free(dat->L_alleles[l]);
+	free(dat->L_alleles);
+	dat->uniquealleles = dat->toff = NULL;
+	dat->L_alleles = NULL;
+	rc = mc_bed_summarize(dat);
+	if (getenv("MC_READER_TIMING")) fprintf(stderr, "INFO [mc_king.c]: %-18s %.3f s\n", "relatedness", now_s() - t_start);
+DONE:
+	if (b.ctx) mchip_destroy(b.ctx);
+	free(keep); free(map); free(bits); free(pairs);
+	return rc;
+}
+
+static FILE *open_out(const char *path)
+{
+	FILE *fp = fopen(path, "w");
+	if (!fp) fprintf(stderr, "ERROR [mc_king.c::open_out]: could not open file '%s'\n", path);
+	return fp;
+}
+
+/* <stem>.king.cutoff.in: "FID\tIID" of the individuals kept, one per line in file order; <stem>.king.cutoff.out: of those removed
+ * (`plink --keep <stem>.king.cutoff.in` writes the fileset the run was made on).  <stem>.king.kin0: one header line, then one line
+ * per pair i < j with phi > t in (i, j) order: the two ids, N_SNP = n_ij, HETHET = hh_ij / n_ij, IBS0 = op_ij / n_ij and KINSHIP =
+ * phi_ij, the three ratios as %.6f. */
+int mc_write_king_lists(const mc_cli_options *opt, const mc_cli_data *dat)
+{
+	char path[4400];
+	if (!dat->individual_of || !dat->fam_fid || !dat->fam_iid) return MC_EXIT_INTERNAL_ERROR;
+	if (opt->outfile_name) {	/* the stem of the result files (mc_writer.c) */
+		snprintf(path, sizeof path, "%s", opt->outfile_name);
+	} else {
+		const size_t pl = strlen(opt->path);
+		const int sep = pl && opt->path[pl - 1] != '/' && opt->path[pl - 1] != '\\';
+		snprintf(path, sizeof path, "%s%s%s", opt->path, sep ? "/" : "", opt->filename_file);
+	}
+	const size_t len = strlen(path);
+	FILE *in, *out, *kin;
+	snprintf(path + len, sizeof path - len, ".king.cutoff.in");
+	if (!(in = open_out(path))) return MC_EXIT_FILE_OPEN_ERROR;
+	snprintf(path + len, sizeof path - len, ".king.cutoff.out");
+	if (!(out = open_out(path))) { fclose(in); return MC_EXIT_FILE_OPEN_ERROR; }
+	snprintf(path + len, sizeof path - len, ".king.kin0");
+	if (!(kin = open_out(path))) { fclose(in); fclose(out); return MC_EXIT_FILE_OPEN_ERROR; }
+	for (int v = 0, x = 0; v < dat->I_file; v++) {
+		const int kept = x < dat->I && dat->individual_of[x] == v;
+		fprintf(kept ? in : out, "%s\t%s\n", dat->fam_fid[v], dat->fam_iid[v]);
+		x += kept;
+	}
+	fprintf(kin, "FID1\tIID1\tFID2\tIID2\tN_SNP\tHETHET\tIBS0\tKINSHIP\n");
+	for (size_t p = 0; p < dat->n_king_pairs; p++) {
+		const mc_king_pair *k = &dat->king_pairs[p];
+		fprintf(kin, "%s\t%s\t%s\t%s\t%u\t%.6f\t%.6f\t%.6f\n", dat->fam_fid[k->i], dat->fam_iid[k->i], dat->fam_fid[k->j], dat->fam_iid[k->j],
+			(unsigned)k->n, (double)k->hh / (double)k->n, (double)k->op / (double)k->n, k->phi);
+	}
+	int rc = ferror(in) || ferror(out) || ferror(kin);
+	rc |= fclose(in);
+	rc |= fclose(out);
+	rc |= fclose(kin);
+	return rc ? MC_EXIT_FILE_OPEN_ERROR : 0;
+}

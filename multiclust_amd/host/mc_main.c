@@ -17,6 +17,8 @@
  * count" of every pair of individuals (one more stdout line per K and two more files; admixture model; without it nothing changes);
  * --prune <t> thins the variants of a fileset (--bed) by linkage disequilibrium on the device before anything is fitted (mc_ld.c; one more stdout
  * line and two more files; the run is the run on the fileset of the variants kept; without it nothing changes);
+ * --king-cutoff <t> removes close relatives from a fileset (--bed) by KING-robust kinship on the device before anything is fitted (mc_king.c; one
+ * more stdout line and three more files; the run is the run on the fileset of the individuals kept; without it nothing changes);
  * --query <file> keeps the individuals the file marks out of every fit and fits their mixing proportions against the best fit of every K
  * afterwards (one more stdout line per K and one more file; without it nothing changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
@@ -94,7 +96,13 @@ static void usage(FILE *fp, const char *prog)
 		"                squared dosage correlation with a variant already kept, on its chromosome and at most W variants before it,\n"
 		"                exceeds t (0 < t <= 1) is removed (forward greedy, as SNPRelate's snpgdsLDpruning; not PLINK's --indep-pairwise);\n"
 		"                one more line 'LD pruning: ...' and the ids kept and removed in <stem>.prune.in / .prune.out; the run is the run\n"
-		"                on the fileset of the kept variants; needs --bed        --prune-window <W>  W in variants, 1..4096 (50)\n", prog);
+		"                on the fileset of the kept variants; needs --bed        --prune-window <W>  W in variants, 1..4096 (50)\n"
+		"  --king-cutoff <t>  remove close relatives from --bed before anything is fitted (after --prune, on the variants kept): while two\n"
+		"                remaining individuals have KING-robust kinship (Manichaikul et al. 2010; over all variants of the data set) above t\n"
+		"                (0 < t < 0.5), the one with the most remaining relatives is removed, of equals the later in the .fam file (greedy, this\n"
+		"                program's own rule; not PLINK 2's algorithm, not a maximum independent set); one more line 'Relatedness: ...', the ids\n"
+		"                kept and removed in <stem>.king.cutoff.in / .king.cutoff.out and the related pairs in <stem>.king.kin0; the run is the\n"
+		"                run on the fileset of the kept individuals: the files of -A and --query describe those, in their order; needs --bed\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -194,7 +202,11 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 		case 'I': BAD("-I / -I1 (alleles as indices) is not supported: the reference's own results differ in that mode");
 		case '1': if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-1"); o->min_K = (int)v; break;
 		case '2': if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-2"); o->max_K = (int)v; break;
-		case 'k': if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-k"); o->min_K = o->max_K = (int)v; break;
+		case 'k':
+			if (!strcmp(argv[i], "--king-cutoff")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--king-cutoff"); o->king = 1; o->king_t = d; break; }	/* (in full: -k... is K) */
+			if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-k");
+			o->min_K = o->max_K = (int)v;
+			break;
 		case 'm':
 			if (!strncmp(w, "mi", 2)) { if (arg_int(argc, argv, ++i, &v)) BAD("--missing"); o->missing_value = (int)v; }
 			else { if (arg_int(argc, argv, ++i, &v) || v < 0) BAD("-m"); o->n_rand_em_init = o->em.n_rand_em_init = (int)v; }
@@ -314,6 +326,9 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			!(o->prune_t > 0 && o->prune_t <= 1) ? "the r2 threshold of --prune must lie in (0, 1]" :
 			o->prune_window < 1 || o->prune_window > MCHIP_LD_MAX_WINDOW ? "--prune-window must lie in 1 ... 4096 variants" : NULL,
 			MC_EXIT_INVALID_USER_SETUP))) return rc;
+	if (o->king && (rc = refuse("--king-cutoff",
+			!o->bed_prefix ? "--king-cutoff needs a PLINK fileset (--bed)" :
+			!(o->king_t > 0 && o->king_t < 0.5) ? "the kinship threshold of --king-cutoff must lie in (0, 0.5)" : NULL))) return rc;
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -1010,6 +1025,12 @@ int main(int argc, const char **argv)
 		if ((rc = mc_ld_prune_data(&o, &d))) return rc;
 		printf("LD pruning: kept %d of %d variants (r2 > %g within %d)\n", d.L, d.L_file, o.prune_t, o.prune_window);
 		if (o.write_files && (rc = mc_write_prune_lists(&o, &d))) return rc;
+	}
+	if (o.king) {	/* the data set is the kept individuals' from here on (on the variants kept above); the lists say who they are */
+		mchip_progress_note("mc_king_data");
+		if ((rc = mc_king_data(&o, &d))) return rc;
+		printf("Relatedness: kept %d of %d individuals (KING-robust kinship > %g: %zu pairs)\n", d.I, d.I_file, o.king_t, d.n_king_pairs);
+		if (o.write_files && (rc = mc_write_king_lists(&o, &d))) return rc;
 	}
 	mchip_progress_note("estimate_model");
 	if (o.em.verbosity >= MC_TALKATIVE)

@@ -371,6 +371,11 @@ void mc_free_data(mc_cli_data *dat)
 	free(dat->pops);
 	free(dat->bed);
 	free(dat->bim_text); free(dat->chrom); free(dat->variant_id); free(dat->variant_of);
+	for (int i = 0; i < dat->I_file; i++) {
+		if (dat->fam_fid) free(dat->fam_fid[i]);
+		if (dat->fam_iid) free(dat->fam_iid[i]);
+	}
+	free(dat->fam_fid); free(dat->fam_iid); free(dat->individual_of); free(dat->king_pairs);
 	if (dat->lazy) dat->lazy->release(dat->lazy);
 	memset(dat, 0, sizeof *dat);
 }
