@@ -59,6 +59,20 @@ __device__ __forceinline__ uint32_t bed_word(const uint8_t *__restrict__ bed, si
 	return sh ? (lo >> sh) | (w[1] << (32u - sh)) : lo;
 }
 
+/* a tile of BT_L records x BT_I individuals into LDS: the 64 bytes from byte i0 / 4 of the records l0 ... l0 + BT_L - 1 as 16 dwords
+ * each, BT_ROW dwords apart; 0 behind the record's last byte and for the records behind the last.  All 256 lanes; the caller syncs. */
+__device__ __forceinline__ void bed_stage_tile(uint32_t *tile, const uint8_t *__restrict__ bed, size_t rb, int L, int l0, int i0)
+{
+	const size_t b0 = (size_t)(i0 / 4);	/* first staged byte of every record */
+	for (int x = threadIdx.x; x < BT_L * 16; x += 256) {
+		const int ll = x / 16, w = x % 16, l = l0 + ll;
+		const size_t off = b0 + 4 * (size_t)w;
+		tile[ll * BT_ROW + w] = (l < L && off < rb) ? bed_word(bed, (size_t)l * rb + off) : 0u;
+	}
+}
+
+constexpr long long QUIET_NAN_BITS = 0x7FF8000000000000ll;	/* the NaN of a pair without a value (k_ld_r2, k_king_phi) */
+
 /* locus pass: ua[l] as the STRUCTURE reader counts it, a1[l] = 1 when allele A1 is observed at locus l (the one thing the recoding
  * of a locus depends on), bit 1 of *flags set when any call is missing */
 __global__ __launch_bounds__(256) void k_bed_locus(const uint8_t *__restrict__ bed, size_t rb, int I, int L, int32_t *__restrict__ ua,
@@ -100,12 +114,7 @@ __global__ __launch_bounds__(256) void k_bed_expand(const uint8_t *__restrict__ 
 	__shared__ __attribute__((aligned(16))) uint32_t tile[BT_L * BT_ROW];
 	__shared__ uint32_t hom2[BT_L];		/* byte pair of a homozygous A2 call of the locus */
 	const int l0 = (blockIdx.x % n_ltiles) * BT_L, i0 = (blockIdx.x / n_ltiles) * BT_I;
-	const size_t b0 = (size_t)(i0 / 4);	/* first staged byte of every record */
-	for (int x = threadIdx.x; x < BT_L * 16; x += 256) {
-		const int ll = x / 16, w = x % 16, l = l0 + ll;
-		const size_t off = b0 + 4 * (size_t)w;
-		tile[ll * BT_ROW + w] = (l < L && off < rb) ? bed_word(bed, (size_t)l * rb + off) : 0u;
-	}
+	bed_stage_tile(tile, bed, rb, L, l0, i0);
 	if (threadIdx.x < BT_L) hom2[threadIdx.x] = (l0 + (int)threadIdx.x < L && a1[l0 + threadIdx.x]) ? 0x0101u : 0u;
 	__syncthreads();
 	const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
@@ -145,26 +154,34 @@ __global__ __launch_bounds__(256) void k_bed_expand(const uint8_t *__restrict__ 
 	if (any) seen[i0 + threadIdx.x] = 1;	/* (every writer stores the same value) */
 }
 
+/* what every entry point asks of its records, and how they go up: n_bytes of whole records and BED_PAD zero bytes behind them in a
+ * buffer of d_bed's own.  d_bed.p stays null when the buffer does not fit; the return value is the first failure's. */
+static bool bed_shape_ok(int I, int L, const uint8_t *bed, size_t record_bytes) { return I > 0 && L > 0 && bed && record_bytes >= ((size_t)I + 3) / 4; }
+static hipError_t bed_upload(mchip_context *ctx, scoped_dev<uint8_t> &d_bed, const uint8_t *records, size_t n_bytes)
+{
+	hipError_t e = d_bed.alloc(n_bytes + BED_PAD);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_bed.p, records, n_bytes, hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(d_bed.p + n_bytes, 0, BED_PAD, ctx->stream);
+	return e;
+}
+
 /* The packed records go up as they are; the locus pass tells the host the allele counts set_shape sizes the column tables from,
  * the expand pass fills gtA / gtS.  No stream buffer (d_draw) and no k_relayout on this route. */
 extern "C" int mchip_set_genotypes_bed(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int32_t *uniquealleles_out)
 {
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
-	if (I <= 0 || L <= 0 || !bed || record_bytes < ((size_t)I + 3) / 4)
+	if (!bed_shape_ok(I, L, bed, record_bytes))
 		return fail(ctx, MCHIP_ERR_INVALID, "set_genotypes_bed: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
-	const size_t bed_bytes = (size_t)L * record_bytes;
 	scoped_dev<uint8_t> d_bed, d_a1, d_seen;
 	scoped_dev<int32_t> d_ua;
-	HIPCHK(d_bed.alloc(bed_bytes + BED_PAD));
+	HIPCHK(bed_upload(ctx, d_bed, bed, (size_t)L * record_bytes));
 	HIPCHK(d_a1.alloc((size_t)L));
 	HIPCHK(d_seen.alloc((size_t)I));
 	HIPCHK(d_ua.alloc((size_t)L));
 	int *d_bad = bad_flag(ctx);
-	HIPCHK(hipMemcpyAsync(d_bed.p, bed, bed_bytes, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(hipMemsetAsync(d_bed.p + bed_bytes, 0, BED_PAD, ctx->stream));
 	HIPCHK(hipMemsetAsync(d_seen.p, 0, (size_t)I, ctx->stream));
 	HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
 	hipLaunchKernelGGL(k_bed_locus, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, ctx->stream, d_bed.p, record_bytes, I, L, d_ua.p, d_a1.p, d_bad);
@@ -290,7 +307,7 @@ __global__ __launch_bounds__(256) void k_ld_r2(const uint32_t *__restrict__ sums
 {
 	for (size_t x = (size_t)blockIdx.x * 256 + threadIdx.x; x < n_pairs; x += (size_t)gridDim.x * 256) {
 		const size_t a = x / (size_t)window, d = x % (size_t)window + 1;
-		double out = __longlong_as_double(0x7FF8000000000000ll);
+		double out = __longlong_as_double(QUIET_NAN_BITS);
 		if (a + d < (size_t)n_up) {
 			const uint32_t *s = sums + x * 6;
 			const int64_t n = s[0], Sx = s[1], Sy = s[2], Sxx = s[3], Syy = s[4], Sxy = s[5];
@@ -306,7 +323,7 @@ extern "C" int mchip_bed_ld_band(mchip_context *ctx, int I, int L, const uint8_t
 {
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
-	if (I <= 0 || L <= 0 || !bed || !r2 || record_bytes < ((size_t)I + 3) / 4)
+	if (!bed_shape_ok(I, L, bed, record_bytes) || !r2)
 		return fail(ctx, MCHIP_ERR_INVALID, "bed_ld_band: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
 	if (l0 < 0 || n_first < 0 || (long long)l0 + n_first > L || window < 1 || window > MCHIP_LD_MAX_WINDOW)
 		return fail(ctx, MCHIP_ERR_INVALID, "bed_ld_band: first variants outside the records, or a window outside 1 ... 4096%s", nullptr);
@@ -321,12 +338,12 @@ extern "C" int mchip_bed_ld_band(mchip_context *ctx, int I, int L, const uint8_t
 	scoped_dev<uint8_t> d_bed;
 	scoped_dev<uint32_t> d_sums;
 	scoped_dev<double> d_r2;
-	if (d_bed.alloc(up_bytes + BED_PAD) != hipSuccess || d_sums.alloc(n_pairs * 6) != hipSuccess || d_r2.alloc(n_pairs) != hipSuccess) {
+	const hipError_t uploaded = bed_upload(ctx, d_bed, bed + (size_t)l0 * record_bytes, up_bytes);
+	if (!d_bed.p || d_sums.alloc(n_pairs * 6) != hipSuccess || d_r2.alloc(n_pairs) != hipSuccess) {
 		(void)hipGetLastError();
 		return fail(ctx, MCHIP_ERR_ALLOC, "bed_ld_band: the records, the sums or the band do not fit on the device%s", nullptr);
 	}
-	HIPCHK(hipMemcpyAsync(d_bed.p, bed + (size_t)l0 * record_bytes, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(hipMemsetAsync(d_bed.p + up_bytes, 0, BED_PAD, ctx->stream));
+	HIPCHK(uploaded);
 	HIPCHK(hipMemsetAsync(d_sums.p, 0, n_pairs * 6 * sizeof(uint32_t), ctx->stream));
 	hipLaunchKernelGGL(k_ld_band, dim3((unsigned)(g.n_tiles * g.n_dchunks), (unsigned)g.n_split), dim3(256), 0, ctx->stream, d_bed.p, record_bytes,
 			   I, n_up, n_first, window, g, d_sums.p);
@@ -351,12 +368,7 @@ __global__ __launch_bounds__(256) void k_king_planes(const uint8_t *__restrict__
 {
 	__shared__ uint32_t tile[BT_L * BT_ROW];
 	const int w = blockIdx.x % n_words, l0 = w * BT_L, i0 = (blockIdx.x / n_words) * BT_I;
-	const size_t b0 = (size_t)(i0 / 4);	/* first staged byte of every record */
-	for (int x = threadIdx.x; x < BT_L * 16; x += 256) {
-		const int ll = x / 16, d = x % 16, l = l0 + ll;
-		const size_t off = b0 + 4 * (size_t)d;
-		tile[ll * BT_ROW + d] = (l < L && off < rb) ? bed_word(bed, (size_t)l * rb + off) : 0u;
-	}
+	bed_stage_tile(tile, bed, rb, L, l0, i0);
 	__syncthreads();
 	const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
 	const int lane = threadIdx.x & 63, first = (threadIdx.x >> 6) * 64;
@@ -463,7 +475,7 @@ __global__ __launch_bounds__(256) void k_king_phi(const uint32_t *__restrict__ s
 		const int64_t hh = sums[4 * x + 1], op = sums[4 * x + 2], hij = sums[4 * x + 3], hj = hji[x];
 		const int64_t m = hij < hj ? hij : hj;
 		const int64_t num = 2 * hh - 4 * op - hij - hj + 2 * m;
-		phi[x] = m ? (double)num / (double)(4 * m) : __longlong_as_double(0x7FF8000000000000ll);
+		phi[x] = m ? (double)num / (double)(4 * m) : __longlong_as_double(QUIET_NAN_BITS);
 	}
 }
 
@@ -472,7 +484,7 @@ extern "C" int mchip_bed_king(mchip_context *ctx, int I, int L, const uint8_t *b
 {
 	MCHIP_ENTRY();
 	if (!ctx) return MCHIP_ERR_INVALID;
-	if (I <= 0 || L <= 0 || !bed || !phi || record_bytes < ((size_t)I + 3) / 4)
+	if (!bed_shape_ok(I, L, bed, record_bytes) || !phi)
 		return fail(ctx, MCHIP_ERR_INVALID, "bed_king: bad shape, null pointer or records shorter than ceil(I/4) bytes%s", nullptr);
 	if (i0 < 0 || n_rows < 0 || (long long)i0 + n_rows > I)
 		return fail(ctx, MCHIP_ERR_INVALID, "bed_king: rows outside the individuals%s", nullptr);
@@ -490,13 +502,13 @@ extern "C" int mchip_bed_king(mchip_context *ctx, int I, int L, const uint8_t *b
 	scoped_dev<uint64_t> d_planes;
 	scoped_dev<uint32_t> d_sums, d_hji;
 	scoped_dev<double> d_phi;
-	if (d_bed.alloc(bed_bytes + BED_PAD) != hipSuccess || d_planes.alloc(n_planes) != hipSuccess || d_sums.alloc(n_pairs * 4) != hipSuccess ||
+	const hipError_t uploaded = bed_upload(ctx, d_bed, bed, bed_bytes);
+	if (!d_bed.p || d_planes.alloc(n_planes) != hipSuccess || d_sums.alloc(n_pairs * 4) != hipSuccess ||
 	    d_hji.alloc(n_pairs) != hipSuccess || d_phi.alloc(n_pairs) != hipSuccess) {
 		(void)hipGetLastError();
 		return fail(ctx, MCHIP_ERR_ALLOC, "bed_king: the records, the planes or the slab's counts and kinships do not fit on the device%s", nullptr);
 	}
-	HIPCHK(hipMemcpyAsync(d_bed.p, bed, bed_bytes, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(hipMemsetAsync(d_bed.p + bed_bytes, 0, BED_PAD, ctx->stream));
+	HIPCHK(uploaded);
 	HIPCHK(hipMemsetAsync(d_sums.p, 0, n_pairs * 4 * sizeof(uint32_t), ctx->stream));
 	HIPCHK(hipMemsetAsync(d_hji.p, 0, n_pairs * sizeof(uint32_t), ctx->stream));
 	hipLaunchKernelGGL(k_king_planes, dim3((unsigned)t_blocks), dim3(256), 0, ctx->stream, d_bed.p, record_bytes, I, L, n_words, Ipad, d_planes.p);

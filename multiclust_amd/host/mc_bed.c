@@ -12,7 +12,6 @@
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 static int fail(const char *fn, int line, int status, const char *msg, const char *arg)
 {
@@ -122,59 +121,14 @@ mc_lazy_geno *mc_bed_lazy_new(void)
 	return &z->base;
 }
 
-static double now_s(void)
-{
-	struct timespec t;
-	clock_gettime(CLOCK_MONOTONIC, &t);
-	return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-}
-
 /* ---- the three files ---- */
-static char *path_of(const char *prefix, const char *ext)
-{
-	char *p = malloc(strlen(prefix) + strlen(ext) + 1);
-	if (p) { strcpy(p, prefix); strcat(p, ext); }
-	return p;
-}
-
-/* whole file into memory, NUL-terminated; *size = its length */
-static int slurp(const char *path, char **out, size_t *size)
-{
-	FILE *f = fopen(path, "rb");
-	*out = NULL;
-	if (!f) return FAIL(MC_EXIT_FILE_OPEN_ERROR, "could not open file '%s'", path);
-	fseek(f, 0, SEEK_END);
-	const long n = ftell(f);
-	fseek(f, 0, SEEK_SET);
-	char *buf = n >= 0 ? malloc((size_t)n + 1) : NULL;
-	if (!buf) { fclose(f); return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory reading '%s'", path); }
-	if (fread(buf, 1, (size_t)n, f) != (size_t)n) { fclose(f); free(buf); return FAIL(MC_EXIT_FILE_FORMAT_ERROR, "short read on '%s'", path); }
-	fclose(f);
-	buf[n] = 0;
-	*out = buf;
-	*size = (size_t)n;
-	return 0;
-}
-
-static int is_blank(char c) { return c == ' ' || c == '\t' || c == '\r'; }
-
 /* lines that hold anything but white space */
-static size_t count_lines(const char *buf, size_t n)
+static size_t count_lines(char *buf, size_t n)
 {
 	size_t lines = 0;
-	int content = 0;
-	for (size_t x = 0; x < n; x++) {
-		if (buf[x] == '\n') { lines += (size_t)content; content = 0; }
-		else if (!is_blank(buf[x])) content = 1;
-	}
-	return lines + (size_t)content;
-}
-
-static char *dup_token(const char *s, size_t len)
-{
-	char *r = malloc(len + 1);
-	if (r) { memcpy(r, s, len); r[len] = 0; }
-	return r;
+	mc_lines it;
+	for (mc_lines_start(&it, buf, n); mc_lines_next(&it);) lines++;
+	return lines;
 }
 
 /* .fam: one line per individual, FID IID ...: the locale (numbered in order of first appearance, as the STRUCTURE reader numbers
@@ -183,7 +137,7 @@ static int read_fam(const char *path, mc_cli_data *dat)
 {
 	char *buf;
 	size_t n;
-	int rc = slurp(path, &buf, &n);
+	int rc = mc_slurp("mc_bed.c", path, &buf, &n);
 	if (rc) return rc;
 	const size_t I = count_lines(buf, n);
 	if (!I || I > 0x7FFFFFFF / 4) { free(buf); return FAIL(MC_EXIT_FILE_FORMAT_ERROR, "no individuals (or too many) in '%s'", path); }
@@ -192,34 +146,27 @@ static int read_fam(const char *path, mc_cli_data *dat)
 	dat->locale = calloc(I, sizeof *dat->locale);
 	if (!dat->names || !dat->locale) { free(buf); return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); }
 	int i = 0;
-	for (char *p = buf, *eof = buf + n; p < eof;) {
-		char *q = memchr(p, '\n', (size_t)(eof - p));
-		if (!q) q = eof;
-		char *s = p;
-		while (s < q && is_blank(*s)) s++;
-		if (s < q) {
-			char *fid = s;
-			while (s < q && !is_blank(*s)) s++;
-			const size_t flen = (size_t)(s - fid);
-			while (s < q && is_blank(*s)) s++;
-			char *iid = s;
-			while (s < q && !is_blank(*s)) s++;
-			const size_t ilen = (size_t)(s - iid);
-			if (!ilen) { free(buf); return FAIL(MC_EXIT_FILE_FORMAT_ERROR, "line without family and individual ID in '%s'", path); }
-			int found = -1;
-			for (int x = 0; x < dat->numpops; x++)
-				if (strlen(dat->pops[x]) == flen && !strncmp(dat->pops[x], fid, flen)) { found = x; break; }
-			if (found < 0) {
-				char **pops2 = realloc(dat->pops, sizeof *dat->pops * (size_t)(dat->numpops + 1));
-				if (pops2) dat->pops = pops2;
-				if (!pops2 || !(dat->pops[dat->numpops] = dup_token(fid, flen))) { free(buf); return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); }
-				found = dat->numpops++;
-			}
-			dat->locale[i] = found;
-			if (!(dat->names[i] = dup_token(iid, ilen))) { free(buf); return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); }
-			i++;
+	mc_lines it;
+	for (mc_lines_start(&it, buf, n); mc_lines_next(&it); i++) {
+		char *s = it.first, *q = it.end, *fid = s;
+		while (s < q && !mc_is_blank(*s)) s++;
+		const size_t flen = (size_t)(s - fid);
+		while (s < q && mc_is_blank(*s)) s++;
+		char *iid = s;
+		while (s < q && !mc_is_blank(*s)) s++;
+		const size_t ilen = (size_t)(s - iid);
+		if (!ilen) { free(buf); return FAIL(MC_EXIT_FILE_FORMAT_ERROR, "line without family and individual ID in '%s'", path); }
+		int found = -1;
+		for (int x = 0; x < dat->numpops; x++)
+			if (strlen(dat->pops[x]) == flen && !strncmp(dat->pops[x], fid, flen)) { found = x; break; }
+		if (found < 0) {
+			char **pops2 = realloc(dat->pops, sizeof *dat->pops * (size_t)(dat->numpops + 1));
+			if (pops2) dat->pops = pops2;
+			if (!pops2 || !(dat->pops[dat->numpops] = mc_dup_token(fid, flen))) { free(buf); return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); }
+			found = dat->numpops++;
 		}
-		p = q + 1;
+		dat->locale[i] = found;
+		if (!(dat->names[i] = mc_dup_token(iid, ilen))) { free(buf); return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); }
 	}
 	free(buf);
 	if (!(dat->i_p = calloc((size_t)dat->numpops, sizeof *dat->i_p))) return FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL);
@@ -264,26 +211,19 @@ static int bim_fields(mc_cli_data *dat, size_t n, size_t nloci)
 	dat->variant_id = calloc(nloci, sizeof *dat->variant_id);
 	if (!dat->chrom || !dat->variant_id) return MC_EXIT_MEMORY_ALLOCATION;
 	size_t l = 0;
-	for (char *p = dat->bim_text, *eof = p + n; p < eof;) {
-		char *q = memchr(p, '\n', (size_t)(eof - p));
-		if (!q) q = eof;
-		char *s = p;
-		while (s < q && is_blank(*s)) s++;
-		if (s < q) {
-			char *c = s;
-			while (s < q && !is_blank(*s)) s++;
-			char *c_end = s;
-			while (s < q && is_blank(*s)) s++;
-			char *id = s;
-			while (s < q && !is_blank(*s)) s++;
-			*c_end = 0;
-			*s = 0;		/* (the line's end, or the blank behind the id; the text has one more byte behind its last.  A line
-					 * without a second field has the empty id) */
-			dat->chrom[l] = c;
-			dat->variant_id[l] = id;
-			l++;
-		}
-		p = q + 1;
+	mc_lines it;
+	for (mc_lines_start(&it, dat->bim_text, n); mc_lines_next(&it); l++) {
+		char *s = it.first, *q = it.end, *c = s;
+		while (s < q && !mc_is_blank(*s)) s++;
+		char *c_end = s;
+		while (s < q && mc_is_blank(*s)) s++;
+		char *id = s;
+		while (s < q && !mc_is_blank(*s)) s++;
+		*c_end = 0;
+		*s = 0;		/* (the line's end, or the blank behind the id; the text has one more byte behind its last.  A line
+				 * without a second field has the empty id) */
+		dat->chrom[l] = c;
+		dat->variant_id[l] = id;
 	}
 	return 0;
 }
@@ -294,15 +234,15 @@ int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat)
 	char *bedf = NULL, *bimf = NULL, *famf = NULL, *buf = NULL;
 	FILE *f = NULL;
 	size_t n;
-	const double t_start = now_s();
+	const double t_start = mc_now_s();
 	memset(dat, 0, sizeof *dat);
 	dat->ploidy = 2;
 	if (!opt->bed_prefix) return FAIL(MC_EXIT_INVALID_USER_SETUP, "no fileset prefix%s", NULL);
-	bedf = path_of(opt->bed_prefix, ".bed"); bimf = path_of(opt->bed_prefix, ".bim"); famf = path_of(opt->bed_prefix, ".fam");
+	bedf = mc_path_of(opt->bed_prefix, ".bed"); bimf = mc_path_of(opt->bed_prefix, ".bim"); famf = mc_path_of(opt->bed_prefix, ".fam");
 	if (!bedf || !bimf || !famf) { rc = FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); goto DONE; }
 	mchip_progress_note("mc_read_bed: .fam and .bim");
 	if ((rc = read_fam(famf, dat))) goto DONE;
-	if ((rc = slurp(bimf, &buf, &n))) goto DONE;
+	if ((rc = mc_slurp("mc_bed.c", bimf, &buf, &n))) goto DONE;
 	const size_t nloci = count_lines(buf, n);
 	if (!nloci || nloci > 0x7FFFFFFF / 4) { rc = FAIL(MC_EXIT_FILE_FORMAT_ERROR, "no variants (or too many) in '%s'", bimf); goto DONE; }
 	dat->bim_text = buf;
@@ -329,8 +269,7 @@ int mc_read_bed(const mc_cli_options *opt, mc_cli_data *dat)
 	mchip_progress_note("mc_read_bed: allele lists");
 	if (!(dat->lazy = mc_bed_lazy_new())) { rc = FAIL(MC_EXIT_MEMORY_ALLOCATION, "out of memory%s", NULL); goto DONE; }
 	if ((rc = mc_bed_summarize(dat))) goto DONE;
-	if (getenv("MC_READER_TIMING"))		/* as mc_read_structure reports its phases */
-		fprintf(stderr, "INFO [mc_bed.c]: %-18s %.3f s\n", "fileset read", now_s() - t_start);
+	mc_timing_line("mc_bed.c", "fileset read", t_start);	/* as mc_read_structure reports its phases */
 	rc = 0;
 DONE:
 	if (f) fclose(f);

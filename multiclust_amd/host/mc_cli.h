@@ -104,6 +104,26 @@ typedef struct mc_cli_data {
 	size_t n_king_pairs;
 } mc_cli_data;
 
+/* ---- file plumbing (mc_files.h, libc only, static inline): one copy of what the readers, the writers and the filters of a fileset share.  `origin`
+ * is the caller's source file: the lines on stderr read "ERROR [<origin>::open_out]: ..." and "ERROR [<origin>::slurp]: ...".
+ * mc_result_path: the stem of the result files -- opt->outfile_name (-o), else opt->path (-d), a '/' unless it is empty or ends in
+ * '/' or '\', and the file part of the data file's name -- followed by the printf-style suffix, into out[n] (cut, never overrun).
+ * Returns the length of the stem as it stands in out: snprintf(out + len, n - len, ...) puts another suffix behind the same stem.
+ * mc_open_result: fopen, and the "could not open file" line on failure.  mc_close_result: fclose; MC_EXIT_FILE_OPEN_ERROR when the
+ * stream had failed or the close does, else 0.
+ * mc_path_of: prefix + ext, allocated.  mc_slurp: the whole file into memory, NUL-terminated, *size = its length; returns 0 or the
+ * exit status of the failure, which it reports (cannot be opened 5, out of memory 3, short read 7).
+ * mc_is_blank: the white space between the tokens of a line.  mc_dup_token: an allocated copy of len bytes, NUL-terminated.
+ * mc_now_s: the monotonic clock in seconds.  mc_timing_line: under MC_READER_TIMING the line "INFO [<origin>]: <what> <seconds> s"
+ * for the time since t_start; returns the clock, i.e. the start of the next phase.
+ * mc_lines: the lines of text[n] that hold anything but white space, in order.  After mc_lines_next returned 1: line = the line's
+ * first byte, first = its first byte that is not blank, end = its '\n' (or the text's end: a last line without one), stop = the
+ * byte behind the line, its '\n' included; 0: no such line is left.
+ * mc_copy_kept_lines: file `to` = of the lines of file `from` that hold anything but white space, the kept[0 .. n - 1]-th
+ * (ascending), byte for byte with their ends.  mc_write_kept_lists: <stem><suffix>.in and <stem><suffix>.out -- of n_file entries
+ * those that kept[0 .. n_kept - 1] (ascending) names and the others, each in file order, entry v as print(fp, arg, v) writes it. */
+#include "mc_files.h"
+
 /* read_file + summarize_alleles + sufficient_statistics (read_file.c:38-300,443-663), default (allele-code) mode */
 int mc_read_structure(const mc_cli_options *opt, mc_cli_data *dat);
 void mc_free_data(mc_cli_data *dat);
@@ -185,6 +205,19 @@ int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const
  * in the header comment of mc_resid.c.  Returns 0 or an exit status of the enum above. */
 int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r);
 
+/* ---- what the filters of a fileset that run before the fit share (mc_filter.h, included at the end of this file); pre_fit() of mc_main.c runs them.
+ * mc_filter_on_device: opens device opt->device, calls decide(opt, &dev, out) -- dev is what a band callback on the device needs --
+ * and closes it; the lines "ERROR [<origin>]: cannot open device .. for <option>" and "ERROR [<origin>]: <noun> failed (status ..):
+ * <the device's last error>" are its.  Returns 0 or the status.
+ * mc_filter_resummarize: the data set has changed -- uniquealleles, toff and L_alleles of the L_before loci it had are dropped and
+ * made anew from the records held now (mc_bed_summarize), and under MC_READER_TIMING the seconds since t_start are reported as the
+ * readers report theirs.  Returns mc_bed_summarize's status. */
+typedef struct mc_device_band {
+	mchip_context *ctx;
+	const mc_cli_data *dat;
+} mc_device_band;
+typedef int (*mc_filter_fn)(const mc_cli_options *opt, mc_device_band *dev, void *out);
+
 /* --prune (an extension, mc_ld.c; r2 is defined in include/multiclust_hip.h, the rule in the header comment of mc_ld.c).
  * mc_ld_band_fn: r2[n_first][window] of the variants l0 ... l0 + n_first - 1 with their successors, as mchip_bed_ld_band fills it;
  * returns 0 or a status.
@@ -235,5 +268,7 @@ int mc_king_data(const mc_cli_options *opt, mc_cli_data *dat);
 int mc_write_king_lists(const mc_cli_options *opt, const mc_cli_data *dat);
 /* a new decoder of the packed records for dat->lazy (mc_bed.c): nothing decoded yet; NULL when out of memory */
 struct mc_lazy_geno *mc_bed_lazy_new(void);
+
+#include "mc_filter.h"
 
 #endif

@@ -129,27 +129,12 @@ static void put(FILE *fp, double v, char end)
 	else fprintf(fp, "%.10f%c", v, end);
 }
 
-static FILE *open_out(const char *path)
-{
-	FILE *fp = fopen(path, "w");
-	if (!fp) fprintf(stderr, "ERROR [mc_diverge.c::open_out]: could not open file '%s'\n", path);
-	return fp;
-}
-
 int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const mc_divergence_result *r)
 {
 	char path[4400];
 	const int K = r->K;
-	if (opt->outfile_name) {	/* the stem of the result files (mc_writer.c) */
-		snprintf(path, sizeof path, "%s", opt->outfile_name);
-	} else {
-		const size_t pl = strlen(opt->path);
-		const int sep = pl && opt->path[pl - 1] != '/' && opt->path[pl - 1] != '\\';
-		snprintf(path, sizeof path, "%s%s%s", opt->path, sep ? "/" : "", opt->filename_file);
-	}
-	const size_t len = strlen(path);
-	snprintf(path + len, sizeof path - len, ".%s.K=%d.fst.txt", opt->em.admixture ? "admix" : "mix", K);
-	FILE *fp = open_out(path);
+	const size_t len = mc_result_path(opt, path, sizeof path, ".%s.K=%d.fst.txt", opt->em.admixture ? "admix" : "mix", K);
+	FILE *fp = mc_open_result("mc_diverge.c", path, "w");
 	if (!fp) return MC_EXIT_FILE_OPEN_ERROR;
 	fprintf(fp, "k\tweight\tH\n");
 	for (int k = 0; k < K; k++) {
@@ -163,18 +148,14 @@ int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const
 		for (int a = 0; a < K; a++)
 			for (int b = 0; b < K; b++) put(fp, m[(size_t)a * K + b], b + 1 < K ? '\t' : '\n');
 	}
-	int bad = ferror(fp);
-	if (fclose(fp)) bad = 1;
-	if (bad) return MC_EXIT_FILE_OPEN_ERROR;
+	if (mc_close_result(fp)) return MC_EXIT_FILE_OPEN_ERROR;
 	snprintf(path + len, sizeof path - len, ".%s.K=%d.fst.loci.txt", opt->em.admixture ? "admix" : "mix", K);
-	if (!(fp = open_out(path))) return MC_EXIT_FILE_OPEN_ERROR;
+	if (!(fp = mc_open_result("mc_diverge.c", path, "w"))) return MC_EXIT_FILE_OPEN_ERROR;
 	fprintf(fp, "l\tcolumns\tHT\tFst\n");
 	for (int l = 0; l < dat->L; l++) {
 		fprintf(fp, "%d\t%d\t", l, (int)dat->uniquealleles[l]);
 		put(fp, r->locus_ht[l], '\t');
 		put(fp, r->locus_f[l], '\n');
 	}
-	bad = ferror(fp);
-	if (fclose(fp)) bad = 1;
-	return bad ? MC_EXIT_FILE_OPEN_ERROR : 0;
+	return mc_close_result(fp);
 }

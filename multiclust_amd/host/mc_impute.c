@@ -62,50 +62,16 @@ int mc_impute(const mc_options *opt, const mc_data *dat, mc_model *mod, uint8_t 
 }
 
 /* ---- the writers ---- */
-static int is_space(char c) { return c == ' ' || c == '\t' || c == '\r'; }
-
-/* whole file into memory; *size = its length */
-static int slurp(const char *path, char **out, size_t *size)
-{
-	FILE *f = fopen(path, "rb");
-	*out = NULL;
-	if (!f) {
-		fprintf(stderr, "ERROR [mc_impute.c::slurp]: could not open file '%s'\n", path);
-		return MC_EXIT_FILE_OPEN_ERROR;
-	}
-	fseek(f, 0, SEEK_END);
-	const long n = ftell(f);
-	fseek(f, 0, SEEK_SET);
-	char *buf = n >= 0 ? malloc((size_t)n + 1) : NULL;
-	if (!buf) { fclose(f); return MC_EXIT_MEMORY_ALLOCATION; }
-	if (fread(buf, 1, (size_t)n, f) != (size_t)n) {
-		fclose(f);
-		free(buf);
-		fprintf(stderr, "ERROR [mc_impute.c::slurp]: short read on '%s'\n", path);
-		return MC_EXIT_FILE_FORMAT_ERROR;
-	}
-	fclose(f);
-	buf[n] = 0;
-	*out = buf;
-	*size = (size_t)n;
-	return 0;
-}
-
-static FILE *open_out(const char *path)
-{
-	FILE *fp = fopen(path, "wb");
-	if (!fp) fprintf(stderr, "ERROR [mc_impute.c::open_out]: could not open file '%s'\n", path);
-	return fp;
-}
+#define open_out(path) mc_open_result("mc_impute.c", path, "wb")
 
 /* next token of [*cur, end): its first byte, *cur behind it; NULL when the line is exhausted */
 static const char *next_token(const char **cur, const char *end)
 {
 	const char *p = *cur;
-	while (p < end && is_space(*p)) p++;
+	while (p < end && mc_is_blank(*p)) p++;
 	if (p >= end) { *cur = p; return NULL; }
 	const char *s = p;
-	while (p < end && !is_space(*p)) p++;
+	while (p < end && !mc_is_blank(*p)) p++;
 	*cur = p;
 	return s;
 }
@@ -119,7 +85,7 @@ int mc_write_filled_structure(const mc_cli_options *opt, const mc_cli_data *dat,
 	const size_t ndata = dat->interleaved ? (size_t)I : (size_t)I * (size_t)pl;
 	char *buf;
 	size_t n;
-	int rc = slurp(opt->filename, &buf, &n);
+	int rc = mc_slurp("mc_impute.c", opt->filename, &buf, &n);
 	if (rc) return rc;
 	if (!dat->geno) { free(buf); return MC_EXIT_INTERNAL_ERROR; }
 	FILE *fp = open_out(out_path);
@@ -127,13 +93,10 @@ int mc_write_filled_structure(const mc_cli_options *opt, const mc_cli_data *dat,
 	const char *done = buf, *eof = buf + n;		/* [buf, done) is written */
 	size_t line = 0, first = 1;
 	rc = 0;
-	for (const char *p = buf; p < eof && !rc;) {
-		const char *q = memchr(p, '\n', (size_t)(eof - p));
-		if (!q) q = eof;
-		const char *c = p;
+	mc_lines it;
+	for (mc_lines_start(&it, buf, n); !rc && mc_lines_next(&it);) {
+		const char *q = it.end, *c = it.first;
 		const char *t = next_token(&c, q);
-		p = q + 1;
-		if (!t) continue;	/* a blank line */
 		const size_t idx = line++;
 		if (idx == 1 && c - t == 2 && !strncmp(t, "-1", 2)) first = 2;
 		if (idx < first || idx - first >= ndata) continue;
@@ -164,7 +127,7 @@ static int copy_file(const char *from, const char *to)
 {
 	char *buf;
 	size_t n;
-	int rc = slurp(from, &buf, &n);
+	int rc = mc_slurp("mc_impute.c", from, &buf, &n);
 	if (rc) return rc;
 	FILE *fp = open_out(to);
 	if (!fp) { free(buf); return MC_EXIT_FILE_OPEN_ERROR; }
@@ -172,39 +135,6 @@ static int copy_file(const char *from, const char *to)
 	fclose(fp);
 	free(buf);
 	return rc;
-}
-
-/* the .bim of a pruned data set: of the lines that hold anything but white space, the variant_of[0 .. L - 1]-th, byte for byte */
-static int copy_kept_lines(const char *from, const char *to, const int *variant_of, int L)
-{
-	char *buf;
-	size_t n;
-	int rc = slurp(from, &buf, &n);
-	if (rc) return rc;
-	FILE *fp = open_out(to);
-	if (!fp) { free(buf); return MC_EXIT_FILE_OPEN_ERROR; }
-	int v = 0, l = 0;
-	for (const char *p = buf, *eof = buf + n; p < eof && l < L;) {
-		const char *q = memchr(p, '\n', (size_t)(eof - p));
-		q = q ? q + 1 : eof;
-		int content = 0;
-		for (const char *c = p; c < q; c++) if (*c != ' ' && *c != '\t' && *c != '\r' && *c != '\n') { content = 1; break; }
-		if (content) {
-			if (variant_of[l] == v) { l++; if (fwrite(p, 1, (size_t)(q - p), fp) != (size_t)(q - p)) rc = MC_EXIT_FILE_OPEN_ERROR; }
-			v++;
-		}
-		p = q;
-	}
-	if (fclose(fp)) rc = rc ? rc : MC_EXIT_FILE_OPEN_ERROR;
-	free(buf);
-	return rc;
-}
-
-static char *path_of(const char *prefix, const char *ext)
-{
-	char *p = malloc(strlen(prefix) + strlen(ext) + 1);
-	if (p) { strcpy(p, prefix); strcat(p, ext); }
-	return p;
 }
 
 /* Index -> allele of a locus is the reader's: L_alleles[l][m] is 1 for A1 and 2 for A2 (mc_read_bed), so a filled pair is
@@ -215,8 +145,8 @@ int mc_write_filled_bed(const mc_cli_options *opt, const mc_cli_data *dat, const
 	const int I = dat->I, L = dat->L;
 	const size_t rb = dat->bed_record_bytes;
 	static const uint8_t magic[3] = { 0x6c, 0x1b, 0x01 };
-	char *src[2] = { path_of(opt->bed_prefix, ".bim"), path_of(opt->bed_prefix, ".fam") };
-	char *dst[3] = { path_of(out_prefix, ".bim"), path_of(out_prefix, ".fam"), path_of(out_prefix, ".bed") };
+	char *src[2] = { mc_path_of(opt->bed_prefix, ".bim"), mc_path_of(opt->bed_prefix, ".fam") };
+	char *dst[3] = { mc_path_of(out_prefix, ".bim"), mc_path_of(out_prefix, ".fam"), mc_path_of(out_prefix, ".bed") };
 	uint8_t *rec = malloc(rb ? rb : 1);
 	FILE *fp = NULL;
 	int rc = MC_EXIT_MEMORY_ALLOCATION;
@@ -243,8 +173,8 @@ int mc_write_filled_bed(const mc_cli_options *opt, const mc_cli_data *dat, const
 	fp = NULL;
 	/* (the variants --prune removed have no record above and no line here; the individuals --king-cutoff removed none there) */
 	for (int x = 0; x < 2 && !rc; x++)
-		rc = (x == 0 && dat->variant_of) ? copy_kept_lines(src[x], dst[x], dat->variant_of, L) :
-		     (x == 1 && dat->individual_of) ? copy_kept_lines(src[x], dst[x], dat->individual_of, I) : copy_file(src[x], dst[x]);
+		rc = (x == 0 && dat->variant_of) ? mc_copy_kept_lines("mc_impute.c", src[x], dst[x], dat->variant_of, L) :
+		     (x == 1 && dat->individual_of) ? mc_copy_kept_lines("mc_impute.c", src[x], dst[x], dat->individual_of, I) : copy_file(src[x], dst[x]);
 DONE:
 	if (fp) fclose(fp);
 	if (rc) fprintf(stderr, "ERROR [mc_impute.c::mc_write_filled_bed]: could not write the fileset '%s' (%d)\n", out_prefix, rc);
@@ -255,14 +185,6 @@ DONE:
 int mc_write_filled(const mc_cli_options *opt, const mc_cli_data *dat, int K, const uint8_t *filled)
 {
 	char path[4400];
-	if (opt->outfile_name) {	/* the stem of the result files (mc_writer.c) */
-		snprintf(path, sizeof path, "%s", opt->outfile_name);
-	} else {
-		const size_t pl = strlen(opt->path);
-		const int sep = pl && opt->path[pl - 1] != '/' && opt->path[pl - 1] != '\\';
-		snprintf(path, sizeof path, "%s%s%s", opt->path, sep ? "/" : "", opt->filename_file);
-	}
-	const size_t len = strlen(path);
-	snprintf(path + len, sizeof path - len, ".admix.K=%d.filled%s", K, opt->bed_prefix ? "" : ".stru");
+	mc_result_path(opt, path, sizeof path, ".admix.K=%d.filled%s", K, opt->bed_prefix ? "" : ".stru");
 	return opt->bed_prefix ? mc_write_filled_bed(opt, dat, filled, path) : mc_write_filled_structure(opt, dat, filled, path);
 }

@@ -16,15 +16,14 @@
  * The kinships come in slabs of at most `slab` rows against all individuals; the host keeps one slab (24 bytes a pair) and the
  * relatedness graph as an I x I bit matrix, I * I / 8 bytes: its only memory quadratic in I.
  *
- * Everything in this file is libc but what mc_king_data calls: the device (mchip_create, mchip_bed_king, mchip_destroy) and the
- * reader (mc_bed_summarize, mc_bed_lazy_new, mc_bed.c).  tests/king_host_driver.c stubs those and runs the rest as a program of its
- * own.
+ * Everything in this file is libc and mc_files.h but what mc_king_data calls: the kinships (mchip_bed_king), the filter stage
+ * (mc_filter.h: the device opened and closed, the reader's summary made anew) and the reader's decoder (mc_bed_lazy_new, mc_bed.c).
+ * tests/king_host_driver.c stubs the device and the reader and runs the rest as a program of its own.
  */
 #include "mc_cli.h"
 
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 static size_t row_words(int I) { return ((size_t)I + 63) / 64; }
 
@@ -119,31 +118,6 @@ int mc_king_compact(int I, int L, size_t record_bytes, const uint8_t *keep, uint
 	return n;
 }
 
-static double now_s(void)
-{
-	struct timespec t;
-	clock_gettime(CLOCK_MONOTONIC, &t);
-	return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-}
-
-typedef struct device_band {
-	mchip_context *ctx;
-	const mc_cli_data *dat;
-} device_band;
-
-static int band_on_device(void *arg, int i0, int n_rows, double *phi, uint32_t *counts)
-{
-	const device_band *b = arg;
-	return mchip_bed_king(b->ctx, b->dat->I, b->dat->L, b->dat->bed, b->dat->bed_record_bytes, i0, n_rows, phi, counts);
-}
-
-static char *dup_string(const char *s)
-{
-	char *r = malloc(strlen(s) + 1);
-	if (r) strcpy(r, s);
-	return r;
-}
-
 /* everything of the data set that is per individual, made anew for the n kept ones (map[x] = the x-th kept one's place in the file):
  * what read_fam (mc_bed.c) yields on their lines.  The file's own ids move to fam_iid / fam_fid. */
 static int rebuild_individuals(mc_cli_data *dat, int n, const int *map)
@@ -152,16 +126,16 @@ static int rebuild_individuals(mc_cli_data *dat, int n, const int *map)
 	char **fid = calloc((size_t)I, sizeof *fid), **names = calloc((size_t)n, sizeof *names), **pops = calloc((size_t)n, sizeof *pops);
 	int *locale = calloc((size_t)n, sizeof *locale), *i_p = NULL, *new_of = malloc(sizeof(int) * (size_t)(dat->numpops ? dat->numpops : 1));
 	int numpops = 0, ok = fid && names && pops && locale && new_of;
-	for (int i = 0; ok && i < I; i++) ok = (fid[i] = dup_string(dat->pops[dat->locale[i]])) != NULL;
+	for (int i = 0; ok && i < I; i++) ok = (fid[i] = strdup(dat->pops[dat->locale[i]])) != NULL;
 	for (int p = 0; ok && p < dat->numpops; p++) new_of[p] = -1;
 	for (int x = 0; ok && x < n; x++) {
 		const int old = dat->locale[map[x]];
 		if (new_of[old] < 0) {
-			if (!(pops[numpops] = dup_string(dat->pops[old]))) { ok = 0; break; }
+			if (!(pops[numpops] = strdup(dat->pops[old]))) { ok = 0; break; }
 			new_of[old] = numpops++;
 		}
 		locale[x] = new_of[old];
-		ok = (names[x] = dup_string(dat->names[map[x]])) != NULL;
+		ok = (names[x] = strdup(dat->names[map[x]])) != NULL;
 	}
 	if (ok) ok = (i_p = calloc((size_t)(numpops ? numpops : 1), sizeof *i_p)) != NULL;
 	free(new_of);
@@ -183,28 +157,36 @@ static int rebuild_individuals(mc_cli_data *dat, int n, const int *map)
 	return 0;
 }
 
+static int band_on_device(void *arg, int i0, int n_rows, double *phi, uint32_t *counts)
+{
+	const mc_device_band *b = arg;
+	return mchip_bed_king(b->ctx, b->dat->I, b->dat->L, b->dat->bed, b->dat->bed_record_bytes, i0, n_rows, phi, counts);
+}
+
+typedef struct king_graph {
+	uint64_t *bits;
+	mc_king_pair *pairs;
+	size_t n_pairs;
+} king_graph;
+
+static int edges_by_device(const mc_cli_options *opt, mc_device_band *dev, void *out)
+{
+	king_graph *g = out;
+	return mc_king_edges(dev->dat->I, opt->king_t, MC_KING_SLAB, band_on_device, dev, &g->bits, &g->pairs, &g->n_pairs);
+}
+
 int mc_king_data(const mc_cli_options *opt, mc_cli_data *dat)
 {
 	const int I = dat->I, L = dat->L;
-	device_band b = { NULL, dat };
 	uint8_t *keep = malloc((size_t)I);
 	int *map = malloc(sizeof(int) * (size_t)I);
-	uint64_t *bits = NULL;
-	mc_king_pair *pairs = NULL;
-	size_t n_pairs = 0;
+	king_graph g = { NULL, NULL, 0 };
 	int rc = MC_EXIT_MEMORY_ALLOCATION;
-	const double t_start = now_s();
+	const double t_start = mc_now_s();
 	if (!keep || !map) goto DONE;
 	if (!dat->bed || dat->individual_of) { rc = MC_EXIT_INTERNAL_ERROR; goto DONE; }	/* a fileset, and not thinned before */
-	if ((rc = mchip_create(&b.ctx, opt->device))) {
-		fprintf(stderr, "ERROR [mc_king.c::mc_king_data]: cannot open device %d for --king-cutoff (status %d)\n", opt->device, rc);
-		goto DONE;
-	}
-	if ((rc = mc_king_edges(I, opt->king_t, MC_KING_SLAB, band_on_device, &b, &bits, &pairs, &n_pairs))) {
-		fprintf(stderr, "ERROR [mc_king.c::mc_king_data]: the kinship matrix failed (status %d): %s\n", rc, mchip_last_error(b.ctx));
-		goto DONE;
-	}
-	if ((rc = mc_king_select(I, bits, keep))) goto DONE;
+	if ((rc = mc_filter_on_device(opt, dat, "mc_king.c::mc_king_data", "--king-cutoff", "the kinship matrix", edges_by_device, &g))) goto DONE;
+	if ((rc = mc_king_select(I, g.bits, keep))) goto DONE;
 	/* the data set is the kept individuals' from here on: their codes in every record, their ids, and the reader's summary of those */
 	const int n = mc_king_compact(I, L, dat->bed_record_bytes, keep, dat->bed, map);
 	if (n < 1) { rc = MC_EXIT_MEMORY_ALLOCATION; goto DONE; }
@@ -212,31 +194,22 @@ int mc_king_data(const mc_cli_options *opt, mc_cli_data *dat)
 	if ((rc = rebuild_individuals(dat, n, map))) goto DONE;
 	dat->individual_of = map;
 	map = NULL;
-	dat->king_pairs = pairs;
-	dat->n_king_pairs = n_pairs;
-	pairs = NULL;
+	dat->king_pairs = g.pairs;
+	dat->n_king_pairs = g.n_pairs;
+	g.pairs = NULL;
 	if (dat->lazy) {	/* (nothing has been decoded yet; a decoded genotype would be the file's) */
 		dat->lazy->release(dat->lazy);
 		if (!(dat->lazy = mc_bed_lazy_new())) { rc = MC_EXIT_MEMORY_ALLOCATION; goto DONE; }
 	}
-	free(dat->uniquealleles); free(dat->toff);
-	if (dat->L_alleles) for (int l = 0; l < L; l++) free(dat->L_alleles[l]);
-	free(dat->L_alleles);
-	dat->uniquealleles = dat->toff = NULL;
-	dat->L_alleles = NULL;
-	rc = mc_bed_summarize(dat);
-	if (getenv("MC_READER_TIMING")) fprintf(stderr, "INFO [mc_king.c]: %-18s %.3f s\n", "relatedness", now_s() - t_start);
+	rc = mc_filter_resummarize(dat, L, "mc_king.c", "relatedness", t_start);
 DONE:
-	if (b.ctx) mchip_destroy(b.ctx);
-	free(keep); free(map); free(bits); free(pairs);
+	free(keep); free(map); free(g.bits); free(g.pairs);
 	return rc;
 }
 
-static FILE *open_out(const char *path)
+static void print_individual(FILE *fp, const void *dat, int v)
 {
-	FILE *fp = fopen(path, "w");
-	if (!fp) fprintf(stderr, "ERROR [mc_king.c::open_out]: could not open file '%s'\n", path);
-	return fp;
+	fprintf(fp, "%s\t%s\n", ((const mc_cli_data *)dat)->fam_fid[v], ((const mc_cli_data *)dat)->fam_iid[v]);
 }
 
 /* <stem>.king.cutoff.in: "FID\tIID" of the individuals kept, one per line in file order; <stem>.king.cutoff.out: of those removed
@@ -246,36 +219,17 @@ static FILE *open_out(const char *path)
 int mc_write_king_lists(const mc_cli_options *opt, const mc_cli_data *dat)
 {
 	char path[4400];
+	int rc;
 	if (!dat->individual_of || !dat->fam_fid || !dat->fam_iid) return MC_EXIT_INTERNAL_ERROR;
-	if (opt->outfile_name) {	/* the stem of the result files (mc_writer.c) */
-		snprintf(path, sizeof path, "%s", opt->outfile_name);
-	} else {
-		const size_t pl = strlen(opt->path);
-		const int sep = pl && opt->path[pl - 1] != '/' && opt->path[pl - 1] != '\\';
-		snprintf(path, sizeof path, "%s%s%s", opt->path, sep ? "/" : "", opt->filename_file);
-	}
-	const size_t len = strlen(path);
-	FILE *in, *out, *kin;
-	snprintf(path + len, sizeof path - len, ".king.cutoff.in");
-	if (!(in = open_out(path))) return MC_EXIT_FILE_OPEN_ERROR;
-	snprintf(path + len, sizeof path - len, ".king.cutoff.out");
-	if (!(out = open_out(path))) { fclose(in); return MC_EXIT_FILE_OPEN_ERROR; }
-	snprintf(path + len, sizeof path - len, ".king.kin0");
-	if (!(kin = open_out(path))) { fclose(in); fclose(out); return MC_EXIT_FILE_OPEN_ERROR; }
-	for (int v = 0, x = 0; v < dat->I_file; v++) {
-		const int kept = x < dat->I && dat->individual_of[x] == v;
-		fprintf(kept ? in : out, "%s\t%s\n", dat->fam_fid[v], dat->fam_iid[v]);
-		x += kept;
-	}
+	if ((rc = mc_write_kept_lists(opt, "mc_king.c", ".king.cutoff", dat->I_file, dat->I, dat->individual_of, print_individual, dat))) return rc;
+	mc_result_path(opt, path, sizeof path, ".king.kin0");
+	FILE *kin = mc_open_result("mc_king.c", path, "w");
+	if (!kin) return MC_EXIT_FILE_OPEN_ERROR;
 	fprintf(kin, "FID1\tIID1\tFID2\tIID2\tN_SNP\tHETHET\tIBS0\tKINSHIP\n");
 	for (size_t p = 0; p < dat->n_king_pairs; p++) {
 		const mc_king_pair *k = &dat->king_pairs[p];
 		fprintf(kin, "%s\t%s\t%s\t%s\t%u\t%.6f\t%.6f\t%.6f\n", dat->fam_fid[k->i], dat->fam_iid[k->i], dat->fam_fid[k->j], dat->fam_iid[k->j],
 			(unsigned)k->n, (double)k->hh / (double)k->n, (double)k->op / (double)k->n, k->phi);
 	}
-	int rc = ferror(in) || ferror(out) || ferror(kin);
-	rc |= fclose(in);
-	rc |= fclose(out);
-	rc |= fclose(kin);
-	return rc ? MC_EXIT_FILE_OPEN_ERROR : 0;
+	return mc_close_result(kin);
 }

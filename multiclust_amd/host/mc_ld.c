@@ -14,15 +14,14 @@
  * reaches a variant, every variant before it is decided) and needs one row of the band at a time: the band comes in slabs of at most
  * `slab` first variants, MC_LD_SLAB * W doubles at the most.
  *
- * Everything in this file is libc but what mc_ld_prune_data calls: the device (mchip_create, mchip_bed_ld_band, mchip_destroy) and the
- * reader's summary of the records left (mc_bed_summarize, mc_bed.c).  tests/ld_host_driver.c stubs those and runs the rest as a
- * program of its own.
+ * Everything in this file is libc and mc_files.h but what mc_ld_prune_data calls: the band (mchip_bed_ld_band) and the filter stage
+ * (mc_filter.h: the device opened and closed, the reader's summary of the records left).  tests/ld_host_driver.c stubs the device
+ * and the reader and runs the rest as a program of its own.
  */
 #include "mc_cli.h"
 
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 int mc_ld_prune_greedy(int L, int W, double t, int slab, mc_ld_band_fn band, void *arg, const char *const *chrom, uint8_t *keep)
 {
@@ -62,95 +61,46 @@ int mc_ld_compact(int L, size_t record_bytes, const uint8_t *keep, uint8_t *bed,
 	return n;
 }
 
-static double now_s(void)
-{
-	struct timespec t;
-	clock_gettime(CLOCK_MONOTONIC, &t);
-	return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-}
-
-typedef struct device_band {
-	mchip_context *ctx;
-	const mc_cli_data *dat;
-} device_band;
-
 static int band_on_device(void *arg, int l0, int n_first, int window, double *r2)
 {
-	const device_band *b = arg;
+	const mc_device_band *b = arg;
 	return mchip_bed_ld_band(b->ctx, b->dat->I, b->dat->L, b->dat->bed, b->dat->bed_record_bytes, l0, n_first, window, r2);
+}
+
+static int keep_by_device(const mc_cli_options *opt, mc_device_band *dev, void *keep)
+{
+	return mc_ld_prune_greedy(dev->dat->L, opt->prune_window, opt->prune_t, MC_LD_SLAB, band_on_device, dev, (const char *const *)dev->dat->chrom, keep);
 }
 
 int mc_ld_prune_data(const mc_cli_options *opt, mc_cli_data *dat)
 {
 	const int L = dat->L;
 	const size_t rb = dat->bed_record_bytes;
-	device_band b = { NULL, dat };
 	uint8_t *keep = malloc((size_t)L);
 	int *map = malloc(sizeof(int) * (size_t)L);
 	int rc = MC_EXIT_MEMORY_ALLOCATION;
-	const double t_start = now_s();
+	const double t_start = mc_now_s();
 	if (!keep || !map) goto DONE;
 	if (!dat->bed || dat->variant_of) { rc = MC_EXIT_INTERNAL_ERROR; goto DONE; }	/* a fileset, and not pruned before */
-	if ((rc = mchip_create(&b.ctx, opt->device))) {
-		fprintf(stderr, "ERROR [mc_ld.c::mc_ld_prune_data]: cannot open device %d for --prune (status %d)\n", opt->device, rc);
-		goto DONE;
-	}
-	if ((rc = mc_ld_prune_greedy(L, opt->prune_window, opt->prune_t, MC_LD_SLAB, band_on_device, &b, (const char *const *)dat->chrom, keep))) {
-		fprintf(stderr, "ERROR [mc_ld.c::mc_ld_prune_data]: the LD band failed (status %d): %s\n", rc, mchip_last_error(b.ctx));
-		goto DONE;
-	}
+	if ((rc = mc_filter_on_device(opt, dat, "mc_ld.c::mc_ld_prune_data", "--prune", "the LD band", keep_by_device, keep))) goto DONE;
 	/* the data set is the kept variants' from here on: their records, and the reader's summary of those */
-	free(dat->uniquealleles); free(dat->toff);
-	if (dat->L_alleles) for (int l = 0; l < L; l++) free(dat->L_alleles[l]);
-	free(dat->L_alleles);
-	dat->uniquealleles = dat->toff = NULL;
-	dat->L_alleles = NULL;
 	dat->L = mc_ld_compact(L, rb, keep, dat->bed, map);
 	memset(dat->bed + (size_t)dat->L * rb, 0, 8);	/* (the reader's spare bytes behind the last record) */
 	free(dat->variant_of);
 	dat->variant_of = map;
 	map = NULL;
-	rc = mc_bed_summarize(dat);
-	if (getenv("MC_READER_TIMING")) fprintf(stderr, "INFO [mc_ld.c]: %-18s %.3f s\n", "LD pruning", now_s() - t_start);
+	rc = mc_filter_resummarize(dat, L, "mc_ld.c", "LD pruning", t_start);
 DONE:
-	if (b.ctx) mchip_destroy(b.ctx);
 	free(keep); free(map);
 	return rc;
 }
 
-static FILE *open_out(const char *path)
-{
-	FILE *fp = fopen(path, "w");
-	if (!fp) fprintf(stderr, "ERROR [mc_ld.c::open_out]: could not open file '%s'\n", path);
-	return fp;
-}
+static void print_variant(FILE *fp, const void *dat, int v) { fprintf(fp, "%s\n", ((const mc_cli_data *)dat)->variant_id[v]); }
 
 /* <stem>.prune.in: the ids (second field of the .bim line) of the variants kept, one per line in file order; <stem>.prune.out: of
  * those removed.  `plink --extract <stem>.prune.in` writes the fileset the run was made on. */
 int mc_write_prune_lists(const mc_cli_options *opt, const mc_cli_data *dat)
 {
-	char path[4400];
 	if (!dat->variant_of || !dat->variant_id) return MC_EXIT_INTERNAL_ERROR;
-	if (opt->outfile_name) {	/* the stem of the result files (mc_writer.c) */
-		snprintf(path, sizeof path, "%s", opt->outfile_name);
-	} else {
-		const size_t pl = strlen(opt->path);
-		const int sep = pl && opt->path[pl - 1] != '/' && opt->path[pl - 1] != '\\';
-		snprintf(path, sizeof path, "%s%s%s", opt->path, sep ? "/" : "", opt->filename_file);
-	}
-	const size_t len = strlen(path);
-	FILE *in, *out;
-	snprintf(path + len, sizeof path - len, ".prune.in");
-	if (!(in = open_out(path))) return MC_EXIT_FILE_OPEN_ERROR;
-	snprintf(path + len, sizeof path - len, ".prune.out");
-	if (!(out = open_out(path))) { fclose(in); return MC_EXIT_FILE_OPEN_ERROR; }
-	for (int v = 0, l = 0; v < dat->L_file; v++) {
-		const int kept = l < dat->L && dat->variant_of[l] == v;
-		fprintf(kept ? in : out, "%s\n", dat->variant_id[v]);
-		l += kept;
-	}
-	int rc = ferror(in) || ferror(out);
-	rc |= fclose(in);
-	rc |= fclose(out);
-	return rc ? MC_EXIT_FILE_OPEN_ERROR : 0;
+	return mc_write_kept_lists(opt, "mc_ld.c", ".prune", dat->L_file, dat->L, dat->variant_of, print_variant, dat);
 }

@@ -29,7 +29,9 @@
  * Where a post-fit analysis plugs in: the serial and the sharded path differ in who fits which unit and share the rest.  Both keep
  * the best fit of a K in a fit_record, hand it to new_maximum() when it improved on the K before (H0 estimate, result files, -A) and
  * end in post_fit(), which puts the record back into a model once and runs --fst, --resid, --cv, --se, --query, --fill; an analysis that refits derived
- * data sets builds on mc_refit_* (mc_refit.c), adds its line to post_fit()'s text and its refusals to parse_options' refuse().
+ * data sets builds on mc_refit_* (mc_refit.c), adds its line to post_fit()'s text and its refusals to parse_options' refuse_post_fit().
+ * Where a filter of the fileset plugs in: pre_fit() runs them between the reader and the first fit, --prune then --king-cutoff; a new
+ * one (--maf, --geno, --keep, ...) is a unit like mc_ld.c on mc_filter.h and mc_files.h, and one more block there.
  */
 #include "mc_cli.h"
 
@@ -151,6 +153,20 @@ static int refuse_as(const char *option, const char *why, int status)
 	return status;
 }
 static int refuse(const char *option, const char *why) { return refuse_as(option, why, MC_EXIT_INVALID_CMD_ARGUMENT); }
+
+/* what every post-fit option refuses, in this order: the mixture model where it needs -a, the bootstrap, --gpus above 1, a timed run;
+ * then `extra`, the option's own rule (NULL: none, or not broken) */
+static int refuse_post_fit(const mc_cli_options *o, const char *option, int needs_admixture, const char *extra)
+{
+	const char *common = needs_admixture && !o->em.admixture ? "%s needs the admixture model (-a)" :
+			     o->n_bootstrap ? "%s cannot be combined with the bootstrap (-b)" :
+			     o->n_gpus > 1 ? "%s cannot be combined with --gpus above 1" :
+			     !o->write_files || o->parallel ? "%s cannot be combined with -w or -M" : NULL;
+	char why[96];
+	if (!common) return refuse(option, extra);
+	snprintf(why, sizeof why, common, option);
+	return refuse(option, why);
+}
 
 static int parse_options(mc_cli_options *o, int argc, const char **argv)
 {
@@ -287,15 +303,8 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 	 * usage error like a bad argument */
 	const int timed = !o->write_files || o->parallel;
 	int rc;
-	if (o->cv_folds && (rc = refuse("--cv",
-			!o->em.admixture ? "--cv needs the admixture model (-a)" :
-			o->n_bootstrap ? "--cv cannot be combined with the bootstrap (-b)" :
-			o->n_gpus > 1 ? "--cv cannot be combined with --gpus above 1" :
-			timed ? "--cv cannot be combined with -w or -M" : NULL))) return rc;
-	if (o->se_replicates && (rc = refuse("--se",
-			o->n_bootstrap ? "--se cannot be combined with the bootstrap (-b)" :
-			o->n_gpus > 1 ? "--se cannot be combined with --gpus above 1" :
-			timed ? "--se cannot be combined with -w or -M" : NULL))) return rc;
+	if (o->cv_folds && (rc = refuse_post_fit(o, "--cv", 1, NULL))) return rc;
+	if (o->se_replicates && (rc = refuse_post_fit(o, "--se", 0, NULL))) return rc;
 	if (o->query_file && (rc = refuse("--query",
 			!o->em.admixture ? "--query needs the admixture model (-a)" :
 			o->em.eta_constrained ? "--query cannot be combined with shared mixing proportions (-c)" :
@@ -305,21 +314,10 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			o->cv_folds || o->se_replicates ? "--query cannot be combined with --cv or --se (they share the fold state of the device)" :
 			o->em.initialization_procedure == MC_RAND_EM ? "--query cannot be combined with --randem (its centers are drawn from the genotypes on the host)" :
 			o->n_gpus > 1 || o->n_streams > 1 ? "--query cannot be combined with --gpus or --streams above 1" : NULL))) return rc;
-	if (o->fill && (rc = refuse("--fill",
-			!o->em.admixture ? "--fill needs the admixture model (-a)" :
-			o->n_bootstrap ? "--fill cannot be combined with the bootstrap (-b)" :
-			o->n_gpus > 1 ? "--fill cannot be combined with --gpus above 1" :
-			timed ? "--fill cannot be combined with -w or -M" :
+	if (o->fill && (rc = refuse_post_fit(o, "--fill", 1,
 			o->query_file ? "--fill cannot be combined with --query (the query individuals are hidden on the device)" : NULL))) return rc;
-	if (o->fst && (rc = refuse("--fst",
-			o->n_bootstrap ? "--fst cannot be combined with the bootstrap (-b)" :
-			o->n_gpus > 1 ? "--fst cannot be combined with --gpus above 1" :
-			timed ? "--fst cannot be combined with -w or -M" : NULL))) return rc;
-	if (o->resid && (rc = refuse("--resid",
-			!o->em.admixture ? "--resid needs the admixture model (-a)" :
-			o->n_bootstrap ? "--resid cannot be combined with the bootstrap (-b)" :
-			o->n_gpus > 1 ? "--resid cannot be combined with --gpus above 1" :
-			timed ? "--resid cannot be combined with -w or -M" : NULL))) return rc;
+	if (o->fst && (rc = refuse_post_fit(o, "--fst", 0, NULL))) return rc;
+	if (o->resid && (rc = refuse_post_fit(o, "--resid", 1, NULL))) return rc;
 	if ((o->prune || o->prune_window_given) && (rc = refuse_as(o->prune ? "--prune" : "--prune-window",
 			!o->bed_prefix ? "--prune and --prune-window need a PLINK fileset (--bed)" :
 			!o->prune ? "--prune-window needs --prune" :
@@ -1004,6 +1002,26 @@ DONE:
 	return rc;
 }
 
+/* ---- the pre-fit stage: the filters of a fileset, --prune then --king-cutoff (on the variants kept), each with its stdout line and,
+ * with result files on, its lists.  The data set is the filtered one from here on; the lists say what of the fileset it holds. ---- */
+static int pre_fit(const mc_cli_options *o, mc_cli_data *d)
+{
+	int rc;
+	if (o->prune) {
+		mchip_progress_note("mc_ld_prune_data");
+		if ((rc = mc_ld_prune_data(o, d))) return rc;
+		printf("LD pruning: kept %d of %d variants (r2 > %g within %d)\n", d->L, d->L_file, o->prune_t, o->prune_window);
+		if (o->write_files && (rc = mc_write_prune_lists(o, d))) return rc;
+	}
+	if (o->king) {
+		mchip_progress_note("mc_king_data");
+		if ((rc = mc_king_data(o, d))) return rc;
+		printf("Relatedness: kept %d of %d individuals (KING-robust kinship > %g: %zu pairs)\n", d->I, d->I_file, o->king_t, d->n_king_pairs);
+		if (o->write_files && (rc = mc_write_king_lists(o, d))) return rc;
+	}
+	return 0;
+}
+
 int main(int argc, const char **argv)
 {
 	mc_cli_options o;
@@ -1020,18 +1038,7 @@ int main(int argc, const char **argv)
 	if ((rc = parse_options(&o, argc, argv))) return rc;	/* -h included: the reference's -h leaves with status 1 */
 	mchip_progress_note(o.bed_prefix ? "mc_read_bed" : "mc_read_structure");
 	if ((rc = o.bed_prefix ? mc_read_bed(&o, &d) : mc_read_structure(&o, &d))) return rc;
-	if (o.prune) {	/* the data set is the pruned one from here on; the lists say which variants it holds */
-		mchip_progress_note("mc_ld_prune_data");
-		if ((rc = mc_ld_prune_data(&o, &d))) return rc;
-		printf("LD pruning: kept %d of %d variants (r2 > %g within %d)\n", d.L, d.L_file, o.prune_t, o.prune_window);
-		if (o.write_files && (rc = mc_write_prune_lists(&o, &d))) return rc;
-	}
-	if (o.king) {	/* the data set is the kept individuals' from here on (on the variants kept above); the lists say who they are */
-		mchip_progress_note("mc_king_data");
-		if ((rc = mc_king_data(&o, &d))) return rc;
-		printf("Relatedness: kept %d of %d individuals (KING-robust kinship > %g: %zu pairs)\n", d.I, d.I_file, o.king_t, d.n_king_pairs);
-		if (o.write_files && (rc = mc_write_king_lists(&o, &d))) return rc;
-	}
+	if ((rc = pre_fit(&o, &d))) return rc;
 	mchip_progress_note("estimate_model");
 	if (o.em.verbosity >= MC_TALKATIVE)
 		fprintf(stderr, "INFO: Finished reading data: %d %d-ploid individuals at %d loci.\n", d.I, d.ploidy, d.L);

@@ -14,7 +14,6 @@
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include <unistd.h>
 
 /* prints and returns the exit status the reference's reader returns for this kind of failure (message.h:21-41: out of memory 3,
@@ -30,16 +29,14 @@ static int fail(const char *fn, int line, const char *msg, const char *arg)
 }
 #define FAIL(msg, arg) fail(__func__, __LINE__, msg, arg)
 
-static int is_space(char c) { return c == ' ' || c == '\t' || c == '\r'; }
-
 /* next token on the line ending at `end`; returns NULL when the line is exhausted */
 static char *next_token(char **cur, char *end, size_t *len)
 {
 	char *p = *cur;
-	while (p < end && is_space(*p)) p++;
+	while (p < end && mc_is_blank(*p)) p++;
 	if (p >= end) { *cur = p; return NULL; }
 	char *s = p;
-	while (p < end && !is_space(*p)) p++;
+	while (p < end && !mc_is_blank(*p)) p++;
 	*len = (size_t)(p - s);
 	*cur = p;
 	return s;
@@ -51,13 +48,6 @@ static int count_tokens(char *s, char *end)
 	size_t len;
 	while (next_token(&s, end, &len)) n++;
 	return n;
-}
-
-static char *dup_token(const char *s, size_t len)
-{
-	char *r = malloc(len + 1);
-	if (r) { memcpy(r, s, len); r[len] = 0; }
-	return r;
 }
 
 /* ---- worker threads ---- */
@@ -81,14 +71,14 @@ static void *parse_main(void *arg)
 		const size_t h0 = j->interleaved ? ln * (size_t)j->pl : ln;
 		for (int l = 0; l < j->L; l++)
 			for (int x = 0; x < per_line; x++) {
-				while (c < end && is_space(*c)) c++;
+				while (c < end && mc_is_blank(*c)) c++;
 				if (c >= end) { j->err = RD_SHORT_LINE; return NULL; }
 				int neg = 0;
 				long v = 0;
 				if (*c == '-' || *c == '+') { neg = *c == '-'; c++; }
 				if (c >= end || *c < '0' || *c > '9') { j->err = RD_NOT_INT; return NULL; }
 				while (c < end && *c >= '0' && *c <= '9') v = v * 10 + (*c++ - '0');
-				while (c < end && !is_space(*c)) c++;		/* trailing characters of the token, as strtol leaves them */
+				while (c < end && !mc_is_blank(*c)) c++;		/* trailing characters of the token, as strtol leaves them */
 				if (neg) v = -v;
 				if ((int)v == j->missing_value) v = MC_MISSING;	/* change_missing_value, read_file.c:266-268 */
 				j->IL[(h0 + (size_t)x) * (size_t)j->L + (size_t)l] = (int)v;
@@ -174,13 +164,7 @@ static void *locus_main(void *arg)
 	return NULL;
 }
 
-static double now_s(void)
-{
-	struct timespec t;
-	clock_gettime(CLOCK_MONOTONIC, &t);
-	return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-}
-#define PHASE(name) do { mchip_progress_note("mc_read_structure: after " name); if (timing) { double t_ = now_s(); fprintf(stderr, "INFO [mc_reader.c]: %-18s %.3f s\n", name, t_ - t_phase); t_phase = t_; } } while (0)
+#define PHASE(name) do { mchip_progress_note("mc_read_structure: after " name); t_phase = mc_timing_line("mc_reader.c", name, t_phase); } while (0)
 
 static int n_threads(size_t work)
 {
@@ -194,8 +178,7 @@ static int n_threads(size_t work)
 
 int mc_read_structure(const mc_cli_options *opt, mc_cli_data *dat)
 {
-	const int timing = getenv("MC_READER_TIMING") != NULL;
-	double t_phase = now_s();
+	double t_phase = mc_now_s();
 	FILE *f = fopen(opt->filename, "rb");
 	if (!f) return FAIL("could not open file '%s'", opt->filename);
 	fseek(f, 0, SEEK_END);
@@ -212,22 +195,16 @@ int mc_read_structure(const mc_cli_options *opt, mc_cli_data *dat)
 	size_t nlines = 0, cap = 1024;
 	char **ls = malloc(cap * sizeof *ls), **le = malloc(cap * sizeof *le);
 	if (!ls || !le) { free(ls); free(le); free(buf); return FAIL("out of memory reading '%s'", opt->filename); }
-	for (char *p = buf, *eof = buf + fsz + 1; p < eof;) {
-		char *q = memchr(p, '\n', (size_t)(eof - p));
-		if (!q) q = eof;
-		char *s = p;
-		while (s < q && is_space(*s)) s++;
-		if (s < q) {
-			if (nlines == cap) {
-				char **ls2 = realloc(ls, 2 * cap * sizeof *ls), **le2 = ls2 ? realloc(le, 2 * cap * sizeof *le) : NULL;
-				if (ls2) ls = ls2;
-				if (le2) le = le2;
-				if (!ls2 || !le2) { free(ls); free(le); free(buf); return FAIL("out of memory reading '%s'", opt->filename); }
-				cap *= 2;
-			}
-			ls[nlines] = p; le[nlines] = q; nlines++;
+	mc_lines it;
+	for (mc_lines_start(&it, buf, (size_t)fsz + 1); mc_lines_next(&it); nlines++) {
+		if (nlines == cap) {
+			char **ls2 = realloc(ls, 2 * cap * sizeof *ls), **le2 = ls2 ? realloc(le, 2 * cap * sizeof *le) : NULL;
+			if (ls2) ls = ls2;
+			if (le2) le = le2;
+			if (!ls2 || !le2) { free(ls); free(le); free(buf); return FAIL("out of memory reading '%s'", opt->filename); }
+			cap *= 2;
 		}
-		p = q + 1;
+		ls[nlines] = it.line; le[nlines] = it.end;
 	}
 	int rc = MC_EXIT_FILE_FORMAT_ERROR;
 	PHASE("file into memory");
@@ -277,7 +254,7 @@ int mc_read_structure(const mc_cli_options *opt, mc_cli_data *dat)
 		char *loc = next_token(&c, end, &llen);
 		if (!name || !loc) { rc = FAIL("line without name/locale columns in '%s'", opt->filename); goto DONE; }
 		if (dat->interleaved || !(ln % (size_t)pl)) {
-			dat->names[i] = dup_token(name, nlen);
+			dat->names[i] = mc_dup_token(name, nlen);
 			int found = -1;				/* add_to_string_set: order of first appearance */
 			for (int n = 0; n < dat->numpops; n++)
 				if (strlen(dat->pops[n]) == llen && !strncmp(dat->pops[n], loc, llen)) { found = n; break; }
@@ -285,7 +262,7 @@ int mc_read_structure(const mc_cli_options *opt, mc_cli_data *dat)
 				char **pops2 = realloc(dat->pops, sizeof *dat->pops * (size_t)(dat->numpops + 1));
 				if (!pops2) { rc = FAIL("out of memory%s", NULL); goto DONE; }
 				dat->pops = pops2;
-				dat->pops[dat->numpops] = dup_token(loc, llen);
+				dat->pops[dat->numpops] = mc_dup_token(loc, llen);
 				found = dat->numpops++;
 			}
 			dat->locale[i] = found;

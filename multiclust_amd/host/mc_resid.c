@@ -114,35 +114,18 @@ static void put(FILE *fp, double v, char end)
 	else fprintf(fp, "%.6f%c", v, end);
 }
 
-static FILE *open_out(const char *path)
-{
-	FILE *fp = fopen(path, "w");
-	if (!fp) fprintf(stderr, "ERROR [mc_resid.c::open_out]: could not open file '%s'\n", path);
-	return fp;
-}
-
 int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r)
 {
 	char path[4400];
 	const int I = r->I;
-	if (opt->outfile_name) {	/* the stem of the result files (mc_writer.c) */
-		snprintf(path, sizeof path, "%s", opt->outfile_name);
-	} else {
-		const size_t pl = strlen(opt->path);
-		const int sep = pl && opt->path[pl - 1] != '/' && opt->path[pl - 1] != '\\';
-		snprintf(path, sizeof path, "%s%s%s", opt->path, sep ? "/" : "", opt->filename_file);
-	}
-	const size_t len = strlen(path);
-	snprintf(path + len, sizeof path - len, ".admix.K=%d.resid.txt", r->K);
-	FILE *fp = open_out(path);
+	const size_t len = mc_result_path(opt, path, sizeof path, ".admix.K=%d.resid.txt", r->K);
+	FILE *fp = mc_open_result("mc_resid.c", path, "w");
 	if (!fp) return MC_EXIT_FILE_OPEN_ERROR;
 	for (int i = 0; i < I; i++)
 		for (int j = 0; j < I; j++) put(fp, r->cor[(size_t)i * I + j], j + 1 < I ? '\t' : '\n');
-	int bad = ferror(fp);
-	if (fclose(fp)) bad = 1;
-	if (bad) return MC_EXIT_FILE_OPEN_ERROR;
+	if (mc_close_result(fp)) return MC_EXIT_FILE_OPEN_ERROR;
 	snprintf(path + len, sizeof path - len, ".admix.K=%d.resid.ind.txt", r->K);
-	if (!(fp = open_out(path))) return MC_EXIT_FILE_OPEN_ERROR;
+	if (!(fp = mc_open_result("mc_resid.c", path, "w"))) return MC_EXIT_FILE_OPEN_ERROR;
 	fprintf(fp, "i\tmean\tmax\tpartner\n");
 	for (int i = 0; i < I; i++) {
 		fprintf(fp, "%d\t", i);
@@ -150,7 +133,5 @@ int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r)
 		put(fp, r->ind_max[i], '\t');
 		fprintf(fp, "%d\n", (int)r->ind_partner[i]);
 	}
-	bad = ferror(fp);
-	if (fclose(fp)) bad = 1;
-	return bad ? MC_EXIT_FILE_OPEN_ERROR : 0;
+	return mc_close_result(fp);
 }

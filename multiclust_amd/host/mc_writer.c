@@ -15,23 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-static void stem(const mc_cli_options *opt, char *out, size_t n)
-{
-	if (opt->outfile_name) {
-		snprintf(out, n, "%s", opt->outfile_name);
-		return;
-	}
-	const size_t pl = strlen(opt->path);
-	const int sep = pl && opt->path[pl - 1] != '/' && opt->path[pl - 1] != '\\';
-	snprintf(out, n, "%s%s%s", opt->path, sep ? "/" : "", opt->filename_file);
-}
-
-static FILE *open_out(const char *path)
-{
-	FILE *fp = fopen(path, "w");
-	if (!fp) fprintf(stderr, "ERROR [mc_writer.c::open_out]: could not open file '%s'\n", path);
-	return fp;
-}
+#define open_out(path) mc_open_result("mc_writer.c", path, "w")
 
 void mc_partition(const mc_cli_data *dat, const mc_fit_view *fit, int *I_K, int *count_K)
 {
@@ -116,11 +100,10 @@ double mc_adjusted_rand(int n, int k1, int k2, const int *cl1, const int *cl2)
 int mc_write_se(const mc_cli_options *opt, const mc_cli_data *dat, int K, const double *q, const double *mean, const double *se,
 		const int32_t *count)
 {
-	char base[4096], path[4200];
+	char path[4400];
 	const int admix = opt->em.admixture, shared_eta = (!admix || opt->em.eta_constrained);
 	FILE *fp;
-	stem(opt, base, sizeof base);
-	snprintf(path, sizeof path, "%s.%s.K=%d.se.txt", base, admix ? "admix" : "mix", K);
+	mc_result_path(opt, path, sizeof path, ".%s.K=%d.se.txt", admix ? "admix" : "mix", K);
 	if (!(fp = open_out(path))) return 1;
 	fprintf(fp, shared_eta ? "k\teta\tse\tmean\tn\n" : "i\tk\teta\tse\tmean\tn\n");
 	for (int i = 0; i < (shared_eta ? 1 : dat->I); i++)
@@ -136,10 +119,9 @@ int mc_write_se(const mc_cli_options *opt, const mc_cli_data *dat, int K, const 
 int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows, const int32_t *iter, const uint8_t *converged,
 		   const double *logL, const double *q)
 {
-	char base[4096], path[4200];
+	char path[4400];
 	FILE *fp;
-	stem(opt, base, sizeof base);
-	snprintf(path, sizeof path, "%s.admix.K=%d.query.txt", base, K);
+	mc_result_path(opt, path, sizeof path, ".admix.K=%d.query.txt", K);
 	if (!(fp = open_out(path))) return 1;
 	fprintf(fp, "i\titer\tconverged\tlogL");
 	for (int k = 0; k < K; k++) fprintf(fp, "\teta%d", k);
@@ -155,15 +137,14 @@ int mc_write_query(const mc_cli_options *opt, int K, int n, const int32_t *rows,
 
 int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc_fit_view *fit, const int *count_K)
 {
-	char base[4096], path[4200];
+	char path[4400];
 	const int K = fit->K, admix = opt->em.admixture;
 	const char *mdl = admix ? "admix" : "mix";
 	const int shared_eta = (!admix || opt->em.eta_constrained);
 	FILE *fp;
-	stem(opt, base, sizeof base);
 
 	/* write_file_detail (write_file.c:203-348) */
-	snprintf(path, sizeof path, "%s.%s.K=%d.out.txt", base, mdl, K);
+	const size_t len = mc_result_path(opt, path, sizeof path, ".%s.K=%d.out.txt", mdl, K);
 	if (!(fp = open_out(path))) return 1;
 	fprintf(fp, "logL = %f (%s)\n", fit->logL, fit->converged ? "converged" : "not converged");
 	fprintf(fp, "AIC = %f\n", fit->aic);
@@ -174,13 +155,13 @@ int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc
 	fclose(fp);
 
 	if (shared_eta) {
-		snprintf(path, sizeof path, "%s.%s.K=%d.etak.txt", base, mdl, K);
+		snprintf(path + len, sizeof path - len, ".%s.K=%d.etak.txt", mdl, K);
 		if (!(fp = open_out(path))) return 1;
 		fprintf(fp, "i\tk\tetak\n");
 		for (int k = 0; k < K; k++) fprintf(fp, "%d\t%f\n", k, fit->q[k]);
 		fprintf(fp, "\n");
 	} else {
-		snprintf(path, sizeof path, "%s.%s.K=%d.etaik.txt", base, mdl, K);
+		snprintf(path + len, sizeof path - len, ".%s.K=%d.etaik.txt", mdl, K);
 		if (!(fp = open_out(path))) return 1;
 		fprintf(fp, "i\tk\tetaik\n");
 		for (int i = 0; i < dat->I; i++)
@@ -189,7 +170,7 @@ int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc
 	}
 	fclose(fp);
 
-	snprintf(path, sizeof path, "%s.%s.K=%d.pklm.txt", base, mdl, K);
+	snprintf(path + len, sizeof path - len, ".%s.K=%d.pklm.txt", mdl, K);
 	if (!(fp = open_out(path))) return 1;
 	fprintf(fp, "k\tl\tm\tKLM\n");
 	for (int k = 0; k < K; k++)
@@ -200,8 +181,8 @@ int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc
 	fclose(fp);
 
 	/* popq (write_file.c:398-475 admixture, 618-690 mixture) */
-	if (admix) snprintf(path, sizeof path, "%s_admix_popq_%d.popq", base, K);
-	else snprintf(path, sizeof path, "%s_mix_popq.popq", base);
+	if (admix) snprintf(path + len, sizeof path - len, "_admix_popq_%d.popq", K);
+	else snprintf(path + len, sizeof path - len, "_mix_popq.popq");
 	if (!(fp = open_out(path))) return 1;
 	double *vp = calloc((size_t)dat->numpops * K, sizeof *vp);
 	if (!vp) { fclose(fp); return 1; }
@@ -219,8 +200,8 @@ int mc_write_results(const mc_cli_options *opt, const mc_cli_data *dat, const mc
 	fclose(fp);
 
 	/* indivq (write_file.c:492-569 admixture, 700-732 mixture) */
-	if (admix) snprintf(path, sizeof path, "%s_admix_indivq_%d.indivq", base, K);
-	else snprintf(path, sizeof path, "%s.mix.K=%d.indivq", base, K);
+	if (admix) snprintf(path + len, sizeof path - len, "_admix_indivq_%d.indivq", K);
+	else snprintf(path + len, sizeof path - len, ".mix.K=%d.indivq", K);
 	if (!(fp = open_out(path))) return 1;
 	for (int i = 0; i < dat->I; i++) {
 		fprintf(fp, "%d\t%s\t(x)\t%s\t:", i, dat->names[i], dat->pops[dat->locale[i]]);
