@@ -129,6 +129,37 @@ int mchip_bed_ld_band(mchip_context *ctx, int I, int L, const uint8_t *bed, size
  */
 int mchip_bed_king(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int i0, int n_rows, double *phi,
 		   uint32_t *counts);
+/*
+ * Genotype counts along both axes of packed records and the Hardy-Weinberg exact test of every variant (an extension): what
+ * --mind, --geno, --maf and --hwe filter a fileset by.  bed, I, L and record_bytes as for mchip_set_genotypes_bed.
+ * Definition.  Codes as above: 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2; padding bits of a record carry no
+ * individual, whatever they hold.
+ *     ind_counts[i][c] = the number of the L variants at which individual i has code c, for every i: ind_keep plays no part in it;
+ *     var_counts[l][c] = the number of individuals i with ind_keep[i] != 0 (ind_keep = NULL: all of them) that have code c at
+ *                        variant l;
+ *     hwe_p[l]         = the exact test of Wigginton, Cutler & Abecasis (2005) on (n0, n2, n3) = var_counts[l][0, 2, 3], as the
+ *                        following fixed sequence of IEEE double operations.
+ * N = n0 + n2 + n3; N = 0 gives p = 1.0.  r = 2 min(n0, n3) + n2, the copies of the rarer allele.  mid = floor(r (2N - r) / (2N)) in
+ * 64-bit integers, plus 1 when its parity differs from r's.  A walk visits every heterozygote count h of r's parity in [0, r] with
+ * a weight w: start at h = mid with a = (r - mid) / 2, b = N - h - a and w = 1.0; downwards while h >= 2,
+ *     w = (w * (double)(h (h - 1))) / (double)(4 (a + 1) (b + 1)),   then h -= 2, a += 1, b += 1;
+ * restart at mid with w = 1.0; upwards while h <= r - 2,
+ *     w = (w * (double)(4 a b)) / (double)((h + 2) (h + 1)),         then h += 2, a -= 1, b -= 1.
+ * Each step is one multiply, then one divide; the integer products are exact in 64 bits (I < 2^30); nothing can be contracted;
+ * subnormal weights are part of the definition and are not flushed.  The first walk gives S, the sum of w in visiting order (mid,
+ * then down, then up), and w_obs, the w at h = n2.  The second walk makes the same weights again -- the same bits -- and gives T, the
+ * sum in the same order of every w with w <= w_obs * 1.0000001 (SNPHWE2's device: weights equal in exact arithmetic are not split by
+ * their roundings).  p = T / S, and 1.0 when that is larger.  No array of weights exists.  The counts are integers and the test is a
+ * fixed sequence of correctly rounded operations: the same bits on every device and under every launch geometry.
+ * Contract.  Any of the three arrays may be NULL, not all; hwe_p needs no var_counts from the caller.  The context supplies the
+ * device, the stream and mchip_last_error and nothing else: no data set need be installed, and nothing of an installed data set,
+ * model, slot, fold or saved set changes.  Checked before anything runs: I, L >= 1, record_bytes >= ceil(I/4), non-null bed, at least
+ * one output array; a failed check returns MCHIP_ERR_INVALID and leaves the arrays untouched.  MCHIP_ERR_UNSUPPORTED, the arrays
+ * untouched as well, for I >= 2^30.  MCHIP_ERR_ALLOC when the records, the mask and the outputs (16 bytes an individual, 24 a
+ * variant) do not fit on the device.
+ */
+int mchip_bed_qc(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, const uint8_t *ind_keep,
+		 uint32_t *ind_counts, uint32_t *var_counts, double *hwe_p);
 /* Counted on the device when a data set is installed: cells (i, l, m) with ILM[i][l][m] > 0 -- the cells the reference's E step
  * visits (em_alg.c:338-342) and the unit the flop count of the path is stated in -- and non-missing allele copies. */
 int mchip_data_counts(mchip_context *ctx, uint64_t *nonempty_cells, uint64_t *allele_copies);

@@ -40,6 +40,21 @@
  *   Compile report (same compiler and flags):  k_king_planes 33 VGPRs, scratch 0, 4352 bytes of static LDS, 8 waves / SIMD;
  *   k_king_pairs 153 VGPRs, scratch 0, 16384 bytes of static LDS, 3 waves / SIMD; k_king_phi 24 VGPRs, scratch 0, 8 waves / SIMD.
  *   Timed once and not tuned (profiles/king.txt, scripts/king_bench.py).
+ *
+ * mchip_bed_qc reads the records for a fourth purpose and installs nothing either: the four genotype counts of every individual and
+ * of every variant (over the individuals a keep mask names) and the Hardy-Weinberg exact test of every variant (the definition is in
+ * the header): what --mind, --geno, --maf and --hwe filter by.
+ *   k_qc_mask        the keep bytes expanded once to bit 2 j of word j / 32 for every kept individual j < I: the padding is cleared here.
+ *   k_qc_variants    a wave per variant, QC_VARIANTS to a workgroup, x a run of individuals (qc_geometry_of,
+ *                    mchip_feature_geometry.h): a lane reads its record as 64-bit words, 64 consecutive ones a wave, forms the two
+ *                    bit planes of the word under the mask and takes four population counts; the wave's sums go to memory with
+ *                    integer atomics.
+ *   k_qc_individuals the transposed direction in k_king_planes' pattern: a workgroup per QC_ITILE individuals x a run of 64-variant
+ *                    words, the record bytes staged as k_bed_expand stages them; a wave-wide __ballot over 64 variants' codes of
+ *                    one individual is that individual's word of a code's plane, and its population count stays in a register of
+ *                    the individual's lane: no plane is stored.  At the end integer atomics.
+ *   k_qc_hwe         a lane per variant, FP64: the walk of the definition twice, nothing staged in memory; lanes of a wave differ
+ *                    in their trip counts, so the workgroups are single waves.
  */
 #include "mchip_context.h"
 
@@ -520,6 +535,186 @@ extern "C" int mchip_bed_king(mchip_context *ctx, int I, int L, const uint8_t *b
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(phi, d_phi.p, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
 	if (counts) HIPCHK(hipMemcpyAsync(counts, d_sums.p, sizeof(uint32_t) * 4 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(hipStreamSynchronize(ctx->stream));
+	return MCHIP_OK;
+}
+
+/* ---- genotype counts along both axes and the Hardy-Weinberg exact test: mchip_bed_qc (include/multiclust_hip.h has the definition) ---- */
+static_assert(QC_ITILE == BT_I && QC_VARIANTS * 64 == 256 && QC_STEP == 64, "k_qc_variants and k_qc_individuals are written for these");
+
+/* mask[w] = bit 2 j for every individual 32 w + j < I with keep[i] != 0 (keep = null: every one): the low bit of each kept
+ * individual's two, nothing where a record holds padding */
+__global__ __launch_bounds__(256) void k_qc_mask(const uint8_t *__restrict__ keep, int I, int n_words, uint64_t *__restrict__ mask)
+{
+	const int w = blockIdx.x * 256 + threadIdx.x;
+	if (w >= n_words) return;
+	uint64_t m = 0;
+	for (int j = 0; j < 32; j++) {
+		const long long i = 32ll * w + j;
+		if (i < I && (!keep || keep[i])) m |= 1ull << (2 * j);
+	}
+	mask[w] = m;
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
+	return v;
+}
+
+/* var[4 l + c] += the kept individuals of this workgroup's run with code c at variant l.  blockIdx.x = group of QC_VARIANTS
+ * variants, a wave each; blockIdx.y = run of individuals.  Word w of a record is its bytes 8 w ... 8 w + 7 (w < n_words =
+ * ceil(I / 32), so byte 8 w lies inside the record); what it holds behind the record's last byte is never read into the high half
+ * and masked in the low one. */
+__global__ __launch_bounds__(256) void k_qc_variants(const uint8_t *__restrict__ bed, size_t rb, int L, int n_words,
+						     const uint64_t *__restrict__ mask, qc_geometry g, uint32_t *__restrict__ var)
+{
+	const int lane = threadIdx.x & 63;
+	const long long l = (long long)blockIdx.x * QC_VARIANTS + (threadIdx.x >> 6);
+	if (l >= L) return;	/* (a whole wave) */
+	const long long w_begin = (long long)blockIdx.y * g.steps_per_split * QC_STEP;
+	const int w_end = (int)min((long long)n_words, w_begin + (long long)g.steps_per_split * QC_STEP);
+	uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+	for (long long w = w_begin + lane; w < w_end; w += QC_STEP) {
+		const size_t off = 8 * (size_t)w;
+		uint64_t v = bed_word(bed, (size_t)l * rb + off);
+		if (off + 4 < rb) v |= (uint64_t)bed_word(bed, (size_t)l * rb + off + 4) << 32;
+		const uint64_t m = mask[w], lo = v & m, hi = (v >> 1) & m;
+		c0 += (uint32_t)__popcll(m & ~lo & ~hi);
+		c1 += (uint32_t)__popcll(lo & ~hi);
+		c2 += (uint32_t)__popcll(hi & ~lo);
+		c3 += (uint32_t)__popcll(lo & hi);
+	}
+	c0 = wave_sum_u32(c0); c1 = wave_sum_u32(c1); c2 = wave_sum_u32(c2); c3 = wave_sum_u32(c3);
+	if (lane == 0) {
+		uint32_t *out = var + 4 * (size_t)l;
+		atomicAdd(out + 0, c0); atomicAdd(out + 1, c1); atomicAdd(out + 2, c2); atomicAdd(out + 3, c3);
+	}
+}
+
+/* ind[4 i + c] += the variants of this workgroup's run at which individual i has code c.  blockIdx.x = tile of QC_ITILE individuals,
+ * blockIdx.y = run of words of 64 variants.  Per word the tile is staged and read as in k_king_planes: lane = variant, a wave walks
+ * its 64 individuals, the ballot of a code over the lanes is the k-th individual's word and lane k counts it.  Code 0 is what is
+ * left of the run's variants. */
+__global__ __launch_bounds__(256) void k_qc_individuals(const uint8_t *__restrict__ bed, size_t rb, int I, int L, int n_words, qc_geometry g,
+							uint32_t *__restrict__ ind)
+{
+	__shared__ uint32_t tile[BT_L * BT_ROW];
+	const int i0 = blockIdx.x * QC_ITILE;
+	const long long w_begin = (long long)blockIdx.y * g.words_per_split;
+	const int w_end = (int)min((long long)n_words, w_begin + g.words_per_split);
+	const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+	const int lane = threadIdx.x & 63, first = (threadIdx.x >> 6) * 64;
+	uint32_t c1 = 0, c2 = 0, c3 = 0;
+	for (int w = (int)w_begin; w < w_end; w++) {
+		__syncthreads();	/* the word before has been read */
+		bed_stage_tile(tile, bed, rb, L, w * BT_L, i0);
+		__syncthreads();
+		const bool l_in = (long long)w * BT_L + lane < L;
+		for (int k = 0; k < 64; k++) {
+			const int r = first + k;
+			const uint32_t c = ((uint32_t)tb[lane * (BT_ROW * 4) + r / 4] >> (2 * (r & 3))) & 3u;
+			const bool in = l_in && i0 + r < I;	/* padding bits and staged zeros carry no call */
+			const uint64_t b1 = __ballot(in && c == 1u), b2 = __ballot(in && c == 2u), b3 = __ballot(in && c == 3u);
+			if (lane == k) { c1 += (uint32_t)__popcll(b1); c2 += (uint32_t)__popcll(b2); c3 += (uint32_t)__popcll(b3); }
+		}
+	}
+	const int i = i0 + first + lane;
+	if (i >= I || w_begin >= w_end) return;
+	const long long l_end = 64ll * w_end < L ? 64ll * w_end : (long long)L;
+	const uint32_t n = (uint32_t)(l_end - 64ll * w_begin);
+	uint32_t *out = ind + 4 * (size_t)i;
+	atomicAdd(out + 0, n - c1 - c2 - c3); atomicAdd(out + 1, c1); atomicAdd(out + 2, c2); atomicAdd(out + 3, c3);
+}
+
+/* the walk of the definition from h = mid: visit(h, w) for mid, then downwards, then upwards.  One multiply and one divide a step,
+ * in this order; the integer products are exact in 64 bits for N < 2^30 */
+template <typename F> __device__ __forceinline__ void qc_hwe_walk(int64_t N, int64_t r, int64_t mid, F &&visit)
+{
+#pragma clang fp contract(off)
+	int64_t h = mid, a = (r - mid) / 2, b = N - h - a;
+	double w = 1.0;
+	visit(h, w);
+	while (h >= 2) {
+		w = (w * (double)(h * (h - 1))) / (double)(4 * (a + 1) * (b + 1));
+		h -= 2; a += 1; b += 1;
+		visit(h, w);
+	}
+	h = mid; a = (r - mid) / 2; b = N - h - a; w = 1.0;
+	while (h <= r - 2) {
+		w = (w * (double)(4 * a * b)) / (double)((h + 2) * (h + 1));
+		h += 2; a -= 1; b -= 1;
+		visit(h, w);
+	}
+}
+
+/* p[l] of the counts var[4 l + 0, 2, 3]: the walk twice, the second time with the same bits, no weight kept */
+__global__ __launch_bounds__(64) void k_qc_hwe(const uint32_t *__restrict__ var, int L, double *__restrict__ p)
+{
+#pragma clang fp contract(off)
+	const long long l = (long long)blockIdx.x * 64 + threadIdx.x;
+	if (l >= L) return;
+	const int64_t n0 = var[4 * l], n2 = var[4 * l + 2], n3 = var[4 * l + 3], N = n0 + n2 + n3;
+	if (N == 0) { p[l] = 1.0; return; }
+	const int64_t r = 2 * (n0 < n3 ? n0 : n3) + n2;
+	int64_t mid = (r * (2 * N - r)) / (2 * N);
+	if ((mid ^ r) & 1) mid += 1;
+	double S = 0.0, w_obs = 0.0, T = 0.0;
+	qc_hwe_walk(N, r, mid, [&](int64_t h, double w) { S += w; if (h == n2) w_obs = w; });
+	const double bound = w_obs * 1.0000001;
+	qc_hwe_walk(N, r, mid, [&](int64_t, double w) { if (w <= bound) T += w; });
+	const double q = T / S;
+	p[l] = q > 1.0 ? 1.0 : q;
+}
+
+extern "C" int mchip_bed_qc(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, const uint8_t *ind_keep,
+			    uint32_t *ind_counts, uint32_t *var_counts, double *hwe_p)
+{
+	MCHIP_ENTRY();
+	if (!ctx) return MCHIP_ERR_INVALID;
+	if (!bed_shape_ok(I, L, bed, record_bytes) || (!ind_counts && !var_counts && !hwe_p))
+		return fail(ctx, MCHIP_ERR_INVALID, "bed_qc: bad shape, null records, records shorter than ceil(I/4) bytes or no output array%s", nullptr);
+	if (I >= (1 << 30))
+		return fail(ctx, MCHIP_ERR_UNSUPPORTED, "bed_qc: 2^30 or more individuals: the products of the exact test leave 64 bits%s", nullptr);
+	const int n_mwords = (I + 31) / 32, n_lwords = (int)(((long long)L + 63) / 64);
+	const qc_geometry g = qc_geometry_of(I, L, (long long)ctx->knob.per_cu_ind * (ctx->n_cu > 0 ? ctx->n_cu : 256));
+	const bool by_variant = var_counts || hwe_p;
+	HIPCHK(hipSetDevice(ctx->device));
+	scoped_dev<uint8_t> d_bed, d_keep;
+	scoped_dev<uint64_t> d_mask;
+	scoped_dev<uint32_t> d_var, d_ind;
+	scoped_dev<double> d_p;
+	const hipError_t uploaded = bed_upload(ctx, d_bed, bed, (size_t)L * record_bytes);
+	if (!d_bed.p || (by_variant && (d_mask.alloc((size_t)n_mwords) != hipSuccess || d_var.alloc(4 * (size_t)L) != hipSuccess)) ||
+	    (by_variant && ind_keep && d_keep.alloc((size_t)I) != hipSuccess) || (hwe_p && d_p.alloc((size_t)L) != hipSuccess) ||
+	    (ind_counts && d_ind.alloc(4 * (size_t)I) != hipSuccess)) {
+		(void)hipGetLastError();
+		return fail(ctx, MCHIP_ERR_ALLOC, "bed_qc: the records, the mask, the counts or the p values do not fit on the device%s", nullptr);
+	}
+	HIPCHK(uploaded);
+	if (by_variant) {
+		if (ind_keep) HIPCHK(hipMemcpyAsync(d_keep.p, ind_keep, (size_t)I, hipMemcpyHostToDevice, ctx->stream));
+		HIPCHK(hipMemsetAsync(d_var.p, 0, 4 * (size_t)L * sizeof(uint32_t), ctx->stream));
+		hipLaunchKernelGGL(k_qc_mask, dim3(nblk((size_t)n_mwords)), dim3(256), 0, ctx->stream, d_keep.p, I, n_mwords, d_mask.p);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(k_qc_variants, dim3((unsigned)g.n_vgroups, (unsigned)g.v_split), dim3(256), 0, ctx->stream, d_bed.p, record_bytes, L,
+				   n_mwords, d_mask.p, g, d_var.p);
+		HIPCHK(hipGetLastError());
+	}
+	if (hwe_p) {
+		hipLaunchKernelGGL(k_qc_hwe, dim3(nblk((size_t)L, 64)), dim3(64), 0, ctx->stream, d_var.p, L, d_p.p);
+		HIPCHK(hipGetLastError());
+	}
+	if (ind_counts) {
+		HIPCHK(hipMemsetAsync(d_ind.p, 0, 4 * (size_t)I * sizeof(uint32_t), ctx->stream));
+		hipLaunchKernelGGL(k_qc_individuals, dim3((unsigned)g.n_itiles, (unsigned)g.i_split), dim3(256), 0, ctx->stream, d_bed.p, record_bytes, I,
+				   L, n_lwords, g, d_ind.p);
+		HIPCHK(hipGetLastError());
+	}
+	if (ind_counts) HIPCHK(hipMemcpyAsync(ind_counts, d_ind.p, 4 * (size_t)I * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	if (var_counts) HIPCHK(hipMemcpyAsync(var_counts, d_var.p, 4 * (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	if (hwe_p) HIPCHK(hipMemcpyAsync(hwe_p, d_p.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(hipStreamSynchronize(ctx->stream));
 	return MCHIP_OK;
 }

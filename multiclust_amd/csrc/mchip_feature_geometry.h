@@ -104,4 +104,41 @@ static inline king_geometry king_geometry_of(int I, int n_rows, int L, long long
 	return g;
 }
 
+/* ---- genotype counts of packed records along both axes (k_qc_variants, k_qc_individuals, mchip_bed.hip; tests/qc_util.py restates
+ * the constants) ----
+ * Variant pass: a workgroup owns QC_VARIANTS variants, a wave each, and a run of whole steps of QC_STEP 64-bit words (32 individuals
+ * each) of their records.  Individual pass: a workgroup owns QC_ITILE individuals and a run of whole 64-bit words of variants (64
+ * each), one word staged at a time.  Either run is cut into several only while that takes the launch towards target_blocks
+ * workgroups: the counts are integers, so the cut shows in no bit of the result. */
+constexpr int QC_VARIANTS = 4;	/* variants per workgroup of the variant pass: one wave each */
+constexpr int QC_STEP = 64;	/* 64-bit words a wave reads of its record at a time: 2048 individuals */
+constexpr int QC_ITILE = 256;	/* individuals per workgroup of the individual pass: a lane each */
+
+struct qc_geometry {
+	int n_vgroups;			/* variant pass: workgroups along the variants */
+	int v_split, steps_per_split;	/*   workgroups along the individuals, and the steps each of them walks */
+	int n_itiles;			/* individual pass: workgroups along the individuals */
+	int i_split, words_per_split;	/*   workgroups along the variants, and the words each of them walks */
+};
+
+static inline void qc_cut(long long base, long long n_units, long long target_blocks, int *n_split, int *per_split)
+{
+	long long want = base > 0 ? (target_blocks + base - 1) / base : 1;
+	if (want > n_units) want = n_units;
+	if (want > 65535) want = 65535;
+	if (want < 1) want = 1;
+	*per_split = (int)((n_units + want - 1) / want);
+	*n_split = (int)((n_units + *per_split - 1) / *per_split);
+}
+
+static inline qc_geometry qc_geometry_of(int I, int L, long long target_blocks)
+{
+	qc_geometry g;
+	g.n_vgroups = (int)(((long long)L + QC_VARIANTS - 1) / QC_VARIANTS);
+	g.n_itiles = (int)(((long long)I + QC_ITILE - 1) / QC_ITILE);
+	qc_cut(g.n_vgroups, (((long long)I + 31) / 32 + QC_STEP - 1) / QC_STEP, target_blocks, &g.v_split, &g.steps_per_split);
+	qc_cut(g.n_itiles, ((long long)L + 63) / 64, target_blocks, &g.i_split, &g.words_per_split);
+	return g;
+}
+
 #endif

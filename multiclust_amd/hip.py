@@ -59,6 +59,7 @@ def load():
         "mchip_set_genotypes_bed": ([vp, i32, i32, vp, C.c_size_t, vp], i32),
         "mchip_bed_ld_band": ([vp, i32, i32, vp, C.c_size_t, i32, i32, i32, vp], i32),
         "mchip_bed_king": ([vp, i32, i32, vp, C.c_size_t, i32, i32, vp, vp], i32),
+        "mchip_bed_qc": ([vp, i32, i32, vp, C.c_size_t, vp, vp, vp, vp], i32),
         "mchip_set_model": ([vp, i32, i32, i32, i32, C.c_double, C.c_double, i32], i32),
         "mchip_set_p": ([vp, i32, vp], i32),
         "mchip_get_p": ([vp, i32, vp], i32),
@@ -138,7 +139,7 @@ ABI_SYMBOLS = [
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
     "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
-    "mchip_residual_products", "mchip_describe_plan", "mchip_bed_ld_band", "mchip_bed_king",
+    "mchip_residual_products", "mchip_describe_plan", "mchip_bed_ld_band", "mchip_bed_king", "mchip_bed_qc",
 ]
 
 
@@ -229,6 +230,25 @@ class Context:
         self._chk(self.lib.mchip_bed_king(self.h, I, L, bed.ctypes.data, rb, i0, n_rows, phi.ctypes.data,
                                           cnt.ctypes.data if counts else None))
         return phi, cnt
+
+    def bed_qc(self, I, bed, ind_keep=None, ind=True, var=True, hwe=True, record_bytes=None, L=None):
+        """mchip_bed_qc: (ind_counts [I][4], var_counts [L][4], hwe_p [L]) of the packed records [L][record_bytes], None for an
+        array that was not asked for: the four genotype counts of every individual over all variants, of every variant over the
+        individuals with ind_keep != 0 (None: all), and the Hardy-Weinberg exact test of the latter (include/multiclust_hip.h has
+        the definition).  Installs nothing and changes nothing of the context."""
+        bed = np.ascontiguousarray(bed, dtype=np.uint8)
+        assert bed.ndim == 2
+        L = bed.shape[0] if L is None else L
+        rb = bed.shape[1] if record_bytes is None else record_bytes
+        keep = None if ind_keep is None else np.ascontiguousarray(ind_keep, dtype=np.uint8)
+        assert keep is None or keep.shape == (I,)
+        ic = np.empty((max(I, 0), 4), dtype=np.uint32) if ind else None
+        vc = np.empty((max(L, 0), 4), dtype=np.uint32) if var else None
+        hp = np.empty(max(L, 0), dtype=np.float64) if hwe else None
+        self._chk(self.lib.mchip_bed_qc(self.h, I, L, bed.ctypes.data, rb, None if keep is None else keep.ctypes.data,
+                                        None if ic is None else ic.ctypes.data, None if vc is None else vc.ctypes.data,
+                                        None if hp is None else hp.ctypes.data))
+        return ic, vc, hp
 
     def data_counts(self):
         """(cells with n_ic > 0, non-missing allele copies) of the data set held, counted on the device"""

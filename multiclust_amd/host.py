@@ -127,7 +127,10 @@ class CliOptionsAll(CliOptions):
                 # --prune / --prune-window
                 ("prune", C.c_int), ("prune_window_given", C.c_int), ("prune_t", C.c_double), ("prune_window", C.c_int),
                 # --king-cutoff
-                ("king", C.c_int), ("king_t", C.c_double)]
+                ("king", C.c_int), ("king_t", C.c_double),
+                # --mind, --geno, --maf, --hwe
+                ("mind", C.c_int), ("geno", C.c_int), ("maf", C.c_int), ("hwe", C.c_int), ("mind_t", C.c_double),
+                ("geno_t", C.c_double), ("maf_t", C.c_double), ("hwe_t", C.c_double)]
 
 
 class McKingPair(C.Structure):
@@ -151,7 +154,8 @@ class CliDataAll(CliData):
     _fields_ = [("L_file", C.c_int), ("bim_text", C.c_void_p), ("chrom", C.POINTER(C.c_char_p)),
                 ("variant_id", C.POINTER(C.c_char_p)), ("variant_of", C.POINTER(C.c_int)),
                 ("I_file", C.c_int), ("individual_of", C.POINTER(C.c_int)), ("fam_fid", C.POINTER(C.c_char_p)),
-                ("fam_iid", C.POINTER(C.c_char_p)), ("king_pairs", C.POINTER(McKingPair)), ("n_king_pairs", C.c_size_t)]
+                ("fam_iid", C.POINTER(C.c_char_p)), ("king_pairs", C.POINTER(McKingPair)), ("n_king_pairs", C.c_size_t),
+                ("filters_run", C.c_int), ("qc", C.c_void_p)]
 
 
 def _cli_data_fields(d, geno):

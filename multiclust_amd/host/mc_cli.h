@@ -60,7 +60,23 @@ typedef struct mc_cli_options {
 	int prune_window;		/* --prune-window <W>: in variants, 1 ... MCHIP_LD_MAX_WINDOW; default 50 */
 	int king;			/* --king-cutoff <t> seen (extension, mc_king.c; needs --bed) */
 	double king_t;			/* --king-cutoff <t>: individuals are removed until no two kept ones have KING-robust kinship > t; 0 < t < 0.5 */
+	int mind, geno, maf, hwe;	/* --mind / --geno / --maf / --hwe <t> seen (extensions, mc_qc.c; each needs --bed) */
+	double mind_t;			/* --mind <t>: individuals whose missing rate over the variants of the file is > t are removed; 0 <= t < 1 */
+	double geno_t;			/* --geno <t>: variants whose missing rate over the individuals kept is > t are removed; 0 <= t < 1 */
+	double maf_t;			/* --maf <t>: variants whose minor-allele frequency over the individuals kept is < t are removed; 0 < t <= 0.5 */
+	double hwe_t;			/* --hwe <t>: variants whose Hardy-Weinberg exact-test p over the individuals kept is < t are removed; 0 < t < 1 */
 } mc_cli_options;
+
+/* what quality control (mc_qc.c) found in a fileset of I individuals and L variants: ind_counts [I][4] over all variants, ind_keep [I];
+ * var_counts [L][4] and hwe_p [L] over the kept individuals (mchip_bed_qc), var_reason [L] = why a variant went */
+enum { MC_QC_KEPT = 0, MC_QC_GENO = 1, MC_QC_MAF = 2, MC_QC_HWE = 3 };
+typedef struct mc_qc_result {
+	int I, L, I_kept, L_kept;
+	int n_reason[4];		/* variants by var_reason */
+	uint32_t *ind_counts, *var_counts;
+	double *hwe_p;
+	uint8_t *ind_keep, *var_reason;
+} mc_qc_result;
 
 /* one related pair of --king-cutoff: individuals i < j of the fileset, their counts n_ij, hh_ij, op_ij and kinship (mchip_bed_king) */
 typedef struct mc_king_pair {
@@ -102,7 +118,12 @@ typedef struct mc_cli_data {
 	char **fam_fid, **fam_iid;
 	mc_king_pair *king_pairs;
 	size_t n_king_pairs;
+	/* the filters that have run (MC_FILTER_*): each runs once, quality control before the other two.  An axis that an earlier filter
+	 * thinned is thinned further: variant_of / individual_of are composed and stay places in the fileset */
+	int filters_run;
+	mc_qc_result *qc;		/* what quality control found (mc_qc_data), NULL without it */
 } mc_cli_data;
+enum { MC_FILTER_QC = 1, MC_FILTER_PRUNE = 2, MC_FILTER_KING = 4 };
 
 /* ---- file plumbing (mc_files.h, libc only, static inline): one copy of what the readers, the writers and the filters of a fileset share.  `origin`
  * is the caller's source file: the lines on stderr read "ERROR [<origin>::open_out]: ..." and "ERROR [<origin>::slurp]: ...".
@@ -211,7 +232,11 @@ int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r);
  * <the device's last error>" are its.  Returns 0 or the status.
  * mc_filter_resummarize: the data set has changed -- uniquealleles, toff and L_alleles of the L_before loci it had are dropped and
  * made anew from the records held now (mc_bed_summarize), and under MC_READER_TIMING the seconds since t_start are reported as the
- * readers report theirs.  Returns mc_bed_summarize's status. */
+ * readers report theirs.  Returns mc_bed_summarize's status.
+ * mc_filter_rebuild_individuals: everything of the data set that is per individual made anew for the n kept ones, map[x] = the x-th
+ * kept one's place among the I held now (ascending): names, locale, pops, numpops, i_p as read_fam (mc_bed.c) yields them on the kept
+ * lines, I = n.  The first time the ids of every .fam line move to fam_fid / fam_iid [I_file]; later they stay.  individual_of is the
+ * caller's to compose.  Returns 0 or MC_EXIT_MEMORY_ALLOCATION, the data set then unchanged. */
 typedef struct mc_device_band {
 	mchip_context *ctx;
 	const mc_cli_data *dat;
@@ -230,7 +255,9 @@ typedef int (*mc_filter_fn)(const mc_cli_options *opt, mc_device_band *dev, void
  * mc_ld_prune_data: a data set as mc_read_bed yields it, pruned by opt->prune_t and opt->prune_window with the band of device
  * opt->device: the data set mc_read_bed yields on the fileset of the variants kept -- bed compacted, L their number, uniquealleles,
  * L_alleles, M, T, toff and missing_data theirs (mc_bed_summarize) -- with variant_of set; L_file, chrom and variant_id stay the
- * fileset's.  Under MC_READER_TIMING it reports its seconds as the readers do.  Returns 0 or a status.
+ * fileset's.  Of a data set whose variants quality control thinned before, variant_of is composed with the map held -- still places in
+ * the fileset -- and the chromosomes are read through it.  Under MC_READER_TIMING it reports its seconds as the readers do.  Returns 0 or a
+ * status; MC_EXIT_INTERNAL_ERROR when it ran before.
  * mc_write_prune_lists: <stem>.prune.in and <stem>.prune.out -- the ids of the variants kept and removed, one per line in file order. */
 #define MC_LD_SLAB 65536
 typedef int (*mc_ld_band_fn)(void *arg, int l0, int n_first, int window, double *r2);
@@ -255,8 +282,10 @@ int mc_write_prune_lists(const mc_cli_options *opt, const mc_cli_data *dat);
  * mc_king_data: a data set as mc_read_bed (and mc_ld_prune_data) yields it, thinned at opt->king_t with the kinships of device
  * opt->device: the data set mc_read_bed yields on the fileset of the individuals kept -- I, names, locale, pops, numpops, i_p (locales
  * in order of first appearance among the kept), bed, bed_record_bytes, lazy, and uniquealleles, L_alleles, M, T, toff and missing_data
- * (mc_bed_summarize) theirs -- with I_file, individual_of, fam_fid, fam_iid and king_pairs set.  Under MC_READER_TIMING it reports
- * its seconds as the readers do.  Returns 0 or a status.
+ * (mc_bed_summarize) theirs -- with I_file, individual_of, fam_fid, fam_iid and king_pairs set.  Of a data set whose individuals quality
+ * control thinned before, individual_of is composed with the map held, I_file, fam_fid and fam_iid stay the fileset's, and king_pairs
+ * name places in the fileset all the same.  Under MC_READER_TIMING it reports its seconds as the readers do.  Returns 0 or a status;
+ * MC_EXIT_INTERNAL_ERROR when it ran before.
  * mc_write_king_lists: <stem>.king.cutoff.in and <stem>.king.cutoff.out -- "FID\tIID" of the individuals kept and removed, one per
  * line in file order -- and <stem>.king.kin0, the related pairs (the format is at the function). */
 #define MC_KING_SLAB 1024
@@ -268,6 +297,30 @@ int mc_king_data(const mc_cli_options *opt, mc_cli_data *dat);
 int mc_write_king_lists(const mc_cli_options *opt, const mc_cli_data *dat);
 /* a new decoder of the packed records for dat->lazy (mc_bed.c): nothing decoded yet; NULL when out of memory */
 struct mc_lazy_geno *mc_bed_lazy_new(void);
+
+/* --mind, --geno, --maf, --hwe (extensions, mc_qc.c; the counts and the exact test are defined in include/multiclust_hip.h, the rules and
+ * their order in the header comment of mc_qc.c).
+ * mc_qc_missing_rate: num / den, one division of two integers converted to double; 0 when den = 0.
+ * mc_qc_maf: min(2 n0 + n2, 2 n3 + n2) / (2 N) of c = {n0, n1, n2, n3} with N = n0 + n2 + n3, one division; 0 when N = 0.
+ * mc_qc_individuals: keep[i] = 0 where individual i's missing rate ind_counts[i][1] / L is > t, else 1; returns the number kept.
+ * mc_qc_variants: reason[l] = the first rule variant l fails in the order geno (missing rate var_counts[l][1] / (the four counts' sum)
+ * > geno_t), maf (MAF < maf_t), hwe (hwe_p[l] < hwe_t), among the rules opt names, or MC_QC_KEPT; n_reason[4] counts them.
+ * mc_qc_result_free (mc_filter.h, libc only: mc_free_data calls it): the arrays and the record.
+ * mc_qc_data: a data set as mc_read_bed yields it, no filter having run, filtered by the rules opt names with the counts of device
+ * opt->device -- one call of mchip_bed_qc without --mind, two with it, the second under the keep bytes: the data set mc_read_bed yields
+ * on the fileset of the individuals and variants kept, individual_of / variant_of set on an axis that lost something, and dat->qc what
+ * was found.  When no individual or no variant is left it says which option emptied the data set and returns
+ * MC_EXIT_INVALID_USER_SETUP.  Returns 0 or a status.
+ * mc_qc_line: the stdout line "Quality control: ..." of dat->qc, only the parts whose option was given.
+ * mc_write_qc_lists: <stem>.mind.in / .out ("FID\tIID", with --mind), <stem>.qc.in / .out (variant ids, with --geno, --maf or --hwe),
+ * <stem>.qc.var.txt and <stem>.qc.ind.txt (the formats are at the function). */
+double mc_qc_missing_rate(uint32_t num, uint32_t den);
+double mc_qc_maf(const uint32_t *c);
+int mc_qc_individuals(int I, int L, const uint32_t *ind_counts, double t, uint8_t *keep);
+void mc_qc_variants(const mc_cli_options *opt, int L, const uint32_t *var_counts, const double *hwe_p, uint8_t *reason, int *n_reason);
+int mc_qc_data(const mc_cli_options *opt, mc_cli_data *dat);
+void mc_qc_line(FILE *fp, const mc_cli_options *opt, const mc_cli_data *dat);
+int mc_write_qc_lists(const mc_cli_options *opt, const mc_cli_data *dat);
 
 #include "mc_filter.h"
 

@@ -1,7 +1,7 @@
 /*
  * mc_filter.h -- what the filters of a fileset that run before the fit (--prune, mc_ld.c; --king-cutoff, mc_king.c) have in common
  * (mc_cli.h, which includes this file at its end, says what each function does): the device opened around the part that asks it
- * for a band, and the reader's summary made anew once the records have changed.  A new filter writes its rule and its compaction,
+ * for a band, the reader's summary made anew once the records have changed, and the per-individual fields made anew for the individuals kept.  A new filter writes its rule and its compaction,
  * calls these two, and is run by pre_fit() of mc_main.c.  static inline, as mc_files.h is and for the same reason; beside libc they
  * call mchip_create / mchip_destroy / mchip_last_error and mc_bed_summarize (mc_bed.c): the drivers under tests/ stub those.
  */
@@ -32,6 +32,55 @@ static inline int mc_filter_resummarize(mc_cli_data *dat, int L_before, const ch
 	const int rc = mc_bed_summarize(dat);
 	mc_timing_line(origin, what, t_start);
 	return rc;
+}
+
+static inline void mc_qc_result_free(mc_qc_result *r)
+{
+	if (!r) return;
+	free(r->ind_counts); free(r->var_counts); free(r->hwe_p); free(r->ind_keep); free(r->var_reason);
+	free(r);
+}
+
+static inline int mc_filter_rebuild_individuals(mc_cli_data *dat, int n, const int *map)
+{
+	const int I = dat->I, first = !dat->fam_iid;
+	char **fid = first ? calloc((size_t)I, sizeof *fid) : NULL, **names = calloc((size_t)n, sizeof *names), **pops = calloc((size_t)n, sizeof *pops);
+	int *locale = calloc((size_t)n, sizeof *locale), *i_p = NULL, *new_of = malloc(sizeof(int) * (size_t)(dat->numpops ? dat->numpops : 1));
+	int numpops = 0, ok = (fid || !first) && names && pops && locale && new_of;
+	for (int i = 0; ok && first && i < I; i++) ok = (fid[i] = strdup(dat->pops[dat->locale[i]])) != NULL;
+	for (int p = 0; ok && p < dat->numpops; p++) new_of[p] = -1;
+	for (int x = 0; ok && x < n; x++) {
+		const int old = dat->locale[map[x]];
+		if (new_of[old] < 0) {
+			if (!(pops[numpops] = strdup(dat->pops[old]))) { ok = 0; break; }
+			new_of[old] = numpops++;
+		}
+		locale[x] = new_of[old];
+		ok = (names[x] = strdup(dat->names[map[x]])) != NULL;
+	}
+	if (ok) ok = (i_p = calloc((size_t)(numpops ? numpops : 1), sizeof *i_p)) != NULL;
+	free(new_of);
+	if (!ok) {
+		for (int i = 0; fid && i < I; i++) free(fid[i]);
+		for (int x = 0; x < n; x++) { if (names) free(names[x]); if (pops) free(pops[x]); }
+		free(fid); free(names); free(pops); free(locale);
+		return MC_EXIT_MEMORY_ALLOCATION;
+	}
+	for (int x = 0; x < n; x++) i_p[locale[x]]++;
+	for (int p = 0; p < dat->numpops; p++) free(dat->pops[p]);
+	free(dat->pops); free(dat->locale); free(dat->i_p);
+	if (first) {	/* the file's own ids move to fam_iid / fam_fid */
+		dat->fam_iid = dat->names;
+		dat->fam_fid = fid;
+		dat->I_file = I;
+	} else {
+		for (int i = 0; i < I; i++) free(dat->names[i]);
+		free(dat->names);
+	}
+	dat->names = names; dat->pops = pops; dat->locale = locale; dat->i_p = i_p;
+	dat->numpops = numpops;
+	dat->I = n;
+	return 0;
 }
 
 #endif

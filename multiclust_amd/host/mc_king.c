@@ -17,7 +17,7 @@
  * relatedness graph as an I x I bit matrix, I * I / 8 bytes: its only memory quadratic in I.
  *
  * Everything in this file is libc and mc_files.h but what mc_king_data calls: the kinships (mchip_bed_king), the filter stage
- * (mc_filter.h: the device opened and closed, the reader's summary made anew) and the reader's decoder (mc_bed_lazy_new, mc_bed.c).
+ * (mc_filter.h: the device opened and closed, the per-individual fields and the reader's summary made anew) and the reader's decoder (mc_bed_lazy_new, mc_bed.c).
  * tests/king_host_driver.c stubs the device and the reader and runs the rest as a program of its own.
  */
 #include "mc_cli.h"
@@ -118,45 +118,6 @@ int mc_king_compact(int I, int L, size_t record_bytes, const uint8_t *keep, uint
 	return n;
 }
 
-/* everything of the data set that is per individual, made anew for the n kept ones (map[x] = the x-th kept one's place in the file):
- * what read_fam (mc_bed.c) yields on their lines.  The file's own ids move to fam_iid / fam_fid. */
-static int rebuild_individuals(mc_cli_data *dat, int n, const int *map)
-{
-	const int I = dat->I;
-	char **fid = calloc((size_t)I, sizeof *fid), **names = calloc((size_t)n, sizeof *names), **pops = calloc((size_t)n, sizeof *pops);
-	int *locale = calloc((size_t)n, sizeof *locale), *i_p = NULL, *new_of = malloc(sizeof(int) * (size_t)(dat->numpops ? dat->numpops : 1));
-	int numpops = 0, ok = fid && names && pops && locale && new_of;
-	for (int i = 0; ok && i < I; i++) ok = (fid[i] = strdup(dat->pops[dat->locale[i]])) != NULL;
-	for (int p = 0; ok && p < dat->numpops; p++) new_of[p] = -1;
-	for (int x = 0; ok && x < n; x++) {
-		const int old = dat->locale[map[x]];
-		if (new_of[old] < 0) {
-			if (!(pops[numpops] = strdup(dat->pops[old]))) { ok = 0; break; }
-			new_of[old] = numpops++;
-		}
-		locale[x] = new_of[old];
-		ok = (names[x] = strdup(dat->names[map[x]])) != NULL;
-	}
-	if (ok) ok = (i_p = calloc((size_t)(numpops ? numpops : 1), sizeof *i_p)) != NULL;
-	free(new_of);
-	if (!ok) {
-		for (int i = 0; fid && i < I; i++) free(fid[i]);
-		for (int x = 0; x < n; x++) { if (names) free(names[x]); if (pops) free(pops[x]); }
-		free(fid); free(names); free(pops); free(locale);
-		return MC_EXIT_MEMORY_ALLOCATION;
-	}
-	for (int x = 0; x < n; x++) i_p[locale[x]]++;
-	for (int p = 0; p < dat->numpops; p++) free(dat->pops[p]);
-	free(dat->pops); free(dat->locale); free(dat->i_p);
-	dat->fam_iid = dat->names;
-	dat->fam_fid = fid;
-	dat->I_file = I;
-	dat->names = names; dat->pops = pops; dat->locale = locale; dat->i_p = i_p;
-	dat->numpops = numpops;
-	dat->I = n;
-	return 0;
-}
-
 static int band_on_device(void *arg, int i0, int n_rows, double *phi, uint32_t *counts)
 {
 	const mc_device_band *b = arg;
@@ -184,16 +145,25 @@ int mc_king_data(const mc_cli_options *opt, mc_cli_data *dat)
 	int rc = MC_EXIT_MEMORY_ALLOCATION;
 	const double t_start = mc_now_s();
 	if (!keep || !map) goto DONE;
-	if (!dat->bed || dat->individual_of) { rc = MC_EXIT_INTERNAL_ERROR; goto DONE; }	/* a fileset, and not thinned before */
+	if (!dat->bed || (dat->filters_run & MC_FILTER_KING) || (dat->individual_of && !(dat->filters_run & MC_FILTER_QC))) {
+		rc = MC_EXIT_INTERNAL_ERROR;	/* a fileset, and not thinned before but by quality control */
+		goto DONE;
+	}
 	if ((rc = mc_filter_on_device(opt, dat, "mc_king.c::mc_king_data", "--king-cutoff", "the kinship matrix", edges_by_device, &g))) goto DONE;
 	if ((rc = mc_king_select(I, g.bits, keep))) goto DONE;
 	/* the data set is the kept individuals' from here on: their codes in every record, their ids, and the reader's summary of those */
 	const int n = mc_king_compact(I, L, dat->bed_record_bytes, keep, dat->bed, map);
 	if (n < 1) { rc = MC_EXIT_MEMORY_ALLOCATION; goto DONE; }
 	dat->bed_record_bytes = ((size_t)n + 3) / 4;
-	if ((rc = rebuild_individuals(dat, n, map))) goto DONE;
+	if ((rc = mc_filter_rebuild_individuals(dat, n, map))) goto DONE;
+	if (dat->individual_of) {	/* thinned before: the places in the fileset, of the kept ones and of the pairs */
+		for (int x = 0; x < n; x++) map[x] = dat->individual_of[map[x]];
+		for (size_t p = 0; p < g.n_pairs; p++) { g.pairs[p].i = dat->individual_of[g.pairs[p].i]; g.pairs[p].j = dat->individual_of[g.pairs[p].j]; }
+		free(dat->individual_of);
+	}
 	dat->individual_of = map;
 	map = NULL;
+	dat->filters_run |= MC_FILTER_KING;
 	dat->king_pairs = g.pairs;
 	dat->n_king_pairs = g.n_pairs;
 	g.pairs = NULL;

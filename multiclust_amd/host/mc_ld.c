@@ -67,9 +67,19 @@ static int band_on_device(void *arg, int l0, int n_first, int window, double *r2
 	return mchip_bed_ld_band(b->ctx, b->dat->I, b->dat->L, b->dat->bed, b->dat->bed_record_bytes, l0, n_first, window, r2);
 }
 
+/* the chromosomes of the loci held: the fileset's, read through variant_of where quality control thinned the variants before */
 static int keep_by_device(const mc_cli_options *opt, mc_device_band *dev, void *keep)
 {
-	return mc_ld_prune_greedy(dev->dat->L, opt->prune_window, opt->prune_t, MC_LD_SLAB, band_on_device, dev, (const char *const *)dev->dat->chrom, keep);
+	const mc_cli_data *dat = dev->dat;
+	const char **chrom = NULL;
+	if (dat->chrom && dat->variant_of) {
+		if (!(chrom = malloc(sizeof *chrom * (size_t)dat->L))) return MCHIP_ERR_ALLOC;
+		for (int l = 0; l < dat->L; l++) chrom[l] = dat->chrom[dat->variant_of[l]];
+	}
+	const int rc = mc_ld_prune_greedy(dat->L, opt->prune_window, opt->prune_t, MC_LD_SLAB, band_on_device, dev,
+					  chrom ? chrom : (const char *const *)dat->chrom, keep);
+	free(chrom);
+	return rc;
 }
 
 int mc_ld_prune_data(const mc_cli_options *opt, mc_cli_data *dat)
@@ -81,14 +91,20 @@ int mc_ld_prune_data(const mc_cli_options *opt, mc_cli_data *dat)
 	int rc = MC_EXIT_MEMORY_ALLOCATION;
 	const double t_start = mc_now_s();
 	if (!keep || !map) goto DONE;
-	if (!dat->bed || dat->variant_of) { rc = MC_EXIT_INTERNAL_ERROR; goto DONE; }	/* a fileset, and not pruned before */
+	if (!dat->bed || (dat->filters_run & MC_FILTER_PRUNE) || (dat->variant_of && !(dat->filters_run & MC_FILTER_QC))) {
+		rc = MC_EXIT_INTERNAL_ERROR;	/* a fileset, and not thinned before but by quality control */
+		goto DONE;
+	}
 	if ((rc = mc_filter_on_device(opt, dat, "mc_ld.c::mc_ld_prune_data", "--prune", "the LD band", keep_by_device, keep))) goto DONE;
 	/* the data set is the kept variants' from here on: their records, and the reader's summary of those */
 	dat->L = mc_ld_compact(L, rb, keep, dat->bed, map);
 	memset(dat->bed + (size_t)dat->L * rb, 0, 8);	/* (the reader's spare bytes behind the last record) */
+	if (dat->variant_of)	/* thinned before: the places in the fileset */
+		for (int l = 0; l < dat->L; l++) map[l] = dat->variant_of[map[l]];
 	free(dat->variant_of);
 	dat->variant_of = map;
 	map = NULL;
+	dat->filters_run |= MC_FILTER_PRUNE;
 	rc = mc_filter_resummarize(dat, L, "mc_ld.c", "LD pruning", t_start);
 DONE:
 	free(keep); free(map);

@@ -19,6 +19,9 @@
  * line and two more files; the run is the run on the fileset of the variants kept; without it nothing changes);
  * --king-cutoff <t> removes close relatives from a fileset (--bed) by KING-robust kinship on the device before anything is fitted (mc_king.c; one
  * more stdout line and three more files; the run is the run on the fileset of the individuals kept; without it nothing changes);
+ * --mind / --geno / --maf / --hwe <t> remove individuals by missing rate and variants by missing rate, minor-allele frequency and Hardy-Weinberg
+ * exact test from a fileset (--bed) on the device before anything is fitted, and before --prune and --king-cutoff (mc_qc.c; one more stdout line
+ * and up to six more files; the run is the run on the fileset of the individuals and variants kept; without them nothing changes);
  * --query <file> keeps the individuals the file marks out of every fit and fits their mixing proportions against the best fit of every K
  * afterwards (one more stdout line per K and one more file; without it nothing changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
@@ -30,8 +33,9 @@
  * the best fit of a K in a fit_record, hand it to new_maximum() when it improved on the K before (H0 estimate, result files, -A) and
  * end in post_fit(), which puts the record back into a model once and runs --fst, --resid, --cv, --se, --query, --fill; an analysis that refits derived
  * data sets builds on mc_refit_* (mc_refit.c), adds its line to post_fit()'s text and its refusals to parse_options' refuse_post_fit().
- * Where a filter of the fileset plugs in: pre_fit() runs them between the reader and the first fit, --prune then --king-cutoff; a new
- * one (--maf, --geno, --keep, ...) is a unit like mc_ld.c on mc_filter.h and mc_files.h, and one more block there.
+ * Where a filter of the fileset plugs in: pre_fit() runs them between the reader and the first fit, quality control, then --prune, then
+ * --king-cutoff, each on what the one before left; a new one (--keep, --extract, ...) is a unit like mc_ld.c on mc_filter.h and mc_files.h, and
+ * one more block there.
  */
 #include "mc_cli.h"
 
@@ -104,7 +108,17 @@ static void usage(FILE *fp, const char *prog)
 		"                (0 < t < 0.5), the one with the most remaining relatives is removed, of equals the later in the .fam file (greedy, this\n"
 		"                program's own rule; not PLINK 2's algorithm, not a maximum independent set); one more line 'Relatedness: ...', the ids\n"
 		"                kept and removed in <stem>.king.cutoff.in / .king.cutoff.out and the related pairs in <stem>.king.kin0; the run is the\n"
-		"                run on the fileset of the kept individuals: the files of -A and --query describe those, in their order; needs --bed\n", prog);
+		"                run on the fileset of the kept individuals: the files of -A and --query describe those, in their order; needs --bed\n"
+		"  --mind <t>    remove the individuals of --bed whose missing rate over all variants of the file exceeds t (0 <= t < 1)\n"
+		"  --geno <t>    remove the variants whose missing rate over the individuals kept exceeds t (0 <= t < 1)\n"
+		"  --maf <t>     remove the variants whose minor-allele frequency over the individuals kept is below t (0 < t <= 0.5)\n"
+		"  --hwe <t>     remove the variants whose Hardy-Weinberg exact-test p (Wigginton et al. 2005) over the individuals kept is below t\n"
+		"                (0 < t < 1; population structure lowers p by itself: keep t lenient, 1e-6 or less).  Quality control runs before\n"
+		"                anything is fitted and before --prune and --king-cutoff, in PLINK 1.9's order: --mind first, then the three variant\n"
+		"                rules from one set of counts, a variant's reason being the first rule it fails (geno, maf, hwe); all variants and\n"
+		"                individuals count (no chromosome is special); one more line 'Quality control: ...', the ids kept and removed in\n"
+		"                <stem>.mind.in / .mind.out and <stem>.qc.in / .qc.out, and the counts, rates and p values of every variant and\n"
+		"                individual of the file in <stem>.qc.var.txt / .qc.ind.txt; the run is the run on the fileset of those kept; need --bed\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -206,10 +220,14 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 				if (o->filename[x] == '/') { o->filename_file = &o->filename[x + 1]; break; }
 			break;
 		case 'g':
+			if (!strcmp(argv[i], "--geno")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--geno"); o->geno = 1; o->geno_t = d; break; }	/* (in full: -g... is the back-tracking) */
 			if (!strncmp(w, "gp", 2)) { if (arg_int(argc, argv, ++i, &v) || v < 1 || v > 64) BAD("--gpus"); o->n_gpus = (int)v; }
 			else { if (arg_int(argc, argv, ++i, &v) || v < 0) BAD("-g"); o->em.adjust_step = (int)v; }
 			break;
-		case 'h': usage(stdout, argv[0]); return 1;
+		case 'h':
+			if (!strcmp(argv[i], "--hwe")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--hwe"); o->hwe = 1; o->hwe_t = d; break; }	/* (in full: -h... is the help) */
+			usage(stdout, argv[0]);
+			return 1;
 		case 'i':
 			if (!strncmp(w, "im", 2)) BAD("--impute is not supported by this build");
 			if (arg_int(argc, argv, ++i, &v) || v < 0) BAD("-i");
@@ -224,6 +242,8 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			o->min_K = o->max_K = (int)v;
 			break;
 		case 'm':
+			if (!strcmp(argv[i], "--mind")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--mind"); o->mind = 1; o->mind_t = d; break; }	/* (in full: --mi... is --missing) */
+			if (!strcmp(argv[i], "--maf")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--maf"); o->maf = 1; o->maf_t = d; break; }	/* (in full: -m... is the candidates) */
 			if (!strncmp(w, "mi", 2)) { if (arg_int(argc, argv, ++i, &v)) BAD("--missing"); o->missing_value = (int)v; }
 			else { if (arg_int(argc, argv, ++i, &v) || v < 0) BAD("-m"); o->n_rand_em_init = o->em.n_rand_em_init = (int)v; }
 			break;
@@ -327,6 +347,14 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 	if (o->king && (rc = refuse("--king-cutoff",
 			!o->bed_prefix ? "--king-cutoff needs a PLINK fileset (--bed)" :
 			!(o->king_t > 0 && o->king_t < 0.5) ? "the kinship threshold of --king-cutoff must lie in (0, 0.5)" : NULL))) return rc;
+	if (o->mind && (rc = refuse("--mind", !o->bed_prefix ? "--mind needs a PLINK fileset (--bed)" :
+			!(o->mind_t >= 0 && o->mind_t < 1) ? "the missing rate of --mind must lie in [0, 1)" : NULL))) return rc;
+	if (o->geno && (rc = refuse("--geno", !o->bed_prefix ? "--geno needs a PLINK fileset (--bed)" :
+			!(o->geno_t >= 0 && o->geno_t < 1) ? "the missing rate of --geno must lie in [0, 1)" : NULL))) return rc;
+	if (o->maf && (rc = refuse("--maf", !o->bed_prefix ? "--maf needs a PLINK fileset (--bed)" :
+			!(o->maf_t > 0 && o->maf_t <= 0.5) ? "the minor-allele frequency of --maf must lie in (0, 0.5]" : NULL))) return rc;
+	if (o->hwe && (rc = refuse("--hwe", !o->bed_prefix ? "--hwe needs a PLINK fileset (--bed)" :
+			!(o->hwe_t > 0 && o->hwe_t < 1) ? "the p value of --hwe must lie in (0, 1)" : NULL))) return rc;
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -1002,21 +1030,30 @@ DONE:
 	return rc;
 }
 
-/* ---- the pre-fit stage: the filters of a fileset, --prune then --king-cutoff (on the variants kept), each with its stdout line and,
- * with result files on, its lists.  The data set is the filtered one from here on; the lists say what of the fileset it holds. ---- */
+/* ---- the pre-fit stage: the filters of a fileset, quality control (--mind, --geno, --maf, --hwe), then --prune, then --king-cutoff, each
+ * on what the one before left, each with its stdout line -- "of <n>" is what the filter itself saw -- and, with result files on, its
+ * lists.  The data set is the filtered one from here on; the lists say what of the fileset it holds. ---- */
 static int pre_fit(const mc_cli_options *o, mc_cli_data *d)
 {
 	int rc;
+	if (o->mind || o->geno || o->maf || o->hwe) {
+		mchip_progress_note("mc_qc_data");
+		if ((rc = mc_qc_data(o, d))) return rc;
+		mc_qc_line(stdout, o, d);
+		if (o->write_files && (rc = mc_write_qc_lists(o, d))) return rc;
+	}
 	if (o->prune) {
+		const int L_seen = d->L;
 		mchip_progress_note("mc_ld_prune_data");
 		if ((rc = mc_ld_prune_data(o, d))) return rc;
-		printf("LD pruning: kept %d of %d variants (r2 > %g within %d)\n", d->L, d->L_file, o->prune_t, o->prune_window);
+		printf("LD pruning: kept %d of %d variants (r2 > %g within %d)\n", d->L, L_seen, o->prune_t, o->prune_window);
 		if (o->write_files && (rc = mc_write_prune_lists(o, d))) return rc;
 	}
 	if (o->king) {
+		const int I_seen = d->I;
 		mchip_progress_note("mc_king_data");
 		if ((rc = mc_king_data(o, d))) return rc;
-		printf("Relatedness: kept %d of %d individuals (KING-robust kinship > %g: %zu pairs)\n", d->I, d->I_file, o->king_t, d->n_king_pairs);
+		printf("Relatedness: kept %d of %d individuals (KING-robust kinship > %g: %zu pairs)\n", d->I, I_seen, o->king_t, d->n_king_pairs);
 		if (o->write_files && (rc = mc_write_king_lists(o, d))) return rc;
 	}
 	return 0;

@@ -353,6 +353,7 @@ void mc_free_data(mc_cli_data *dat)
 		if (dat->fam_iid) free(dat->fam_iid[i]);
 	}
 	free(dat->fam_fid); free(dat->fam_iid); free(dat->individual_of); free(dat->king_pairs);
+	mc_qc_result_free(dat->qc);
 	if (dat->lazy) dat->lazy->release(dat->lazy);
 	memset(dat, 0, sizeof *dat);
 }
