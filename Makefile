@@ -26,7 +26,7 @@ $(OBJ)/mchip_k%.o: multiclust_amd/csrc/mchip_kernels_k.hip multiclust_amd/csrc/m
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_K=$* -c $< -o $@
 
 # the K-independent units: a new one costs one word here
-HIPUNITS = mchip mchip_comm mchip_bed mchip_cv mchip_generators mchip_query mchip_resample mchip_impute mchip_divergence mchip_residuals
+HIPUNITS = mchip mchip_comm mchip_bed mchip_cv mchip_generators mchip_query mchip_resample mchip_impute mchip_divergence mchip_residuals mchip_pca
 HIPOBJ   = $(HIPUNITS:%=$(OBJ)/%.o)
 HIPHDRS  = $(wildcard multiclust_amd/csrc/*.h) include/multiclust_hip.h
 $(OBJ)/%.o: multiclust_amd/csrc/%.hip $(HIPHDRS)

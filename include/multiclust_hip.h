@@ -160,6 +160,50 @@ int mchip_bed_king(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t 
  */
 int mchip_bed_qc(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, const uint8_t *ind_keep,
 		 uint32_t *ind_counts, uint32_t *var_counts, double *hwe_p);
+/*
+ * Principal components of packed records (an extension): what --pca reports.  bed, I, L and record_bytes as for
+ * mchip_set_genotypes_bed.
+ * Definition.  Codes as above: 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2, with the dosages x = 0, none, 1, 2;
+ * padding bits carry no individual.  For variant l: n_l = the number of typed individuals and s_l = the sum of their dosages, both
+ * integers from population counts.  The variant is USED iff 0 < s_l < 2 n_l: an all-missing and a monomorphic variant are not.  L' is
+ * the number of used variants.  For a used variant
+ *     mu = (double)s / (double)n,   inv = 1 / sqrt(mu (1 - 0.5 mu)),
+ *     z_il = ((double)x_il - mu) inv for a typed individual, 0 for a missing one (mean imputation),
+ * and z_il = 0 on an unused variant.  G = Z Z^T / L', an I x I matrix; its trace is (sum_l t_l) / L' with
+ * t_l = (n0 mu^2 + n2 (1 - mu)^2 + n3 (2 - mu)^2) inv^2 from the counts, the sum in index order.
+ * This is the mean-imputed standardised matrix of flashpca and of PLINK 2's --pca approx.  It is NOT PLINK 1.9's pairwise-complete
+ * GRM (--make-rel / --pca), and not smartpca's normalisation.  The four values z takes at a variant involve a square root and a
+ * reciprocal: no bit-for-bit claim is made about them.  What is fixed is the order of every sum: W = Z^T X adds over the individuals
+ * in an order that depends on (I, padded column count) alone; Y adds over the variants within constant slabs of 4096 variants and
+ * then over the slabs in index order; no floating-point atomics.  The same call gives the same bits on every device of a kind, under
+ * every launch geometry and every knob of the environment.
+ * mchip_bed_pca_apply: Y = Z (Z^T X) / L' for x [I][n_vec] -> y [I][n_vec], 1 <= n_vec <= MCHIP_PCA_MAX_VECTORS; w, when not NULL,
+ * receives W = Z^T X [L][n_vec]; scale, when not NULL, [L][2] = mu, inv of every variant (0, 0 for an unused one); *n_used = L';
+ * *trace (may be NULL) the trace of G.  The column count is padded to a multiple of 16 with zero columns inside the library; they
+ * are never returned.
+ * mchip_bed_pca: the first n_pc eigenpairs of G by block subspace iteration with a Rayleigh-Ritz step every iteration (the
+ * iteration, its start vectors -- a fixed function of the indices, no seed -- and its stopping rule are stated in
+ * multiclust_amd/csrc/mchip_pca_algebra.h): block width b = min(I, n_pc + n_extra rounded up to a multiple of 16, at most 64);
+ * eigenvalues [n_pc] descending, eigenvectors [I][n_pc] of unit norm, the component of largest magnitude positive (the lowest index
+ * among equals), residuals [n_pc] = || G u - theta u || / theta_1, *n_iter the iterations run.  The records, the per-variant
+ * tables, X, W and Y stay on the device from the first launch to the last; the I x b blocks cross once each way an iteration, the
+ * small dense algebra runs on the host.  Not converging within max_iter is NO error: MCHIP_OK, and the residuals say which
+ * components are still loose.  Component c converges at the rate lambda_{b+1} / lambda_c per iteration: components inside the
+ * noise bulk of the spectrum converge slowly and mean nothing.
+ * Contract (both).  The context supplies the device, the stream and mchip_last_error and nothing else: no data set need be
+ * installed, and nothing of an installed data set, model, slot, fold or saved set changes.  Checked before anything runs: I, L >= 1,
+ * record_bytes >= ceil(I/4), non-null pointers (but w, scale and apply's trace), 1 <= n_vec <= 64; 1 <= n_pc <= I, 0 <= n_extra,
+ * n_pc + n_extra <= 64, max_iter >= 1, 0 < tol < 1; a failed check returns MCHIP_ERR_INVALID and leaves the outputs untouched.  L' = 0
+ * is MCHIP_ERR_INVALID as well ("no polymorphic variant"), the outputs untouched.  MCHIP_ERR_ALLOC when the records, the tables
+ * (60 bytes a variant), X and Y, W (8 b bytes a variant) and the slabs' partial sums (ceil(L/4096) x I rounded up to 64 x b doubles)
+ * do not fit on the device.  MCHIP_ERR_UNSUPPORTED for a shape beyond one launch: more than 2^31 - 65 individuals or more than 65535
+ * slabs of variants.
+ */
+#define MCHIP_PCA_MAX_VECTORS 64
+int mchip_bed_pca_apply(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int n_vec, const double *x, double *y,
+			double *w, double *scale, int *n_used, double *trace);
+int mchip_bed_pca(mchip_context *ctx, int I, int L, const uint8_t *bed, size_t record_bytes, int n_pc, int n_extra, int max_iter, double tol,
+		  double *eigenvalues, double *eigenvectors, double *residuals, double *trace, int *n_used, int *n_iter);
 /* Counted on the device when a data set is installed: cells (i, l, m) with ILM[i][l][m] > 0 -- the cells the reference's E step
  * visits (em_alg.c:338-342) and the unit the flop count of the path is stated in -- and non-missing allele copies. */
 int mchip_data_counts(mchip_context *ctx, uint64_t *nonempty_cells, uint64_t *allele_copies);

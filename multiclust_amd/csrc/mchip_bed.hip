@@ -58,34 +58,6 @@
  */
 #include "mchip_context.h"
 
-constexpr int BED_PAD = 8;	/* bytes allocated behind the last record: records are read as dwords from any byte offset */
-constexpr int BT_L = 64;	/* loci per tile */
-constexpr int BT_I = 256;	/* individuals per tile: 64 staged bytes of each record */
-constexpr int BT_ROW = 17;	/* dwords between staged records: 16 of data and one of padding, so that the 64 lanes that read the
-				 * same byte pair of 64 consecutive records (gtA side) fall on 64 different banks */
-
-/* four packed bytes from any byte offset of the buffer: records are record_bytes apart, whatever that is modulo 4.  Two aligned
- * loads; the second may reach BED_PAD - 1 bytes behind the last record */
-__device__ __forceinline__ uint32_t bed_word(const uint8_t *__restrict__ bed, size_t off)
-{
-	const uint32_t *w = reinterpret_cast<const uint32_t *>(bed + (off & ~(size_t)3));
-	const unsigned sh = 8u * (unsigned)(off & 3);
-	const uint32_t lo = w[0];
-	return sh ? (lo >> sh) | (w[1] << (32u - sh)) : lo;
-}
-
-/* a tile of BT_L records x BT_I individuals into LDS: the 64 bytes from byte i0 / 4 of the records l0 ... l0 + BT_L - 1 as 16 dwords
- * each, BT_ROW dwords apart; 0 behind the record's last byte and for the records behind the last.  All 256 lanes; the caller syncs. */
-__device__ __forceinline__ void bed_stage_tile(uint32_t *tile, const uint8_t *__restrict__ bed, size_t rb, int L, int l0, int i0)
-{
-	const size_t b0 = (size_t)(i0 / 4);	/* first staged byte of every record */
-	for (int x = threadIdx.x; x < BT_L * 16; x += 256) {
-		const int ll = x / 16, w = x % 16, l = l0 + ll;
-		const size_t off = b0 + 4 * (size_t)w;
-		tile[ll * BT_ROW + w] = (l < L && off < rb) ? bed_word(bed, (size_t)l * rb + off) : 0u;
-	}
-}
-
 constexpr long long QUIET_NAN_BITS = 0x7FF8000000000000ll;	/* the NaN of a pair without a value (k_ld_r2, k_king_phi) */
 
 /* locus pass: ua[l] as the STRUCTURE reader counts it, a1[l] = 1 when allele A1 is observed at locus l (the one thing the recoding
@@ -167,17 +139,6 @@ __global__ __launch_bounds__(256) void k_bed_expand(const uint8_t *__restrict__ 
 		*reinterpret_cast<uint4 *>(gtS + ((size_t)(lfirst / 8) * I + i) * 16) = make_uint4(out[0], out[1], out[2], out[3]);
 	}
 	if (any) seen[i0 + threadIdx.x] = 1;	/* (every writer stores the same value) */
-}
-
-/* what every entry point asks of its records, and how they go up: n_bytes of whole records and BED_PAD zero bytes behind them in a
- * buffer of d_bed's own.  d_bed.p stays null when the buffer does not fit; the return value is the first failure's. */
-static bool bed_shape_ok(int I, int L, const uint8_t *bed, size_t record_bytes) { return I > 0 && L > 0 && bed && record_bytes >= ((size_t)I + 3) / 4; }
-static hipError_t bed_upload(mchip_context *ctx, scoped_dev<uint8_t> &d_bed, const uint8_t *records, size_t n_bytes)
-{
-	hipError_t e = d_bed.alloc(n_bytes + BED_PAD);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_bed.p, records, n_bytes, hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(d_bed.p + n_bytes, 0, BED_PAD, ctx->stream);
-	return e;
 }
 
 /* The packed records go up as they are; the locus pass tells the host the allele counts set_shape sizes the column tables from,
@@ -554,13 +515,6 @@ __global__ __launch_bounds__(256) void k_qc_mask(const uint8_t *__restrict__ kee
 		if (i < I && (!keep || keep[i])) m |= 1ull << (2 * j);
 	}
 	mask[w] = m;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-	return v;
 }
 
 /* var[4 l + c] += the kept individuals of this workgroup's run with code c at variant l.  blockIdx.x = group of QC_VARIANTS

@@ -141,4 +141,30 @@ static inline qc_geometry qc_geometry_of(int I, int L, long long target_blocks)
 	return g;
 }
 
+/* ---- principal components of packed records (k_pca_project, k_pca_expand, k_pca_fold, mchip_pca.hip; tests/pca_util.py restates the
+ * constants) ----
+ * Projection W = Z^T X: a workgroup owns PCA_VARIANTS variants and walks all the individuals, nothing is cut.  Expansion Y = Z W / L':
+ * a workgroup owns PCA_ITILE individuals and one slab of PCA_LSLAB variants; the slabs' partial sums are added in index order.  The
+ * sums are floating point, so unlike the cuts above this one is a CONSTANT of the shape: no target_blocks enters, and no launch knob
+ * can show in any bit of Y. */
+constexpr int PCA_VARIANTS = 64;	/* variants per workgroup of the projection: a wave per 16 */
+constexpr int PCA_ITILE = 64;		/* individuals per workgroup of the expansion: a wave per 16 */
+constexpr int PCA_LSLAB = 4096;		/* variants per slab of the expansion */
+
+struct pca_geometry {
+	int n_vgroups;		/* projection: workgroups along the variants */
+	int n_itiles, Ipad;	/* expansion: workgroups along the individuals, and the rows of a slab's partial sums */
+	int n_slabs;		/*   workgroups along the variants = slabs of partial sums */
+};
+
+static inline pca_geometry pca_geometry_of(int I, int L)
+{
+	pca_geometry g;
+	g.n_vgroups = (int)(((long long)L + PCA_VARIANTS - 1) / PCA_VARIANTS);
+	g.n_itiles = (int)(((long long)I + PCA_ITILE - 1) / PCA_ITILE);
+	g.Ipad = g.n_itiles * PCA_ITILE;
+	g.n_slabs = (int)(((long long)L + PCA_LSLAB - 1) / PCA_LSLAB);
+	return g;
+}
+
 #endif

@@ -60,6 +60,8 @@ def load():
         "mchip_bed_ld_band": ([vp, i32, i32, vp, C.c_size_t, i32, i32, i32, vp], i32),
         "mchip_bed_king": ([vp, i32, i32, vp, C.c_size_t, i32, i32, vp, vp], i32),
         "mchip_bed_qc": ([vp, i32, i32, vp, C.c_size_t, vp, vp, vp, vp], i32),
+        "mchip_bed_pca_apply": ([vp, i32, i32, vp, C.c_size_t, i32, vp, vp, vp, vp, vp, vp], i32),
+        "mchip_bed_pca": ([vp, i32, i32, vp, C.c_size_t, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp], i32),
         "mchip_set_model": ([vp, i32, i32, i32, i32, C.c_double, C.c_double, i32], i32),
         "mchip_set_p": ([vp, i32, vp], i32),
         "mchip_get_p": ([vp, i32, vp], i32),
@@ -140,6 +142,7 @@ ABI_SYMBOLS = [
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
     "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
     "mchip_residual_products", "mchip_describe_plan", "mchip_bed_ld_band", "mchip_bed_king", "mchip_bed_qc",
+    "mchip_bed_pca_apply", "mchip_bed_pca",
 ]
 
 
@@ -249,6 +252,39 @@ class Context:
                                         None if ic is None else ic.ctypes.data, None if vc is None else vc.ctypes.data,
                                         None if hp is None else hp.ctypes.data))
         return ic, vc, hp
+
+    def bed_pca_apply(self, I, bed, x, w=True, scale=True, record_bytes=None, L=None):
+        """mchip_bed_pca_apply: (y [I][n_vec], w [L][n_vec] or None, scale [L][2] or None, L', trace) of the packed records
+        [L][record_bytes] and x [I][n_vec]: Y = Z (Z^T X) / L' with Z the mean-imputed standardised genotypes, W = Z^T X, scale = (mu, inv)
+        of every variant (include/multiclust_hip.h has the definition).  Installs nothing and changes nothing of the context."""
+        bed = np.ascontiguousarray(bed, dtype=np.uint8)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert bed.ndim == 2 and x.ndim == 2 and x.shape[0] == I
+        L = bed.shape[0] if L is None else L
+        rb = bed.shape[1] if record_bytes is None else record_bytes
+        n_vec = x.shape[1]
+        y = np.empty((I, n_vec), dtype=np.float64)
+        wo = np.empty((L, n_vec), dtype=np.float64) if w else None
+        sc = np.empty((L, 2), dtype=np.float64) if scale else None
+        n_used, trace = C.c_int(), C.c_double()
+        self._chk(self.lib.mchip_bed_pca_apply(self.h, I, L, bed.ctypes.data, rb, n_vec, x.ctypes.data, y.ctypes.data,
+                                               wo.ctypes.data if w else None, sc.ctypes.data if scale else None,
+                                               C.byref(n_used), C.byref(trace)))
+        return y, wo, sc, n_used.value, trace.value
+
+    def bed_pca(self, I, bed, n_pc, n_extra=10, max_iter=200, tol=1e-6, record_bytes=None, L=None):
+        """mchip_bed_pca: dict(eigenvalues [n_pc], eigenvectors [I][n_pc], residuals [n_pc], trace, n_used, n_iter) of the packed
+        records [L][record_bytes]: the leading eigenpairs of G = Z Z^T / L' by block subspace iteration
+        (include/multiclust_hip.h, csrc/mchip_pca_algebra.h).  Installs nothing and changes nothing of the context."""
+        bed = np.ascontiguousarray(bed, dtype=np.uint8)
+        assert bed.ndim == 2
+        L = bed.shape[0] if L is None else L
+        rb = bed.shape[1] if record_bytes is None else record_bytes
+        val, vec, res = np.empty(n_pc), np.empty((I, n_pc)), np.empty(n_pc)
+        trace, n_used, n_iter = C.c_double(), C.c_int(), C.c_int()
+        self._chk(self.lib.mchip_bed_pca(self.h, I, L, bed.ctypes.data, rb, n_pc, n_extra, max_iter, tol, val.ctypes.data,
+                                         vec.ctypes.data, res.ctypes.data, C.byref(trace), C.byref(n_used), C.byref(n_iter)))
+        return dict(eigenvalues=val, eigenvectors=vec, residuals=res, trace=trace.value, n_used=n_used.value, n_iter=n_iter.value)
 
     def data_counts(self):
         """(cells with n_ic > 0, non-missing allele copies) of the data set held, counted on the device"""

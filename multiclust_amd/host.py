@@ -130,7 +130,9 @@ class CliOptionsAll(CliOptions):
                 ("king", C.c_int), ("king_t", C.c_double),
                 # --mind, --geno, --maf, --hwe
                 ("mind", C.c_int), ("geno", C.c_int), ("maf", C.c_int), ("hwe", C.c_int), ("mind_t", C.c_double),
-                ("geno_t", C.c_double), ("maf_t", C.c_double), ("hwe_t", C.c_double)]
+                ("geno_t", C.c_double), ("maf_t", C.c_double), ("hwe_t", C.c_double),
+                # --pca, --pca-iter, --pca-tol
+                ("pca", C.c_int), ("pca_iter", C.c_int), ("pca_tol", C.c_double)]
 
 
 class McKingPair(C.Structure):

@@ -65,7 +65,18 @@ typedef struct mc_cli_options {
 	double geno_t;			/* --geno <t>: variants whose missing rate over the individuals kept is > t are removed; 0 <= t < 1 */
 	double maf_t;			/* --maf <t>: variants whose minor-allele frequency over the individuals kept is < t are removed; 0 < t <= 0.5 */
 	double hwe_t;			/* --hwe <t>: variants whose Hardy-Weinberg exact-test p over the individuals kept is < t are removed; 0 < t < 1 */
+	int pca;			/* --pca <n> (extension, mc_pca.c; needs --bed): the n leading principal components of the fileset the filters left; 0 = off, 1 ... MC_PCA_MAX */
+	int pca_iter;			/* --pca-iter <m>: iterations of the subspace iteration at most; default 200 */
+	double pca_tol;			/* --pca-tol <t>: a component has converged when its residual is <= t; 0 < t < 1, default 1e-6 */
 } mc_cli_options;
+
+/* what --pca found (mc_pca.c): the n_pc leading eigenpairs of the matrix of mchip_bed_pca on the I individuals and L variants held, L' =
+ * n_used of them polymorphic: eigenvalues [n_pc], eigenvectors [I][n_pc], residuals [n_pc], the trace of the matrix, the iterations run */
+typedef struct mc_pca_result {
+	int n_pc, I, L, n_used, n_iter;
+	double trace;
+	double *eigenvalues, *eigenvectors, *residuals;
+} mc_pca_result;
 
 /* what quality control (mc_qc.c) found in a fileset of I individuals and L variants: ind_counts [I][4] over all variants, ind_keep [I];
  * var_counts [L][4] and hwe_p [L] over the kept individuals (mchip_bed_qc), var_reason [L] = why a variant went */
@@ -321,6 +332,23 @@ void mc_qc_variants(const mc_cli_options *opt, int L, const uint32_t *var_counts
 int mc_qc_data(const mc_cli_options *opt, mc_cli_data *dat);
 void mc_qc_line(FILE *fp, const mc_cli_options *opt, const mc_cli_data *dat);
 int mc_write_qc_lists(const mc_cli_options *opt, const mc_cli_data *dat);
+
+/* --pca, --pca-iter, --pca-tol (extensions, mc_pca.c; the matrix is defined in include/multiclust_hip.h, the iteration in
+ * csrc/mchip_pca_algebra.h).  MC_PCA_EXTRA start vectors run beside the n asked for.
+ * mc_pca_data: the opt->pca leading components of the data set as the filters left it, with device opt->device; the data set is not
+ * changed.  More components than I - 1 end the run: it says so, naming the option, and returns MC_EXIT_INVALID_USER_SETUP.  Not
+ * converging is no error.  On success the caller owns the arrays (mc_pca_result_free).  Returns 0 or a status.
+ * mc_pca_line: the stdout line "PCA: <n> components of <I> individuals x <L'> of <L> variants (<it> iterations, largest residual <r>):
+ * variance explained <lambda_1 / trace> ...".
+ * mc_pca_warn: when a residual exceeds opt->pca_tol, one line naming those components; returns their number.
+ * mc_write_pca: <stem>.eigenvec, <stem>.eigenval and <stem>.pca.txt (the formats are at the function). */
+#define MC_PCA_MAX 48
+#define MC_PCA_EXTRA 10
+int mc_pca_data(const mc_cli_options *opt, const mc_cli_data *dat, mc_pca_result *r);
+void mc_pca_result_free(mc_pca_result *r);
+void mc_pca_line(FILE *fp, const mc_pca_result *r);
+int mc_pca_warn(FILE *fp, const mc_cli_options *opt, const mc_pca_result *r);
+int mc_write_pca(const mc_cli_options *opt, const mc_cli_data *dat, const mc_pca_result *r);
 
 #include "mc_filter.h"
 

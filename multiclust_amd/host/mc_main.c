@@ -22,6 +22,8 @@
  * --mind / --geno / --maf / --hwe <t> remove individuals by missing rate and variants by missing rate, minor-allele frequency and Hardy-Weinberg
  * exact test from a fileset (--bed) on the device before anything is fitted, and before --prune and --king-cutoff (mc_qc.c; one more stdout line
  * and up to six more files; the run is the run on the fileset of the individuals and variants kept; without them nothing changes);
+ * --pca <n> reports the n leading principal components of a fileset (--bed) as the filters left it, computed on the device before anything is
+ * fitted (mc_pca.c; one more stdout line and three more files; no filter: the data set and every fit are unchanged; without it nothing changes);
  * --query <file> keeps the individuals the file marks out of every fit and fits their mixing proportions against the best fit of every K
  * afterwards (one more stdout line per K and one more file; without it nothing changes);
  * --device <n> selects the HIP device; --streams <n> runs n fits at a time per GPU; --gpus <n> shards the initialisations of each K over n GPUs of
@@ -35,7 +37,7 @@
  * data sets builds on mc_refit_* (mc_refit.c), adds its line to post_fit()'s text and its refusals to parse_options' refuse_post_fit().
  * Where a filter of the fileset plugs in: pre_fit() runs them between the reader and the first fit, quality control, then --prune, then
  * --king-cutoff, each on what the one before left; a new one (--keep, --extract, ...) is a unit like mc_ld.c on mc_filter.h and mc_files.h, and
- * one more block there.
+ * one more block there.  --pca is the last block: it reads what the filters left and changes nothing.
  */
 #include "mc_cli.h"
 
@@ -118,7 +120,16 @@ static void usage(FILE *fp, const char *prog)
 		"                rules from one set of counts, a variant's reason being the first rule it fails (geno, maf, hwe); all variants and\n"
 		"                individuals count (no chromosome is special); one more line 'Quality control: ...', the ids kept and removed in\n"
 		"                <stem>.mind.in / .mind.out and <stem>.qc.in / .qc.out, and the counts, rates and p values of every variant and\n"
-		"                individual of the file in <stem>.qc.var.txt / .qc.ind.txt; the run is the run on the fileset of those kept; need --bed\n", prog);
+		"                individual of the file in <stem>.qc.var.txt / .qc.ind.txt; the run is the run on the fileset of those kept; need --bed\n"
+		"  --pca <n>     the n leading principal components (1..48) of --bed as the filters above left it, on the device, before anything is\n"
+		"                fitted; no filter: the data set and every fit stay as they are.  The matrix is Z Z'/L' of the genotypes standardised\n"
+		"                per variant, missing calls imputed by the mean, monomorphic and all-missing variants left out (flashpca's and PLINK\n"
+		"                2's --pca approx; NOT PLINK 1.9's pairwise-complete GRM, not smartpca's normalisation), by block subspace iteration\n"
+		"                with n + 10 vectors; one more line 'PCA: ...', <stem>.eigenvec (FID IID PC1..PCn, no header), <stem>.eigenval and\n"
+		"                <stem>.pca.txt (eigenvalue, share of the trace, residual, converged 0/1).  A component converges at the rate\n"
+		"                lambda_{b+1}/lambda_c per iteration: components inside the noise bulk of the spectrum converge slowly and mean\n"
+		"                nothing; those still loose are named in a warning on stderr, the exit status is unchanged; needs --bed\n"
+		"                --pca-iter <m>  iterations at most (200)        --pca-tol <t>  residual a component has converged at, 0 < t < 1 (1e-6)\n", prog);
 }
 
 static int arg_int(int argc, const char **argv, int i, long *out)
@@ -155,6 +166,8 @@ static void defaults(mc_cli_options *o)
 	o->n_streams = 1;
 	o->se_block = 1;
 	o->prune_window = 50;
+	o->pca_iter = 200;
+	o->pca_tol = 1e-6;
 }
 
 #define BAD(msg) do { fprintf(stderr, "ERROR [mc_main.c::parse_options]: %s (argument '%s'); try -h\n", msg, i < argc ? argv[i] : ""); return MC_EXIT_INVALID_CMD_ARGUMENT; } while (0)
@@ -251,6 +264,9 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 		case 'n': if (arg_int(argc, argv, ++i, &v)) BAD("-n"); o->n_init = (int)v; if (!v) o->n_repeat = 0; break;
 		case 'o': if (++i >= argc) BAD("-o"); o->outfile_name = argv[i]; break;
 		case 'p':
+			if (!strcmp(argv[i], "--pca")) { if (arg_int(argc, argv, ++i, &v)) BAD("--pca"); o->pca = (int)(v < 1 ? -1 : v > 1000000 ? 1000000 : v); break; }	/* (in full, like --prune) */
+			if (!strcmp(argv[i], "--pca-iter")) { if (arg_int(argc, argv, ++i, &v) || v < 1 || v > 2147483647L) BAD("--pca-iter"); o->pca_iter = (int)v; break; }
+			if (!strcmp(argv[i], "--pca-tol")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--pca-tol"); o->pca_tol = d; break; }
 			if (!strcmp(argv[i], "--prune")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--prune"); o->prune = 1; o->prune_t = d; break; }	/* (in full: --pr... is --projection) */
 			if (!strcmp(argv[i], "--prune-window")) { if (arg_int(argc, argv, ++i, &v)) BAD("--prune-window"); o->prune_window_given = 1; o->prune_window = (int)(v < -1 ? -1 : v > 1000000 ? 1000000 : v); break; }
 			if (!strncmp(w, "pr", 2)) o->em.do_projection = 0;
@@ -355,6 +371,9 @@ static int parse_options(mc_cli_options *o, int argc, const char **argv)
 			!(o->maf_t > 0 && o->maf_t <= 0.5) ? "the minor-allele frequency of --maf must lie in (0, 0.5]" : NULL))) return rc;
 	if (o->hwe && (rc = refuse("--hwe", !o->bed_prefix ? "--hwe needs a PLINK fileset (--bed)" :
 			!(o->hwe_t > 0 && o->hwe_t < 1) ? "the p value of --hwe must lie in (0, 1)" : NULL))) return rc;
+	if (o->pca && (rc = refuse("--pca", !o->bed_prefix ? "--pca needs a PLINK fileset (--bed)" :
+			o->pca < 1 || o->pca > MC_PCA_MAX ? "the number of components of --pca must lie in 1 ... 48" :
+			!(o->pca_tol > 0 && o->pca_tol < 1) ? "the tolerance of --pca-tol must lie in (0, 1)" : NULL))) return rc;
 	if (o->bed_prefix) {	/* extension: a PLINK fileset is the data file; its name in the output is <prefix>.bed */
 		if (o->filename || o->R_format || o->ploidy != 2) {
 			fprintf(stderr, "ERROR [mc_main.c::parse_options]: --bed reads a diploid PLINK fileset: it cannot be combined with -f, -R or a ploidy (-p) other than 2.\n");
@@ -1032,7 +1051,8 @@ DONE:
 
 /* ---- the pre-fit stage: the filters of a fileset, quality control (--mind, --geno, --maf, --hwe), then --prune, then --king-cutoff, each
  * on what the one before left, each with its stdout line -- "of <n>" is what the filter itself saw -- and, with result files on, its
- * lists.  The data set is the filtered one from here on; the lists say what of the fileset it holds. ---- */
+ * lists.  The data set is the filtered one from here on; the lists say what of the fileset it holds.  --pca comes last and only
+ * reads that data set: its line and, with result files on, its three files. ---- */
 static int pre_fit(const mc_cli_options *o, mc_cli_data *d)
 {
 	int rc;
@@ -1055,6 +1075,16 @@ static int pre_fit(const mc_cli_options *o, mc_cli_data *d)
 		if ((rc = mc_king_data(o, d))) return rc;
 		printf("Relatedness: kept %d of %d individuals (KING-robust kinship > %g: %zu pairs)\n", d->I, I_seen, o->king_t, d->n_king_pairs);
 		if (o->write_files && (rc = mc_write_king_lists(o, d))) return rc;
+	}
+	if (o->pca) {	/* no filter: it reads what is left and changes nothing */
+		mc_pca_result r;
+		mchip_progress_note("mc_pca_data");
+		if ((rc = mc_pca_data(o, d, &r))) return rc;
+		mc_pca_line(stdout, &r);
+		mc_pca_warn(stderr, o, &r);
+		if (o->write_files) rc = mc_write_pca(o, d, &r);
+		mc_pca_result_free(&r);
+		if (rc) return rc;
 	}
 	return 0;
 }
