@@ -26,7 +26,7 @@ $(OBJ)/mchip_k%.o: multiclust_amd/csrc/mchip_kernels_k.hip multiclust_amd/csrc/m
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_K=$* -c $< -o $@
 
 # the K-independent units: a new one costs one word here
-HIPUNITS = mchip mchip_comm mchip_bed mchip_cv mchip_generators mchip_query mchip_resample mchip_impute mchip_divergence mchip_residuals mchip_pca
+HIPUNITS = mchip mchip_plan mchip_em mchip_accel mchip_init mchip_profile mchip_comm mchip_bed mchip_cv mchip_generators mchip_query mchip_resample mchip_impute mchip_divergence mchip_residuals mchip_pca
 HIPOBJ   = $(HIPUNITS:%=$(OBJ)/%.o)
 HIPHDRS  = $(wildcard multiclust_amd/csrc/*.h) include/multiclust_hip.h
 $(OBJ)/%.o: multiclust_amd/csrc/%.hip $(HIPHDRS)
@@ -65,14 +65,15 @@ exp-scatter: $(LIB)/libmulticlust_hip.so
 
 # diagnosis behind profiles/r03_k52_spill.md: the K = 52 kernels with one lane per individual (MCHIP_FORCE_SPLIT1: the instance
 # that returned -inf / NaN before the lane split) built with hipcc's default VGPR->AGPR spilling and with KFLAGS, each linked
-# with a matching mchip.o into a library of its own; scripts/diag/k52_spill.sh runs both through MCHIP_LIB_PATH
+# with a matching mchip_plan.o (the macro reaches host code through model_geometry alone) into a library of its own;
+# scripts/diag/k52_spill.sh runs both through MCHIP_LIB_PATH
 exp-k52: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_FORCE_SPLIT1 -c multiclust_amd/csrc/mchip.hip -o build/exp/mchip_split1.o
+	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_FORCE_SPLIT1 -c multiclust_amd/csrc/mchip_plan.hip -o build/exp/mchip_plan_split1.o
 	$(HIPCC) $(HIPFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k52_agpr.o
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k52_scratch.o
 	for v in agpr scratch; do $(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_k52$$v.so \
-		build/exp/mchip_split1.o $(filter-out $(OBJ)/mchip.o,$(HIPOBJ)) $(filter-out $(OBJ)/mchip_k52.o,$(KOBJ)) build/exp/mchip_k52_$$v.o -ldl; done
+		build/exp/mchip_plan_split1.o $(filter-out $(OBJ)/mchip_plan.o,$(HIPOBJ)) $(filter-out $(OBJ)/mchip_k52.o,$(KOBJ)) build/exp/mchip_k52_$$v.o -ldl; done
 
 # A/B builds of the K = 8 kernels: `make exp-k8 EXPNAME=w5 EXPFLAGS=-DMCHIP_SPARSE_WAVES=5` -> scripts/exp/libmulticlust_hip_w5.so
 # (the K = 8 object rebuilt with EXPFLAGS, everything else the product's); scripts/diag/ab.sh times variants against the shipped

@@ -1,7 +1,9 @@
 /*
- * mchip_context.h -- the per-context state of libmulticlust_hip.so and the few helpers of mchip.hip that the units holding a
- * data-set feature's kernels and entry points call (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_generators.hip, mchip_impute.hip, mchip_pca.hip, mchip_query.hip, mchip_resample.hip, mchip_residuals.hip).
- * Private to the library's host-side units; not part of the C-ABI, and mchip_kernels_k.hip does not include it.
+ * mchip_context.h -- the per-context state of libmulticlust_hip.so and what its host-side units call of one another: the units of
+ * the core (mchip.hip the context, the install path and the model; mchip_plan.hip geometry and plan; mchip_em.hip the EM step;
+ * mchip_accel.hip; mchip_init.hip; mchip_profile.hip) and the units holding a data-set feature's kernels and entry points
+ * (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_generators.hip, mchip_impute.hip, mchip_pca.hip, mchip_query.hip, mchip_resample.hip, mchip_residuals.hip).
+ * Private to those units; not part of the C-ABI, and mchip_kernels_k.hip does not include it.
  */
 #ifndef MCHIP_CONTEXT_H
 #define MCHIP_CONTEXT_H
@@ -35,12 +37,19 @@ struct mchip_knobs {
 	double slab_frac;
 };
 
-/* launch geometry of a model on a data set (mchip.hip: model_geometry) */
+/* launch geometry of a model on a data set (mchip_plan.hip: model_geometry) */
 struct mchip_geometry {
 	int ichunk, n_ichunks, lchunk, n_lchunks, n_llpart, flush_blocks, safe_rcp, sparse;
 	int ind_waves;			/* waves per workgroup of the cooperating individual-side kernels (mchip_internal.h) */
 	int xcd_rows;			/* their slab rows come in whole groups of eight: one row, one XCD */
 };
+
+/* what a data set's shape is to the launch geometry and the plan */
+struct mchip_shape { int I, L, T, ploidy, min_M, max_M, count_bits; };
+
+/* the finalisers behind an E step's passes: both in one launch (k_finalize_qp: an M step with individual mixing proportions whose P
+ * side takes the tiled form), or k_finalize_q and the P side's, the latter behind k_sum_slabs where the column pass left many slabs */
+struct estep_finish { int p_loci; bool slab_sum, fused; };
 
 /* The small results of the device code, one allocation per context (d_scalars): every field has one use and shares storage with
  * no other, so which launch runs before which decides nothing here.  Kernels are handed the record or &rec->field. */
@@ -163,7 +172,7 @@ struct mchip_context {
 	std::vector<hipEvent_t> ev_pool;
 	std::vector<int> ev_kind;	/* kernel kind of pair p = events 2p, 2p+1 */
 	size_t ev_used;
-	/* profiled paired E steps (k_estep_pair; mchip.hip: k_pair_spans): two clock readings per block of the latest such launch, and
+	/* profiled paired E steps (k_estep_pair; mchip_profile.hip: k_pair_spans): two clock readings per block of the latest such launch, and
 	 * one span per launch since mchip_profile_begin, in allocations of a fixed number of spans */
 	unsigned long long *d_pair_marks;
 	size_t pair_marks_cap;		/* blocks d_pair_marks has room for */
@@ -291,9 +300,15 @@ static hipError_t bed_upload(mchip_context *ctx, scoped_dev<uint8_t> &d_bed, con
 	return e;
 }
 
-/* ---- what the feature units call; defined in mchip.hip unless noted, never exported from the library ---- */
+/* ---- what the units call of one another, never exported from the library; first mchip.hip's ---- */
 #pragma GCC visibility push(hidden)
 
+/* the testing / tuning knobs as the environment has them now */
+void read_knobs(mchip_knobs *knob);
+/* raw [I][L][pl] -> gtA, gtS, validated against ua or, without one, `limit`; flags land in *bad; nonzero: too large for the kernel */
+int launch_relayout(hipStream_t stream, const uint8_t *raw, int I, int L, int pl, const int32_t *ua, int limit, uint8_t *gtA, uint8_t *gtS, int *bad);
+/* the model's K*T doubles from host order [K][T] to device order [T][K] (to_tk) or back */
+void launch_transpose(mchip_context *ctx, const double *src, double *dst, bool to_tk);
 int check_slot(mchip_context *ctx, int slot);
 void free_model(mchip_context *ctx);
 /* free_data and set_shape drop both saved sets with the data set that goes, unless told to keep the base of the selections */
@@ -322,15 +337,62 @@ int install_derived(mchip_context *ctx, const std::function<void(uint8_t *d_out,
 int stream_buffer(mchip_context *ctx);
 /* genotype held on the device as [I][L][ploidy] bytes -> the kernels' layouts (validated), packed counts */
 int install_raw(mchip_context *ctx, const uint8_t *d_raw);
+
+/* mchip_plan.hip: host arithmetic alone */
+/* bits per packed allele count of the column pass's second genotype layout (gtC), 0 = none */
+int count_bits_for(int ploidy, const mchip_knobs &kn);
+mchip_shape shape_of(const mchip_context *ctx);
+/* a function of the shape, the model, the knobs and the device's CU count alone: it touches neither the device nor a context */
+mchip_geometry model_geometry(const mchip_shape &sh, int K, int admixture, int do_projection, double p_lb, const mchip_knobs &kn, int n_cu);
+/* the arguments of a pass over the installed data set that reads parameter slot `slot` */
+mchip_pass_args pass_args(mchip_context *ctx, int slot);
+/* the plan of these arguments, less what the knobs switch off */
+mchip_plan plan_for(const mchip_ktable *kt, const mchip_pass_args &a, const mchip_knobs &kn);
+estep_finish finish_for(const mchip_plan &p, int K, int max_M, bool indiv, int do_mstep, const mchip_knobs &kn);
+/* loci per block of k_finalize_p_tile for this data set and K, or 0 where a locus can outgrow the tile (k_finalize_p then) */
+int finalize_p_loci(int K, int max_M);
+/* partial log likelihoods k_mix_finalize leaves; whether the projection of P keeps its "fixed" flags in d_flags (above 64 alleles) */
+int mix_ll_parts(int I);
+bool needs_byte_flags(int max_M);
+
+/* mchip_em.hip */
+/* out[0 .. count) = the `count` doubles of d_scalars from `field` on, after a wait for the stream; a null out: nothing happens */
+int fetch_scalars(mchip_context *ctx, const double *field, int count, double *out);
+/* an E step on slot `from`, with do_mstep the M step into slot `to`; defer_ll: the caller's stop_check adds the partial log
+ * likelihoods up; run_mixture is the mixture model's (mode 1: logL_mixture alone), *ll the field of d_scalars that receives it */
+int run_estep(mchip_context *ctx, int from, int to, int do_mstep, const int *stop = nullptr, const int *skip_ind = nullptr, bool defer_ll = false);
+int run_mixture(mchip_context *ctx, int from, int to, int do_mstep, int mode, const int *stop = nullptr, double *ll = nullptr, bool defer_ll = false);
+/* one pass that takes the log likelihood, between the marks of a profiled run; ll given: the partial sums' sum goes there */
+typedef void (*ll_pass_fn)(const mchip_pass_args &a, const mchip_plan &p, hipStream_t s);
+void ll_pass(mchip_context *ctx, int kind, ll_pass_fn launch, const mchip_pass_args &a, const mchip_plan &p, double *ll, const int *stop = nullptr);
+/* the stop rule of the batched loops on the E step that has just run */
+void stop_check(mchip_context *ctx);
+/* whether *exec holds a graph to launch: unless it does already, what enqueue() puts on the stream is captured into it */
+bool captured(mchip_context *ctx, hipGraphExec_t *exec, const std::function<int()> &enqueue);
+/* projection of slot `to` where the model projects */
+int project_slot(mchip_context *ctx, int to, const int *stop = nullptr);
+/* shared eta: eta[to] = normalise(sum_i S_ik + add), projected where the model projects and `project` says so */
+int finalize_shared_eta(mchip_context *ctx, int to, const int *stop = nullptr, double add = 0.0, int project = 1);
+/* P[to] in place from n_slabs slabs of Apart by k_finalize_p itself, unweighted, with the byte flags */
+void launch_finalize_p_untiled(mchip_context *ctx, int n_slabs, int to, double add_lb, int do_projection);
+/* out[0] = in[0] + ... + in[n - 1] in k_reduce_sum's fixed order, one workgroup */
+void launch_reduce_sum(mchip_context *ctx, const double *in, int n, double *out);
+/* out[r] = in[r][0] + ... + in[r][n - 1] for the n_rows rows of in, each as launch_reduce_sum adds it, in one launch */
+void launch_reduce_rows(mchip_context *ctx, const double *in, int n_rows, int n, double *out);
+
+/* mchip_init.hip */
 /* the hard partition: argument checks of its entry points; relayout of a partition held in stream order + M step into slot `to`;
  * normalisation of counts already in Spart and n_aslabs slabs of Apart */
 int check_partition_call(mchip_context *ctx, const void *arg, int to);
 int partition_mstep(mchip_context *ctx, const uint8_t *d_raw, int to, int counts = 0);
 int partition_finalize(mchip_context *ctx, int to, int counts, int n_aslabs);
-/* out[0] = in[0] + ... + in[n - 1] in k_reduce_sum's fixed order, one workgroup */
-void launch_reduce_sum(mchip_context *ctx, const double *in, int n, double *out);
-/* out[r] = in[r][0] + ... + in[r][n - 1] for the n_rows rows of in, each as launch_reduce_sum adds it, in one launch */
-void launch_reduce_rows(mchip_context *ctx, const double *in, int n_rows, int n, double *out);
+
+/* mchip_profile.hip */
+/* an event on the stream in front of (start) or behind a pass of kernel kind `kind`; nothing unless the context is profiling */
+void prof_mark(mchip_context *ctx, int kind, bool start);
+/* room for the next profiled paired launch: its blocks' clock readings (*marks) and its span, which launch_pair_spans fills */
+int pair_profile_slot(mchip_context *ctx, size_t n_blocks, unsigned long long **marks);
+void launch_pair_spans(mchip_context *ctx, const unsigned long long *marks, const mchip_plan &plan);
 
 /* what an entry point that reads a fitted slot asks first: a data set, a model, a slot; admixture_message (NULL: either model
  * will do) refuses the mixture model in the unit's own words */

@@ -18,7 +18,7 @@
  *                same with every lane walking the in-fold loci of its own row, so that the lanes of a wave are busy at different
  *                loci (12.3 ms; 10.5 ms with eight staging loads in flight per thread).  What binds is not established.
  *                Sums: a lane adds its terms in locus order; the workgroup's lanes by block_tree_sum; one partial per workgroup,
- *                k_reduce_sum (mchip.hip) adds the partials.  The two counts are integers: block_add_counts.
+ *                k_reduce_sum (mchip_em.hip) adds the partials.  The two counts are integers: block_add_counts.
  */
 #include "mchip_context.h"
 

@@ -1,12 +1,14 @@
 /*
  * mchip_device_util.h -- the building blocks every device unit shares: LDS row staging at an odd pitch, the fixed summation tree
- * over a workgroup's lanes, integer counts through atomics.  Rule of the library: no floating-point atomics, one fixed order per
+ * over a workgroup's lanes, sums of partials in one fixed order, integer counts through atomics.  Rule of the library: no floating-point atomics, one fixed order per
  * sum, so that the same state gives the same bits; a new unit's kernel is its body plus calls of these.
  */
 #ifndef MCHIP_DEVICE_UTIL_H
 #define MCHIP_DEVICE_UTIL_H
 
 #include <hip/hip_runtime.h>
+
+#define MCHIP_BLOCK 256	/* lanes per workgroup of the library's own kernels */
 
 /* doubles between two LDS rows of K doubles that the lanes of a wave read side by side (lane i its own row: q rows, staged P rows).
  * Lane i reads dwords 2 (pitch i + k) and the next one; with the pitch odd the 32 lanes of a ds_read_b64 lane group fall on 32
@@ -75,6 +77,32 @@ template <int N> __device__ __forceinline__ void block_add_counts(const unsigned
 	if (threadIdx.x == 0)
 		for (int x = 0; x < N; x++)
 			if (cnt[x]) atomicAdd(&global[x], cnt[x]);
+}
+
+/* acc + in[first] + in[first + stride] + ... (count terms, added in that order): the loads of eight terms are issued
+ * together, the additions keep their order, so the result is the plain loop's to the last bit */
+__device__ __forceinline__ double ordered_sum(double acc, const double *__restrict__ in, size_t first, size_t stride, int count)
+{
+	int x = 0;
+	for (; x + 8 <= count; x += 8) {
+		double v[8];
+#pragma unroll
+		for (int y = 0; y < 8; y++) v[y] = in[first + (size_t)(x + y) * stride];
+#pragma unroll
+		for (int y = 0; y < 8; y++) acc += v[y];
+	}
+	for (; x < count; x++) acc += in[first + (size_t)x * stride];
+	return acc;
+}
+
+/* deterministic sum of n doubles by one block (fixed strided order, then a fixed tree); every thread must call it; the result is
+ * valid in thread 0 (and red[] may be reused after the trailing barrier) */
+__device__ __forceinline__ double block_ordered_sum(const double *__restrict__ in, int n, double *red)
+{
+	const double s = (int)threadIdx.x < n ? ordered_sum(0.0, in, threadIdx.x, MCHIP_BLOCK, (n - (int)threadIdx.x + MCHIP_BLOCK - 1) / MCHIP_BLOCK) : 0.0;
+	const double v = block_tree_sum<MCHIP_BLOCK>(red, s);
+	__syncthreads();
+	return v;
 }
 
 #endif

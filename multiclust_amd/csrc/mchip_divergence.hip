@@ -8,7 +8,7 @@
  *                 constant: the chunk, hence the order of every addition, does not depend on the device's compute units -- and
  *                 reads its part of the [T][K] slot once, DIV_STAGE columns at a time into LDS, rows lds_pitch(K) apart.  Thread t
  *                 owns entries t, t + 256, ... (at most DIV_EPT = 9 at K = 64) in registers and walks the staged columns in column
- *                 order; one partial per entry and chunk, stored [entry][chunk]; launch_reduce_rows (mchip.hip) adds each entry's.
+ *                 order; one partial per entry and chunk, stored [entry][chunk]; launch_reduce_rows (mchip_em.hip) adds each entry's.
  *   k_div_loci    runtime K, lane = locus; the weights sit in LDS (every lane reads the same word: a broadcast).  The M_l K doubles
  *                 of a locus are contiguous from toff[l] K.  Per column: pbar = sum_k w_k p_k as an fma chain in k order, HT +=
  *                 pbar (1 - pbar), then the K values of the column once more (they are in the cache) for V += w_k (p_k - pbar)^2:

@@ -15,7 +15,7 @@
  *              memory and stored into the missing positions of the upload-form scratch in copy order; the observed bytes of the
  *              scratch are never written.  c = prod_j j t_mj / ((c_mj + 1) sum_m t_m).
  *              sum_conf: a lane adds its c in locus order; the workgroup's lanes by block_tree_sum; one partial per workgroup,
- *              k_reduce_sum (mchip.hip) adds the partials.  The three counts are integers: block_add_counts.
+ *              k_reduce_sum (mchip_em.hip) adds the partials.  The three counts are integers: block_add_counts.
  *              Not yet timed on a device and not tuned (profiles/impute.txt, scripts/impute_bench.py).
  */
 #include "mchip_context.h"

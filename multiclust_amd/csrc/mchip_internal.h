@@ -22,7 +22,6 @@
 #include "multiclust_hip.h"
 #include "mchip_device_util.h"
 
-#define MCHIP_BLOCK 256
 #define MCHIP_SPARSE_MAX_M 32	/* sparse individual pass is used when no locus has more alleles than this */
 #ifndef MCHIP_QBLOCK
 #define MCHIP_QBLOCK 128	/* individuals per workgroup of the individual-side kernels (lane = individual) */

@@ -1262,7 +1262,7 @@ __global__ __launch_bounds__(64 * MCHIP_IND_WAVES_MAX) void k_individual_sparse_
  * a.skip_ind: the individual blocks return at once (the sums are cached), the column blocks work.
  * marks (profiled runs): overlapping kinds have no event-to-event duration, so each working block leaves its first wave start and
  * last wave end (s_memrealtime) in marks[2 * block], [2 * block + 1]; a block that returned leaves start > end.  One lane stores
- * them after the waves' readings met in LDS; mchip.hip's k_pair_spans takes each kind's minimum and maximum.
+ * them after the waves' readings met in LDS; mchip_profile.hip's k_pair_spans takes each kind's minimum and maximum.
  * Registers (-Rpass-analysis=kernel-resource-usage): the function takes what the S-side body takes and runs at its waves per
  * SIMD -- K = 8: 93 VGPRs, five waves (S-side instance 90-92, column instance 68 and seven waves); K = 12: 123-125, four waves
  * (122-124).  No vector register spills; the column body's scalar registers are all taken (99 at K = 8), so a few of the

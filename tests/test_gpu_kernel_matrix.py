@@ -85,7 +85,7 @@ def ind_waves_for(K, tile_cols):     # mchip_ind_waves (mchip_internal.h)
     return 1
 
 
-def lds_sparse(K, max_M):    # model_geometry's sparse (mchip.hip): two staged tiles of 8 loci fit 64 KiB
+def lds_sparse(K, max_M):    # model_geometry's sparse (mchip_plan.hip): two staged tiles of 8 loci fit 64 KiB
     return max_M <= SPARSE_MAX_M and (2 * 8 * max_M * kp(K) + qblock(K)) * 8 <= 65536
 
 
@@ -93,13 +93,13 @@ def sparse_edge(K):          # the largest max_M that still takes the sparse pas
     return max(m for m in range(1, SPARSE_MAX_M + 1) if lds_sparse(K, m))
 
 
-def count_bits(ploidy, knobs):       # count_bits_for (mchip.hip)
+def count_bits(ploidy, knobs):       # count_bits_for (mchip_plan.hip)
     if "MCHIP_NO_COUNTS" in knobs:
         return 0
     return 2 if ploidy <= 3 else (4 if ploidy <= 15 else 0)
 
 
-def finalize_p_loci(K, max_M):       # finalize_p_loci (mchip.hip)
+def finalize_p_loci(K, max_M):       # finalize_p_loci (mchip_plan.hip)
     if max_M > 64 or max_M < 1:
         return 0
     n = FP_TILE // (max_M * K)
@@ -107,7 +107,7 @@ def finalize_p_loci(K, max_M):       # finalize_p_loci (mchip.hip)
 
 
 def flush_blocks(K, ploidy, projection, p_lb):
-    """(safe_rcp, flush_blocks) of model_geometry (mchip.hip).  The column passes on packed counts take the
+    """(safe_rcp, flush_blocks) of model_geometry (mchip_plan.hip).  The column passes on packed counts take the
     reciprocal per cell where safe_rcp; the individual-side passes and the dense pair wherever flush_blocks < 1 (sparse_instance:
     `safe = a.flush_blocks < 1`), which a lower bound such as 1e-40 gives without safe_rcp."""
     safe = (not projection) or not (p_lb >= 1e-75)
@@ -120,7 +120,7 @@ def flush_blocks(K, ploidy, projection, p_lb):
 
 
 def geometry(K, I, L, T, ploidy, max_M, admixture, cbits, knobs, n_cu=N_CU):
-    """model_geometry (mchip.hip): chunks of either pass, waves of the cooperating sparse pass"""
+    """model_geometry (mchip_plan.hip): chunks of either pass, waves of the cooperating sparse pass"""
     def num(name, dflt):
         v = int(knobs.get(name, "0"))
         return v if v > 0 else dflt
@@ -225,14 +225,14 @@ def reach(case):
     if "MCHIP_FORCE_SAFE" in knobs:
         safe, flush = True, 0
     ind_safe = flush < 1
-    biallelic = min_M == 2 and max_M == 2 and "MCHIP_NO_BIAL" not in knobs      # shape_args (mchip.hip)
+    biallelic = min_M == 2 and max_M == 2 and "MCHIP_NO_BIAL" not in knobs      # shape_args (mchip_plan.hip)
     nomiss = not missing
     out = set()
     p_loci = finalize_p_loci(K, max_M)
     if max_M > 64:
-        out.add("byte_flag_projection")          # k_finalize_p / k_project_p with d_flags (mchip.hip: needs_byte_flags)
+        out.add("byte_flag_projection")          # k_finalize_p / k_project_p with d_flags (mchip_plan.hip: needs_byte_flags)
     if not admixture:
-        # run_mixture (mchip.hip): k_logp, mix_gather, k_mix_finalize, shared eta, mix_column, finalize_p; plan()'s mix_gather, mix_col
+        # run_mixture (mchip_em.hip): k_logp, mix_gather, k_mix_finalize, shared eta, mix_column, finalize_p; plan()'s mix_gather, mix_col
         out.add("k_mix_gather<%d,%s>" % (2 if pl == 2 else 0, B(sparse)))
         out |= {"k_mix_finalize", "finalize_shared_eta"}
         out.add("k_column_counts<%d,true,false>" % cbits if cbits else "k_mix_column<%d>" % (2 if pl == 2 else 0))
@@ -268,7 +268,7 @@ def reach(case):
     pair = "MCHIP_NO_PAIR" not in knobs and pair_available(K, sparse, cbits, pl, g["waves"], safe, ind_safe, biallelic,
                                                            cdiv(T, 64) * n_slabs, cdiv(I, 64) * s_slabs)
     dual = "MCHIP_NO_DUAL" not in knobs and dual_available(K, sparse, ind_safe, pl, biallelic, g["waves"], max_M)
-    # run_estep (mchip.hip) with the M step: the two passes, where the pair exists as one launch that runs the bodies of both
+    # run_estep (mchip_em.hip) with the M step: the two passes, where the pair exists as one launch that runs the bodies of both
     # (mchip_describe_plan lists all three), then the finalisers (finish_for)
     out |= {col, sside}
     if pair:
@@ -283,7 +283,7 @@ def reach(case):
         out.add("k_finalize_p_tile" if p_loci else "k_finalize_p")
     if constrained:
         out.add("finalize_shared_eta")
-    if accel:               # accel_cycle_enqueue (mchip.hip): log L of the second iterate and of the extrapolated point
+    if accel:               # accel_cycle_enqueue (mchip_accel.hip): log L of the second iterate and of the extrapolated point
         out |= {"k_individual_sparse_w<2,true,false,%s,true>" % B(nomiss)} if dual else {ll, sside}
     else:                   # mchip_loglik; mchip_e_step (run_estep without the M step: k_finalize_q); mchip_loglik_prefetch
         out |= {ll, sside, "k_finalize_q"}

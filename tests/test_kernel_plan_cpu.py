@@ -1,6 +1,6 @@
 """The Python dispatch rule of tests/test_gpu_kernel_matrix.py against the library's own kernel selection, without a GPU.
 
-mchip_describe_plan runs the library's launch geometry (model_geometry, mchip.hip) and the plan of the K's translation unit
+mchip_describe_plan runs the library's launch geometry (model_geometry, mchip_plan.hip) and the plan of the K's translation unit
 (plan(), mchip_kernels_k.hip) for a query and prints the kernel instances and the geometry facts.  For every case of the GPU
 matrix and every configuration of its coverage grid, at every K:
 

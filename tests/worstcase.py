@@ -4,7 +4,7 @@ The rest of the suite draws Q and P from Dirichlet(1): every t = sum_k q_k p_k a
 numerical contracts of DESIGN.md section 4.2 are never near their limits:
 
   * the running-product log likelihood is looked at every `flush_blocks` units of 16 multiplications, an interval the host
-    sizes (model_geometry, mchip.hip) so that a product that starts above 1e-100 stays above 1e-300;
+    sizes (model_geometry, mchip_plan.hip) so that a product that starts above 1e-100 stays above 1e-300;
   * shared reciprocals (rcp4, rcp_group, the pair and the tetraploid four of the individual side, k_individual_bial's
     rcp_full(t0 t1)) are allowed down to a bound of 1e-75.
 
@@ -64,7 +64,7 @@ WORST_ROW_EVERY, WORST_COL_EVERY, VERTEX_EVERY = 5, 4, 5       # worst rows 0, 5
 
 # ------------------------------------------------------------------------------------------------------------ the host's sizing
 def host_flush_blocks(K, p_lb, ploidy=2, projection=True):
-    """model_geometry (mchip.hip), the block behind "log-product check interval":
+    """model_geometry (mchip_plan.hip), the block behind "log-product check interval":
         tmin = p_lb / K;  mults = floor(200.0 / -log10(tmin));  blocks = (int)(mults / (ploidy == 4 ? 16.0 : 8.0 * ploidy));
         safe_rcp = !do_projection || !(p_lb >= 1e-75);  if (safe_rcp) flush_blocks = 0
     Returns (safe_rcp, flush_blocks)."""
