@@ -37,15 +37,20 @@ $(LIB)/libmulticlust_hip.so: $(HIPOBJ) $(KOBJ)
 	@mkdir -p $(LIB)
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o $@ $^ -ldl
 
-HOST_SRC = $(filter-out multiclust_amd/host/mc_main.c,$(wildcard multiclust_amd/host/*.c))
-$(LIB)/libmulticlust_host.so: $(HOST_SRC) $(wildcard multiclust_amd/host/*.h) include/multiclust_hip.h $(LIB)/libmulticlust_hip.so
+# the units of the command line (mc_main.c and every mc_cli_<unit>.c: a new one costs its file) go into the binary, every other
+# unit of host/ into the library
+HOST_ALL = $(wildcard multiclust_amd/host/*.c)
+CLI_SRC  = $(filter multiclust_amd/host/mc_main.c multiclust_amd/host/mc_cli_%.c,$(HOST_ALL))
+HOST_SRC = $(filter-out $(CLI_SRC),$(HOST_ALL))
+HOST_HDR = $(wildcard multiclust_amd/host/*.h) include/multiclust_hip.h
+$(LIB)/libmulticlust_host.so: $(HOST_SRC) $(HOST_HDR) $(LIB)/libmulticlust_hip.so
 	@mkdir -p $(LIB)
 	$(CC) $(CFLAGS) -Imulticlust_amd/host -shared -o $@ $(HOST_SRC) -L$(LIB) -lmulticlust_hip -Wl,-rpath,'$$ORIGIN' -lm -lpthread
 
 # the drop-in command line (same flags, reader and output files as the reference's `multiclust`)
-$(BIN)/multiclust: multiclust_amd/host/mc_main.c $(LIB)/libmulticlust_host.so
+$(BIN)/multiclust: $(CLI_SRC) $(HOST_HDR) $(LIB)/libmulticlust_host.so
 	@mkdir -p $(BIN)
-	$(CC) $(CFLAGS) -Imulticlust_amd/host -o $@ $< -L$(LIB) -lmulticlust_host -lmulticlust_hip -Wl,-rpath,'$$ORIGIN/../lib' -lm -lpthread
+	$(CC) $(CFLAGS) -Imulticlust_amd/host -o $@ $(CLI_SRC) -L$(LIB) -lmulticlust_host -lmulticlust_hip -Wl,-rpath,'$$ORIGIN/../lib' -lm -lpthread
 
 oracle: $(LIB)/libmulticlust_host.so
 	$(MAKE) -C oracle all

@@ -121,7 +121,7 @@ class CliOptions(C.Structure):
 
 class CliOptionsAll(CliOptions):
     """the whole of mc_cli_options: what the readers and writers are handed, since mc_read_bed reads the last fields"""
-    _fields_ = [  # the command line's --cv, --se, --query, --fill, --fst and --resid: only mc_main.c reads them
+    _fields_ = [  # the command line's --cv, --se, --query, --fill, --fst and --resid: only the binary (mc_main.c, mc_cli_*.c) reads them
                 ("cv_folds", C.c_int), ("cv_floor", C.c_double), ("se_replicates", C.c_int), ("se_block", C.c_int),
                 ("query_file", C.c_char_p), ("fill", C.c_int), ("fst", C.c_int), ("resid", C.c_int),
                 # --prune / --prune-window

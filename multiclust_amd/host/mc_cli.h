@@ -237,7 +237,7 @@ int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const
  * in the header comment of mc_resid.c.  Returns 0 or an exit status of the enum above. */
 int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r);
 
-/* ---- what the filters of a fileset that run before the fit share (mc_filter.h, included at the end of this file); pre_fit() of mc_main.c runs them.
+/* ---- what the filters of a fileset that run before the fit share (mc_filter.h, included at the end of this file); pre_fit() of mc_cli_stages.c runs them.
  * mc_filter_on_device: opens device opt->device, calls decide(opt, &dev, out) -- dev is what a band callback on the device needs --
  * and closes it; the lines "ERROR [<origin>]: cannot open device .. for <option>" and "ERROR [<origin>]: <noun> failed (status ..):
  * <the device's last error>" are its.  Returns 0 or the status.

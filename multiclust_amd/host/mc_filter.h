@@ -2,7 +2,7 @@
  * mc_filter.h -- what the filters of a fileset that run before the fit (--prune, mc_ld.c; --king-cutoff, mc_king.c) have in common
  * (mc_cli.h, which includes this file at its end, says what each function does): the device opened around the part that asks it
  * for a band, the reader's summary made anew once the records have changed, and the per-individual fields made anew for the individuals kept.  A new filter writes its rule and its compaction,
- * calls these two, and is run by pre_fit() of mc_main.c.  static inline, as mc_files.h is and for the same reason; beside libc they
+ * calls these two, and is run by pre_fit() of mc_cli_stages.c.  static inline, as mc_files.h is and for the same reason; beside libc they
  * call mchip_create / mchip_destroy / mchip_last_error and mc_bed_summarize (mc_bed.c): the drivers under tests/ stub those.
  */
 #ifndef MC_FILTER_H

@@ -1,6 +1,6 @@
 /*
  * mc_pca.c -- --pca <n> (an extension): the leading principal components of a PLINK fileset, the companion of every Q plot and the
- * usual cross-check on the choice of K.  It runs as the last stage of pre_fit() (mc_main.c), on the fileset quality control, --prune
+ * usual cross-check on the choice of K.  It runs as the last stage of pre_fit() (mc_cli_stages.c), on the fileset quality control, --prune
  * and --king-cutoff left, and it is no filter: the data set is unchanged and every fit afterwards is the same, byte for byte.
  *
  * The matrix is defined in include/multiclust_hip.h (mchip_bed_pca): G = Z Z^T / L' with Z the genotypes standardised per variant by

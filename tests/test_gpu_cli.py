@@ -147,6 +147,42 @@ def test_cli_bootstrap_device_host_and_sharded_agree(tmp_path, monkeypatch):
     assert outs[0] == outs[2], outs
 
 
+def test_cli_bootstrap_with_partition_agrees_on_every_route(tmp_path, monkeypatch):
+    """-b with -A and result files on: the bootstrap fits are not partitioned, so what a K's best record must hold differs between
+    the observed data and the replicates, and the serial and the sharded routes decide it by one rule.  The serial run, the forced
+    sharded route on one device, --streams 2 (whole replicates per worker) and --streams 3 (more workers than replicates: the
+    replicates run in turn, the initialisations of each fit sharded) print the same lines and write the same files."""
+    stru = os.path.join(GOLD, "data", "multi.stru")
+    individuals = (sum(1 for ln in open(stru) if ln.strip()) - 1) // 2       # one header line, two lines per diploid individual
+    partition = tmp_path / "partition.txt"
+    partition.write_text(" ".join(str(i % 3 + 1) for i in range(individuals)) + "\n")
+    monkeypatch.delenv("MC_HOST_BOOTSTRAP", raising=False)
+    monkeypatch.setenv("MC_TRACE_EXCHANGE", "1")
+    runs = {}
+    for route, extra in (("serial", []), ("forced", ["--gpus", "1"]), ("streams2", ["--streams", "2"]), ("streams3", ["--streams", "3"])):
+        monkeypatch.delenv("MC_FORCE_SHARDED", raising=False)
+        if route == "forced":
+            monkeypatch.setenv("MC_FORCE_SHARDED", "1")
+        out = tmp_path / route
+        out.mkdir()
+        cmd = [BIN, "-f", stru, "-a", "-k", "3", "-n", "2", "-b", "2", "-r", "9", "-s", "3", "-A", str(partition), "-o", "stem",
+               "-d", os.path.join(str(out), "")]
+        res = run_program(cmd + extra, cwd=str(out), timeout=600)
+        assert res.returncode == 0, res.stderr
+        trace = [l for l in res.stderr.split("\n") if l.startswith("exchange: RCCL")]
+        assert (len(trace) > 0) == (route == "forced"), res.stderr
+        files = {f: open(os.path.join(str(out), f), "rb").read() for f in sorted(os.listdir(str(out)))}
+        runs[route] = (CLOCK.sub("HH:MM:SS", res.stdout), files)
+    text, files = runs["serial"]
+    assert text.count("Bootstrap dataset") == 2 and "p-value to reject H0: K=2" in text and " ND " not in text
+    assert len(files) >= 5
+    for route in ("forced", "streams2", "streams3"):
+        assert runs[route][0] == text, route
+        assert sorted(runs[route][1]) == sorted(files), route
+        for f in files:
+            assert runs[route][1][f] == files[f], (route, f)
+
+
 @pytest.mark.parametrize("case,streams", [("multi_admix_k4", 1), ("tetra_admix_k3", 1), ("multi_admix_k4", 3)])
 def test_cli_sharded_path_on_one_gpu_reproduces_serial_reference(case, streams, tmp_path, monkeypatch):
     """The --gpus machinery (host thread per device, unit = initialisation, rand() jump-ahead, RCCL all-reduce of the

@@ -1,4 +1,4 @@
-"""No GPU: what the command line refuses of --pca, --pca-iter and --pca-tol before anything is read (multiclust_amd/host/mc_main.c),
+"""No GPU: what the command line refuses of --pca, --pca-iter and --pca-tol before anything is read (multiclust_amd/host/mc_cli_options.c),
 and what the usage text says about the option."""
 import os
 
