@@ -21,12 +21,13 @@ all: $(LIB)/libmulticlust_hip.so $(LIB)/libmulticlust_host.so $(BIN)/multiclust 
 # With the flag tuples spill to scratch whole.  Only kernels that use the whole register file spill (K > 20); applied to every
 # translation unit all the same.  Reproducer: `make exp-k52`, scripts/diag/k52_spill.sh.
 KFLAGS = -mllvm -amdgpu-spill-vgpr-to-agpr=false
-$(OBJ)/mchip_k%.o: multiclust_amd/csrc/mchip_kernels_k.hip multiclust_amd/csrc/mchip_internal.h multiclust_amd/csrc/mchip_device_util.h multiclust_amd/csrc/mchip_finalize.h include/multiclust_hip.h
+# (a static pattern rule, for the objects of KS alone: a unit whose name begins with mchip_k, as mchip_kinship, takes the rule below)
+$(KOBJ): $(OBJ)/mchip_k%.o: multiclust_amd/csrc/mchip_kernels_k.hip multiclust_amd/csrc/mchip_internal.h multiclust_amd/csrc/mchip_device_util.h multiclust_amd/csrc/mchip_finalize.h include/multiclust_hip.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_K=$* -c $< -o $@
 
 # the K-independent units: a new one costs one word here
-HIPUNITS = mchip mchip_plan mchip_em mchip_accel mchip_init mchip_profile mchip_comm mchip_bed mchip_cv mchip_generators mchip_query mchip_resample mchip_impute mchip_divergence mchip_residuals mchip_pca
+HIPUNITS = mchip mchip_plan mchip_em mchip_accel mchip_init mchip_profile mchip_comm mchip_bed mchip_cv mchip_generators mchip_query mchip_resample mchip_impute mchip_divergence mchip_residuals mchip_kinship mchip_pca
 HIPOBJ   = $(HIPUNITS:%=$(OBJ)/%.o)
 HIPHDRS  = $(wildcard multiclust_amd/csrc/*.h) include/multiclust_hip.h
 $(OBJ)/%.o: multiclust_amd/csrc/%.hip $(HIPHDRS)

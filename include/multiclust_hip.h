@@ -559,6 +559,44 @@ int mchip_divergence(mchip_context *ctx, int slot, const double *weights /* [K] 
  */
 int mchip_residual_products(mchip_context *ctx, int slot, double *gram /* [I][I] */, double *norms /* [I][I] or NULL */);
 
+/* ---- kinship between individuals under the fitted admixture model (an extension: REAP's estimator, Thornton et al. 2012,
+ * "Estimating kinship in recently admixed populations"; PC-Relate has the same form) ----
+ * The admixture model with individual or shared mixing proportions, the parameters of `slot`, the INSTALLED data set (under a
+ * cross-validation hold-out the hidden copies are missing copies like any other), ALL uniquealleles[l] columns of every locus, the
+ * phantom slot included.  a_il, n_ic, t_ic and r_ic are those of mchip_residual_products above, double for double: t_ic the fma
+ * chain in k order, r_ic = fma(-a_il, t_ic, n_ic), 0 where a_il = 0.  New here:
+ *   v_ic    = t_ic * fmax(1 - t_ic, 0): the variance of one copy's indicator; a chain that rounds to 1 + ulp gives 0, never a NaN;
+ *   w_ic    = a_il * sqrt(v_ic); 0 where a_il = 0.
+ * Returned are the sums; the caller forms phi_ij = G_ij / V_ij, NaN where V_ij = 0 (an individual without an observed copy, a query
+ * individual, a pair without a shared locus):
+ *   gram[i*I+j]    G_ij = sum_c r_ic r_jc: the bits of mchip_residual_products' gram on the same state (the same chunks, kernel
+ *                  and order of addition);
+ *   scale[i*I+j]   V_ij = sum_c w_ic w_jc; symmetric bit for bit (the entries on and above the diagonal are computed, the others
+ *                  are copies).
+ * Both sums are pairwise-complete by construction: r and w are 0 where the individual has no observed copy at the locus.
+ * Why the ratio is a kinship coefficient.  Given the individual-specific frequencies t_i. = sum_k q_ik p_k., the copies of i and j at
+ * a column are indicators with means t_ic, t_jc, and a copy of i is identical by descent to a copy of j with probability phi_ij; to
+ * first order Cov(n_ic, n_jc) = a_il a_jl phi_ij sqrt(t_ic (1 - t_ic) t_jc (1 - t_jc)), so E[r_ic r_jc] = phi_ij w_ic w_jc, and the
+ * ratio of the sums is the moment estimator.  Diploid biallelic data without a missing copy: x = n_i1 is the dosage, mu = t_i1, a = 2,
+ * the two columns of a locus carry the same products ((n_i0 - 2 t_i0) = -(x_i - 2 mu_i), t_i0 (1 - t_i0) = mu_i (1 - mu_i)), the
+ * factor 2 cancels and phi_ij = sum (x_i - 2 mu_i)(x_j - 2 mu_j) / (4 sum sqrt(mu_i (1 - mu_i) mu_j (1 - mu_j))) over the SNPs typed in
+ * both: REAP's formula.  For other ploidies, partially missing genotypes and multi-allelic loci it is the same moment estimator, a
+ * generalisation of this project's own.  phi_ii is the self-kinship; for ploidy 2 the inbreeding coefficient is 2 phi_ii - 1.
+ * Precision.  No bit-for-bit claim is made about w, which goes through a square root; the claim is the bound on V that
+ * tests/kin_util.py derives: (T + 8) u on the sum of the terms plus the terms' own error from t's chain and the root.
+ * An element's terms are added in the order of the columns, four to an instruction of the FP64 matrix unit, the order inside an
+ * instruction being the hardware's: at most two roundings per term.  The chunks depend on uniquealleles alone; no floating-point
+ * atomics; the same state gives the same bits on any device and under every geometry knob of the environment
+ * (MCHIP_KIN_TWO_LAUNCHES, the two products of a chunk as two launches instead of one, included).
+ * Cost: 2 I^2 T multiply-adds, the half below the diagonal skipped, and two I x I arrays of doubles on the device.
+ * Writes its two host arrays and nothing else: no parameter slot, secant, expected count, held S-side sum, data set, fold or saved
+ * set changes.
+ * MCHIP_ERR_STATE without a data set or model; MCHIP_ERR_UNSUPPORTED for the mixture model (admixture = 0); MCHIP_ERR_INVALID for a
+ * slot out of range or a null gram or scale -- all checked before anything runs, the arrays stay untouched; MCHIP_ERR_ALLOC when
+ * the I x I sums or the chunk buffers do not fit on the device.
+ */
+int mchip_kinship_products(mchip_context *ctx, int slot, double *gram /* [I][I] */, double *scale /* [I][I] */);
+
 /* ---- a selection of loci with repeats: the data sets of the non-parametric bootstrap over loci (an extension) ----
  * Let the base be the data set the context held when the first resample was asked for (I, L_base, ploidy, uniquealleles,
  * genotypes).  After the call the context holds exactly what

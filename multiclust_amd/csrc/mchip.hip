@@ -73,6 +73,7 @@ void read_knobs(mchip_knobs *knob)
 	knob->no_slab_sum = on("MCHIP_NO_SLAB_SUM");
 	knob->no_fused_finalize = on("MCHIP_NO_FUSED_FINALIZE");
 	knob->no_pair = on("MCHIP_NO_PAIR");
+	knob->kin_two_launches = on("MCHIP_KIN_TWO_LAUNCHES");
 	knob->no_col_split = on("MCHIP_NO_COL_SPLIT");
 	knob->part_no_tile = on("MCHIP_PART_NO_TILE");
 	knob->sim_no_tile = on("MCHIP_SIM_NO_TILE");

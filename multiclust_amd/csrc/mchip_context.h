@@ -2,7 +2,7 @@
  * mchip_context.h -- the per-context state of libmulticlust_hip.so and what its host-side units call of one another: the units of
  * the core (mchip.hip the context, the install path and the model; mchip_plan.hip geometry and plan; mchip_em.hip the EM step;
  * mchip_accel.hip; mchip_init.hip; mchip_profile.hip) and the units holding a data-set feature's kernels and entry points
- * (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_generators.hip, mchip_impute.hip, mchip_pca.hip, mchip_query.hip, mchip_resample.hip, mchip_residuals.hip).
+ * (mchip_bed.hip, mchip_cv.hip, mchip_divergence.hip, mchip_generators.hip, mchip_impute.hip, mchip_pca.hip, mchip_query.hip, mchip_resample.hip, mchip_residuals.hip, mchip_kinship.hip).
  * Private to those units; not part of the C-ABI, and mchip_kernels_k.hip does not include it.
  */
 #ifndef MCHIP_CONTEXT_H
@@ -33,6 +33,7 @@ struct saved_set {
 struct mchip_knobs {
 	int no_bial, no_counts, force_dense, force_safe, no_graph, no_dual, no_slab_sum, no_col_split, part_no_tile, sim_no_tile;
 	int no_fused_finalize, no_pair;
+	int kin_two_launches;		/* mchip_kinship_products: its two products a chunk as two launches (the same bits) */
 	int per_cu_col, per_cu_ind, geometry_given, no_roundup;
 	double slab_frac;
 };

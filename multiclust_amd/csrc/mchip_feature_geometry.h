@@ -1,6 +1,6 @@
 /*
  * mchip_feature_geometry.h -- launch geometry of a lane-per-individual pass over blocks of 8 loci (k_cv_score, k_impute,
- * k_resid_tile).  Plain C++, no HIP types: tests/feature_geometry_driver.cpp compiles it alone and tests/feature_geometry.py
+ * k_resid_tile, k_kin_tile).  Plain C++, no HIP types: tests/feature_geometry_driver.cpp compiles it alone and tests/feature_geometry.py
  * restates it.
  */
 #ifndef MCHIP_FEATURE_GEOMETRY_H

@@ -116,6 +116,7 @@ def load():
         "mchip_impute_missing": ([vp, i32, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp], i32),
         "mchip_divergence": ([vp, i32, vp, vp, vp, vp, vp, dp, dp, ip], i32),
         "mchip_residual_products": ([vp, i32, vp, vp], i32),
+        "mchip_kinship_products": ([vp, i32, vp, vp], i32),
         "mchip_describe_plan": ([C.POINTER(PlanQuery), C.c_char_p, i32], i32),
     }
     for name, (args, res) in sig.items():
@@ -141,7 +142,7 @@ ABI_SYMBOLS = [
     "mchip_simulate_genotypes_mixture", "mchip_init_from_individual_centers", "mchip_set_genotypes_bed",
     "mchip_cv_draw_folds", "mchip_cv_set_folds", "mchip_cv_get_folds", "mchip_cv_hold_out", "mchip_cv_heldout_loglik",
     "mchip_resample_loci", "mchip_fit_q_rows", "mchip_impute_missing", "mchip_divergence",
-    "mchip_residual_products", "mchip_describe_plan", "mchip_bed_ld_band", "mchip_bed_king", "mchip_bed_qc",
+    "mchip_residual_products", "mchip_kinship_products", "mchip_describe_plan", "mchip_bed_ld_band", "mchip_bed_king", "mchip_bed_qc",
     "mchip_bed_pca_apply", "mchip_bed_pca",
 ]
 
@@ -384,6 +385,13 @@ class Context:
         D = np.empty((self.I, self.I)) if want_norms else None
         self._chk(self.lib.mchip_residual_products(self.h, slot, G.ctypes.data, None if D is None else D.ctypes.data))
         return G, D
+
+    def kinship_products(self, slot):
+        """mchip_kinship_products: the sums behind the kinship coefficients under the admixture fit in `slot`
+        (include/multiclust_hip.h): (gram [I][I], scale [I][I]); phi = gram / scale, NaN where scale is 0."""
+        G, V = np.empty((self.I, self.I)), np.empty((self.I, self.I))
+        self._chk(self.lib.mchip_kinship_products(self.h, slot, G.ctypes.data, V.ctypes.data))
+        return G, V
 
     def resample_loci(self, src):
         """install the selection `src` (locus indices into the base, repeats allowed) of the base: the data set held when the first

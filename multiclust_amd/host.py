@@ -132,7 +132,9 @@ class CliOptionsAll(CliOptions):
                 ("mind", C.c_int), ("geno", C.c_int), ("maf", C.c_int), ("hwe", C.c_int), ("mind_t", C.c_double),
                 ("geno_t", C.c_double), ("maf_t", C.c_double), ("hwe_t", C.c_double),
                 # --pca, --pca-iter, --pca-tol
-                ("pca", C.c_int), ("pca_iter", C.c_int), ("pca_tol", C.c_double)]
+                ("pca", C.c_int), ("pca_iter", C.c_int), ("pca_tol", C.c_double),
+                # --kinship
+                ("kinship", C.c_int), ("kinship_t", C.c_double)]
 
 
 class McKingPair(C.Structure):

@@ -68,6 +68,8 @@ typedef struct mc_cli_options {
 	int pca;			/* --pca <n> (extension, mc_pca.c; needs --bed): the n leading principal components of the fileset the filters left; 0 = off, 1 ... MC_PCA_MAX */
 	int pca_iter;			/* --pca-iter <m>: iterations of the subspace iteration at most; default 200 */
 	double pca_tol;			/* --pca-tol <t>: a component has converged when its residual is <= t; 0 < t < 1, default 1e-6 */
+	int kinship;			/* --kinship <t> seen (extension, mc_kinship.c): kinship between the individuals under the best fit of every K */
+	double kinship_t;		/* --kinship <t>: the pairs with phi > t are reported; 0 < t < 0.5 */
 } mc_cli_options;
 
 /* what --pca found (mc_pca.c): the n_pc leading eigenpairs of the matrix of mchip_bed_pca on the I individuals and L variants held, L' =
@@ -236,6 +238,11 @@ int mc_write_divergence(const mc_cli_options *opt, const mc_cli_data *dat, const
  * <stem>.admix.K=<K>.resid.ind.txt -- per individual its index, mean and largest correlation and the partner of that; the formats are
  * in the header comment of mc_resid.c.  Returns 0 or an exit status of the enum above. */
 int mc_write_resid(const mc_cli_options *opt, const mc_resid_result *r);
+/* --kinship (an extension, mc_kinship.c): <stem>.admix.K=<K>.kin0 -- the pairs above the threshold with phi, the two sums and the
+ * degree -- and <stem>.admix.K=<K>.kin.ind.txt -- per individual its self-kinship, inbreeding coefficient, number of partners above the
+ * threshold, largest phi and the partner of that; the formats are in the header comment of mc_kinship.c.  Returns 0 or an exit status
+ * of the enum above. */
+int mc_write_kinship(const mc_cli_options *opt, const mc_kinship_result *r);
 
 /* ---- what the filters of a fileset that run before the fit share (mc_filter.h, included at the end of this file); pre_fit() of mc_cli_stages.c runs them.
  * mc_filter_on_device: opens device opt->device, calls decide(opt, &dev, out) -- dev is what a band callback on the device needs --

@@ -64,6 +64,12 @@ static void usage(FILE *fp, const char *prog)
 		"                relatives, duplicates and a K that is too small show as positive blocks): one more line 'Residual correlation\n"
 		"                (K=..)' per K and the files <stem>.admix.K=<K>.resid.txt (the I x I matrix: I*I numbers) and .resid.ind.txt (mean,\n"
 		"                largest and partner per individual); needs -a, not with -b, -w, -M or --gpus above 1\n"
+		"  --kinship <t> kinship coefficients between the individuals under the best fit of every K, from the fit's individual-specific allele\n"
+		"                frequencies (REAP, Thornton et al. 2012; PC-Relate's form; unlike --king-cutoff it holds for admixed pairs); the\n"
+		"                pairs with phi > t (0 < t < 0.5) are reported: one more line 'Kinship (K=..)' per K with their number by degree\n"
+		"                (duplicate > 0.354, first > 0.177, second > 0.0884, third > 0.0442) and the files <stem>.admix.K=<K>.kin0 (i, j, phi,\n"
+		"                the two sums, degree) and .kin.ind.txt (self-kinship, inbreeding, partners above t, largest phi and partner per\n"
+		"                individual); relatives fitted as a cluster of their own show none; needs -a, not with -b, -w, -M or --gpus above 1\n"
 		"  --prune <t>   thin the variants of --bed by linkage disequilibrium before anything is fitted: in file order, a variant whose\n"
 		"                squared dosage correlation with a variant already kept, on its chromosome and at most W variants before it,\n"
 		"                exceeds t (0 < t <= 1) is removed (forward greedy, as SNPRelate's snpgdsLDpruning; not PLINK's --indep-pairwise);\n"
@@ -235,6 +241,7 @@ int parse_options(mc_cli_options *o, int argc, const char **argv)
 		case '1': if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-1"); o->min_K = (int)v; break;
 		case '2': if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-2"); o->max_K = (int)v; break;
 		case 'k':
+			if (!strcmp(argv[i], "--kinship")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--kinship"); o->kinship = 1; o->kinship_t = d; break; }	/* (in full as well) */
 			if (!strcmp(argv[i], "--king-cutoff")) { if (arg_dbl(argc, argv, ++i, &d)) BAD("--king-cutoff"); o->king = 1; o->king_t = d; break; }	/* (in full: -k... is K) */
 			if (arg_int(argc, argv, ++i, &v) || v < 1) BAD("-k");
 			o->min_K = o->max_K = (int)v;
@@ -337,6 +344,8 @@ int parse_options(mc_cli_options *o, int argc, const char **argv)
 			o->query_file ? "--fill cannot be combined with --query (the query individuals are hidden on the device)" : NULL))) return rc;
 	if (o->fst && (rc = refuse_post_fit(o, "--fst", 0, NULL))) return rc;
 	if (o->resid && (rc = refuse_post_fit(o, "--resid", 1, NULL))) return rc;
+	if (o->kinship && (rc = refuse_post_fit(o, "--kinship", 1,
+			!(o->kinship_t > 0 && o->kinship_t < 0.5) ? "the kinship threshold of --kinship must lie in (0, 0.5)" : NULL))) return rc;
 	if ((o->prune || o->prune_window_given) && (rc = refuse_as(o->prune ? "--prune" : "--prune-window",
 			!o->bed_prefix ? "--prune and --prune-window need a PLINK fileset (--bed)" :
 			!o->prune ? "--prune-window needs --prune" :

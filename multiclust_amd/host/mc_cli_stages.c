@@ -9,7 +9,7 @@
  *
  * Where a post-fit analysis plugs in: the serial and the sharded route of mc_main.c differ in who fits which unit and share the rest.
  * Both keep the best fit of a K in a fit_record with its parameters whenever wants_post_fit() says so, and end in post_fit(), which puts
- * the record back into a model once and runs --fst, --resid, --cv, --se, --query, --fill.  A new analysis is one more block there with
+ * the record back into a model once and runs --fst, --resid, --kinship, --cv, --se, --query, --fill.  A new analysis is one more block there with
  * its line of text, its flag in wants_post_fit(), and its option with its refusals (refuse_post_fit) in mc_cli_options.c; one that
  * refits derived data sets builds on mc_refit_* (mc_refit.c).  Nothing in the scheduling of the fits changes for either.
  */
@@ -57,13 +57,13 @@ int pre_fit(const mc_cli_options *o, mc_cli_data *d)
 	return 0;
 }
 
-/* ---- the post-fit stage: --fst, --resid, --cv, --se, --query and --fill, in that order, on the best fit of one K ----
+/* ---- the post-fit stage: --fst, --resid, --kinship, --cv, --se, --query and --fill, in that order, on the best fit of one K ----
  * fit: that fit, with its parameters.  mod: the model that fitted it (its slots are free again; --query needs this one: the
  * hold-out that hides the query individuals is in force on its context), or NULL: a model is created on `device` for the purpose
  * (the workers of a sharded fit are gone by the time the best unit is known).  The fit goes back into the model once: every
  * analysis leaves slot pindex and the host state of the model as it found them (mc_host.h).  Each analysis writes its file
  * (result files on) and adds its stdout line to st->post_lines. */
-int wants_post_fit(const mc_cli_options *o, int bootstrap) { return (o->fst || o->resid || o->cv_folds || o->se_replicates || o->query_file || o->fill) && !bootstrap; }
+int wants_post_fit(const mc_cli_options *o, int bootstrap) { return (o->fst || o->resid || o->kinship || o->cv_folds || o->se_replicates || o->query_file || o->fill) && !bootstrap; }
 
 int post_fit(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, run_state *st, const fit_record *fit, mc_model *mod, int device)
 {
@@ -99,6 +99,17 @@ int post_fit(const mc_cli_options *o, const mc_cli_data *d, const mc_data *md, r
 			fputc('\n', say);
 			if (o->write_files) rc = mc_write_resid(o, &res);
 			mc_resid_result_free(&res);
+		}
+	}
+	if (!rc && o->kinship) {	/* like --resid: the slot and the installed data set, before anything installs another.  With result files
+					 * on: <stem>.admix.K=<K>.kin0, .kin.ind.txt */
+		mc_kinship_result res;
+		mchip_progress_note("kinship");
+		if (!(rc = mc_kinship(md, mod, o->kinship_t, &res))) {
+			mc_kinship_line(say, &res);
+			fputc('\n', say);
+			if (o->write_files) rc = mc_write_kinship(o, &res);
+			mc_kinship_result_free(&res);
 		}
 	}
 	if (!rc && o->cv_folds) {

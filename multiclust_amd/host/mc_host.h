@@ -390,6 +390,40 @@ void mc_resid_result_free(mc_resid_result *r);
  * when no pair has a number; no line end */
 void mc_resid_line(FILE *fp, const mc_resid_result *r);
 
+/* ---- kinship between individuals under the fitted admixture model (mc_kinship.c; an extension: REAP's estimator) ----
+ * `mod` holds a fit of the admixture model (individual or shared mixing proportions) in slot mod->pindex; dat gives I and the ploidy.
+ * mchip_kinship_products (include/multiclust_hip.h has every definition and the derivation) gives, over the data set installed on
+ * the context, G_ij = sum_c r_ic r_jc of the residuals and V_ij = sum_c w_ic w_jc of w = observed copies x sqrt(t (1 - t)), t the
+ * individual-specific allele frequency; phi_ij = G_ij / V_ij, NaN where V_ij = 0 -- an individual without an observed copy, a query
+ * individual, a pair without a shared locus.  mc_kinship_from_sums forms what is reported: `pairs`, the n_pairs pairs i < j with
+ * phi > t in (i, j) order, each with its sums and its degree (mc_kinship_degree: 0 duplicate / MZ twin > 0.354, 1 first degree >
+ * 0.177, 2 second > 0.0884, 3 third > 0.0442, 4 more distant), n_degree [5] how many of each; over the n_finite pairs i < j with a
+ * number their mean and the largest with its pair (NaN and -1 without one); per individual self = phi_ii, inbreeding = 2 phi_ii - 1
+ * (ploidy 2, otherwise NaN), ind_count = the others it has phi > t with, ind_max and ind_partner = its largest finite phi with
+ * another and the first it has it with (NaN, -1 without one).  A NaN compares false: it is above no threshold.
+ * Limits: P and Q were estimated with the pair in the data, so estimates of true relatives are biased slightly towards zero; a family
+ * fitted as a cluster of its own shows no kinship (remove it before the fit: --king-cutoff); no k0 / k1 / k2.
+ * Cost: quadratic in I -- 2 I^2 T multiply-adds on the device, half skipped by symmetry; two I x I arrays of doubles on the host.
+ * Nothing of the model or the context changes.  Mixture model: MCHIP_ERR_UNSUPPORTED.  Release the arrays with
+ * mc_kinship_result_free; on failure nothing is held. */
+typedef struct mc_kin_pair { int i, j, degree; double phi, G, V; } mc_kin_pair;
+typedef struct mc_kinship_result {
+	int K, I, ploidy, max_i, max_j;
+	double t, mean, max;
+	long long n_finite, n_degree[5];
+	size_t n_pairs;
+	mc_kin_pair *pairs;
+	double *self, *inbreeding, *ind_max;
+	int32_t *ind_count, *ind_partner;
+} mc_kinship_result;
+int mc_kinship_degree(double phi);
+int mc_kinship_from_sums(int I, int ploidy, double t, const double *G /* [I][I] */, const double *V /* [I][I] */, mc_kinship_result *r /* r->K set */);
+int mc_kinship(const mc_data *dat, mc_model *mod, double t, mc_kinship_result *out);
+void mc_kinship_result_free(mc_kinship_result *r);
+/* "Kinship (K=<K>): <n> pairs above <t> (<d> duplicates, <f> first, <s> second, <h> third degree); largest <%.6f> (<i>, <j>); mean over
+ * <m> pairs <%.6f>", with "no pairs" behind the colon when no pair has a number; no line end */
+void mc_kinship_line(FILE *fp, const mc_kinship_result *r);
+
 /* ---- opt-in watchdog (mc_watchdog.c): nothing in the reference corresponds -- it has nothing to wait for ----
  * mc_watchdog_start(s): a detached thread that polls the library's event count (mchip_progress_report) and, when it has stood
  * still for s seconds, prints where every thread stands (library record + /proc/self/task) on stderr and leaves with _exit(3).
