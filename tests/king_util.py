@@ -11,6 +11,7 @@ import hashlib
 import numpy as np
 
 import bedfiles
+from bits import canonical_bytes
 from ld_util import codes_of, repack, same_bits      # noqa: F401  (the tests take them from here)
 
 # restated from multiclust_amd/csrc/mchip_feature_geometry.h and mchip_bed.hip
@@ -183,9 +184,7 @@ def cli_case():
 
 
 def digest(phi, cnt):
-    phi = np.ascontiguousarray(phi, dtype=np.float64)
-    canon = np.where(np.isnan(phi), np.float64("nan"), phi)      # one NaN pattern: the positions count, not the payload
-    return hashlib.sha256(canon.tobytes() + np.ascontiguousarray(cnt, dtype=np.uint32).tobytes()).hexdigest()
+    return hashlib.sha256(canonical_bytes(phi) + np.ascontiguousarray(cnt, dtype=np.uint32).tobytes()).hexdigest()
 
 
 FIXED = dict(I=130, L=1100)

@@ -10,6 +10,7 @@ import hashlib
 import numpy as np
 
 import bedfiles
+from bits import canonical_bytes, same_bits, ulp_distance      # noqa: F401  (the tests take the last two from here)
 
 # restated from multiclust_amd/csrc/mchip_feature_geometry.h
 TILE = 64        # first variants per workgroup
@@ -145,19 +146,8 @@ def plant(codes, seed=0):
     return where
 
 
-def same_bits(a, b):
-    """equal as bit patterns where neither is NaN, NaN in the same places"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
-        return False
-    ok = ~np.isnan(a)
-    return np.array_equal(a[ok].view(np.uint64), b[ok].view(np.uint64))
-
-
 def digest(r2):
-    r2 = np.ascontiguousarray(r2, dtype=np.float64)
-    canon = np.where(np.isnan(r2), np.float64("nan"), r2)      # one NaN pattern: the positions count, not the payload
-    return hashlib.sha256(canon.tobytes()).hexdigest()
+    return hashlib.sha256(canonical_bytes(r2)).hexdigest()
 
 
 FIXED = dict(I=1001, L=300, window=305)
@@ -196,12 +186,6 @@ def write_bim(prefix, chrom, ids=None, pos=None):
     with open(prefix + ".bim", "w") as f:
         for l, c in enumerate(chrom):
             f.write("%s\t%s\t0\t%d\tA\tC\n" % (c, ids[l] if ids else "snp%d" % l, pos[l] if pos is not None else l + 1))
-
-
-def ulp_distance(a, b):
-    """units in the last place between two finite doubles of the same sign"""
-    x, y = np.float64(a).view(np.int64), np.float64(b).view(np.int64)
-    return abs(int(x) - int(y))
 
 
 if __name__ == "__main__":

@@ -6,10 +6,9 @@ import re
 
 import pytest
 
+from cli_util import ROOT
 import multiclust_amd as mc
 from multiclust_amd import hip
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def header_symbols():

@@ -8,10 +8,8 @@ import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import BIN
 from multiclust_amd import host
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 
 SHAPE_I = (1, 3, 4, 5, 8, 9, 63, 65, 257)
 SHAPE_L = (1, 7, 8, 9, 63, 65, 300)

@@ -4,7 +4,7 @@ import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cli_util import ROOT
 
 
 def test_gpus_flag_needs_that_many_devices():

@@ -7,8 +7,8 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
+from cli_util import BIN, ROOT
+
 REFBIN = os.path.join(ROOT, "oracle", "_ref", "multiclust_ref")
 MULTI = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")
 

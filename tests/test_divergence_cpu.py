@@ -10,11 +10,10 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from cli_util import BIN, ROOT
 import divergence_util as du
 from multiclust_amd import host
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 MULTI = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")
 F = Fraction
 

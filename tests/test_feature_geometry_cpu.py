@@ -1,29 +1,22 @@
 """The geometry of the lane-per-individual passes (k_cv_score, k_impute, k_resid_tile): the C++ rule
 (multiclust_amd/csrc/mchip_feature_geometry.h), compiled alone into a program of its own under AddressSanitizer + UBSan, against
 its Python restatement (tests/feature_geometry.py) that the GPU tests place their cases with."""
-import os
-import subprocess
 
 import pytest
 
 import feature_geometry as fg
+import host_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(257, 9, 256), (1, 1, 0), (10000, 100000, 256), (63, 33001, 304)]      # (I, L, compute units; 0 = unknown)
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("geometry") / "feature_geometry_driver")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                    "-I" + os.path.join(ROOT, "multiclust_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "feature_geometry_driver.cpp")],
-                   check=True)
+    exe = host_driver.build(tmp_path_factory.mktemp("geometry"), "feature_geometry_driver", ["tests/feature_geometry_driver.cpp"], cxx=True,
+                            werror=True)
 
     def run(I, L, n_cu, red, smallest, budget):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-        res = subprocess.run([exe] + [str(x) for x in (I, L, n_cu, red, smallest, budget)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                             text=True, env=env, timeout=120)
-        assert res.returncode == 0 and not res.stderr, res.stderr[-2000:]
+        res = host_driver.run(exe, (I, L, n_cu, red, smallest, budget), quiet_stderr=True)
         rows = [tuple(int(x) for x in line.split()) for line in res.stdout.splitlines()]
         assert [r[:2] for r in rows] == [(K, M) for K in range(1, 65) for M in range(1, 256)]
         return {r[:2]: r[2:] for r in rows}

@@ -4,38 +4,17 @@ fit, the line a failed open leaves, the lines of a text that hold anything but w
 kept-lines copy writes -- and the two writers of a filter at the ends of their maps.  Every expectation is restated here in Python
 from the wording of mc_cli.h; nothing is read back from the code under test."""
 import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_driver
+
 BLANK = b" \t\r"
 
 
-def build_driver(tmp, sanitize):
-    exe = os.path.join(tmp, "files_host_san" if sanitize else "files_host")
-    hostdir = os.path.join(ROOT, "multiclust_amd", "host")
-    srcs = [os.path.join(ROOT, "tests", "files_host_driver.c")]        # (mc_files.h comes with mc_cli.h)
-    flags = ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if sanitize else ["-O2"]
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Wextra", "-Werror"] + flags + ["-I" + os.path.join(ROOT, "include"), "-I" + hostdir, "-o", exe] +
-                   srcs + ["-lm"], check=True)
-    return exe
-
-
-@pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
-def driver(request, tmp_path_factory):
-    if shutil.which("gcc") is None:
-        pytest.skip("needs gcc")
-    exe = build_driver(str(tmp_path_factory.mktemp("files_driver")), request.param)
-
-    def run(*args, cwd):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-        res = subprocess.run([exe] + [str(a) for a in args], cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=60)
-        assert res.returncode == 0, (args, res.returncode, res.stderr[-2000:])
-        assert b"AddressSanitizer" not in res.stderr and b"runtime error" not in res.stderr
-        return res.stdout.decode(), res.stderr.decode()
-    return run
+# (mc_files.h comes with mc_cli.h; the program's output is taken as bytes and decoded here)
+driver = host_driver.plain_and_sanitized("files_host", ["tests/files_host_driver.c"], werror=True, timeout=60, text=False,
+                                         result=lambda res: (res.stdout.decode(), res.stderr.decode()))
 
 
 # ---- the result path ----

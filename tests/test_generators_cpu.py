@@ -18,13 +18,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_util import ROOT
 import oracle_bind as ob
 import rand_window as rw
 from multiclust_amd import host
 from synth import random_params
 from test_bootstrap_cpu import counts_of, walk_threshold
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_TIME = os.path.join(ROOT, "oracle", "_ref", "ref_time")
 D = 2147483647.0
 RAND_MAX = rw.RAND_MAX

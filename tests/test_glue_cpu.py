@@ -7,7 +7,8 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cli_util import ROOT
+
 REF = "/root/reference"
 
 

@@ -24,19 +24,12 @@ import numpy as np
 import pytest
 
 import accel_ops as ao
-import multiclust_amd as mc
+from device_util import ctx
 import oracle_bind as ob
 
 pytestmark = pytest.mark.gpu
 
 STEPS = (-1.0, -2.5, -37.25, -1e-3)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = mc.Context(0)
-    yield c
-    c.close()
 
 
 def bound_of(shape, lb=1e-8):

@@ -3,21 +3,19 @@ plain-C decoder (mc_bed_decode) uploaded the usual way (mchip_set_genotypes): th
 the command line's --bed against -f on the equivalent STRUCTURE file.  Every comparison is exact."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 import bedfiles as bf
+from bits import bits
+from cli_util import BIN, CLOCK, result_files
 import oracle_bind as ob
 from multiclust_amd import hip, host
 from procutil import run_program
 from synth import random_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")       # elapsed CPU time of a fit: the one thing two runs of one program differ in
 
 SHAPE_I = (1, 3, 4, 5, 8, 9, 63, 65, 257)
 SHAPE_L = (1, 7, 8, 9, 63, 65, 300)
@@ -86,10 +84,6 @@ def test_many_tiles(contexts):
     assert_same_install(contexts, 2000, bf.pack(codes))
 
 
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
 def admixture_fit(ctx, K, window, steps=5):
     ctx.set_model(K, admixture=1)
     ctx.mstep_from_rand_partition(window, to=0)
@@ -139,10 +133,6 @@ def test_fits_are_bit_identical(case, contexts):
     assert np.isfinite(b[0]).all()
     for x, y in zip(a, b):
         assert x.shape == y.shape and bits(x) == bits(y)
-
-
-def result_files(d):
-    return {f: open(os.path.join(d, f), "rb").read() for f in sorted(os.listdir(d))}
 
 
 # n_models: the K values a run fits and writes its five result files for (-b fits H0: K - 1 beside HA: K)

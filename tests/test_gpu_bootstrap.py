@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import multiclust_amd as mc
+from device_util import ctx
 import oracle_bind as ob
 from golden_util import Golden
 from multiclust_amd import host
@@ -15,13 +15,6 @@ from synth import make_dataset, random_params
 from test_bootstrap_cpu import counts_of, golden_bootstrap, host_options
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = mc.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.mark.parametrize("name", ["multi_admix_k4", "tetra_admix_k3", "missing_admix_k3", "multi_admix_c_k3"])

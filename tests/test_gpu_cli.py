@@ -8,15 +8,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_util import BIN, CLOCK
 from procutil import run_program
 
 from golden_util import GOLD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 NUM = re.compile(r"-?\d+\.\d+(?:e[+-]?\d+)?|-?\d+")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")       # elapsed CPU time: not comparable between machines
 
 
 def run_cli(case, tmp_path, extra=()):

@@ -13,13 +13,14 @@ import sys
 
 import pytest
 
+from cli_util import BIN, CLOCK, ROOT
 import procutil
 
 import test_gpu_cli as cli
 
-sys.path.insert(0, os.path.join(cli.ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 pytestmark = pytest.mark.gpu
-REFBIN = os.path.join(cli.ROOT, "oracle", "_ref", "multiclust_ref")
+REFBIN = os.path.join(ROOT, "oracle", "_ref", "multiclust_ref")
 
 
 SIZE = int(os.environ.get("MC_DIFF_SIZE", "1"))        # soaks: individuals and loci multiplied by this
@@ -32,7 +33,6 @@ def run_program(cmd, cwd, timeout=None):
     was waiting in.  (One launch in about 4 000 of round 3's soaks, a 60-locus mixture fit of 0.3 s, did not return within 300 s
     and left no such record: DESIGN.md section 9.)"""
     return procutil.run_program(cmd, cwd=cwd, timeout=timeout or 120 * SIZE_LIMIT)
-
 
 
 def draw_cases(n, seed):
@@ -78,7 +78,7 @@ def test_command_line_against_the_reference_program_on_drawn_cases(c, I, L, ploi
     if scheme:
         args += ["-s", str(scheme)]
     outs = {}
-    for name, exe in (("ref", REFBIN), ("hip", cli.BIN)):
+    for name, exe in (("ref", REFBIN), ("hip", BIN)):
         d = tmp_path / name
         d.mkdir()
         res = run_program([exe, "-f", stru, "-d", os.path.join(str(d), "")] + args, str(d))
@@ -98,7 +98,7 @@ def test_command_line_against_the_reference_program_on_drawn_cases(c, I, L, ploi
                         if phantom.get(int(l_)) == int(m_) and v_ != "0.000000":
                             pytest.skip("heap garbage in the reference's phantom allele slot matched an allele code")
         assert res.returncode == 0, (name, args, res.stderr[-2000:])
-        outs[name] = (cli.CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n"), d)
+        outs[name] = (CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n"), d)
     (ref_lines, ref_dir), (got_lines, got_dir) = outs["ref"], outs["hip"]
     assert len(ref_lines) == len(got_lines), (args, ref_lines, got_lines)
     # plain EM: same iteration counts, files to 6 decimals.  Accelerated schemes: the extrapolated path amplifies last-bit
@@ -171,13 +171,13 @@ def test_command_line_against_the_reference_program_on_drawn_cases(c, I, L, ploi
 
 def run_both(tmp_path, args, stru, status=0):
     outs = {}
-    for name, exe in (("ref", REFBIN), ("hip", cli.BIN)):
+    for name, exe in (("ref", REFBIN), ("hip", BIN)):
         d = tmp_path / name
         d.mkdir()
         res = run_program([exe, "-f", stru] + args, str(d), timeout=300)
         open(str(tmp_path / (name + ".stderr")), "w").write(res.stderr)
         assert res.returncode == status, (name, args, res.returncode, res.stderr[-2000:])
-        outs[name] = (cli.CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n"), d)
+        outs[name] = (CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n"), d)
     return outs["ref"], outs["hip"]
 
 
@@ -266,7 +266,6 @@ def test_bootstrap_whose_null_model_fits_as_well_as_the_alternative_ends_like_th
     assert len(ref_lines) == len(got_lines) >= 4
     for r, g in zip(ref_lines, got_lines):
         assert cli.NUM.sub("#", r) == cli.NUM.sub("#", g), (r, g)
-
 
 
 @pytest.mark.skipif(not os.access(REFBIN, os.X_OK), reason="oracle/_ref/multiclust_ref not built (needs /root/reference at build time)")
@@ -399,7 +398,7 @@ def test_starting_values_from_files_against_the_reference_program(c, tmp_path):
         # exist (read_file.c:950, past the allocation) and carries on; this build refuses the combination
         d = tmp_path / "hip"
         d.mkdir()
-        res = run_program([cli.BIN, "-f", stru] + args, str(d), timeout=120)
+        res = run_program([BIN, "-f", stru] + args, str(d), timeout=120)
         assert res.returncode == 11 and "-P needs two alleles at every locus" in res.stderr
         return
     (ref_lines, ref_dir), (got_lines, got_dir) = run_both(tmp_path, args, stru)
@@ -439,7 +438,7 @@ def test_a_sample_without_a_single_genotype_against_the_reference_program(args, 
     open(stru, "w").write("\n".join(rows))
     phantom = phantom_slots(stru, 2)
     outs = {}
-    for name, exe in (("ref", REFBIN), ("hip", cli.BIN)):
+    for name, exe in (("ref", REFBIN), ("hip", BIN)):
         d = tmp_path / name
         d.mkdir()
         res = run_program([exe, "-f", stru, "-d", "./"] + args.split(), str(d))
@@ -453,7 +452,7 @@ def test_a_sample_without_a_single_genotype_against_the_reference_program(args, 
                         if phantom.get(int(l_)) == int(m_) and v_ != "0.000000":
                             pytest.skip("heap garbage in the reference's phantom allele slot matched an allele code")
         assert res.returncode == 0, (name, res.stderr[-1000:])
-        outs[name] = (cli.CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n"), d)
+        outs[name] = (CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n"), d)
     (ref_lines, ref_dir), (got_lines, got_dir) = outs["ref"], outs["hip"]
     assert len(ref_lines) == len(got_lines)
     for r, g in zip(ref_lines, got_lines):

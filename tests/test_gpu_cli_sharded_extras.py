@@ -6,13 +6,10 @@ import re
 
 import pytest
 
-from procutil import run_program
+from cli_util import ROOT, run_fresh
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 DATA = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")       # elapsed CPU time of a fit: the one thing two runs of one program differ in
 CV_LINE = re.compile(r"^CV error \(K=(\d+), ")
 SE_LINE = re.compile(r"^Bootstrap SE \(K=(\d+), ")
 COMMON = ["-f", DATA, "-a", "-s", "3", "-r", "7"]
@@ -24,12 +21,7 @@ def individuals():
 
 
 def run(args, d):
-    d.mkdir()
-    res = run_program([BIN] + COMMON + args + ["-o", "stem", "-d", os.path.join(str(d), "")], cwd=str(d), timeout=300)
-    assert res.returncode == 0, res.stderr
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(d), f), "rb").read() for f in sorted(os.listdir(str(d)))}
-    return lines, files
+    return run_fresh(COMMON + args, d)[:2]
 
 
 def partition_file(tmp_path):

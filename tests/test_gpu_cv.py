@@ -7,7 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from bits import bits
 import cv_util as cu
+from device_util import contexts, status_of
 import impute_util as iu
 import oracle_bind as ob
 import rand_window as rw
@@ -19,18 +21,6 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(I, L, pl) for I in (67, 300) for L in (61, 130) for pl in (1, 2, 4)]
 STATUS = {v: k for k, v in hip.STATUS.items()}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-@pytest.fixture(scope="module")
-def contexts():
-    ctxs = [hip.Context(0) for _ in range(2)]
-    yield ctxs
-    for c in ctxs:
-        c.close()
 
 
 def windows():
@@ -46,10 +36,6 @@ def windows():
     far = np.array([rng.r[(rng.f + t) % 31] for t in range(31)], dtype=np.int64).astype(np.uint32)
     assert not np.array_equal(far, first)
     return {"first": first, "placed": placed, "far": far}
-
-
-def status_of(rc):
-    return hip.STATUS.get(rc, rc)
 
 
 # ---------------------------------------------------------------- 1. folds

@@ -6,14 +6,10 @@ import re
 import numpy as np
 import pytest
 
+from cli_util import DATA, run_fresh
 from multiclust_amd import host
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-DATA = os.path.join(ROOT, "tests", "golden", "data")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")       # elapsed CPU time of a fit: the one thing two runs of one program differ in
 CV_LINE = re.compile(r"^CV error \(K=(\d+), (\d+) folds\): (\S+)  \[(\d+) held-out copies, (\d+) floored\]$")
 
 FIXTURES = {
@@ -22,16 +18,9 @@ FIXTURES = {
 }
 
 
-def result_files(d):
-    return {f: open(os.path.join(d, f), "rb").read() for f in sorted(os.listdir(d))}
-
-
 def run(data, args, d):
-    d.mkdir()
-    res = run_program([BIN] + data + args + ["-o", "stem", "-d", os.path.join(str(d), "")], cwd=str(d), timeout=300)
-    assert res.returncode == 0, res.stderr
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    return [ln for ln in lines if not CV_LINE.match(ln)], [CV_LINE.match(ln).groups() for ln in lines if CV_LINE.match(ln)], result_files(str(d))
+    others, own, files = run_fresh(data + args, d, own=CV_LINE)
+    return others, [m.groups() for m in own], files
 
 
 def read_fixture(name):

@@ -27,27 +27,17 @@ import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import ROOT
+from device_util import ctx, snapshot, status_of
 import divergence_util as du
 from multiclust_amd import hip, host
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK, STAGE, LANES = 1024, 64, 256
 KS = [1, 2, 3, 8, 27, 28, 64]
 LS = [1, 63, 64, 65, 257]
 FORMS = [dict(admixture=1, eta_constrained=0), dict(admixture=1, eta_constrained=1), dict(admixture=0, eta_constrained=0)]
 I = 8
-
-
-def status_of(rc):
-    return hip.STATUS.get(rc, rc)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def install(ctx, ua, K, P, form=FORMS[0], seed=0, geno=None):
@@ -152,17 +142,6 @@ def test_bits_do_not_depend_on_the_launch_geometry(ctx):
         assert res.returncode == 0, res.stderr[-2000:]
         seen.append(res.stdout.strip())
     assert seen == [here] * 3
-
-
-def snapshot(ctx, n_secants):
-    out = [ctx.get_genotypes().tobytes(), ctx.expected_counts().tobytes(), repr(ctx.data_counts()), repr(ctx.empty_individuals())]
-    for slot in range(3):
-        out += [ctx.get_q(slot).tobytes(), ctx.get_p(slot).tobytes()]
-    for j in range(n_secants):
-        for which in (0, 1):
-            p, q = ctx.get_secant(which, j)
-            out += [p.tobytes(), q.tobytes()]
-    return out
 
 
 @pytest.mark.parametrize("held_out", [False, True])

@@ -10,68 +10,35 @@ program used.  With c = T / L1 columns per locus that moves a weight by eps at m
 2 c eps, HT_l by M_l (K + 1) eps and V_l by M_l K eps + 2 (K + 2) eps A_l (A_l = sum_m sum_k w_k |p - pbar|: divergence_util), and
 a quotient n / d by (dn d + n dd) / d^2; second-order terms are covered by a factor 1.5.  The program's own figures carry ten
 (files) or six (stdout) decimals."""
-import os
 import re
 
 import numpy as np
 import pytest
 
 import bedfiles as bf
-import cv_util as cu
+from cli_util import clustered_codes, fit_inputs, Runs, written_fit
 import divergence_util as du
 from multiclust_amd import host
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 NUM = r"(-?\d+\.\d+|nan|-nan)"
 FST_LINE = re.compile(r"^Divergence \(K=(\d+)\): (?:pairwise Fst mean " + NUM + " min " + NUM + " max " + NUM +
                       r" over (\d+) pairs|(no pairs)); among clusters " + NUM + r" \[(\d+) loci\]$")
 I, L, CLUSTERS = 72, 400, 3
 ARGS = ["-s", "3", "-n", "2", "-r", "7", "-k", "3"]
 EPS = 5.1e-7
-_runs = {}
-
-
-def codes():
-    """clustered diploid biallelic data as .bed codes, 5 % of the calls missing, one locus without a call"""
-    _, geno = cu.clustered_dataset(I, L, CLUSTERS, 4)
-    n = geno.astype(np.int64).sum(axis=2)
-    c = np.array([bf.HOM1, bf.HET, bf.HOM2], dtype=np.uint8)[n]
-    c[np.random.default_rng(6).random((I, L)) < 0.05] = bf.MISS
-    c[:, 17] = bf.MISS
-    return c
 
 
 @pytest.fixture(scope="module")
 def inputs(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("fst_in"))
-    stru = os.path.join(d, "data.stru")
-    bf.write_equivalent_stru(stru, codes())
-    bf.write_fileset(os.path.join(d, "data"), codes(), padding=1)
-    query = os.path.join(d, "query.txt")
-    with open(query, "w") as f:
-        f.write(" ".join("1" if i % 9 == 4 else "0" for i in range(I)) + "\n")
-    rc, data = host.read_structure(stru)
-    assert rc == 0
-    return dict(dir=d, stru=stru, bed=os.path.join(d, "data"), query=query, ua=data["ua"], tmp=tmp_path_factory)
+    inputs = fit_inputs(tmp_path_factory, "fst_in", clustered_codes(I, L, CLUSTERS))
+    return dict(inputs, runs=Runs(lambda: tmp_path_factory.mktemp("fst_out"), own="Divergence"))
 
 
 def run(inputs, args, bed=False):
     """one run of the program per distinct command line: (other stdout lines, the groups of the Divergence lines, files)"""
-    key = (bed,) + tuple(args)
-    if key not in _runs:
-        out = str(inputs["tmp"].mktemp("fst_out"))
-        data = ["--bed", inputs["bed"]] if bed else ["-f", inputs["stru"]]
-        res = run_program([BIN] + data + list(args) + ["-o", "stem", "-d", os.path.join(out, "")], cwd=out, timeout=300)
-        assert res.returncode == 0, res.stderr
-        lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-        files = {f: open(os.path.join(out, f), "rb").read() for f in sorted(os.listdir(out))}
-        _runs[key] = ([ln for ln in lines if not ln.startswith("Divergence")], [FST_LINE.match(ln) for ln in lines if ln.startswith("Divergence")],
-                      files)
-    return _runs[key]
+    others, own, files = inputs["runs"]((["--bed", inputs["bed"]] if bed else ["-f", inputs["stru"]]) + list(args))
+    return others, [FST_LINE.match(ln) for ln in own], files
 
 
 FORMS = {"admix": ["-a"], "shared": ["-a", "-c"], "mix": []}
@@ -93,28 +60,6 @@ def test_nothing_else_changes(name, extra, bed, inputs):
     if extra:                                                    # ... and --fst says what it says without the other analyses
         _, fst2, files2 = run(inputs, FORMS[name] + ARGS + ["--fst"], bed)
         assert fst2[0].groups() == fst1[0].groups() and all(files2[f] == files1[f] for f in own)
-
-
-def table(text, skip=1):
-    return [ln.split("\t") for ln in text.decode().split("\n")[skip:] if ln.strip()]
-
-
-def written_fit(files, mdl, ua, K=3):
-    """Q ([I][K], or [K]) and P [K][T] as the result files print them"""
-    T, off = int(ua.sum()), du.offsets(ua)
-    P = np.full((K, T), np.nan)
-    for k, l, m, v in table(files["stem.%s.K=%d.pklm.txt" % (mdl, K)]):
-        P[int(k), off[int(l)] + int(m)] = float(v)
-    assert not np.isnan(P).any()
-    name = "stem.%s.K=%d.etaik.txt" % (mdl, K)
-    if name in files:
-        q = np.full((I, K), np.nan)
-        for i, k, v in table(files[name]):
-            q[int(i), int(k)] = float(v)
-    else:
-        q = np.array([float(v) for _, v in table(files["stem.%s.K=%d.etak.txt" % (mdl, K)])])
-        assert q.shape == (K,)
-    return q, P
 
 
 def own_files(files, mdl, K=3):
@@ -143,7 +88,7 @@ def agree_with_the_written_fit(inputs, name, args, query_rows=()):
     _, fst, files = run(inputs, args)
     K, T, L1 = 3, int(ua.sum()), int((ua > 0).sum())
     assert T > 2 * L1 and (ua == 0).sum() == 1                   # phantom columns and a locus without a column are in play
-    q, P = written_fit(files, mdl, ua)
+    q, P = written_fit(files, ua, I, 3, mdl)
     if q.ndim == 2:
         assert np.flatnonzero(np.isnan(q).any(axis=1)).tolist() == list(query_rows)
     w = du.weights_from_q(q, K)
@@ -220,7 +165,7 @@ def test_the_clusters_drawn_furthest_apart_have_the_largest_fst(inputs):
     allele frequencies of the groups) exceeds the other two by 0.02.  A fit that recovers the groups -- checked below: every fitted
     cluster is the most probable one of the individuals of one group of its own -- has those observed frequencies for its P but for
     the admixture it leaves in Q, so its F_ST follow the groups' far more closely than that margin"""
-    c = codes()
+    c = clustered_codes(I, L, CLUSTERS)
     obs = (c != bf.MISS)
     z = np.arange(I) % CLUSTERS
     a2 = np.select([c == bf.HOM1, c == bf.HET, c == bf.HOM2], [0, 1, 2], 0)
@@ -232,7 +177,7 @@ def test_the_clusters_drawn_furthest_apart_have_the_largest_fst(inputs):
     assert order[0][0] >= order[1][0] + 0.02, order
     _, fst, files = run(inputs, ["-a"] + ARGS + ["--fst"])
     _, _, _, F, _, _, _ = own_files(files, "admix")
-    q, _ = written_fit(files, "admix", inputs["ua"])
+    q, _ = written_fit(files, inputs["ua"], I, 3)
     group_of = [int(np.bincount(z[q.argmax(axis=1) == k], minlength=CLUSTERS).argmax()) for k in range(CLUSTERS)]
     assert sorted(group_of) == list(range(CLUSTERS))
     got = max(((F[a, b], tuple(sorted((group_of[a], group_of[b])))) for a in range(CLUSTERS) for b in range(a + 1, CLUSTERS)))

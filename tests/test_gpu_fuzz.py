@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-import multiclust_amd as mc
+from device_util import ctx
 import oracle_bind as ob
 from synth import make_dataset, random_params
 
@@ -26,13 +26,6 @@ def cases(n, seed):
         out.append((I, L, int(rs.integers(1, 13)), int(rs.integers(1, 7)), int(rs.integers(2, 8)),
                     float(rs.choice([0.0, 0.0, 0.03, 0.2])), int(rs.integers(0, 2)), int(rs.integers(0, 1 << 30))))
     return out
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = mc.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.mark.parametrize("I,L,K,ploidy,maxal,missing,constrained,seed", cases(120 * SCALE, 20250117 + SEED_SHIFT))

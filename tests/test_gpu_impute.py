@@ -15,7 +15,9 @@ import math
 import numpy as np
 import pytest
 
+from bits import bits
 import cv_util as cu
+from device_util import contexts, status_of
 import impute_util as iu
 from feature_geometry import EDGES, geometry
 from multiclust_amd import hip
@@ -24,22 +26,6 @@ from synth import random_params
 pytestmark = pytest.mark.gpu
 MISSING = iu.MISSING
 KS = [1, 2, 8, 27, 28, 64]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-def status_of(rc):
-    return hip.STATUS.get(rc, rc)
-
-
-@pytest.fixture(scope="module")
-def contexts():
-    ctxs = [hip.Context(0) for _ in range(2)]
-    yield ctxs
-    for c in ctxs:
-        c.close()
 
 
 def install(ctx, ua, geno, K, q, p, shared=False, projection=1):

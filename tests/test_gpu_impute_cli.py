@@ -8,15 +8,12 @@ import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import run_fresh
 import cv_util as cu
 import impute_util as iu
 from multiclust_amd import host
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 FILL_LINE = re.compile(r"^Imputation \(K=(\d+)\): (\d+) copies filled in (\d+) genotypes, (\d+) left missing, mean confidence (\S+)$")
 STANDARD = ["stem.admix.K=%d.out.txt", "stem.admix.K=%d.etaik.txt", "stem.admix.K=%d.pklm.txt", "stem_admix_indivq_%d.indivq",
             "stem_admix_popq_%d.popq"]
@@ -46,14 +43,8 @@ def write_inputs(d, bed=False):
 
 
 def run(data, args, d):
-    out = d / "out"
-    out.mkdir(parents=True)
-    res = run_program([BIN] + data + args + ["-o", "stem", "-d", os.path.join(str(out), "")], cwd=str(out), timeout=300)
-    assert res.returncode == 0, res.stderr
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(out), f), "rb").read() for f in sorted(os.listdir(str(out)))}
-    return ([ln for ln in lines if not FILL_LINE.match(ln)], [FILL_LINE.match(ln).groups() for ln in lines if FILL_LINE.match(ln)], files,
-            str(out))
+    others, own, files = run_fresh(data + args, d / "out", own=FILL_LINE)
+    return others, [m.groups() for m in own], files, str(d / "out")
 
 
 def test_nothing_else_changes(tmp_path):

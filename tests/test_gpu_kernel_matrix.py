@@ -23,6 +23,7 @@ import math
 import numpy as np
 import pytest
 
+from device_util import knob_contexts, set_knobs
 import multiclust_amd as mc
 import oracle_bind as ob
 from synth import make_dataset, random_params
@@ -537,28 +538,6 @@ def test_the_case_list_covers_every_reachable_cell():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU tests
-@pytest.fixture(scope="module")
-def contexts():
-    """one Context per knob setting: nothing reuses buffers or a geometry that an older setting chose"""
-    held = {}
-
-    def get(knobs):
-        key = tuple(sorted(knobs.items()))
-        if key not in held:
-            held[key] = mc.Context(0)
-        return held[key]
-    yield get
-    for c in held.values():
-        c.close()
-
-
-def set_knobs(monkeypatch, knobs):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-
-
 def finite_except_empty(a, empty):
     keep = np.ones(a.shape[0], dtype=bool)
     keep[empty] = False
@@ -567,7 +546,7 @@ def finite_except_empty(a, empty):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", CASES, ids=case_id)
-def test_kernel_matrix_em_step_vs_oracle(contexts, monkeypatch, c):
+def test_kernel_matrix_em_step_vs_oracle(knob_contexts, monkeypatch, c):
     ua, geno = build_data(c)
     K, I, L, pl = c["K"], c["I"], c["L"], c["ploidy"]
     cd = case_dict(c, ua)
@@ -583,8 +562,8 @@ def test_kernel_matrix_em_step_vs_oracle(contexts, monkeypatch, c):
     mod = ob.Model(ob.Data(I, L, pl, ua, geno), opt, K)
     mod.q(0)[...] = q0
     mod.p(0)[...] = p0
-    set_knobs(monkeypatch, c["knobs"])
-    ctx = contexts(c["knobs"])
+    set_knobs(monkeypatch, c["knobs"], KNOBS)
+    ctx = knob_contexts(c["knobs"])
     ctx.set_genotypes(ua, geno)
     ctx.set_model(K, admixture=admixture, eta_constrained=con, do_projection=c["projection"], lower_bound=lb)
     n_cu = ctx.device_info()[1]
@@ -628,7 +607,7 @@ def test_kernel_matrix_em_step_vs_oracle(contexts, monkeypatch, c):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", DUAL, ids=case_id)
-def test_kernel_matrix_dual_cycle_vs_oracle(contexts, monkeypatch, c):
+def test_kernel_matrix_dual_cycle_vs_oracle(knob_contexts, monkeypatch, c):
     """One batched SQUAREM-3 cycle (mchip_accel_run; the dual individual pass where the plan has one) against the oracle's
     accelerated_em_step from the same point, and bit for bit against the same cycle with the dual pass off (MCHIP_NO_DUAL=1)."""
     ua, geno = build_data(c)
@@ -642,8 +621,8 @@ def test_kernel_matrix_dual_cycle_vs_oracle(contexts, monkeypatch, c):
     stop_o, trace = mod.accelerated_em_step()
     out = []
     for knobs in ({}, {"MCHIP_NO_DUAL": "1"}):
-        set_knobs(monkeypatch, knobs)
-        ctx = contexts(knobs)
+        set_knobs(monkeypatch, knobs, KNOBS)
+        ctx = knob_contexts(knobs)
         ctx.set_genotypes(ua, geno)
         ctx.set_model(K, lower_bound=lb, n_secants=1)
         ctx.set_q(0, q0)

@@ -16,23 +16,17 @@ import numpy as np
 import pytest
 
 import bedfiles
+from cli_util import ROOT
+from device_util import ctx
 import king_util as ku
 from multiclust_amd import hip
 from synth import random_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 assert (ku.TILE, ku.STAGE_VARIANTS, ku.PLANE_INDIVIDUALS) == (64, 256, 256)      # the cases below are written for these
 IS = [1, 2, 3, 5, ku.TILE - 1, ku.TILE, ku.TILE + 1, 2 * ku.TILE - 1, 2 * ku.TILE, 2 * ku.TILE + 2, ku.PLANE_INDIVIDUALS - 1,
       ku.PLANE_INDIVIDUALS, ku.PLANE_INDIVIDUALS + 1]
 LS = [1, 63, 64, 65, 128, 129, ku.STAGE_VARIANTS - 1, ku.STAGE_VARIANTS, ku.STAGE_VARIANTS + 1, 2 * ku.STAGE_VARIANTS + 1]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def records(I, L, seed, missing, extra):

@@ -14,15 +14,13 @@ import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import BIN, id_lines, option_is_there, run_cli, write_fileset_inputs
 import king_util as ku
 import ld_util as lu
 from multiclust_amd import hip, host
 from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 KING_LINE = re.compile(r"^Relatedness: kept (\d+) of (\d+) individuals \(KING-robust kinship > (\S+): (\d+) pairs\)$")
 PRUNE_LINE = re.compile(r"^LD pruning: kept \d+ of \d+ variants ")
 T = ku.CLI["t"]
@@ -35,8 +33,7 @@ LISTS = {"stem.king.cutoff.in", "stem.king.cutoff.out", "stem.king.kin0"}
 @pytest.fixture(autouse=True, scope="module")
 def the_option_is_there():
     """every test of this file is about --king-cutoff, the one on its absence included: the usage text names the option"""
-    res = run_program([BIN, "-h"], timeout=60)
-    assert res.returncode == 1 and "--king-cutoff <t>" in res.stdout
+    option_is_there("--king-cutoff <t>")
 
 
 @pytest.fixture(scope="module")
@@ -57,28 +54,12 @@ def case():
 def write_inputs(d, case, keep=None, vkeep=None):
     """the fileset `data` in directory d: everything, or the individuals of keep (what `plink --keep` would write) at the variants of
     vkeep (`plink --extract`)"""
-    d.mkdir(parents=True)
-    rows = np.arange(case["I"]) if keep is None else np.flatnonzero(keep)
-    cols = np.arange(case["L"]) if vkeep is None else np.flatnonzero(vkeep)
-    prefix = os.path.join(str(d), "data")
-    # (the whole fileset with its padding bits set; the kept one as plink writes it, with padding bits 0)
-    bf.write_fileset(prefix, case["codes"][np.ix_(rows, cols)], padding=1 if keep is None else 0, fids=[case["fids"][i] for i in rows], iids=[case["iids"][i] for i in rows])
-    lu.write_bim(prefix, ["1"] * len(cols), ["rs%d" % (7 * l) for l in cols], [1000 + 13 * l for l in cols])
-    return d
+    return write_fileset_inputs(d, case, None if keep is None else np.flatnonzero(keep), None if vkeep is None else np.flatnonzero(vkeep))
 
 
 def run(d, args, expect=0):
     """the program in directory d on its fileset `data`; its stdout lines (clock normalised) and every file it wrote"""
-    before = set(os.listdir(str(d)))
-    res = run_program([BIN, "--bed", "data"] + args + ["-o", "stem"], cwd=str(d), timeout=300)
-    assert res.returncode == expect, (res.returncode, res.stderr[-2000:])
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(d), f), "rb").read() for f in sorted(set(os.listdir(str(d))) - before)}
-    return lines, files, res
-
-
-def id_lines(case, which):
-    return "".join("%s\t%s\n" % (case["fids"][i], case["iids"][i]) for i in range(case["I"]) if which[i])
+    return run_cli(["--bed", "data"] + args + ["-o", "stem"], d, expect)
 
 
 def test_line_and_lists_are_the_rule_on_the_devices_kinships(case, tmp_path):

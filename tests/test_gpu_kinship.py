@@ -13,20 +13,14 @@ import sys
 import numpy as np
 import pytest
 
+from cli_util import ROOT
+from device_util import ctx, snapshot, status_of
 import kin_util as ku
 import resid_util as ru
 from multiclust_amd import hip
-from test_gpu_resid import CHUNK, FORMS, IS, TS, install, n_chunks, shaped_ua, snapshot, status_of
+from test_gpu_resid import CHUNK, FORMS, IS, TS, install, n_chunks, shaped_ua
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def run_case(ctx, ua, geno, K, Q, P, form=FORMS[0], what=""):
@@ -177,14 +171,14 @@ def test_state_is_untouched():
             c.secant(0, 0, 1, 0)
             c.secant(1, 0, 2, 1)
             ll0 = c.loglik_prefetch(2)                           # the S-side sums of slot 2 are held
-            before = snapshot(c)
+            before = snapshot(c, 1)
             if n == 0:
                 for slot in (0, 1, 2):
                     G, V = c.kinship_products(slot)
                     ku.check(G, V, ku.reference(ua, geno, c.get_q(slot), c.get_p(slot)))
-                assert snapshot(c) == before
+                assert snapshot(c, 1) == before
             ll1 = c.em_step(2, 0)                                # uses the held sums
-            seen.append((ll0, ll1, snapshot(c)))
+            seen.append((ll0, ll1, snapshot(c, 1)))
         assert seen[0] == seen[1]
     finally:
         for c in ctxs:

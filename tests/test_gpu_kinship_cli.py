@@ -10,61 +10,35 @@ To the printed digits: etaik and pklm carry six decimals, so every q and p read 
 program used.  That moves t by dt = (K + 1) eps at most, a residual by a dt and G_ij by a dt (|r_i|_1 + |r_j|_1); v = t (1 - t) by dt
 and w = a sqrt(v) by dw = a min(dt / (2 sqrt(v)), sqrt(dt)); V_ij by sum_c (dw_i w_j + w_i dw_j + dw_i dw_j); phi = G / V by
 (dG + |phi| dV) / V, second-order terms covered by a factor 1.5.  The program's own figures carry six decimals."""
-import os
-import re
 
 import numpy as np
 import pytest
 
-import bedfiles as bf
-import divergence_util as du
+from cli_util import fit_inputs, Runs, table, written_fit
 import kin_util as ku
 import resid_util as ru
 from multiclust_amd import hip, host
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 PED = dict(seed=1, L=1500, founders=40)
 K, T_CUT = 2, 0.0884
 ARGS = ["-a", "-s", "3", "-n", "2", "-r", "7", "-k", "2"]
 OWN = ["stem.admix.K=2.kin.ind.txt", "stem.admix.K=2.kin0"]
 EPS, P6 = 5.1e-7, 5.1e-7
-_runs = {}
 
 
 @pytest.fixture(scope="module")
 def inputs(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("kin_in"))
     ped = ku.pedigree(**PED)
-    stru = os.path.join(d, "data.stru")
-    bf.write_equivalent_stru(stru, ped["codes"])
-    bf.write_fileset(os.path.join(d, "data"), ped["codes"], padding=1)
     I = ped["codes"].shape[0]
     assert 24 <= I <= 50
-    query = os.path.join(d, "query.txt")
-    with open(query, "w") as f:
-        f.write(" ".join("1" if i % 9 == 4 else "0" for i in range(I)) + "\n")
-    rc, data = host.read_structure(stru)
-    assert rc == 0
-    return dict(dir=d, stru=stru, bed=os.path.join(d, "data"), query=query, ua=data["ua"], geno=data["geno"], ped=ped, I=I,
-                tmp=tmp_path_factory)
+    return dict(fit_inputs(tmp_path_factory, "kin_in", ped["codes"]), ped=ped, I=I,
+                runs=Runs(lambda: tmp_path_factory.mktemp("kin_out"), own="Kinship"))
 
 
 def run(inputs, args, bed=True):
     """one run of the program per distinct command line: (other stdout lines, the Kinship lines, files)"""
-    key = (bed,) + tuple(args)
-    if key not in _runs:
-        out = str(inputs["tmp"].mktemp("kin_out"))
-        data = ["--bed", inputs["bed"]] if bed else ["-f", inputs["stru"]]
-        res = run_program([BIN] + data + list(args) + ["-o", "stem", "-d", os.path.join(out, "")], cwd=out, timeout=300)
-        assert res.returncode == 0, res.stderr
-        lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-        files = {f: open(os.path.join(out, f), "rb").read() for f in sorted(os.listdir(out))}
-        _runs[key] = ([ln for ln in lines if not ln.startswith("Kinship")], [ln for ln in lines if ln.startswith("Kinship")], files)
-    return _runs[key]
+    return inputs["runs"]((["--bed", inputs["bed"]] if bed else ["-f", inputs["stru"]]) + list(args))
 
 
 KIN = ["--kinship", "%g" % T_CUT]
@@ -125,26 +99,10 @@ def test_line_and_files_are_the_restatement_of_the_device_sums(inputs):
     ku.check(G, V, ku.reference(inputs["ua"], inputs["geno"], q, p))
 
 
-def table(text, skip=1):
-    return [ln.split("\t") for ln in text.decode().split("\n")[skip:] if ln.strip()]
-
-
-def written_fit(files, ua, I):
-    T, off = int(ua.sum()), du.offsets(ua)
-    P = np.full((K, T), np.nan)
-    for k, l, m, v in table(files["stem.admix.K=%d.pklm.txt" % K]):
-        P[int(k), off[int(l)] + int(m)] = float(v)
-    assert not np.isnan(P).any()
-    q = np.full((I, K), np.nan)
-    for i, k, v in table(files["stem.admix.K=%d.etaik.txt" % K]):
-        q[int(i), int(k)] = float(v)
-    return q, P
-
-
 def agree_with_the_written_fit(inputs, args, query_rows=()):
     ua, geno, I = inputs["ua"], inputs["geno"].copy(), inputs["I"]
     _, own, files = run(inputs, args)
-    q, P = written_fit(files, ua, I)
+    q, P = written_fit(files, ua, I, K)
     assert np.flatnonzero(np.isnan(q).any(axis=1)).tolist() == list(query_rows)
     q[list(query_rows)] = 1.0 / K                                 # hidden from the fit: no observed copy on the device, any finite row serves
     geno[list(query_rows)] = ru.MISSING

@@ -13,25 +13,19 @@ import sys
 import numpy as np
 import pytest
 
+from cli_util import ROOT
+from device_util import ctx
 import ld_util as lu
 from multiclust_amd import hip
 from synth import random_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IS = [1, 2, 3, 4, 5, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1001]
 LS = [1, 2, lu.TILE - 1, lu.TILE, lu.TILE + 1, 2 * lu.TILE - 1, 2 * lu.TILE, 2 * lu.TILE + 1]
 
 
 def windows(L):
     return sorted({w for w in (1, 2, lu.TILE - 1, lu.TILE, lu.TILE + 1, L - 1, L + 5) if w >= 1})
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def records(I, L, seed, missing, extra):

@@ -11,14 +11,12 @@ import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import BIN, run_cli, write_fileset_inputs
 import ld_util as lu
 from multiclust_amd import hip, host
 from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 PRUNE_LINE = re.compile(r"^LD pruning: kept (\d+) of (\d+) variants \(r2 > (\S+) within (\d+)\)$")
 I, L, T, W = lu.CLI["I"], lu.CLI["L"], lu.CLI["t"], lu.CLI["window"]
 FIT = ["-s", "3", "-n", "2", "-r", "7"]
@@ -38,22 +36,12 @@ def case():
 
 def write_inputs(d, case, keep=None):
     """the fileset `data` in directory d: all variants, or the ones of keep (what `plink --extract` would write)"""
-    d.mkdir(parents=True)
-    sel = np.arange(L) if keep is None else np.flatnonzero(keep)
-    prefix = os.path.join(str(d), "data")
-    bf.write_fileset(prefix, case["codes"][:, sel], padding=1)
-    lu.write_bim(prefix, [case["chrom"][l] for l in sel], [case["ids"][l] for l in sel], [1000 + 13 * l for l in sel])
-    return d
+    return write_fileset_inputs(d, case, cols=None if keep is None else np.flatnonzero(keep), chrom=case["chrom"], ids=case["ids"])
 
 
 def run(d, args, expect=0):
     """the program in directory d on its fileset `data`; its stdout lines (clock normalised) and every file it wrote"""
-    before = set(os.listdir(str(d)))
-    res = run_program([BIN, "--bed", "data"] + args + ["-o", "stem"], cwd=str(d), timeout=300)
-    assert res.returncode == expect, (res.returncode, res.stderr[-2000:])
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(d), f), "rb").read() for f in sorted(set(os.listdir(str(d))) - before)}
-    return lines, files, res
+    return run_cli(["--bed", "data"] + args + ["-o", "stem"], d, expect)
 
 
 def without_prune_line(lines):

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from cli_util import BIN, CLOCK
 import test_gpu_cli as cli
 from multiclust_amd import host
 from procutil import run_program
@@ -105,7 +106,7 @@ ARGS = ["-k", "3", "-n", "2", "-b", "3", "-r", "9"]
 
 def test_cli_mixture_bootstrap_device_host_and_sharded_agree(tmp_path, monkeypatch):
     stru = os.path.join(cli.GOLD, "data", "multi.stru")
-    cmd = [cli.BIN, "-f", stru] + ARGS + ["-d", str(tmp_path)]
+    cmd = [BIN, "-f", stru] + ARGS + ["-d", str(tmp_path)]
     outs = []
     for mode in ("device", "host", "sharded"):
         for k in ("MC_HOST_BOOTSTRAP", "MC_HOST_INIT", "MC_FORCE_SHARDED", "MC_TRACE_EXCHANGE"):
@@ -126,7 +127,7 @@ def test_cli_mixture_bootstrap_device_host_and_sharded_agree(tmp_path, monkeypat
             assert len(trace) == 1, res.stderr
             assert "bootstrap test statistics" in trace[0] and "6 doubles" in trace[0] and "all-reduce #1" in trace[0]
         assert res.stdout.count("Bootstrap dataset") == 3 and "p-value to reject H0: K=2" in res.stdout
-        text = cli.CLOCK.sub("HH:MM:SS", res.stdout)
+        text = CLOCK.sub("HH:MM:SS", res.stdout)
         outs.append(text[text.index("Bootstrap dataset 1"):])
     assert outs[0] == outs[1], outs
     assert outs[0] == outs[2], outs

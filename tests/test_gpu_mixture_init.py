@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import multiclust_amd as mc
+from device_util import ctx
 import oracle_bind as ob
 from golden_util import Golden
 from multiclust_amd import hip, host
@@ -71,13 +71,6 @@ def check_against_host(ctx, ua, geno, K, seed, monkeypatch):
     assert np.array_equal(fit.get_q(0), q_host) and np.array_equal(fit.get_p(0), p_host)
     fit.close()
     return centers, assign
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = mc.Context(0)
-    yield c
-    c.close()
 
 
 # (I, L, ploidy, K, max alleles, missing rate): K = 1, 2, 3, 8, 27, 64; ploidy 1..8 and 9; 2..254 alleles; I = 255 / 257 / 513

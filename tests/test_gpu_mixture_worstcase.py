@@ -27,36 +27,14 @@ loglik_prefetch."""
 import numpy as np
 import pytest
 
+from device_util import knob_contexts, set_knobs
 import mixture_worstcase as mw
-import multiclust_amd as mc
 from test_gpu_kernel_matrix import KNOBS
 
 pytestmark = pytest.mark.gpu
 
 CASES = mw.all_cases()
 WINDOW = mw.window_cases()
-
-
-@pytest.fixture(scope="module")
-def contexts():
-    """one Context per knob setting: nothing reuses buffers or a geometry that an older setting chose"""
-    held = {}
-
-    def get(knobs):
-        key = tuple(sorted(knobs.items()))
-        if key not in held:
-            held[key] = mc.Context(0)
-        return held[key]
-    yield get
-    for c in held.values():
-        c.close()
-
-
-def set_knobs(monkeypatch, knobs):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
 
 
 def run_point(ctx, c, name, ua, geno, eta, p, lb):
@@ -87,9 +65,9 @@ def run_point(ctx, c, name, ua, geno, eta, p, lb):
 
 
 @pytest.mark.parametrize("c", CASES, ids=mw.case_id)
-def test_mixture_step_vs_longdouble(contexts, monkeypatch, c):
-    set_knobs(monkeypatch, c["knobs"])
-    ctx = contexts(c["knobs"])
+def test_mixture_step_vs_longdouble(knob_contexts, monkeypatch, c):
+    set_knobs(monkeypatch, c["knobs"], KNOBS)
+    ctx = knob_contexts(c["knobs"])
     K = c["K"]
     failures = []
     for regime in mw.REGIMES:
@@ -112,7 +90,7 @@ def test_mixture_step_vs_longdouble(contexts, monkeypatch, c):
 
 
 @pytest.mark.parametrize("c", WINDOW, ids=mw.case_id)
-def test_mixture_loglik_window_vs_longdouble(contexts, monkeypatch, c):
-    set_knobs(monkeypatch, c["knobs"])
-    failures, _, _ = run_point(contexts(c["knobs"]), c, "window", *mw.build_window(c))
+def test_mixture_loglik_window_vs_longdouble(knob_contexts, monkeypatch, c):
+    set_knobs(monkeypatch, c["knobs"], KNOBS)
+    failures, _, _ = run_point(knob_contexts(c["knobs"]), c, "window", *mw.build_window(c))
     assert not failures, failures

@@ -8,6 +8,7 @@ Tolerances (north_star): Q/P within 1e-6 relative, logL within 1e-8 absolute at 
 import numpy as np
 import pytest
 
+from device_util import ctx
 import multiclust_amd as mc
 import oracle_bind as ob
 from golden_util import Golden
@@ -25,13 +26,6 @@ ADMIX_C = ["multi_admix_c_k3", "missing_admix_c_k2"]      # shared mixing propor
 # keep p = 0 for every k) and --bound 1e-120: the reciprocal-per-cell kernel variants (mchip_set_model)
 UNPROJECTED = ["missing_admix_k3_noproj", "multi_admix_k4_noproj", "rare_admix_k3_noproj", "tetra_admix_k3_noproj",
                "multi_admix_k4_tinybound"]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = mc.Context(0)
-    yield c
-    c.close()
 
 
 def setup_case(ctx, g, n_secants=1):

@@ -18,24 +18,18 @@ import numpy as np
 import pytest
 
 import bedfiles
+from cli_util import ROOT
+from device_util import ctx
 import pca_util as pu
 from multiclust_amd import hip
 from synth import random_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LD = pu.LD
 assert (pu.LSLAB, pu.VARIANTS, pu.ITILE) == (4096, 64, 64)      # the cases below are written for these
 IS = [5, 15, 16, 17, 63, 65, 255, 257]
 LS = [1, 63, 65, pu.LSLAB - 1, pu.LSLAB, pu.LSLAB + 1, 2 * pu.LSLAB + 1]
 NS = [1, 15, 16, 17, 33, 64]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def check_apply(ctx, I, L, n_vec, seed, missing=0.1, extra=0, wide=False, plant=True):

@@ -4,22 +4,17 @@ two duplicates for --king-cutoff to remove, a run of copied variants for --prune
 --pca is no filter: a run with it is, byte for byte, the run without it, apart from the `PCA:` line and the three new files -- plain
 and after every filter; the components are those of the fileset the filters left, which the test writes out from the .in lists and
 runs on its own; the files agree with the entry point, whose numbers tests/test_gpu_pca.py holds to the definition."""
-import os
 import re
 
 import numpy as np
 import pytest
 
 import bedfiles as bf
-import ld_util as lu
+from cli_util import option_is_there, run_cli, write_fileset_inputs
 import pca_util as pu
 from multiclust_amd import hip
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 PCA_LINE = re.compile(r"^PCA: (\d+) components of (\d+) individuals x (\d+) of (\d+) variants \((\d+) iterations, largest residual (\S+)\): variance explained((?: \S+)+)$")
 FIT = ["-a", "-k", "3", "-s", "3", "-n", "1", "-r", "7"]
 PCA = ["--pca", "3"]
@@ -45,30 +40,19 @@ def case():
 
 
 def write_inputs(d, case, rows=None, cols=None):
-    """the fileset `data` in directory d: everything, or the individuals `rows` at the variants `cols`"""
-    d.mkdir(parents=True)
-    rows = np.arange(case["I"]) if rows is None else np.asarray(rows)
-    cols = np.arange(case["L"]) if cols is None else np.asarray(cols)
-    prefix = os.path.join(str(d), "data")
-    bf.write_fileset(prefix, case["codes"][np.ix_(rows, cols)], padding=1 if len(rows) == case["I"] else 0, fids=[case["fids"][i] for i in rows],
-                     iids=[case["iids"][i] for i in rows])
-    lu.write_bim(prefix, ["1"] * len(cols), [case["vids"][l] for l in cols], [1000 + 13 * l for l in cols])
-    return d
+    """the fileset `data` in directory d: everything, or the individuals `rows` at the variants `cols`; the padding bits are set
+    whenever every individual is in it"""
+    return write_fileset_inputs(d, case, rows, cols, ids=case["vids"], padding=1 if rows is None or len(rows) == case["I"] else 0)
 
 
 def run(d, args, expect=0):
-    before = set(os.listdir(str(d)))
-    res = run_program([BIN, "--bed", "data"] + args + ["-o", "stem"], cwd=str(d), timeout=300)
-    assert res.returncode == expect, (res.returncode, res.stderr[-2000:])
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(d), f), "rb").read() for f in sorted(set(os.listdir(str(d))) - before)}
-    return lines, files, res
+    """the program in directory d on its fileset `data`; its stdout lines (clock normalised) and every file it wrote"""
+    return run_cli(["--bed", "data"] + args + ["-o", "stem"], d, expect)
 
 
 @pytest.fixture(autouse=True, scope="module")
 def the_option_is_there():
-    res = run_program([BIN, "-h"], timeout=60)
-    assert res.returncode == 1 and "--pca <n>" in res.stdout
+    option_is_there("--pca <n>")
 
 
 @pytest.fixture(scope="module")

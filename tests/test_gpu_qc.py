@@ -17,22 +17,16 @@ import sys
 import numpy as np
 import pytest
 
+from cli_util import ROOT
+from device_util import ctx
 import qc_util as qu
 from multiclust_amd import hip
 from synth import random_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 assert (qu.QC_VARIANTS, qu.QC_STEP, qu.QC_ITILE) == (4, 64, 256)      # the cases below are written for these
 IS = [1, 3, 4, 5, 31, 32, 33, 63, 64, 65, 255, 256, 257, qu.STEP_INDIVIDUALS - 1, qu.STEP_INDIVIDUALS + 1]
 LS = [1, 3, 4, 5, 63, 64, 65, 255, 256, 257]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def same_p(a, b):

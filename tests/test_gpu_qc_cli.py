@@ -8,21 +8,16 @@ device to); a run with each option, and with all four, is byte for byte the run 
 which the test writes itself -- plain, followed by --prune, by --king-cutoff and by both, with --fill and with --query; the lists of
 the chained filters name the final fileset; an emptied data set ends the run; and without the options nothing of them appears."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import id_lines, option_is_there, run_cli, write_fileset_inputs
 import king_util as ku
-import ld_util as lu
 import qc_util as qu
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 FIT = ["-a", "-k", "3", "-s", "3", "-n", "2", "-r", "7"]
 C = qu.CLI
 ALL = dict(mind=C["mind"], geno=C["geno"], maf=C["maf"], hwe=C["hwe"])
@@ -34,8 +29,8 @@ QC_FILES = {"stem.mind.in", "stem.mind.out", "stem.qc.in", "stem.qc.out", "stem.
 @pytest.fixture(autouse=True, scope="module")
 def the_options_are_there():
     """every test of this file is about the four options, the one on their absence included: the usage text names them"""
-    res = run_program([BIN, "-h"], timeout=60)
-    assert res.returncode == 1 and all("--%s <t>" % o in res.stdout for o in ALL)
+    for o in ALL:
+        option_is_there("--%s <t>" % o)
 
 
 @pytest.fixture(scope="module")
@@ -54,18 +49,7 @@ def pipeline(case, options, prune=False, king=False):
 
 
 def write_inputs(d, case, rows=None, cols=None):
-    """the fileset `data` in directory d: everything, or the individuals `rows` (what `plink --keep` would write) at the variants
-    `cols` (`plink --extract`)"""
-    d.mkdir(parents=True)
-    whole = rows is None
-    rows = np.arange(case["I"]) if rows is None else rows
-    cols = np.arange(case["L"]) if cols is None else cols
-    prefix = os.path.join(str(d), "data")
-    # (the whole fileset with its padding bits set; the kept one as plink writes it, with padding bits 0)
-    bf.write_fileset(prefix, case["codes"][np.ix_(rows, cols)], padding=1 if whole else 0, fids=[case["fids"][i] for i in rows],
-                     iids=[case["iids"][i] for i in rows])
-    lu.write_bim(prefix, [case["chrom"][l] for l in cols], [case["ids"][l] for l in cols], [1000 + 13 * l for l in cols])
-    return d
+    return write_fileset_inputs(d, case, rows, cols, chrom=case["chrom"], ids=case["ids"])
 
 
 def flags(options):
@@ -74,18 +58,7 @@ def flags(options):
 
 def run(d, args, expect=0):
     """the program in directory d on its fileset `data`; its stdout lines (clock normalised) and every file it wrote"""
-    before = set(os.listdir(str(d)))
-    res = run_program([BIN, "--bed", "data"] + args + ["-o", "stem"], cwd=str(d), timeout=300)
-    assert res.returncode == expect, (res.returncode, res.stderr[-2000:])
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(d), f), "rb").read() for f in sorted(set(os.listdir(str(d))) - before)}
-    return lines, files, res
-
-
-def id_lines(case, rows):
-    rows = set(int(i) for i in rows)
-    return ("".join("%s\t%s\n" % (case["fids"][i], case["iids"][i]) for i in range(case["I"]) if i in rows),
-            "".join("%s\t%s\n" % (case["fids"][i], case["iids"][i]) for i in range(case["I"]) if i not in rows))
+    return run_cli(["--bed", "data"] + args + ["-o", "stem"], d, expect)
 
 
 def variant_lines(case, cols):
@@ -135,13 +108,14 @@ def test_a_run_with_the_options_is_the_run_on_the_kept_fileset(case, name, optio
     assert text["stem.qc.var.txt"] == qu.var_table_text(qc, case["ids"])
     assert text["stem.qc.ind.txt"] == qu.ind_table_text(qc, case["fids"], case["iids"], case["L"])
     if "mind" in options:
-        assert (text["stem.mind.in"], text["stem.mind.out"]) == id_lines(case, np.flatnonzero(qc["ind_keep"]))
+        assert (text["stem.mind.in"], text["stem.mind.out"]) == (id_lines(case, qc["ind_keep"]), id_lines(case, ~qc["ind_keep"]))
     if "stem.qc.in" in lists:
         assert (text["stem.qc.in"], text["stem.qc.out"]) == variant_lines(case, np.flatnonzero(qc["reason"] == qu.KEPT))
     if prune:       # `plink --extract` on it writes the fileset the run was made on
         assert (text["stem.prune.in"], text["stem.prune.out"]) == variant_lines(case, cols)
     if king:
-        assert (text["stem.king.cutoff.in"], text["stem.king.cutoff.out"]) == id_lines(case, rows)
+        kept_rows = np.isin(np.arange(case["I"]), rows)
+        assert (text["stem.king.cutoff.in"], text["stem.king.cutoff.out"]) == (id_lines(case, kept_rows), id_lines(case, ~kept_rows))
         seen = want["rows_seen"]
         assert text["stem.king.kin0"] == ku.kin0_text(case["codes"][np.ix_(seen, cols)], [case["fids"][i] for i in seen],
                                                       [case["iids"][i] for i in seen], C["king_t"])

@@ -4,26 +4,13 @@ mchip_set_p / mchip_set_q: one update against the Q side of mchip_em_step, traje
 import numpy as np
 import pytest
 
+from bits import bits
+from device_util import ctx, status_of
 import query_util as qu
 from multiclust_amd import hip
 
 pytestmark = pytest.mark.gpu
 ROWS = np.arange(qu.I_ROWS, dtype=np.int32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-def status_of(rc):
-    return hip.STATUS.get(rc, rc)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def install(ctx, ua, geno, K, q=None, p=None, do_projection=1, slot=0):

@@ -8,15 +8,12 @@ import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import run_fresh
 import cv_util as cu
 import query_util as qu
 from multiclust_amd import host
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 QUERY_LINE = re.compile(r"^Query fit \(K=(\d+)\): (\d+) individuals, (\d+) converged, (\d+) failed, at most (\d+) iterations, "
                         r"log likelihood (\S+)$")
 STANDARD = ["stem.admix.K=%d.out.txt", "stem.admix.K=%d.etaik.txt", "stem.admix.K=%d.pklm.txt", "stem_admix_indivq_%d.indivq",
@@ -69,13 +66,8 @@ def write_inputs(d, codes, bed=False):
 
 
 def run(data, args, d):
-    out = d / "out"
-    out.mkdir(parents=True)
-    res = run_program([BIN] + data + args + ["-o", "stem", "-d", os.path.join(str(out), "")], cwd=str(out), timeout=300)
-    assert res.returncode == 0, res.stderr
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(out), f), "rb").read() for f in sorted(os.listdir(str(out)))}
-    return [ln for ln in lines if not QUERY_LINE.match(ln)], [QUERY_LINE.match(ln).groups() for ln in lines if QUERY_LINE.match(ln)], files
+    others, own, files = run_fresh(data + args, d / "out", own=QUERY_LINE)
+    return others, [m.groups() for m in own], files
 
 
 def query_table(text):

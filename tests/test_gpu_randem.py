@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_util import BIN
 from procutil import run_program
 
 import oracle_bind as ob
@@ -17,8 +18,6 @@ from multiclust_amd import host
 from synth import make_dataset
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 
 
 def randem_fit(g, n, **kw):

@@ -17,11 +17,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_util import ROOT
 from multiclust_amd import host
 from synth import make_dataset, random_params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_TIME = os.path.join(ROOT, "oracle", "_ref", "ref_time")
 
 

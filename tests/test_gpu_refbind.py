@@ -16,12 +16,13 @@ import os
 
 import pytest
 
+from cli_util import CLOCK, ROOT
 from procutil import run_program
 
 import test_gpu_cli as cli
 
 pytestmark = pytest.mark.gpu
-BOUND = os.path.join(cli.ROOT, "oracle", "_ref", "multiclust_ref_hip")
+BOUND = os.path.join(ROOT, "oracle", "_ref", "multiclust_ref_hip")
 
 
 @pytest.mark.skipif(not os.access(BOUND, os.X_OK), reason="oracle/_ref/multiclust_ref_hip not built (needs /root/reference at build time)")
@@ -39,7 +40,7 @@ def test_reference_program_on_the_hip_path_reproduces_its_own_goldens(case, atol
     cli.test_cli_matches_reference_binary(case, atol, tmp_path)
 
 
-REFBIN = os.path.join(cli.ROOT, "oracle", "_ref", "multiclust_ref")
+REFBIN = os.path.join(ROOT, "oracle", "_ref", "multiclust_ref")
 
 
 @pytest.mark.skipif(not (os.access(BOUND, os.X_OK) and os.access(REFBIN, os.X_OK)), reason="oracle/_ref binaries not built")
@@ -60,7 +61,7 @@ def test_bound_program_beside_the_unmodified_one_on_bootstrap_runs(args, tmp_pat
         d.mkdir()
         res = run_program([exe, "-f", stru, "-d", os.path.join(str(d), "")] + args, cwd=str(d), timeout=600)
         assert res.returncode == 0, (name, res.stderr[-2000:])
-        lines[name] = cli.CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n")
+        lines[name] = CLOCK.sub("HH:MM:SS", res.stdout).strip().split("\n")
     assert len(lines["ref"]) == len(lines["bound"])
     exact = "-s" not in args
     for r, g in zip(lines["ref"], lines["bound"]):

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 
 import bedfiles as bf
+from bits import bits
 import cv_util as cu
+from device_util import status_of
 import oracle_bind as ob
 import se_util as su
 from multiclust_amd import hip
@@ -17,14 +19,6 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(I, L, pl) for I in (67, 300) for L in (61, 130) for pl in (1, 2, 4)]
 MODELS = {"individual": (1, 0), "shared": (1, 1), "mixture": (0, 0)}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-def status_of(rc):
-    return hip.STATUS.get(rc, rc)
 
 
 @pytest.fixture(scope="module")

@@ -19,26 +19,16 @@ import sys
 import numpy as np
 import pytest
 
+from cli_util import ROOT
+from device_util import ctx, snapshot, status_of
 import resid_util as ru
 from multiclust_amd import hip, host
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK, TILE = 512, 64
 IS = [1, 2, 15, 16, 17, 63, 64, 65, 130]
 TS = [CHUNK - 1, CHUNK, CHUNK + 1, CHUNK + 2, 2 * CHUNK + 5]
 FORMS = [dict(admixture=1, eta_constrained=0), dict(admixture=1, eta_constrained=1)]
-
-
-def status_of(rc):
-    return hip.STATUS.get(rc, rc)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
 
 
 def n_chunks(ua):
@@ -223,16 +213,6 @@ def test_bits_do_not_depend_on_the_launch_geometry(ctx):
     assert seen == [here] * 3
 
 
-def snapshot(c):
-    out = [c.get_genotypes().tobytes(), c.expected_counts().tobytes(), repr(c.data_counts()), repr(c.empty_individuals())]
-    for slot in range(3):
-        out += [c.get_q(slot).tobytes(), c.get_p(slot).tobytes()]
-    for which in (0, 1):
-        p, q = c.get_secant(which, 0)
-        out += [p.tobytes(), q.tobytes()]
-    return out
-
-
 def test_state_is_untouched():
     """slots, secants, expected counts and the data set before and after, bit for bit; and a context that asked for the products goes
     on exactly as one that did not (the held S-side sums included)"""
@@ -249,14 +229,14 @@ def test_state_is_untouched():
             c.secant(0, 0, 1, 0)
             c.secant(1, 0, 2, 1)
             ll0 = c.loglik_prefetch(2)                           # the S-side sums of slot 2 are held
-            before = snapshot(c)
+            before = snapshot(c, 1)
             if n == 0:
                 for slot in (0, 1, 2):
                     G, D = c.residual_products(slot)
                     ru.check(G, D, ru.reference(ua, geno, c.get_q(slot), c.get_p(slot)))
-                assert snapshot(c) == before
+                assert snapshot(c, 1) == before
             ll1 = c.em_step(2, 0)                                # uses the held sums
-            seen.append((ll0, ll1, snapshot(c)))
+            seen.append((ll0, ll1, snapshot(c, 1)))
         assert seen[0] == seen[1]
     finally:
         for c in ctxs:

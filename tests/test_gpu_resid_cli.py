@@ -10,24 +10,17 @@ program used.  That moves t = sum_k q_k p_k by (K + 1) eps at most and a residua
 dr (|r_i|_1 + |r_j|_1) and D_ij by 2 dr |r_i|_1, where |r_i|_1 <= sqrt(T D_i); so cor_ij = G_ij / sqrt(D_ij D_ji) moves by at most
 dr sqrt(T) (1 / sqrt(D_ij) + 1 / sqrt(D_ji)) (1 + |cor_ij|), second-order terms covered by a factor 1.5.  The program's own figures
 carry six decimals."""
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
-import bedfiles as bf
-import cv_util as cu
-import divergence_util as du
+from cli_util import BIN, clustered_codes, fit_inputs, Runs, written_fit
 import resid_util as ru
 from multiclust_amd import host
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")
 NUM = r"(-?\d+\.\d+)"
 LINE = re.compile(r"^Residual correlation \(K=(\d+)\): mean " + NUM + r" mean \|r\| " + NUM + " max " + NUM +
                   r" \((\d+), (\d+)\) over (\d+) pairs$")
@@ -35,46 +28,18 @@ I, L, CLUSTERS, K = 72, 400, 3, 3
 ARGS = ["-s", "3", "-n", "2", "-r", "7", "-k", "3"]
 EPS, P6 = 5.1e-7, 5.1e-7
 OWN = ["stem.admix.K=3.resid.txt", "stem.admix.K=3.resid.ind.txt"]
-_runs = {}
-
-
-def codes():
-    """clustered diploid biallelic data as .bed codes, 5 % of the calls missing, one locus without a call"""
-    _, geno = cu.clustered_dataset(I, L, CLUSTERS, 4)
-    n = geno.astype(np.int64).sum(axis=2)
-    c = np.array([bf.HOM1, bf.HET, bf.HOM2], dtype=np.uint8)[n]
-    c[np.random.default_rng(6).random((I, L)) < 0.05] = bf.MISS
-    c[:, 17] = bf.MISS
-    return c
 
 
 @pytest.fixture(scope="module")
 def inputs(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("resid_in"))
-    stru = os.path.join(d, "data.stru")
-    bf.write_equivalent_stru(stru, codes())
-    bf.write_fileset(os.path.join(d, "data"), codes(), padding=1)
-    query = os.path.join(d, "query.txt")
-    with open(query, "w") as f:
-        f.write(" ".join("1" if i % 9 == 4 else "0" for i in range(I)) + "\n")
-    rc, data = host.read_structure(stru)
-    assert rc == 0
-    return dict(dir=d, stru=stru, bed=os.path.join(d, "data"), query=query, ua=data["ua"], geno=data["geno"], tmp=tmp_path_factory)
+    inputs = fit_inputs(tmp_path_factory, "resid_in", clustered_codes(I, L, CLUSTERS))
+    return dict(inputs, runs=Runs(lambda: tmp_path_factory.mktemp("resid_out"), own="Residual"))
 
 
 def run(inputs, args, bed=False):
     """one run of the program per distinct command line: (other stdout lines, the matches of the Residual lines, files)"""
-    key = (bed,) + tuple(args)
-    if key not in _runs:
-        out = str(inputs["tmp"].mktemp("resid_out"))
-        data = ["--bed", inputs["bed"]] if bed else ["-f", inputs["stru"]]
-        res = run_program([BIN] + data + list(args) + ["-o", "stem", "-d", os.path.join(out, "")], cwd=out, timeout=300)
-        assert res.returncode == 0, res.stderr
-        lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-        files = {f: open(os.path.join(out, f), "rb").read() for f in sorted(os.listdir(out))}
-        _runs[key] = ([ln for ln in lines if not ln.startswith("Residual")], [LINE.match(ln) for ln in lines if ln.startswith("Residual")],
-                      files)
-    return _runs[key]
+    others, own, files = inputs["runs"]((["--bed", inputs["bed"]] if bed else ["-f", inputs["stru"]]) + list(args))
+    return others, [LINE.match(ln) for ln in own], files
 
 
 FORMS = {"admix": ["-a"], "shared": ["-a", "-c"]}
@@ -96,28 +61,6 @@ def test_nothing_else_changes(name, extra, bed, inputs):
         assert own2[0].groups() == own1[0].groups() and all(files2[f] == files1[f] for f in OWN)
 
 
-def table(text, skip=1):
-    return [ln.split("\t") for ln in text.decode().split("\n")[skip:] if ln.strip()]
-
-
-def written_fit(files, ua):
-    """Q ([I][K], or [K]) and P [K][T] as the result files print them"""
-    T, off = int(ua.sum()), du.offsets(ua)
-    P = np.full((K, T), np.nan)
-    for k, l, m, v in table(files["stem.admix.K=%d.pklm.txt" % K]):
-        P[int(k), off[int(l)] + int(m)] = float(v)
-    assert not np.isnan(P).any()
-    name = "stem.admix.K=%d.etaik.txt" % K
-    if name in files:
-        q = np.full((I, K), np.nan)
-        for i, k, v in table(files[name]):
-            q[int(i), int(k)] = float(v)
-    else:
-        q = np.array([float(v) for _, v in table(files["stem.admix.K=%d.etak.txt" % K])])
-        assert q.shape == (K,)
-    return q, P
-
-
 def own_files(files):
     """(cor [I][I], per individual: mean, max, partner) as --resid wrote them"""
     text = files[OWN[0]].decode().split("\n")
@@ -135,7 +78,7 @@ def agree_with_the_written_fit(inputs, args, query_rows=()):
     ua, geno = inputs["ua"], inputs["geno"].copy()
     _, own, files = run(inputs, args)
     T = int(ua.sum())
-    q, P = written_fit(files, ua)
+    q, P = written_fit(files, ua, I, K)
     if q.ndim == 2:
         assert np.flatnonzero(np.isnan(q).any(axis=1)).tolist() == list(query_rows)
         q[list(query_rows)] = 1.0 / K                             # hidden from the fit: no observed copy on the device, any finite row serves

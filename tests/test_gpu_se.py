@@ -4,6 +4,7 @@ error falling with the number of loci as it does on the CPU."""
 import numpy as np
 import pytest
 
+from bits import bits
 import cv_util as cu
 import oracle_bind as ob
 import rand_window as rw
@@ -11,10 +12,6 @@ import se_util as su
 from multiclust_amd import host
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def host_state(fit):

@@ -7,14 +7,10 @@ import re
 import numpy as np
 import pytest
 
+from cli_util import DATA, run_fresh, split_own
 from multiclust_amd import host
-from procutil import run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
-DATA = os.path.join(ROOT, "tests", "golden", "data")
-CLOCK = re.compile(r"\d\d:\d\d:\d\d")       # elapsed CPU time of a fit: the one thing two runs of one program differ in
 SE_LINE = re.compile(r"^Bootstrap SE \(K=(\d+), (\d+) replicates, block (\d+)\): mean (\S+)  max (\S+)  \[(\d+) failed\]$")
 CV_LINE = re.compile(r"^CV error \(K=(\d+), (\d+) folds\): (\S+)  \[(\d+) held-out copies, (\d+) floored\]$")
 
@@ -25,16 +21,12 @@ FIXTURES = {
 
 
 def run(data, args, d):
-    d.mkdir()
-    res = run_program([BIN] + data + args + ["-o", "stem", "-d", os.path.join(str(d), "")], cwd=str(d), timeout=300)
-    assert res.returncode == 0, res.stderr
-    lines = CLOCK.sub("HH:MM:SS", res.stdout).split("\n")
-    files = {f: open(os.path.join(str(d), f), "rb").read() for f in sorted(os.listdir(str(d)))}
-    return lines, files
+    return run_fresh(data + args, d)[:2]
 
 
 def split(lines):
-    return [ln for ln in lines if not SE_LINE.match(ln)], [SE_LINE.match(ln).groups() for ln in lines if SE_LINE.match(ln)]
+    others, own = split_own(lines, SE_LINE)
+    return others, [m.groups() for m in own]
 
 
 def read_fixture(name):

@@ -36,7 +36,7 @@ prints one WORST line per case and path with the same ratios of the GPU result."
 import numpy as np
 import pytest
 
-import multiclust_amd as mc
+from device_util import knob_contexts, set_knobs
 import worstcase as wc
 from test_gpu_kernel_matrix import KNOBS
 
@@ -45,32 +45,10 @@ pytestmark = pytest.mark.gpu
 CASES = wc.all_cases()
 
 
-@pytest.fixture(scope="module")
-def contexts():
-    """one Context per knob setting: nothing reuses buffers or a geometry that an older setting chose"""
-    held = {}
-
-    def get(knobs):
-        key = tuple(sorted(knobs.items()))
-        if key not in held:
-            held[key] = mc.Context(0)
-        return held[key]
-    yield get
-    for c in held.values():
-        c.close()
-
-
-def set_knobs(monkeypatch, knobs):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-
-
-def gpu_step(contexts, monkeypatch, c, knobs, ua, geno, q, p):
+def gpu_step(knob_contexts, monkeypatch, c, knobs, ua, geno, q, p):
     """(logL, Q1, P1, S) of em_step(0, 1), and loglik / e_step / loglik_prefetch of slot 0"""
-    set_knobs(monkeypatch, knobs)
-    ctx = contexts(knobs)
+    set_knobs(monkeypatch, knobs, KNOBS)
+    ctx = knob_contexts(knobs)
     ctx.set_genotypes(ua, geno)
     ctx.set_model(c["K"], admixture=1, eta_constrained=int(c["model"] == "admix_c"), do_projection=1, lower_bound=c["lb"])
     ctx.set_q(0, q)
@@ -81,14 +59,14 @@ def gpu_step(contexts, monkeypatch, c, knobs, ua, geno, q, p):
 
 
 @pytest.mark.parametrize("c", CASES, ids=wc.case_id)
-def test_worst_case_step_vs_longdouble(contexts, monkeypatch, c):
+def test_worst_case_step_vs_longdouble(knob_contexts, monkeypatch, c):
     ua, geno, q, p = wc.build(c)
     ref = wc.reference_step(ua, geno, q, p, c["lb"], c["model"])
     orc = wc.oracle_step(c, ua, geno, q, p)
     tol = max(1e-8, 1e-12 * abs(ref[0]))
     failures = []
     for path, knobs in (("fast", c["knobs"]), ("safe", dict(c["knobs"], MCHIP_FORCE_SAFE="1"))):
-        step, lls = gpu_step(contexts, monkeypatch, c, knobs, ua, geno, q, p)
+        step, lls = gpu_step(knob_contexts, monkeypatch, c, knobs, ua, geno, q, p)
         finite = all(np.isfinite(x).all() for x in step) and all(np.isfinite(x) for x in lls)
         r_ref, r_orc = wc.ratios(step, ref), wc.ratios(step, orc)
         r_ll = max(abs(x - ref[0]) for x in lls) / tol

@@ -2,19 +2,18 @@
 oracle's fit, the two writers of --fill on hand-made files (through host.py and, under the sanitizers, through a C program of their
 own), and the command line's refusals."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import bedfiles as bf
+from cli_util import BIN, DATA, ROOT
 import cv_util as cu
+import host_driver
 import impute_util as iu
 from multiclust_amd import host
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 MULTI = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")
 
 
@@ -213,16 +212,10 @@ def test_refused_combinations(args, tmp_path):
 
 
 # ---- the writers under AddressSanitizer + UBSan, as a program of their own ----
-@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_writers_are_sanitizer_clean(tmp_path):
-    exe = str(tmp_path / "impute_writers")
-    hostdir = os.path.join(ROOT, "multiclust_amd", "host")
-    srcs = [os.path.join(ROOT, "tests", "impute_writers_driver.c")] + [os.path.join(hostdir, f) for f in ("mc_impute.c", "mc_reader.c", "mc_bed.c")]
-    subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + hostdir, "-o", exe] + srcs + ["-lm", "-lpthread"], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-    data = os.path.join(ROOT, "tests", "golden", "data")
-    runs = [["stru", os.path.join(data, fn), str(pl), str(miss), "0", str(tmp_path / ("out%d.stru" % n))]
+    exe = host_driver.build(tmp_path, "impute_writers", ["tests/impute_writers_driver.c"] +
+                            ["multiclust_amd/host/" + f for f in ("mc_impute.c", "mc_reader.c", "mc_bed.c")], libs=("-lm", "-lpthread"), werror=True)
+    runs = [["stru", os.path.join(DATA, fn), str(pl), str(miss), "0", str(tmp_path / ("out%d.stru" % n))]
             for n, (fn, pl, miss) in enumerate((("missing.stru", 2, -9), ("tetra.stru", 4, -9), ("multi_interleaved.stru", 2, -9),
                                                 ("missing99.stru", 2, 99), ("multi.stru", 2, -9)))]
     for I in (7, 8):
@@ -230,9 +223,8 @@ def test_writers_are_sanitizer_clean(tmp_path):
         bf.write_fileset(str(tmp_path / ("set%d" % I)), codes, padding=1)
         runs.append(["bed", str(tmp_path / ("set%d" % I)), str(tmp_path / ("filled%d" % I))])
     for args in runs:
-        res = subprocess.run([exe] + args, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=120)
-        assert res.returncode == 0, (args, res.stderr[-2000:])
-        assert "wrote 0" in res.stdout and "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
+        res = host_driver.run(exe, args, cwd=tmp_path)
+        assert "wrote 0" in res.stdout, args
     # what the program wrote is what the library writes: the filled file reads back without a missing copy where a locus has alleles
     rc, d = host.read_structure(runs[0][-1])
     rc0, d0 = host.read_structure(runs[0][1])

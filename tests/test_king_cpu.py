@@ -7,7 +7,6 @@ the command-line tests.
 There is no tolerance in this file.  The counts are integers; num and 4 m stay below 2^33 for L < 2^31, so their conversions to
 double are exact and the one division is the correctly rounded quotient: float(Fraction) of the same rational, bit for bit."""
 import os
-import shutil
 import subprocess
 from fractions import Fraction
 
@@ -15,10 +14,9 @@ import numpy as np
 import pytest
 
 import bedfiles
+from cli_util import BIN, ROOT
+import host_driver
 import king_util as ku
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 
 
 @pytest.fixture(autouse=True, scope="module")
@@ -145,30 +143,8 @@ def test_rule_properties_and_brute_force_on_random_graphs(I, p, seed):
 
 
 # ---- mc_king.c as a program of its own ----
-def build_driver(tmp, sanitize):
-    exe = os.path.join(tmp, "king_host_san" if sanitize else "king_host")
-    hostdir = os.path.join(ROOT, "multiclust_amd", "host")
-    srcs = [os.path.join(ROOT, "tests", "king_host_driver.c"), os.path.join(hostdir, "mc_king.c")]
-    flags = ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if sanitize else ["-O2"]
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Wextra"] + flags + ["-I" + os.path.join(ROOT, "include"), "-I" + hostdir, "-o", exe] + srcs + ["-lm"],
-                   check=True)
-    return exe
-
-
-@pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
-def driver(request, tmp_path_factory):
-    if shutil.which("gcc") is None:
-        pytest.skip("needs gcc")
-    exe = build_driver(str(tmp_path_factory.mktemp("king_driver")), request.param)
-
-    def run(*args, cwd):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-        res = subprocess.run([exe] + [str(a) for a in args], cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             env=env, timeout=120)
-        assert res.returncode == 0, (args, res.returncode, res.stderr[-2000:])
-        assert "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
-        return res.stdout
-    return run
+driver = host_driver.plain_and_sanitized("king_host", ["tests/king_host_driver.c", "multiclust_amd/host/mc_king.c"], werror=True,
+                                         result=lambda res: res.stdout)
 
 
 def test_driver_band_restatement_is_the_reference(driver, tmp_path):
@@ -262,19 +238,13 @@ def test_library_select_and_compact_through_the_python_view():
 
 # ---- the launch geometry of the pair kernel ----
 def test_king_geometry(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    exe = str(tmp_path / "king_geometry")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                    "-I" + os.path.join(ROOT, "multiclust_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "king_geometry_driver.cpp")],
-                   check=True)
+    exe = host_driver.build(tmp_path, "king_geometry", ["tests/king_geometry_driver.cpp"], cxx=True, werror=True)
     cases = [(I, n, L, target) for I in (1, 63, 64, 65, 130, 10000, 2 ** 29) for n in (1, 64, 65, 1024) if n <= I
              for L in (1, 256, 257, 1100, 100000, 2 ** 31 - 1) for target in (1, 256, 256 * 8, 256 * 4096, 2 ** 40)]
     # the launches of tests/test_gpu_king.py's geometry test, on 256 compute units
     named = {(name, knob): (g["I"], g["I"], g["L"], knob * 256) for name, g in ku.GEOMETRY.items() for knob in (1, 64, 4096)}
     cases += list(named.values())
-    res = subprocess.run([exe], input="".join("%d %d %d %d\n" % c for c in cases), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
-    assert res.returncode == 0 and not res.stderr, res.stderr[-2000:]
+    res = host_driver.run(exe, stdin="".join("%d %d %d %d\n" % c for c in cases), quiet_stderr=True)
     rows = [tuple(int(x) for x in line.split()) for line in res.stdout.splitlines()]
     assert len(rows) == len(cases)
     split_seen = set()

@@ -8,18 +8,17 @@ duplicate, two families with sibs and a trio, 3 000 SNPs, 5 % missing, seed 1.  
 0.487, the parent-child and sib pairs from 0.236 up, every other pair at 0.031 at most: visible room to the cuts 0.354, 0.177 and
 0.0884.  With the pooled sample frequencies (the homogeneous estimator) an unrelated pair reaches 0.137, past the second-degree cut."""
 import os
-import shutil
 import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from cli_util import BIN, ROOT
+import host_driver
 import kin_util as ku
 import resid_util as ru
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 MULTI = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")
 PED = dict(seed=1, L=3000, founders=40)
 
@@ -203,20 +202,12 @@ def driver_sums(n):
     return G, V
 
 
-@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 @pytest.mark.parametrize("n,ploidy", [(1, 2), (2, 2), (9, 2), (9, 4)])
 def test_host_code_is_sanitizer_clean_and_follows_the_rules(n, ploidy, tmp_path):
-    exe = str(tmp_path / "kinship_host")
-    hostdir = os.path.join(ROOT, "multiclust_amd", "host")
-    srcs = [os.path.join(ROOT, "tests", "kinship_host_driver.c"), os.path.join(hostdir, "mc_kinship.c")]
-    subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + hostdir, "-o", exe] + srcs + ["-lm"], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    exe = host_driver.build(tmp_path, "kinship_host", ["tests/kinship_host_driver.c", "multiclust_amd/host/mc_kinship.c"], werror=True)
     t = 0.04
-    res = subprocess.run([exe, str(n), str(ploidy), repr(t), str(tmp_path / "stem")], cwd=str(tmp_path), stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True, env=env, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
-    assert "wrote 0" in res.stdout and "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
+    res = host_driver.run(exe, [n, ploidy, repr(t), tmp_path / "stem"], cwd=tmp_path)
+    assert "wrote 0" in res.stdout
     G, V = driver_sums(n)
     want = ku.report(G, V, ploidy, t, K=2)
     assert res.stdout.split("\n")[0] == want["line"]

@@ -8,8 +8,6 @@ conversions and both products are exact and the division is the correctly rounde
 bit.  Beyond that there are three conversions (c's enters squared) and three operations, seven factors (1 + e), |e| <= 2^-53: at
 most 3.5 * 2^-52 relative in the worst case, and the errors of drawn cases are of both signs; the bound asserted on the drawn cases
 is 2 ulp of the rounded rational, and the worst distance seen is printed."""
-import os
-import shutil
 import subprocess
 from fractions import Fraction
 
@@ -17,10 +15,9 @@ import numpy as np
 import pytest
 
 import bedfiles
+from cli_util import BIN
+import host_driver
 import ld_util as lu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 
 
 def exact(n, Sx, Sy, Sxx, Syy, Sxy):
@@ -166,29 +163,8 @@ def test_a_chromosome_boundary_splits_a_run_of_duplicates():
 
 
 # ---- mc_ld.c as a program of its own ----
-def build_driver(tmp, sanitize):
-    exe = os.path.join(tmp, "ld_host_san" if sanitize else "ld_host")
-    hostdir = os.path.join(ROOT, "multiclust_amd", "host")
-    srcs = [os.path.join(ROOT, "tests", "ld_host_driver.c"), os.path.join(hostdir, "mc_ld.c")]
-    flags = ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if sanitize else ["-O2"]
-    subprocess.run(["gcc", "-std=gnu11"] + flags + ["-I" + os.path.join(ROOT, "include"), "-I" + hostdir, "-o", exe] + srcs + ["-lm"], check=True)
-    return exe
-
-
-@pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
-def driver(request, tmp_path_factory):
-    if shutil.which("gcc") is None:
-        pytest.skip("needs gcc")
-    exe = build_driver(str(tmp_path_factory.mktemp("ld_driver")), request.param)
-
-    def run(*args, cwd):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-        res = subprocess.run([exe] + [str(a) for a in args], cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             env=env, timeout=120)
-        assert res.returncode == 0, (args, res.returncode, res.stderr[-2000:])
-        assert "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
-        return res.stdout
-    return run
+driver = host_driver.plain_and_sanitized("ld_host", ["tests/ld_host_driver.c", "multiclust_amd/host/mc_ld.c"], werror=True,
+                                         result=lambda res: res.stdout)
 
 
 def test_driver_greedy_is_ld_util_on_the_same_bands(driver, tmp_path):

@@ -1,11 +1,9 @@
 """No GPU: what the command line refuses of --pca, --pca-iter and --pca-tol before anything is read (multiclust_amd/host/mc_cli_options.c),
 and what the usage text says about the option."""
-import os
 
+from cli_util import BIN
 from procutil import run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 INVALID_CMD_ARGUMENT = 10
 
 

@@ -8,19 +8,17 @@ multiclust_amd/csrc/mchip_pca_algebra.h as a sanitized program of its own (tests
   - mutants of the definition and of the iteration, each caught by the check the GPU tests apply;
   - the constants and the start vectors of the restatement held to the headers."""
 import os
-import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import bedfiles
+from cli_util import ROOT
+import host_driver
 import pca_util as pu
 from multiclust_amd import hip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "multiclust_amd", "csrc")
 LD = pu.LD
 
 
@@ -113,12 +111,8 @@ def test_float64_in_three_orders_lies_within_half_of_the_bounds(I, L, n_vec, wid
 # ---- the algebra as a sanitized program ----
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
     tmp = tmp_path_factory.mktemp("pca_algebra")
-    exe = str(tmp / "pca_algebra")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                    "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tests", "pca_algebra_driver.cpp")], check=True)
+    exe = host_driver.build(tmp, "pca_algebra", ["tests/pca_algebra_driver.cpp"], cxx=True, werror=True)
 
     def run(*args, arrays=(), outputs=(), stdin=""):
         """arrays: the input files' contents in argument order; outputs: the shapes of the output files; returns (stdout, arrays)"""
@@ -128,10 +122,7 @@ def driver(tmp_path_factory):
             np.ascontiguousarray(a, dtype=np.float64).tofile(path)
             ins.append(path)
         outs = [str(tmp / ("out%d" % k)) for k in range(len(outputs))]
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-        res = subprocess.run([exe] + [str(a) for a in args] + ins + outs, input=stdin, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             env=env, timeout=300)
-        assert res.returncode == 0 and not res.stderr, (args, res.returncode, res.stderr[-2000:])
+        res = host_driver.run(exe, list(args) + ins + outs, stdin=stdin, timeout=300, quiet_stderr=True)
         return res.stdout, [np.fromfile(o, dtype=np.float64).reshape(shape) for o, shape in zip(outs, outputs)]
     return run
 

@@ -1,13 +1,12 @@
 """The command line of --mind, --geno, --maf and --hwe where it needs no GPU: parse_options runs before any file or device is opened,
 so what it refuses, and that the four options are matched in full and leave -m, -g, -h and --missing their meaning, shows here.  (An
 emptied data set ends the run behind the device: tests/test_gpu_qc_cli.py, and tests/test_qc_cpu.py through the driver.)"""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
+from cli_util import BIN
+
 RANGE = {"--mind": "the missing rate of --mind must lie in [0, 1)", "--geno": "the missing rate of --geno must lie in [0, 1)",
          "--maf": "the minor-allele frequency of --maf must lie in (0, 0.5]", "--hwe": "the p value of --hwe must lie in (0, 1)"}
 BAD = {"--mind": ["-0.1", "1", "nan"], "--geno": ["-0.1", "1", "2", "nan"], "--maf": ["0", "-0.01", "0.51", "nan"], "--hwe": ["0", "1", "-1e-6", "nan"]}

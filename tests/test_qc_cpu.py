@@ -7,18 +7,17 @@ definition and of the rules that the cases of the tests have to tell from the re
 The counts are integers and have no tolerance.  The one tolerance of this file, of the float restatement against the rationals, is
 derived at the test from the number of roundings of the walk."""
 import os
-import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import bedfiles
+from cli_util import ROOT
+import host_driver
 import king_util
 import qc_util as qu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = Fraction(1, 2 ** 53)        # unit roundoff of float64
 
 
@@ -156,30 +155,8 @@ def test_composition_of_maps_against_brute_force():
 
 
 # ---- mc_qc.c, and the two filters behind it, as a program of their own ----
-def build_driver(tmp, sanitize):
-    exe = os.path.join(tmp, "qc_host_san" if sanitize else "qc_host")
-    hostdir = os.path.join(ROOT, "multiclust_amd", "host")
-    srcs = [os.path.join(ROOT, "tests", "qc_host_driver.c")] + [os.path.join(hostdir, f) for f in ("mc_qc.c", "mc_ld.c", "mc_king.c")]
-    flags = ["-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if sanitize else ["-O2"]
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Wextra"] + flags + ["-I" + os.path.join(ROOT, "include"), "-I" + hostdir, "-o", exe] + srcs + ["-lm"],
-                   check=True)
-    return exe
-
-
-@pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
-def driver(request, tmp_path_factory):
-    if shutil.which("gcc") is None:
-        pytest.skip("needs gcc")
-    exe = build_driver(str(tmp_path_factory.mktemp("qc_driver")), request.param)
-
-    def run(*args, cwd):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-        res = subprocess.run([exe] + [str(a) for a in args], cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             env=env, timeout=120)
-        assert res.returncode == 0, (args, res.returncode, res.stderr[-2000:])
-        assert "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
-        return res
-    return run
+driver = host_driver.plain_and_sanitized("qc_host", ["tests/qc_host_driver.c"] + ["multiclust_amd/host/" + f for f in ("mc_qc.c", "mc_ld.c", "mc_king.c")],
+                                         werror=True)
 
 
 def test_driver_stub_of_the_device_is_the_reference(driver, tmp_path):
@@ -292,18 +269,12 @@ def test_driver_ends_on_an_emptied_data_set(driver, tmp_path):
 
 # ---- the launch geometry ----
 def test_qc_geometry(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    exe = str(tmp_path / "qc_geometry")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                    "-I" + os.path.join(ROOT, "multiclust_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "qc_geometry_driver.cpp")],
-                   check=True)
+    exe = host_driver.build(tmp_path, "qc_geometry", ["tests/qc_geometry_driver.cpp"], cxx=True, werror=True)
     cases = [(I, L, target) for I in (1, 31, 32, 33, 256, 257, 2048, 2049, 6149, 10000, 2 ** 30 - 1)
              for L in (1, 4, 5, 64, 65, 600, 1100, 100000, 2 ** 31 - 1) for target in (1, 256, 256 * 64, 256 * 4096, 2 ** 40)]
     named = {(name, knob): (g["I"], g["L"], knob * 256) for name, g in qu.GEOMETRY.items() for knob in (1, 64, 4096)}
     cases += list(named.values())
-    res = subprocess.run([exe], input="".join("%d %d %d\n" % c for c in cases), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
-    assert res.returncode == 0 and not res.stderr, res.stderr[-2000:]
+    res = host_driver.run(exe, stdin="".join("%d %d %d\n" % c for c in cases), quiet_stderr=True)
     rows = [tuple(int(x) for x in line.split()) for line in res.stdout.splitlines()]
     assert len(rows) == len(cases)
     cut = set()

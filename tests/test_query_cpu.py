@@ -6,11 +6,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_util import BIN, ROOT
 import query_util as qu
 from multiclust_amd import host
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 MULTI = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")      # 40 diploid individuals
 I_MULTI = 40
 

@@ -13,9 +13,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_util import ROOT
 from test_reader_cpu import read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HARNESS = os.path.join(ROOT, "oracle", "_ref", "ref_harness")
 pytestmark = pytest.mark.skipif(not os.access(HARNESS, os.X_OK), reason="oracle/_ref/ref_harness not built")
 

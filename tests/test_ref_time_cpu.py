@@ -8,10 +8,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_util import ROOT
 import oracle_bind as ob
 from golden_util import Golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_TIME = os.path.join(ROOT, "oracle", "_ref", "ref_time")
 pytestmark = pytest.mark.skipif(not os.access(REF_TIME, os.X_OK), reason="oracle/_ref/ref_time not built")
 

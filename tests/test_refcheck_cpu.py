@@ -5,9 +5,8 @@ import shutil
 import subprocess
 import sys
 
+from cli_util import ROOT
 import conftest
-
-ROOT = conftest.ROOT
 
 
 def fake_tree(tmp_path, binaries):

@@ -15,19 +15,18 @@ The teeth, sized here (I, L and the seeds below; the figures are printed):
                true cluster then miss the merged frequencies the same way, a positive correlation of the order of the F_ST between
                the two; with K = 3 the same pairs have the baseline, about -1 / 30."""
 import os
-import shutil
 import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from cli_util import BIN, ROOT
 import cv_util as cu
+import host_driver
 import resid_util as ru
 from multiclust_amd import host
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
 MULTI = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")
 
 
@@ -212,19 +211,11 @@ def test_refused_combinations(args, why, tmp_path):
 
 
 # ---- mc_resid.c under AddressSanitizer + UBSan, as a program of its own (the device entry point stubbed) ----
-@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 @pytest.mark.parametrize("n", [1, 2, 7])
 def test_host_code_is_sanitizer_clean(n, tmp_path):
-    exe = str(tmp_path / "resid_host")
-    hostdir = os.path.join(ROOT, "multiclust_amd", "host")
-    srcs = [os.path.join(ROOT, "tests", "resid_host_driver.c"), os.path.join(hostdir, "mc_resid.c")]
-    subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + hostdir, "-o", exe] + srcs + ["-lm"], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-    res = subprocess.run([exe, str(n), str(tmp_path / "stem")], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                         text=True, env=env, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
-    assert "wrote 0" in res.stdout and "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr
+    exe = host_driver.build(tmp_path, "resid_host", ["tests/resid_host_driver.c", "multiclust_amd/host/mc_resid.c"], werror=True)
+    res = host_driver.run(exe, [n, tmp_path / "stem"], cwd=tmp_path)
+    assert "wrote 0" in res.stdout
     line = res.stdout.split("\n")[0]
     rows = open(str(tmp_path / "stem.admix.K=2.resid.txt")).read().split("\n")
     ind = open(str(tmp_path / "stem.admix.K=2.resid.ind.txt")).read().split("\n")

@@ -6,8 +6,8 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "multiclust_amd", "bin", "multiclust")
+from cli_util import BIN, ROOT
+
 MULTI = os.path.join(ROOT, "tests", "golden", "data", "multi.stru")
 INVALID_CMD_ARGUMENT = 10
 INVALID_USER_SETUP = 11

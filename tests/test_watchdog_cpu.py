@@ -9,10 +9,10 @@ import time
 
 import pytest
 
+from cli_util import ROOT
 import procutil
 from multiclust_amd import hip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOSTLIB = os.path.join(ROOT, "multiclust_amd", "lib", "libmulticlust_host.so")
 
 STALL = r"""
