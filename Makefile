@@ -9,6 +9,9 @@ OBJ  = build/obj
 LIB  = multiclust_amd/lib
 KS   = $(shell seq 1 64)
 KOBJ = $(foreach k,$(KS),$(OBJ)/mchip_k$(k).o)
+# the per-K kernel unit and what it includes: every header of kernels_k/ (a new one costs nothing here) and four of csrc/
+KSRC  = multiclust_amd/csrc/mchip_kernels_k.hip
+KHDRS = $(wildcard multiclust_amd/csrc/kernels_k/*.h) multiclust_amd/csrc/mchip_internal.h multiclust_amd/csrc/mchip_device_util.h multiclust_amd/csrc/mchip_finalize.h include/multiclust_hip.h
 
 BIN  = multiclust_amd/bin
 
@@ -22,7 +25,7 @@ all: $(LIB)/libmulticlust_hip.so $(LIB)/libmulticlust_host.so $(BIN)/multiclust 
 # translation unit all the same.  Reproducer: `make exp-k52`, scripts/diag/k52_spill.sh.
 KFLAGS = -mllvm -amdgpu-spill-vgpr-to-agpr=false
 # (a static pattern rule, for the objects of KS alone: a unit whose name begins with mchip_k, as mchip_kinship, takes the rule below)
-$(KOBJ): $(OBJ)/mchip_k%.o: multiclust_amd/csrc/mchip_kernels_k.hip multiclust_amd/csrc/mchip_internal.h multiclust_amd/csrc/mchip_device_util.h multiclust_amd/csrc/mchip_finalize.h include/multiclust_hip.h
+$(KOBJ): $(OBJ)/mchip_k%.o: $(KSRC) $(KHDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_K=$* -c $< -o $@
 
@@ -65,7 +68,7 @@ scripts/micro/%: scripts/micro/%.hip
 # the product's other objects into a library of its own; scripts/diag/scatter_exp.sh loads it through MCHIP_LIB_PATH
 exp-scatter: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_EXP_SCATTER -DMCHIP_K=8 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k8.o
+	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_EXP_SCATTER -DMCHIP_K=8 -c $(KSRC) -o build/exp/mchip_k8.o
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_scatter.so \
 		$(filter-out $(OBJ)/mchip_k8.o,$(HIPOBJ) $(KOBJ)) build/exp/mchip_k8.o -ldl
 
@@ -76,8 +79,8 @@ exp-scatter: $(LIB)/libmulticlust_hip.so
 exp-k52: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_FORCE_SPLIT1 -c multiclust_amd/csrc/mchip_plan.hip -o build/exp/mchip_plan_split1.o
-	$(HIPCC) $(HIPFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k52_agpr.o
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k52_scratch.o
+	$(HIPCC) $(HIPFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c $(KSRC) -o build/exp/mchip_k52_agpr.o
+	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DMCHIP_FORCE_SPLIT1 -DMCHIP_K=52 -c $(KSRC) -o build/exp/mchip_k52_scratch.o
 	for v in agpr scratch; do $(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_k52$$v.so \
 		build/exp/mchip_plan_split1.o $(filter-out $(OBJ)/mchip_plan.o,$(HIPOBJ)) $(filter-out $(OBJ)/mchip_k52.o,$(KOBJ)) build/exp/mchip_k52_$$v.o -ldl; done
 
@@ -87,7 +90,7 @@ exp-k52: $(LIB)/libmulticlust_hip.so
 EXPNAME ?= exp
 exp-k8: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(EXPFLAGS) -DMCHIP_K=8 -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k8_$(EXPNAME).o
+	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(EXPFLAGS) -DMCHIP_K=8 -c $(KSRC) -o build/exp/mchip_k8_$(EXPNAME).o
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_$(EXPNAME).so \
 		$(filter-out $(OBJ)/mchip_k8.o,$(HIPOBJ) $(KOBJ)) build/exp/mchip_k8_$(EXPNAME).o -ldl
 
@@ -95,7 +98,7 @@ exp-k8: $(LIB)/libmulticlust_hip.so
 EXPK ?= 8
 exp-k: $(LIB)/libmulticlust_hip.so
 	@mkdir -p build/exp scripts/exp
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(EXPFLAGS) -DMCHIP_K=$(EXPK) -c multiclust_amd/csrc/mchip_kernels_k.hip -o build/exp/mchip_k$(EXPK)_$(EXPNAME).o
+	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(EXPFLAGS) -DMCHIP_K=$(EXPK) -c $(KSRC) -o build/exp/mchip_k$(EXPK)_$(EXPNAME).o
 	$(HIPCC) --offload-arch=$(ARCH) --offload-compress -shared -fPIC -o scripts/exp/libmulticlust_hip_$(EXPNAME).so \
 		$(filter-out $(OBJ)/mchip_k$(EXPK).o,$(HIPOBJ) $(KOBJ)) build/exp/mchip_k$(EXPK)_$(EXPNAME).o -ldl
 

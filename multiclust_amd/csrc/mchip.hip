@@ -32,30 +32,17 @@ mchip_progress_slot *mchip_progress_my_slot(void)
 
 /* ------------------------------------------------------------------ per-K tables */
 #define DECL_KT(n) const mchip_ktable *mchip_ktable_get_##n();
-DECL_KT(1) DECL_KT(2) DECL_KT(3) DECL_KT(4) DECL_KT(5) DECL_KT(6) DECL_KT(7) DECL_KT(8)
-DECL_KT(9) DECL_KT(10) DECL_KT(11) DECL_KT(12) DECL_KT(13) DECL_KT(14) DECL_KT(15) DECL_KT(16)
-DECL_KT(17) DECL_KT(18) DECL_KT(19) DECL_KT(20) DECL_KT(21) DECL_KT(22) DECL_KT(23) DECL_KT(24)
-DECL_KT(25) DECL_KT(26) DECL_KT(27) DECL_KT(28) DECL_KT(29) DECL_KT(30) DECL_KT(31) DECL_KT(32)
-DECL_KT(33) DECL_KT(34) DECL_KT(35) DECL_KT(36) DECL_KT(37) DECL_KT(38) DECL_KT(39) DECL_KT(40)
-DECL_KT(41) DECL_KT(42) DECL_KT(43) DECL_KT(44) DECL_KT(45) DECL_KT(46) DECL_KT(47) DECL_KT(48)
-DECL_KT(49) DECL_KT(50) DECL_KT(51) DECL_KT(52) DECL_KT(53) DECL_KT(54) DECL_KT(55) DECL_KT(56)
-DECL_KT(57) DECL_KT(58) DECL_KT(59) DECL_KT(60) DECL_KT(61) DECL_KT(62) DECL_KT(63) DECL_KT(64)
+MCHIP_FOR_EACH_K(DECL_KT)
+#undef DECL_KT
 
 const mchip_ktable *mchip_get_ktable(int K)
 {
 	typedef const mchip_ktable *(*getter)();
-	static const getter tabs[MCHIP_MAX_K + 1] = {
-		nullptr,
-		mchip_ktable_get_1, mchip_ktable_get_2, mchip_ktable_get_3, mchip_ktable_get_4, mchip_ktable_get_5, mchip_ktable_get_6, mchip_ktable_get_7, mchip_ktable_get_8,
-		mchip_ktable_get_9, mchip_ktable_get_10, mchip_ktable_get_11, mchip_ktable_get_12, mchip_ktable_get_13, mchip_ktable_get_14, mchip_ktable_get_15, mchip_ktable_get_16,
-		mchip_ktable_get_17, mchip_ktable_get_18, mchip_ktable_get_19, mchip_ktable_get_20, mchip_ktable_get_21, mchip_ktable_get_22, mchip_ktable_get_23, mchip_ktable_get_24,
-		mchip_ktable_get_25, mchip_ktable_get_26, mchip_ktable_get_27, mchip_ktable_get_28, mchip_ktable_get_29, mchip_ktable_get_30, mchip_ktable_get_31, mchip_ktable_get_32,
-		mchip_ktable_get_33, mchip_ktable_get_34, mchip_ktable_get_35, mchip_ktable_get_36, mchip_ktable_get_37, mchip_ktable_get_38, mchip_ktable_get_39, mchip_ktable_get_40,
-		mchip_ktable_get_41, mchip_ktable_get_42, mchip_ktable_get_43, mchip_ktable_get_44, mchip_ktable_get_45, mchip_ktable_get_46, mchip_ktable_get_47, mchip_ktable_get_48,
-		mchip_ktable_get_49, mchip_ktable_get_50, mchip_ktable_get_51, mchip_ktable_get_52, mchip_ktable_get_53, mchip_ktable_get_54, mchip_ktable_get_55, mchip_ktable_get_56,
-		mchip_ktable_get_57, mchip_ktable_get_58, mchip_ktable_get_59, mchip_ktable_get_60, mchip_ktable_get_61, mchip_ktable_get_62, mchip_ktable_get_63, mchip_ktable_get_64,
-	};
-	static_assert(MCHIP_MAX_K == 64, "one kernel translation unit per K (Makefile: KS)");
+#define KT_ENTRY(n) mchip_ktable_get_##n,
+	static const getter tabs[] = { nullptr, MCHIP_FOR_EACH_K(KT_ENTRY) };
+#undef KT_ENTRY
+	static_assert(MCHIP_MAX_K == 64 && sizeof(tabs) / sizeof(tabs[0]) == MCHIP_MAX_K + 1,
+		      "one kernel translation unit per K (mchip_internal.h: MCHIP_FOR_EACH_K; Makefile: KS)");
 	return (K >= 1 && K <= MCHIP_MAX_K) ? tabs[K]() : nullptr;
 }
 

@@ -1,5 +1,5 @@
 /*
- * mchip_em.hip -- the EM step: the K-independent reductions and finalisers behind the passes of mchip_kernels_k.hip, the E step of
+ * mchip_em.hip -- the EM step: the K-independent reductions and finalisers behind the passes of mchip_kernels_k.hip (kernels_k/), the E step of
  * either model with its M step (run_estep, run_mixture), graph capture, and the entry points that run steps and take log likelihoods.
  */
 #include "mchip_context.h"

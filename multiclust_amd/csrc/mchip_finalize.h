@@ -1,6 +1,6 @@
 /* mchip_finalize.h -- device code of the P-side finaliser that two translation units launch: mchip_em.hip (k_finalize_p_tile by
- * itself: mixture model, first M step, shared mixing proportions) and every mchip_kernels_k.hip (k_finalize_qp: the finalisers of
- * an EM step's two sides in one launch).  Internal to the library. */
+ * itself: mixture model, first M step, shared mixing proportions) and every mchip_kernels_k.hip (k_finalize_qp of
+ * kernels_k/finalize_q.h: the finalisers of an EM step's two sides in one launch).  Internal to the library. */
 #ifndef MCHIP_FINALIZE_H
 #define MCHIP_FINALIZE_H
 
@@ -74,7 +74,7 @@ __device__ __forceinline__ void michelot_small(double (&x)[8], int len, double m
  * copy; phase 3 stores the run, coalesced.  Same bits as k_finalize_p.  Used while FP_LOCI loci of max_M alleles fit the tile. */
 constexpr int FP_TILE = 1024;	/* doubles of LDS per block: four elements per thread, all of a thread's slab loads in flight at once */
 /* (the body: block `block` of the launch, `tile` = FP_TILE doubles of LDS; k_finalize_p_tile in mchip_em.hip, and the second part of
- * the grid of k_finalize_qp in mchip_kernels_k.hip) */
+ * the grid of k_finalize_qp in kernels_k/finalize_q.h) */
 __device__ __forceinline__ void finalize_p_tile_body(int block, double *tile, int L, int K, int T, const int32_t *__restrict__ toff, int loci_per_block,
 		int n_slabs, const double *__restrict__ Apart, const double *Pfrom, double *Pto,
 		int weighted, double add_lb, int do_projection, double lb)

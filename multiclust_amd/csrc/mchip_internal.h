@@ -252,6 +252,13 @@ struct mchip_ktable {
 	void (*estep_pair)(const mchip_pass_args &a, const mchip_plan &p, unsigned long long *marks, hipStream_t s);
 };
 
+/* every K a kernel unit is built for (Makefile: KS): X(1) ... X(64) */
+#define MCHIP_FOR_EACH_K(X) \
+	X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
+	X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32) \
+	X(33) X(34) X(35) X(36) X(37) X(38) X(39) X(40) X(41) X(42) X(43) X(44) X(45) X(46) X(47) X(48) \
+	X(49) X(50) X(51) X(52) X(53) X(54) X(55) X(56) X(57) X(58) X(59) X(60) X(61) X(62) X(63) X(64)
+
 const mchip_ktable *mchip_get_ktable(int K);
 
 inline int mchip_ind_waves(int K, int tile_cols)

@@ -78,7 +78,7 @@ mchip_geometry model_geometry(const mchip_shape &sh, int K, int admixture, int d
 	g.ind_waves = ind_coop ? mchip_ind_waves(K, 8 * sh.max_M) : 1;
 	if (ind_coop) {
 		/* ... and a multiple of eight slab rows where possible: the sparse kernel then keeps a row on one XCD (coop_rows() in
-		 * mchip_kernels_k.hip), and eight XCDs with 52 rows between them would have 7 and 6 each */
+		 * kernels_k/sparse_w.h), and eight XCDs with 52 rows between them would have 7 and 6 each */
 		const int w8 = 8 * g.ind_waves, w1 = g.ind_waves;
 		const int up8 = ((want + w8 - 1) / w8) * w8, up1 = ((want + w1 - 1) / w1) * w1;
 		if (up8 <= cap && up8 <= lblocks) want = up8;

@@ -6,7 +6,7 @@ k_column_counts, the add_lb branch of k_finalize_p / k_finalize_p_tile) are comp
 rtol = 1e-7 on Dirichlet(1) parameters.  Here they are compared against `reference` (numpy.longdouble; it shares no code with
 oracle/, only the projection, applied to the rounded result as worstcase.reference_step does) within `bounds`.
 
-THE STEP (em_alg.c:763-1011, mchip_kernels_k.hip "mixture model", mchip_em.hip run_mixture).  n_ic = copies of allele column c
+THE STEP (em_alg.c:763-1011, kernels_k/mixture.h "mixture model", mchip_em.hip run_mixture).  n_ic = copies of allele column c
 individual i carries (missing copies are skipped), eta = shared mixing proportions, p = (K, T):
     v_ik  = log eta_k + sum_c n_ic log p_kc          (a cell with p == 0 adds 0 in the E step, -inf in the log likelihood: k_logp)
     vik   = exp(v_ik - max_k v_ik) / sum_k exp(v_ik - max_k v_ik),      ll = sum_i ll_i,  ll_i = log sum_k exp(v_ik)

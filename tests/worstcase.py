@@ -346,7 +346,7 @@ def col_slots(c, ua, geno, q, p, l, m):
 
 def simulate_product(slots, interval):
     """The kernels' rule in double precision: multiply, look every `interval` slots, move the exponent out below 1e-100 (rescale()
-    of mchip_kernels_k.hip: frexp), one log at the end.  Returns (log of the product, smallest product seen)."""
+    of kernels_k/common.h: frexp), one log at the end.  Returns (log of the product, smallest product seen)."""
     prod, ex, low = 1.0, 0, 1.0
     for s, t in enumerate(slots, 1):
         prod *= t
